@@ -463,13 +463,97 @@ def cap_e2e_pso_fallback():
     print("e2e pso fallback: fitness", r["stats"][4], "path cells", len(r["path"]), "curve", r["curve"])
     np.savez_compressed(os.path.join(OUT, "e2e_pso_fallback.npz"), **d, **{"meta_" + k: v for k, v in META.items()})
 
+def cap_vs_reference(G):
+    """The random cases of tests/test_oracle_vs_reference.py (same seeds, same order) with the reference's answers: A* /
+    MPA._a_star / Dijkstra triples with avoid sets, GA and PSO decodes + scores, four MAACO iterations of 12 ants (beta 7
+    and 2) with the pheromone after every update, MPA segment rebuilds (levy beta 1.5 and 2) -> vs_reference.npz."""
+    g = G["fig7"]
+    d = {}
+    free = [tuple(x) for x in np.argwhere(g != 1)]
+
+    ra, rd, mpa = rh.RefAStar(g), rh.RefDijkstra(g), rh.make_mpa(g)
+    rnd = random.Random(2024)
+    se, has_avoid, avoid, out = [], [], [], {0: ([], []), 1: ([], []), 2: ([], [])}
+    for t in range(250):
+        s, e = rnd.choice(free), rnd.choice(free)
+        if t % 7 == 0: e = s
+        if t % 11 == 0: s = (0, 4)
+        av = set(rnd.sample(free, rnd.randint(0, 40))) if t % 3 else None
+        se.append([s[0] * 20 + s[1], e[0] * 20 + e[1]])
+        has_avoid.append(av is not None)
+        avoid.append([a[0] * 20 + a[1] for a in av] if av is not None else [])
+        for v, (pc, _, cnt) in enumerate((ra.solve(s, e, av), rh.mpa_astar(mpa, s, e, av), rd.solve(s, e, av))):
+            out[v][0].append(pc)
+            out[v][1].append([cnt["pops"], cnt["pushes"]])
+    d["astar_se"], d["astar_has_avoid"] = np.array(se, np.int32), np.array(has_avoid)
+    d["astar_avoid_off"], d["astar_avoid"] = csr(avoid)
+    for v in range(3):
+        d[f"astar_v{v}_path_off"], d[f"astar_v{v}_path"] = csr(out[v][0])
+        d[f"astar_v{v}_counts"] = np.array(out[v][1], np.int64)
+
+    ga, ps = rh.make_ga(g, **MAIN_W), rh.make_pso(g, **MAIN_W)
+    rnd = random.Random(99)
+    chroms, ga_paths, ga_stats, poss, pso_paths = [], [], [], [], []
+    for t in range(120):
+        chrom = [rnd.choice(free) for _ in range(5)]
+        with rh.quiet():
+            p = ga._reconstruct_path_from_chromosome(chrom)
+            rs = ga._calculate_stats_for_path(p)
+        chroms.append([r * 20 + c for r, c in chrom]); ga_paths.append(rh.to_cells(p, 20)); ga_stats.append(rs[1:6])
+        pos = [[rnd.uniform(-2, 21), rnd.uniform(-2, 21)] for _ in range(5)]
+        with rh.quiet():
+            p = ps._reconstruct_path_from_position(pos)
+        poss.append(pos); pso_paths.append(rh.to_cells(p, 20))
+    d["decode_chrom"], d["decode_ga_stats"], d["decode_pos"] = np.array(chroms, np.int32), np.array(ga_stats, np.float64), np.array(poss)
+    d["decode_ga_path_off"], d["decode_ga_path"] = csr(ga_paths)
+    d["decode_pso_path_off"], d["decode_pso_path"] = csr(pso_paths)
+
+    for beta in (7.0, 2.0):
+        ma = rh.make_maaco(g, num_ants=12, num_iterations=10, alpha=1.0, beta=beta, rho=0.1, Q=2.5, a_turn_coef=1.0,
+                           wh_max=0.9, wh_min=0.2, k_h_adaptive=0.9, q0_initial=0.5, C0_initial_pheromone=0.1)
+        k = f"maaco_b{beta:g}"
+        d[k + "_tau0"] = ma.pheromone_matrix.copy()
+        paths, LT, taus = [], [], []
+        best = float("inf")
+        for it in range(1, 5):
+            it_paths = []
+            for ant in range(12):
+                pc, L, T, _ = rh.maaco_walk(ma, it, 31, ant)
+                paths.append(pc); LT.append([L, T]); best = min(best, L)
+                it_paths.append((rh.to_rc(pc, 20), L, 0))
+            ma.best_path_length_overall = best
+            ma._update_pheromone_trails_maaco(it_paths, None)
+            taus.append(ma.pheromone_matrix.copy())
+        d[k + "_path_off"], d[k + "_path"] = csr(paths)
+        d[k + "_len_turns"], d[k + "_tau"] = np.array(LT, np.float64), np.array(taus)
+
+    for beta in (1.5, 2.0):
+        mpa = rh.make_mpa(g, levy_beta=beta)
+        base = rh.to_cells(mpa.population[0]["path"], 20)
+        a1, _, _ = rh.mpa_astar(mpa, (0, 0), (10, 0))
+        a2, _, _ = rh.mpa_astar(mpa, (10, 0), (19, 19), set(rh.to_rc(a1[:-1], 20)))
+        alt = np.concatenate([a1, a2[1:]])
+        rnd = random.Random(8)
+        cases, paths, res_, draws_ = [], [], [], []
+        for t in range(150):
+            path_c, el_c = (base, alt) if t % 2 else (alt, base)
+            idx = rnd.randint(0, len(path_c) - 1)
+            is_levy, scale = t % 3 == 0, rnd.choice([0.5, 0.25, 0.05, 5.0, 40.0])
+            pc, res, draws = rh.mpa_rebuild(mpa, rh.to_rc(path_c, 20), rh.to_rc(el_c, 20), idx, is_levy, scale, 17, 2, t)
+            cases.append([idx, is_levy, scale]); paths.append(pc); res_.append(res[1:6]); draws_.append(draws)
+        k = f"mpa_b{beta:g}"
+        d[k + "_base"], d[k + "_alt"] = base, alt
+        d[k + "_cases"], d[k + "_res"], d[k + "_draws"] = np.array(cases, np.float64), np.array(res_, np.float64), np.array(draws_, np.int64)
+        d[k + "_path_off"], d[k + "_path"] = csr(paths)
+    np.savez_compressed(os.path.join(OUT, "vs_reference.npz"), **d, **{"meta_" + k: v for k, v in META.items()})
+
 
 if __name__ == "__main__":
     assert rh.available(), "needs /root/reference"
     os.makedirs(OUT, exist_ok=True)
     rh.install()
     G = grids()
-    which = sys.argv[1:] or ["grids", "rng", "astar", "decode", "maaco", "mpa", "pso", "dijkstra", "e2e"]
+    which = sys.argv[1:] or ["grids", "rng", "astar", "decode", "maaco", "mpa", "pso", "dijkstra", "e2e", "vs_reference"]
     if "grids" in which: cap_grids(G)
     if "rng" in which: cap_rng()
     if "astar" in which: cap_astar(G)
@@ -480,4 +564,5 @@ if __name__ == "__main__":
     if "dijkstra" in which: cap_dijkstra(G)
     if "e2e" in which: cap_e2e(G)
     if "e2e" in which or "pso_fallback" in which: cap_e2e_pso_fallback()
+    if "vs_reference" in which: cap_vs_reference(G)
     print("golden fixtures written to", OUT)

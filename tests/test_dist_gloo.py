@@ -36,6 +36,30 @@ def _worker(rank, world, port, out_dir, strict, ants=21, chunks=8, cap_factor=No
     dist.destroy_process_group()
 
 
+def _spawn(fn, args, nprocs, timeout=300):
+    """torch.multiprocessing.spawn without importing torch into this process (a later test in the same process binds the
+    system librccl, and torch's bundled copy has the same soname): fresh `spawn` interpreters, rank as the first argument,
+    the survivors killed as soon as one rank fails."""
+    import multiprocessing
+    import time
+    ctx = multiprocessing.get_context("spawn")
+    procs = [ctx.Process(target=fn, args=(r,) + tuple(args)) for r in range(nprocs)]
+    for pr in procs:
+        pr.start()
+    t_end = time.monotonic() + timeout
+    try:
+        while any(pr.exitcode is None for pr in procs):
+            if any(pr.exitcode not in (None, 0) for pr in procs) or time.monotonic() > t_end:
+                break
+            time.sleep(0.05)
+    finally:
+        for pr in procs:
+            if pr.exitcode is None:
+                pr.kill()
+            pr.join(10)
+    assert all(pr.exitcode == 0 for pr in procs), [pr.exitcode for pr in procs]
+
+
 def _single(strict=True, ants=21):
     import golden_io as gio
     from dist_fakes import FakeMAACO
@@ -48,9 +72,8 @@ def _single(strict=True, ants=21):
 
 @pytest.mark.parametrize("strict", [True, False])
 def test_sharded_maaco_two_ranks_equals_one(tmp_path, strict):
-    import torch.multiprocessing as mp
     port = 29500 + (os.getpid() % 2000) + (1 if strict else 0)
-    mp.spawn(_worker, args=(2, port, str(tmp_path), strict), nprocs=2, join=True)
+    _spawn(_worker, args=(2, port, str(tmp_path), strict), nprocs=2)
     ref = _single(strict)
     for r in (0, 1):
         z = np.load(tmp_path / f"r{r}.npz")
@@ -65,9 +88,8 @@ def test_sharded_maaco_two_ranks_equals_one(tmp_path, strict):
 def test_sharded_maaco_three_ranks_uneven_blocks_pipelined_fold(tmp_path):
     """20 ants over 3 ranks (7 + 7 + 6: the uneven all_gather path) with the ordered fold pipelined over 5 row chunks:
     rank 1 folds chunk j while rank 2 folds chunk j - 1; the matrix every rank ends with is the sequential one."""
-    import torch.multiprocessing as mp
     port = 27300 + (os.getpid() % 2000)
-    mp.spawn(_worker, args=(3, port, str(tmp_path), True, 20, 5), nprocs=3, join=True)
+    _spawn(_worker, args=(3, port, str(tmp_path), True, 20, 5), nprocs=3)
     ref = _single(True, 20)
     for r in (0, 1, 2):
         z = np.load(tmp_path / f"r{r}.npz")
@@ -78,9 +100,8 @@ def test_sharded_maaco_three_ranks_uneven_blocks_pipelined_fold(tmp_path):
 def test_sharded_maaco_ranks_with_different_path_cap(tmp_path):
     """One rank has grown its path rows (an ant overflowed there, only there): the exchange must not depend on path_cap being
     the same everywhere -- the best row travels as (length, exactly that many cells)."""
-    import torch.multiprocessing as mp
     port = 25100 + (os.getpid() % 2000)
-    mp.spawn(_worker, args=(2, port, str(tmp_path), True, 21, 8, (1, 4)), nprocs=2, join=True)
+    _spawn(_worker, args=(2, port, str(tmp_path), True, 21, 8, (1, 4)), nprocs=2)
     ref = _single(True)
     for r in (0, 1):
         z = np.load(tmp_path / f"r{r}.npz")

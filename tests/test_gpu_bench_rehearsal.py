@@ -18,7 +18,7 @@ def test_two_rank_line_carries_the_multi_gpu_configs():
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK")}
     env.update(PF_BENCH_SHARE_GPU="1", PF_BENCH_EXTRA_BUDGET="400")
     pr = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1", "--backend", "gloo",
-                         "--no-cpu"], env=env, capture_output=True, text=True, timeout=900)
+                         "--full", "--no-cpu"], env=env, capture_output=True, text=True, timeout=900)
     assert pr.returncode == 0, pr.stderr[-2000:]
     line = [ln for ln in pr.stdout.splitlines() if ln.startswith("{")][-1]
     d = json.loads(line)

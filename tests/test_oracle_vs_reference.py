@@ -1,105 +1,74 @@
-"""CPU oracle == the live, unmodified reference on fresh random cases.
-Build container only (needs /root/reference); skipped on the GPU box."""
-import random
-
+"""CPU oracle == the unmodified reference on random cases (fixed seeds): the reference's answers were captured into
+tests/golden/vs_reference.npz (oracle/capture_golden.py, `vs_reference`).  Runs anywhere (no GPU, no reference tree)."""
 import numpy as np
 import pytest
 
-pytestmark = pytest.mark.reference
+import golden_io as gio
 
 
 @pytest.fixture(scope="module")
 def env():
-    import ref_harness as rh
     import pf_oracle as po
-    rh.install()
-    g = rh.mark_grid(np.array(rh.mods()["env"].grid_fig7_layout_data), (0, 0), (19, 19))
-    return rh, po, g
+    g, _, _ = gio.grid("fig7")
+    return gio.load("vs_reference"), po, g
 
 
 def test_astar_random_triples(env):
-    rh, po, g = env
-    ra, rd, mpa, orc = rh.RefAStar(g), rh.RefDijkstra(g), rh.make_mpa(g), po.Oracle(g)
-    rnd = random.Random(2024)
-    free = [tuple(x) for x in np.argwhere(g != 1)]
-    for t in range(250):
-        s, e = rnd.choice(free), rnd.choice(free)
-        if t % 7 == 0: e = s
-        if t % 11 == 0: s = (0, 4)
-        avoid = set(rnd.sample(free, rnd.randint(0, 40))) if t % 3 else None
-        ac = [orc.cell(a) for a in avoid] if avoid is not None else None
-        pc, _, cnt = ra.solve(s, e, avoid)
-        oc, st = orc.astar(orc.cell(s), orc.cell(e), ac, 0)
-        assert np.array_equal(pc, oc) and (len(pc) <= 1 or (cnt["pops"], cnt["pushes"]) == (st[0], st[1]))
-        pc, _, cnt = rh.mpa_astar(mpa, s, e, avoid)
-        oc, st = orc.astar(orc.cell(s), orc.cell(e), ac, 1)
-        assert np.array_equal(pc, oc) and (len(pc) <= 1 or (cnt["pops"], cnt["pushes"]) == (st[0], st[1]))
-        pc, _, cnt = rd.solve(s, e, avoid)                      # dijkstra.DijkstraSolver.solve
-        oc, st = orc.astar(orc.cell(s), orc.cell(e), ac, 2)
-        assert np.array_equal(pc, oc) and (len(pc) <= 1 or (cnt["pops"], cnt["pushes"]) == (st[0], st[1]))
+    z, po, g = env
+    orc = po.Oracle(g)
+    for t, (s, e) in enumerate(z["astar_se"]):
+        ac = [int(a) for a in gio.csr_get(z["astar_avoid_off"], z["astar_avoid"], t)] if z["astar_has_avoid"][t] else None
+        for v in range(3):                                      # AStarSolver.solve, MPA._a_star, DijkstraSolver.solve
+            pc = gio.csr_get(z[f"astar_v{v}_path_off"], z[f"astar_v{v}_path"], t)
+            oc, st = orc.astar(int(s), int(e), ac, v)
+            cnt = z[f"astar_v{v}_counts"][t]
+            assert np.array_equal(pc, oc) and (len(pc) <= 1 or (cnt[0], cnt[1]) == (st[0], st[1])), (t, v)
 
 
 def test_decode_score_random(env):
-    rh, po, g = env
-    W = dict(turn_penalty_factor=0.3, safety_penalty_factor=0.8, min_safe_distance=1.8, diagonal_obstacle_penalty_value=100.0)
-    ga, ps, orc = rh.make_ga(g, **W), rh.make_pso(g, **W), po.Oracle(g)
-    rnd = random.Random(99)
-    free = [tuple(x) for x in np.argwhere(g != 1)]
-    for t in range(120):
-        chrom = [rnd.choice(free) for _ in range(5)]
-        with rh.quiet():
-            p = ga._reconstruct_path_from_chromosome(chrom)
-            rs = ga._calculate_stats_for_path(p)
-        oc, _ = orc.decode(0, 399, [orc.cell(w) for w in chrom])
-        assert np.array_equal(rh.to_cells(p, 20), oc)
-        assert list(orc.score(oc, 0, 0.3, 0.8, 1.8, True, 100.0)) == [rs[1], rs[2], rs[3], rs[4], rs[5]]
-        pos = [[rnd.uniform(-2, 21), rnd.uniform(-2, 21)] for _ in range(5)]
-        with rh.quiet():
-            p = ps._reconstruct_path_from_position(pos)
-        oc, _ = orc.decode(0, 399, orc.pso_round(pos))
-        assert np.array_equal(rh.to_cells(p, 20), oc)
+    z, po, g = env
+    orc = po.Oracle(g)
+    for t, chrom in enumerate(z["decode_chrom"]):
+        oc, _ = orc.decode(0, 399, [int(w) for w in chrom])
+        assert np.array_equal(gio.csr_get(z["decode_ga_path_off"], z["decode_ga_path"], t), oc)
+        assert list(orc.score(oc, 0, 0.3, 0.8, 1.8, True, 100.0)) == list(z["decode_ga_stats"][t])
+        oc, _ = orc.decode(0, 399, orc.pso_round(z["decode_pos"][t]))
+        assert np.array_equal(gio.csr_get(z["decode_pso_path_off"], z["decode_pso_path"], t), oc)
 
 
 @pytest.mark.parametrize("beta", [7.0, 2.0])
 def test_maaco_iterations(env, beta):
-    rh, po, g = env
+    z, po, g = env
+    k = f"maaco_b{beta:g}"
     orc = po.Oracle(g)
-    ma = rh.make_maaco(g, num_ants=12, num_iterations=10, alpha=1.0, beta=beta, rho=0.1, Q=2.5, a_turn_coef=1.0,
-                       wh_max=0.9, wh_min=0.2, k_h_adaptive=0.9, q0_initial=0.5, C0_initial_pheromone=0.1)
     P = po.MaacoParams(alpha=1.0, beta=beta, rho=0.1, Q=2.5, a_turn=1.0, wh_max=0.9, wh_min=0.2, k_h=0.9,
                        q0_initial=0.5, C0=0.1, num_iterations=10)
     tau, dist = orc.maaco_init(0, 399, 0.1)
-    assert np.array_equal(tau.reshape(20, 20), ma.pheromone_matrix)
+    assert np.array_equal(tau.reshape(20, 20), z[k + "_tau0"])
     best = float("inf")
     for it in range(1, 5):
         paths, lens = [], []
         for ant in range(12):
-            pc, L, T, draws = rh.maaco_walk(ma, it, 31, ant)
+            j = (it - 1) * 12 + ant
+            pc, (L, T) = gio.csr_get(z[k + "_path_off"], z[k + "_path"], j), z[k + "_len_turns"][j]
             oc, oL, oT, _ = orc.maaco_walk(0, 399, P, tau, dist, it, 31, ant)
             assert np.array_equal(pc, oc) and L == oL and T == oT
             paths.append(oc); lens.append(oL); best = min(best, oL)
-        ma.best_path_length_overall = best
-        ma._update_pheromone_trails_maaco([(rh.to_rc(p, 20), l, 0) for p, l in zip(paths, lens)], None)
         orc.maaco_update(tau, 0.1, 2.5, paths, lens, best)
-        assert np.array_equal(tau.reshape(20, 20), ma.pheromone_matrix)
+        assert np.array_equal(tau.reshape(20, 20), z[k + "_tau"][it - 1])
 
 
 @pytest.mark.parametrize("beta", [1.5, 2.0])
 def test_mpa_rebuild_random(env, beta):
-    rh, po, g = env
+    z, po, g = env
     from pathfit import rng as pfrng
-    orc, mpa = po.Oracle(g), rh.make_mpa(g, levy_beta=beta)
-    base = rh.to_cells(mpa.population[0]["path"], 20)
-    a1, _, _ = rh.mpa_astar(mpa, (0, 0), (10, 0))
-    a2, _, _ = rh.mpa_astar(mpa, (10, 0), (19, 19), set(rh.to_rc(a1[:-1], 20)))
-    alt = np.concatenate([a1, a2[1:]])
-    rnd = random.Random(8)
-    for t in range(150):
+    from pathfit.mpa import levy_sigma
+    k = f"mpa_b{beta:g}"
+    orc = po.Oracle(g)
+    base, alt = z[k + "_base"], z[k + "_alt"]
+    for t, (idx, is_levy, scale) in enumerate(z[k + "_cases"]):
         path_c, el_c = (base, alt) if t % 2 else (alt, base)
-        idx = rnd.randint(0, len(path_c) - 1)
-        is_levy, scale = t % 3 == 0, rnd.choice([0.5, 0.25, 0.05, 5.0, 40.0])
-        pc, res, draws = rh.mpa_rebuild(mpa, rh.to_rc(path_c, 20), rh.to_rc(el_c, 20), idx, is_levy, scale, 17, 2, t)
         gR = orc.rng(17, pfrng.DOM_MPA, 2, t)
-        oc, _, _, _ = orc.mpa_rebuild(0, 399, path_c, el_c, idx, is_levy, scale, beta, rh.levy_sigma(beta), gR)
-        assert np.array_equal(pc, oc) and gR.ctr == draws
-        assert list(orc.score(oc, 1, 0.1, 0.05, 1.5, True, 1000.0)) == [res[1], res[2], res[3], res[4], res[5]]
+        oc, _, _, _ = orc.mpa_rebuild(0, 399, path_c, el_c, int(idx), bool(is_levy), float(scale), beta, levy_sigma(beta), gR)
+        assert np.array_equal(gio.csr_get(z[k + "_path_off"], z[k + "_path"], t), oc) and gR.ctr == z[k + "_draws"][t]
+        assert list(orc.score(oc, 1, 0.1, 0.05, 1.5, True, 1000.0)) == list(z[k + "_res"][t])
