@@ -209,6 +209,33 @@ void* pf_maaco_tau_dev(pf_handle* h); /* device pointer, for collectives */
 int pf_maaco_best_scan(int32_t n, const double* plen, const int32_t* turns, int32_t idx0, double* best_len,
                        double* best_turns, int32_t* best_idx);
 
+/* ---- K4/K5 batched: K independent MAACO colonies in one iteration -------- */
+/* K colonies share the handle's grid and one parameter set (p->start / p->target are ignored); colony c has its own start
+ * starts[c], target targets[c], seed seeds[c] and n ants, and its own pheromone, eta table (shared between colonies with the
+ * same start / target), deposit matrix and overall best path -- owned by the batch, so the handle's solo MAACO state
+ * (pf_maaco_setup) is never touched, and several batches may live on one handle.  The tabu slot pool is the handle's.
+ * Colony c computes exactly what a solo run (pf_maaco_setup with start / target = starts[c] / targets[c], pf_maaco_iterate
+ * with seed seeds[c], ant0 0, n ants) computes: ant a of colony c draws the stream (seeds[c], DOM_MAACO, iter, a).
+ * The device memory is checked at creation (tau, tau^alpha when alpha != 1, tep, ceil(n / 64) RC bit words, flags, deposits
+ * and a best row per colony: ~1.3 MB at 128^2 x 256 ants): a batch that does not fit fails with a message.  pf_destroy
+ * frees every batch of the handle; after pf_update_grid a batch only accepts pf_maaco_batch_destroy. */
+typedef struct pf_maaco_batch pf_maaco_batch;
+int pf_maaco_batch_create(pf_handle* h, const pf_maaco_params* p, int32_t K, int32_t n, const int32_t* starts, const int32_t* targets,
+                          const uint64_t* seeds, pf_maaco_batch** out);
+void pf_maaco_batch_destroy(pf_maaco_batch* b);
+/* One iteration of every colony, as pf_maaco_iterate: one walk over the K n ants (colony c's ants are rows [c n, (c + 1) n) of
+ * d_cells [K n][path_cap] and of the other columns), one best-of-iteration / take-over launch (a block per colony, against
+ * best_len[c] / best_turns[c]), one pheromone pass, ONE wait.  out[13 c ...] = colony c's 13 doubles (pf_maaco_iterate's out13;
+ * steps ... overflow_agents count the whole batch).  overflow_agents > 0 anywhere: no colony's pheromone moved; repeat the
+ * call with longer rows. */
+int pf_maaco_batch_iterate(pf_maaco_batch* b, int32_t iter, int32_t n, int32_t path_cap, int32_t* d_cells, int32_t* d_len,
+                           double* d_plen, int32_t* d_turns, int32_t* d_status, const double* best_len, const double* best_turns,
+                           double* out);
+/* colony k's overall best path (pf_maaco_best_path), and its pheromone matrix round trip (double[R*C]) */
+int pf_maaco_batch_best_path(pf_maaco_batch* b, int32_t k, int32_t* cells_out, int32_t cap, int32_t* len_out);
+int pf_maaco_batch_get_pheromone(pf_maaco_batch* b, int32_t k, double* tau);
+int pf_maaco_batch_set_pheromone(pf_maaco_batch* b, int32_t k, const double* tau);
+
 /* ---- GA host operators (native, no device work) ------------------------ */
 /* GASolver._selection, ga_solver.py:136-142: one generation of tournaments on the stream (seed, DOM_GA_SELECT, gen, 0):
  * random.sample(population, min(tournament_size, n)) then the first minimum of fitness.  parent_idx[n] = indices into

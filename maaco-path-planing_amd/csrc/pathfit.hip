@@ -550,7 +550,28 @@ __global__ void k_pack_tep(int RC, const double* tau, const double* eta, double*
   const int i = blockIdx.x * blockDim.x + threadIdx.x;
   if (i < RC) { tep[(size_t)i * 3] = eta[(size_t)i * 2]; tep[(size_t)i * 3 + 1] = tau[i]; tep[(size_t)i * 3 + 2] = eta[(size_t)i * 2 + 1]; }
 }
-typedef double pf_d2u __attribute__((ext_vector_type(2), aligned(8)));
+// K colonies walked, scored and updated together (pf_maaco_batch_*): one grid, one hyper-parameter set; per colony its own seed,
+// start / target, pheromone (tau, tau^alpha and tep at c RC / c 3 RC), deposit bit matrix, flags and deposits.  Ant a of a batched
+// walk is local ant a % nper of colony a / nper and draws the stream (seed[c], DOM_MAACO, iter, a % nper), as colony c's solo walk.
+struct MaacoColonies {
+  int nper;
+  const unsigned long long* seed; const int* start; const int* target;   // [K]
+  const int* eta_of;        // [K] the colony's eta table, at eta_of[c] 2 RC (colonies with the same start / target share one)
+  size_t bits_stride, flag_stride; int dep_stride;                 // per colony: bit-matrix words, flag bytes, deposits
+};
+// the K colonies' tep tables (grid: RC / 256 x K)
+__global__ void k_pack_tep_batch(int RC, const double* tau, const double* eta, const int* eta_of, double* tep) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  const size_t c = blockIdx.y;
+  tau += c * RC; eta += (size_t)eta_of[c] * 2 * RC; tep += c * 3 * RC;
+  if (i < RC) { tep[(size_t)i * 3] = eta[(size_t)i * 2]; tep[(size_t)i * 3 + 1] = tau[i]; tep[(size_t)i * 3 + 2] = eta[(size_t)i * 2 + 1]; }
+}
+// MAACO.py:147-150, the start -> target orientation of a colony: move k is kept iff its row step does not oppose sign(vr) and its
+// column step does not oppose sign(vc) -- the walks' RowMask[sign vr] & ColMask[sign vc] (see k_maaco_walk8), without a ballot
+PF_DEV unsigned colony_o1(int sr, int sc, int tr, int tc) {
+  return __builtin_amdgcn_ubfe(0xF8FF1Fu, (unsigned)min(max(tr + 1 - sr, 0), 2) << 3, 8u) &
+         __builtin_amdgcn_ubfe(0xD6FF6Bu, (unsigned)min(max(tc + 1 - sc, 0), 2) << 3, 8u);
+}typedef double pf_d2u __attribute__((ext_vector_type(2), aligned(8)));
 
 // The tabu set of one resident ant (MAACO.py:281 `visited`), packed: one 32-bit word covers 16 cells of a grid row, its
 // upper half is the epoch (the ant's number in this slot) the 16 bits belong to, so a new ant needs no clearing and a word
@@ -603,482 +624,29 @@ PF_DEV double glast8(double v) {
   const double lo = dpp_d<0x157, 0xF>(v), hi = dpp_d<0x15F, 0xF>(v);   // row_newbcast:7 / :15
   return (lane_id() & 8) ? hi : lo;
 }
-__global__ __launch_bounds__(64) void k_maaco_walk(MaacoArgs p) {
-  const int lane = lane_id();
-  const Grid& G = p.G;
-  const int R = G.R, C = G.C, RC = R * C;
-  unsigned* visit = p.visit + (size_t)blockIdx.x * p.vstride;
-  unsigned epoch = p.slot_epoch[blockIdx.x];
-  const int WPR = p.wpr;
-  TabuLast tl;
-  const int k = lane & 7;
-  const int mdr = AM_DR[k], mdc = AM_DC[k];
-  const unsigned hbit = 1u << AM_TO_HM[k];
-  const int sr = row_of(G, p.start), sc = p.start - sr * C;
-  const int tr = row_of(G, p.target), tc = p.target - tr * C;
-  // MAACO.py:147-150 start->target orientation: static per move
-  const int vrS = tr - sr, vcS = tc - sc;
-  const bool o1 = !((vcS > 0 && mdc < 0) || (vcS < 0 && mdc > 0) || (vrS > 0 && mdr < 0) || (vrS < 0 && mdr > 0));
-  const unsigned O1 = (unsigned)(__ballot(o1 && lane < 8) & 0xFF);
-  const double mcost = (mdr != 0 && mdc != 0) ? PF_SQRT2 : 1.0;
-  const uint64_t q0_bits = p.q0 >= 1.0 ? ~0ull : (p.q0 < 0.0 ? 0ull : (uint64_t)(p.q0 * 9007199254740992.0));   // q <= q0 as an integer test (k_maaco_walk8)
-  unsigned long long steps_tot = 0, cand_tot = 0, cells_tot = 0, ovf_tot = 0;
-  for (;;) {
-    const int a = next_work(p.work, lane);
-    if (a >= p.n) break;
-    epoch += 1;
-    if (epoch >= PF_TABU_WRAP) {
-      for (int i = lane; i < p.vstride; i += 64) visit[i] = 0;
-      __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
-      epoch = 1;
-    }
-    Rng g; g.init(p.seed, DOM_MAACO, (unsigned long long)p.iter, (unsigned long long)(p.ant0 + a));
-    int* out = p.cells + (size_t)a * p.path_cap;
-    int cr = sr, cc = sc, n = 1, prev_k = -1, nturn = 0, rc = 0;
-    double plen = 0.0;
-    tl.reset();
-    {
-      const int wi = sr * WPR + (sc >> 4); const unsigned wv = tabu_set(0u, epoch, sc);
-      if (lane == 0) { out[0] = p.start; visit[wi] = wv; }
-      tl.stored(wi, wv);
-    }
-    const int max_steps = RC * 2;                                  // MAACO.py:283 (<= 2^25)
-    int steps = 0;
-    while (!(cr == tr && cc == tc) && steps < max_steps) {
-      const int cur = cr * C + cc;
-      const int nr = cr + mdr, nc = cc + mdc;
-      const bool inb = lane < 8 && nr >= 0 && nr < R && nc >= 0 && nc < C;
-      const int nidx = nr * C + nc;
-      const int turn = (prev_k >= 0 && k != prev_k) ? 1 : 0;     // MAACO.py:184-195
-      unsigned vw = 0, mmask = 0; double tv = 0.0, ev = 0.0;
-      const int widx = nr * WPR + (nc >> 4);
-      if (inb) { vw = tl.patch(widx, visit[widx]); tv = p.tau[nidx]; ev = p.eta[(size_t)nidx * 2 + turn]; }
-      else if (lane == 9) mmask = G.mm[cur];
-      const unsigned M = (unsigned)bcast_i((int)mmask, 9);
-      // valid, not tabu, no corner cut (:93-95,:100-120); the low byte of the mask = lanes 0..7
-      const unsigned mall = (unsigned)(B((unsigned)nr < (unsigned)R) & B((unsigned)nc < (unsigned)C) & B((M & hbit) != 0u) &
-                                       ~(B((vw >> 16) == epoch) & B(((vw >> (nc & 15)) & 1u) != 0u))) & 0xFFu;
-      // strategy 2 orientation: current -> target (:152-157)
-      // (RowMask[sign vr] & ColMask[sign vc] from two constants: see k_maaco_walk8)
-      const unsigned ur = (unsigned)min(max(tr + 1 - cr, 0), 2), uc = (unsigned)min(max(tc + 1 - cc, 0), 2);
-      const unsigned O2 = __builtin_amdgcn_ubfe(0xF8FF1Fu, ur << 3, 8u) & __builtin_amdgcn_ubfe(0xD6FF6Bu, uc << 3, 8u);
-      unsigned cand = mall & O1;                                  // :165
-      if (!cand) cand = mall & O2;                                // :168-169
-      if (!cand) cand = mall;                                     // :172-180
-      if (!cand) { rc = 1; break; }                               // :287-288
-      const int ncand = __builtin_popcount(cand);
-      cand_tot += ncand;
-      const bool cmine = lane < 8 && ((cand >> k) & 1u);
-      // ONE mix serves the step (see k_maaco_walk8): lane j mixes word j + 1 of the ant's stream -- q, the first word of the choice
-      // and six more for random.choice's rejection loop, which used to cost a full mix64 per extra draw.
-      const uint64_t Wk = g.peek64(1 + (uint64_t)k);
-      const bool greedy = (__builtin_amdgcn_ballot_w64((Wk >> 11) <= q0_bits) & 1ull) != 0;   // :232 q = word 1 (lane 0); q <= q0 as integers
-      const double attr = cmine ? tv * ev : 0.0;                  // :238 tau^alpha * eta'^beta; the other lanes add exact zeros
-      const double Mx = gmax8(cmine ? attr : -1.0);               // (lanes 0..7 are one 8-lane group)
-      int pick = 0;
-      unsigned msel = cand;                                       // the set random.choice draws from
-      bool chosen = false;
-      if (greedy) {                                               // :241-250 running max with absolute tolerance, closed form (k_maaco_walk8)
-        const unsigned eq = (unsigned)(B(attr == Mx)) & cand;      // (cand = the lanes 0..7 that hold a candidate)
-        if (!eq) { rc = 1; break; }
-        msel = (unsigned)(B(k >= __builtin_ctz(eq)) & B(fabs(attr - Mx) < 1e-9)) & cand;
-      } else if (!(bcast_d(Mx, 0) * 8.0 < 5e-10)) {               // (else the ordered sum is below 1e-9 whatever its rounding: k_maaco_walk8)
-        const double sum = bcast_d(gscan8(attr, k), 7);           // :252 sum() in candidate order (ordered 8-lane scan)
-        if (!(sum < 1e-9)) {                                      // else :253-254: random.choice over all candidates
-          const double p0 = attr / sum;                           // :255
-          double pj = p0;
-          if (!(sum < 1.0e300)) {                                 // :256-258 cannot renormalise for a finite sum (see k_maaco_walk8)
-            const double ps = bcast_d(gscan8(p0, k), 7);
-            if (fabs(ps - 1.0) > 1e-6) pj = p0 / ps;
-          }
-          const double u = Rng::to_unit(((uint64_t)(unsigned)bcast_i((int)(Wk >> 32), 1) << 32) | (unsigned)bcast_i((int)Wk, 1));   // :259 np.random.choice -> one random_sample: word 2
-          const double mine = gscan8(pj, k);                      // cdf = cumsum(p); cdf /= cdf[-1]
-          const double last = bcast_d(mine, 7);
-          const unsigned tm = (unsigned)__ballot(cmine && mine / last <= u) & 0xFFu;   // searchsorted(cdf, u, side='right')
-          int idx = tm ? __builtin_popcount(cand & ((2u << (31 - __builtin_clz(tm))) - 1u)) : 0;
-          if (idx > ncand - 1) idx = ncand - 1;
-          pick = nth_set_bit(cand, idx);
-          chosen = true;
-          g.advance(2);
-        }
-      }
-      if (!chosen) {
-        // random.choice(set) = set[_randbelow(n)]: the first of words 2..8 whose top bit_length(n) bits are below n (a ballot)
-        const unsigned nsel = (unsigned)__builtin_popcount(msel);
-        const int kb = 32 - __builtin_clz(nsel);
-        const unsigned rk = (unsigned)(Wk >> (64 - kb));
-        const unsigned acc = (unsigned)B(rk < nsel) & 0xFEu;
-        unsigned r;
-        if (acc) { const int first = __builtin_ctz(acc); r = (unsigned)bcast_i((int)rk, first); g.advance(1u + (unsigned)first); }
-        else { g.advance(8); do { r = (unsigned)(g.next64() >> (64 - kb)); } while (r >= nsel); }
-        pick = nth_set_bit(msel, (int)r);
-      }
-      plen += bcast_d(mcost, pick);                               // :293
-      if (prev_k >= 0 && pick != prev_k) nturn += 1;              // :264-276 counted on the fly
-      prev_k = pick;
-      cr += bcast_i(mdr, pick); cc += bcast_i(mdc, pick);
-      if (n >= p.path_cap) { rc = 3; break; }
-      {
-        const int wi = cr * WPR + (cc >> 4);                        // = lane `pick`'s word, which it holds up to date
-        const unsigned wv = tabu_set((unsigned)bcast_i((int)vw, pick), epoch, cc);
-        if (lane == 0) { out[n] = cr * C + cc; visit[wi] = wv; }
-        tl.stored(wi, wv);
-      }
-      n += 1; steps += 1;
-    }
-    if (rc == 0 && !(cr == tr && cc == tc)) rc = 2;               // :301-302 step cap
-    steps_tot += (unsigned long long)steps;
-    if (lane == 0) {
-      p.len[a] = rc == 0 ? n : 0;
-      p.plen[a] = rc == 0 ? plen : PF_INF;
-      p.turns[a] = rc == 0 ? nturn : -1;
-      p.status[a] = rc;
-    }
-    if (p.bits) {
-      const bool good = rc == 0 && n > 0 && plen > 1e-6;           // MAACO.py:307
-      if (lane == 0) p.dep[a] = good ? p.Q / plen : 0.0;            // :308
-      if (good) {
-        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup"); __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");   // lane 0 wrote the path
-        const unsigned long long bit = 1ull << (a & 63);
-        uint8_t* fl = p.flag + (a >> 6);
-        for (int i = lane; i < n; i += 64) { const int c = out[i]; atomicOr(&p.bits[bits_idx(c, a >> 6, p.fstride)], bit); fl[(size_t)(c >> 6) * p.fstride] = 1; }
-      }
-    }
-    cells_tot += rc == 0 ? n : 0; ovf_tot += rc == 3;
-  }
-  if (lane == 0) {
-    p.slot_epoch[blockIdx.x] = epoch;
-    atomicAdd(&p.cnt->steps, steps_tot); atomicAdd(&p.cnt->candidates, cand_tot); atomicAdd(&p.cnt->path_cells, cells_tot);
-    if (ovf_tot) atomicAdd(&p.cnt->overflow, ovf_tot);
-  }
-}
-
-// ---------------------------------------------------------------------------
-// K4, packed form: EIGHT ants per wavefront.  A walk step only ever uses 8 lanes (the 8 moves), so each group
-// of 8 lanes walks its own ant; "per-ant uniform" values are replicated in the group's lanes, broadcasts are
-// ds_bpermute inside the group, candidate masks are 8-bit slices of the wave ballot.  A group that finishes
-// its ant emits the result and immediately fetches the next ant from the queue inside the same loop, so no
-// lanes idle until the queue is empty.  Same draws, same arithmetic, same order as k_maaco_walk.
-// ---------------------------------------------------------------------------
-PF_DEV unsigned gballot8(bool p) { return (unsigned)(__builtin_amdgcn_ballot_w64(p) >> (lane_id() & 56)) & 0xFFu; }
-// (g8: my group's byte of a wave mask; compound predicates as B(a) & B(b): pf_device.h)
-PF_DEV unsigned g8(pf_u64 m) { return (unsigned)(m >> (lane_id() & 56)) & 0xFFu; }
-PF_DEV int gbcast8_i(int v, int k) { return __builtin_amdgcn_ds_bpermute(((lane_id() & 56) + k) << 2, v); }
-// index of the idx-th set bit of an 8-bit mask (lane k tests bit k)
-PF_DEV int gnth8(unsigned m, int idx, int k) {
-  return __builtin_ctz(g8(B(((m >> k) & 1u) != 0u) & B(__builtin_popcount(m & ((1u << k) - 1u)) == idx)) | 0x100u);
-}
-PF_DEV double gbcast8_d(double v, int k) {
-  const int lo = gbcast8_i(__double2loint(v), k), hi = gbcast8_i(__double2hiint(v), k);
-  return __hiloint2double(hi, lo);
-}
-
-// eight ants per wavefront: the 8 lanes of a group hold the 8 moves of one ant
-// AHEAD, the form for batches that leave a SIMD ONE wavefront (8 192 ants: a step then waits ~2 000 clocks for memory, and nothing
-// else runs meanwhile): all of a step's loads are issued before anything waits for one of them (the compiler otherwise sinks the
-// pheromone load behind the candidate test: a second round trip), and every move lane also asks for the pheromone record and
-// the tabu word two steps ahead in its direction -- where the NEXT step's neighbours live -- right behind the step's own loads
-// (memory returns in order: they cannot delay them; results unused).  A/B on one box (M evals/s): 8 192 ants @1024^2 2.87 -> 3.04;
-// 16 384 ants @512^2 (two wavefronts per SIMD, issue-bound) 8.75 -> 8.50 -- so the host picks the form by occupancy.
-template <bool AHEAD>
-__global__ __launch_bounds__(64) void k_maaco_walk8(MaacoArgs p) {
-  const Grid& G = p.G;
-  const int R = G.R, C = G.C, RC = R * C;
-  const int lane = lane_id();
-  const int k = lane & 7, grp = lane >> 3;
-  const int slot = blockIdx.x * 8 + grp;
-  unsigned* visit = p.visit + (size_t)slot * p.vstride;
-  unsigned epoch = p.slot_epoch[slot];
-  const int WPR = p.wpr;
-  TabuLast tl; tl.reset();
-  const int mdr = AM_DR[k], mdc = AM_DC[k];
-  const unsigned hbit = 1u << AM_TO_HM[k];
-  const int sr = row_of(G, p.start), sc = p.start - sr * C;
-  const int tr = row_of(G, p.target), tc = p.target - tr * C;
-  const int vrS = tr - sr, vcS = tc - sc;
-  const bool o1 = !((vcS > 0 && mdc < 0) || (vcS < 0 && mdc > 0) || (vrS > 0 && mdr < 0) || (vrS < 0 && mdr > 0));
-  const unsigned O1 = gballot8(o1);
-  const int max_steps = RC * 2;                                    // MAACO.py:283
-  // q0 is in [0.01, 0.99] (MAACO.py:226): q0 2^53 is exact, its floor the largest 53-bit draw that still takes the greedy rule
-  // (as `draw < q0_lim`: a `<=` against a run-time bound compiles to two compares, one for the bound's all-ones case)
-  const uint64_t q0_lim = p.q0 >= 1.0 ? (1ull << 53) : (p.q0 < 0.0 ? 0ull : (uint64_t)(p.q0 * 9007199254740992.0) + 1ull);
-  unsigned long long steps_tot = 0, cand_tot = 0, cells_tot = 0, ovf_tot = 0;
-  // per-ant state (replicated in the 8 lanes of the group)
-  int a = -1, cr = 0, cc = 0, n = 0, prev_k = -1, nturn = 0, rc = 0;
-  int steps = 0;                                                   // (<= 2 R C <= 2^25)
-  double plen = 0.0;
-  Rng g; g.key = 0; g.ctr = 0; g.kc = 0;
-  int* out = p.cells;
-  bool alive = grp < p.groups;
-#ifdef PF_WALK_PROBE
-  unsigned long long pr_wait = 0, pr_rounds = 0, pr_mark = 0, pr_sel0 = 0, pr_sel1 = 0, pr_head = 0, pr_emit = 0, pr_upd = 0, pr_loop = 0, pr_end = 0, pr_act = 0; const unsigned long long pr_t0 = __builtin_amdgcn_s_memtime();
-#endif
-  // fetch + initialise the next ant of this group (alive = false when the queue is empty)
-  auto fetch = [&]() {
-    int w = 0;
-    if (k == 0) w = atomicAdd(p.work, 1);
-    w = gbcast8_i(w, 0);
-    if (w >= p.n) alive = false;
-    else {
-      a = w;
-      epoch += 1;
-      if (epoch >= PF_TABU_WRAP) {
-        for (int i = k; i < p.vstride; i += 8) visit[i] = 0;
-        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
-        epoch = 1;
-      }
-      g.init(p.seed, DOM_MAACO, (unsigned long long)p.iter, (unsigned long long)(p.ant0 + a));
-      out = p.cells + (size_t)a * p.path_cap;
-      cr = sr; cc = sc; n = 1; prev_k = -1; nturn = 0; rc = 0; plen = 0.0; steps = 0;
-      tl.reset();
-      const int wi = sr * WPR + (sc >> 4); const unsigned wv = tabu_set(0u, epoch, sc);
-      if (k == 0) { out[0] = p.start; visit[wi] = wv; }
-      tl.stored(wi, wv);
-    }
-  };
-  if (alive) fetch();
-  // One wave-uniform test per round: "did an ant finish?" (one round in a hundred).  Emitting, deposit marking, fetching the group's
-  // next ant and the end-of-queue test all sit behind it; a round that only steps pays for nothing else.  (A wave none of whose
-  // groups got an ant -- the queue was drained by the others' first fetches -- never enters the loop: every exit is behind any_fin.)
-  unsigned pft0 = 0, pft1 = 0;
-  if (__ballot(alive)) for (;;) {
-    bool done = alive & (((cr == tr) & (cc == tc)) | (steps >= max_steps));
-    const unsigned pft0_prev = pft0, pft1_prev = pft1;
-#ifdef PF_WALK_PROBE
-    __builtin_amdgcn_sched_barrier(0); const unsigned long long pr_r0 = __builtin_amdgcn_s_memtime(); __builtin_amdgcn_sched_barrier(0);
-    bool pr_stepped = false; unsigned long long pr_u0 = 0;
-    if (pr_end) pr_loop += pr_r0 - pr_end;
-#endif
-    if (alive && !done) {
-      // (rows, columns and cells fit 24 bits -- R, C <= 4096 --: v_mad_u32_u24 at full rate and 32-bit byte offsets on a scalar
-      // base, where `int` indices cost a quarter-rate 64-bit multiply-add, a sign extension and a 64-bit add per load)
-      const unsigned cur = __umul24((unsigned)cr, (unsigned)C) + (unsigned)cc;
-      const int nr = cr + mdr, nc = cc + mdc;
-      const bool inb = ((unsigned)nr < (unsigned)R) & ((unsigned)nc < (unsigned)C);
-      const unsigned nidx = __umul24((unsigned)nr, (unsigned)C) + (unsigned)nc;
-      const int turn = ((prev_k >= 0) & (k != prev_k)) ? 1 : 0;    // MAACO.py:184-195
-      unsigned vw = 0; double tv = 0.0, ev = 0.0;
-      const unsigned M = *((const uint8_t*)G.mm + (size_t)cur);
-      const unsigned widx = __umul24((unsigned)nr, (unsigned)WPR) + ((unsigned)nc >> 4);
-      // Every step that finds a candidate draws q (:232) and then at least one more 64-bit word (random.choice's first
-      // getrandbits at :250 / :254, or numpy's random_sample at :259): both words are mixed here, before the loads below
-      // are waited for, and the counter advances only when the step gets that far.
-      // ONE mix serves the whole step: lane j of the ant's group mixes word j + 1 of the stream (the same instructions in every
-      // lane), i.e. the eight next words at once -- q, the first word of the choice, and six more for random.choice's rejection
-      // loop (_randbelow redraws while the k-bit value is >= n: every second draw for n = 1, every fourth for n = 3), which used to
-      // cost the wave a full mix64 (~25 instructions, eight quarter-rate multiplies) per extra draw of its unluckiest ant.
-      uint64_t Wk = 0;
-      if (!AHEAD) Wk = g.peek64(1 + (uint64_t)k);
-#ifdef PF_WALK_PROBE
-      __builtin_amdgcn_sched_barrier(0); const unsigned long long pr_ta = __builtin_amdgcn_s_memtime(); __builtin_amdgcn_sched_barrier(0);
-      pr_head += pr_ta - pr_r0; pr_stepped = true; pr_act += 1;   // (per-lane copies: lane 0 reports, so the in-step stamps cover the rounds in which group 0 stepped)
-#endif
-      {
-        // unconditional loads (a move that leaves the map reads cell 0 and is rejected by `inb` below): a branch around them costs
-        // a scalar round trip on the mask, and loads under a branch keep the compiler from counting them
-        const unsigned widx_c = inb ? widx : 0u, nidx_c = inb ? nidx : 0u;
-        const unsigned vw_raw = visit[widx_c];
-        // one divergent vector load less per step: tau and eta'[turn] in one
-        const unsigned toff = __umul24(nidx_c, 24u) + ((unsigned)turn << 3);
-        const pf_d2u te = *(const pf_d2u*)((const char*)p.tep + (size_t)toff);
-        if (AHEAD) {
-          const int r2 = nr + mdr, c2 = nc + mdc;
-          const bool in2 = ((unsigned)r2 < (unsigned)R) & ((unsigned)c2 < (unsigned)C);
-          const unsigned t2 = in2 ? __umul24((unsigned)r2, (unsigned)C) + (unsigned)c2 : nidx_c;
-          const unsigned w2 = in2 ? __umul24((unsigned)r2, (unsigned)WPR) + ((unsigned)c2 >> 4) : widx_c;
-          pft0 = *(const unsigned*)((const char*)p.tep + (size_t)__umul24(t2, 24u));
-          pft1 = visit[w2];
-          __builtin_amdgcn_sched_barrier(0);                        // (all of the step's loads are issued before anything waits for one of them)
-        }
-        vw = tl.patch((int)widx_c, vw_raw);
-        tv = turn ? te.x : te.y; ev = turn ? te.y : te.x;
-        if (AHEAD) asm volatile("" :: "v"(pft0_prev), "v"(pft1_prev));   // (the previous step's touches: older than the loads just waited for)
-      }
-      if (AHEAD) Wk = g.peek64(1 + (uint64_t)k);                    // (in the shadow of the loads just issued)
-#ifdef PF_WALK_PROBE
-      { __builtin_amdgcn_sched_barrier(0);
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); __builtin_amdgcn_sched_barrier(0);
-        pr_wait += __builtin_amdgcn_s_memtime() - pr_ta; }
-#endif
-      // (bitwise on purpose: the short-circuit forms compiled to branches, each a scalar round trip on a freshly written lane mask)
-      const unsigned mall = g8(B((unsigned)nr < (unsigned)R) & B((unsigned)nc < (unsigned)C) & B((M & hbit) != 0u) &
-                               ~(B((vw >> 16) == epoch) & B(((vw >> (nc & 15)) & 1u) != 0u)));
-      // strategy 2 orientation, current -> target (:152-157): a move is kept iff its row step does not oppose sign(vr) and its column
-      // step does not oppose sign(vc) -- the eight-move mask is RowMask[sign vr] & ColMask[sign vc], two bit-field extracts from
-      // constants (moves 0..7 = AM_DR / AM_DC order) instead of eight compares, their scalar mask logic and a ballot
-      const unsigned ur = (unsigned)min(max(tr + 1 - cr, 0), 2), uc = (unsigned)min(max(tc + 1 - cc, 0), 2);
-      const unsigned O2 = __builtin_amdgcn_ubfe(0xF8FF1Fu, ur << 3, 8u) & __builtin_amdgcn_ubfe(0xD6FF6Bu, uc << 3, 8u);
-      unsigned cand = mall & O1;                                    // :165
-      if (!cand) cand = mall & O2;                                  // :168-169
-      if (!cand) cand = mall;                                       // :172-180
-      // (AHEAD: the dead end "uses" the pheromone record too, so that its load stays in front of the candidate test)
-      if (!cand) { rc = 1; done = true; if (AHEAD) asm volatile("" :: "v"(tv), "v"(ev)); }   // :287-288
-      else {
-        const int ncand = __builtin_popcount(cand);
-        cand_tot += ncand;
-        const bool cmine = (cand >> k) & 1u;
-        // :232 q = word 1 of the step (lane 0 of the group holds it): one ballot tells the group which rule applies
-        // (q = (w >> 11) 2^-53 exactly, so q <= q0 iff w >> 11 <= floor(q0 2^53): two integer instructions instead of the conversion)
-        const bool greedy = (g8(B((Wk >> 11) < q0_lim)) & 1u) != 0;
-        const double attr = cmine ? tv * ev : 0.0;                  // :238; the other lanes add an exact zero to the ordered sums below
-        int pick = 0;
-#ifdef PF_WALK_PROBE
-        __builtin_amdgcn_sched_barrier(0); const unsigned long long pr_s0 = __builtin_amdgcn_s_memtime(); __builtin_amdgcn_sched_barrier(0);
-        pr_sel0 += pr_s0 - pr_ta;
-#endif
-        // Both rules end in random.choice over a set of candidates: the greedy rule (:241-250) over its tie set, the other one
-        // (:252-254) over all candidates whenever the attractiveness sum is below 1e-9 -- on the 512^2 and 1024^2 maps with beta = 7
-        // that is EVERY non-greedy step (eta'^7 ~ 1e-19: SURVEY H8 measured 0 % roulette picks).  So the two rules only differ in
-        // the set, and ONE choice serves every ant of the wave; the roulette proper runs behind a wave-uniform test.
-        // The largest attractiveness among the candidates is the greedy rule's maximum AND a bound on the other rule's sum: the
-        // ordered sum of at most 8 non-negative terms, none above Mx, is at most 8 Mx (1 + 2^-53)^7 -- with 8 Mx < 5e-10 it is
-        // below 1e-9 whatever its rounding, and the 7-step ordered scan need not run.
-        const double Mx = gmax8(cmine ? attr : -1.0);
-        // :241-250, the running maximum with its absolute tolerance, in closed form: the tie set restarts at the FIRST occurrence of
-        // the maximum (`attr > max` drops every earlier member there) and from then on collects the candidates within 1e-9 of it
-        // (none can exceed it).  NaN neither restarts nor joins, as in the loop.
-        const pf_u64 cmm = B(((cand >> k) & 1u) != 0u);
-        const unsigned eq = g8(cmm & B(attr == Mx));
-        const unsigned bm = g8(cmm & B(k >= __builtin_ctz(eq | 0x100u)) & B(fabs(attr - Mx) < 1e-9));
-        const bool tiny = Mx * 8.0 < 5e-10;                         // (a NaN maximum compares false: the sum decides)
-        if (greedy && !eq) { rc = 1; done = true; }
-        bool chosen = false;                                        // the roulette proper picked (two words of the stream: q and u)
-        if (B(true) & ~B(greedy) & ~B(tiny)) {
-          // The sums of :252-259 run over the candidates in candidate order.  Candidate j lives in lane j, so each is one
-          // ordered 8-lane scan (7 dependent DPP steps, no LDS round trip per candidate); every quotient belongs to one
-          // candidate and is computed in its lane.  (The scans run for the whole wave; only the ants that need them use the result.)
-          const double sum = glast8(gscan8(attr, k));               // :252
-          if (!greedy && !tiny && !(sum < 1e-9)) {                  // else :253-254: random.choice over all candidates, below
-            const double p0 = attr / sum;                           // :255 probabilities[j]
-            // :256-258 renormalise when |sum(probabilities) - 1| > 1e-6.  For a finite sum of at most 8 non-negative terms
-            // that never happens: sum = S(1 + e), |e| <= 7u (u = 2^-53), every quotient is a_j / sum (1 + d_j), |d_j| <= u
-            // (an underflowing quotient errs by < 2^-1074), and adding them in order costs another 7u, so
-            // |sum(probabilities) - 1| < 16u ~ 2e-15.  Only an overflowed sum takes the general route.
-            double pj = p0;
-            if (!(sum < 1.0e300)) {
-              const double ps = glast8(gscan8(p0, k));              // :256 sum(probabilities)
-              if (fabs(ps - 1.0) > 1e-6) pj = p0 / ps;              // :257-258
-            }
-            const double u = gbcast8_d(Rng::to_unit(Wk), 1);        // :259 numpy.random.choice: cdf = cumsum(p); cdf /= cdf[-1]; word 2 of the step
-            const double mine = gscan8(pj, k);                      // cdf[position of my move]
-            const double last = glast8(mine);
-            const unsigned tm = gballot8(cmine && mine / last <= u);   // searchsorted(cdf, u, side="right")
-            int idx = tm ? __builtin_popcount(cand & ((2u << (31 - __builtin_clz(tm))) - 1u)) : 0;
-            if (idx > ncand - 1) idx = ncand - 1;
-            pick = gnth8(cand, idx, k);
-            chosen = true;
-            g.advance(2);
-          }
-        }
-        {
-          // random.choice(set) = set[_randbelow(n)]: kb = n.bit_length() bits of a word, redrawn while >= n (:250 / :254).  Word j + 1
-          // of the step sits in lane j: every lane tests ITS word, the first acceptable one (a ballot) is the draw.
-          const unsigned msel = greedy ? bm : cand;
-          const unsigned nsel = (unsigned)__builtin_popcount(msel) | (msel ? 0u : 1u);   // (>= 1: a failed ant's value is never used)
-          const int kb = 32 - __builtin_clz(nsel);
-          unsigned rk = (unsigned)(Wk >> (64 - kb));
-          const unsigned acc = g8(B(rk < nsel)) & 0xFEu;             // (word 1 is q: lanes k >= 1)
-          unsigned r = (unsigned)gbcast8_i((int)rk, __builtin_ctz(acc | 0x80u));
-          if (!chosen) g.advance(acc ? 1u + (unsigned)__builtin_ctz(acc) : 8u);
-          if (B(acc == 0u)) {                                        // all seven rejected (n = 1: once in 128 steps): draw on, one word at a time
-            if (!chosen && !done && acc == 0u) { do { r = (unsigned)(g.next64() >> (64 - kb)); } while (r >= nsel); }
-          }
-          if (!chosen) pick = gnth8(msel, (int)r, k);
-        }
-#ifdef PF_WALK_PROBE
-        int t_ = pick; asm volatile("" : "+v"(t_)); __builtin_amdgcn_sched_barrier(0); const unsigned long long pr_s1 = __builtin_amdgcn_s_memtime(); __builtin_amdgcn_sched_barrier(0);
-        pr_sel1 += pr_s1 - pr_s0; pr_u0 = pr_s1;
-#endif
-        if (!done) {
-          plen += ((0xA5u >> pick) & 1u) ? PF_SQRT2 : 1.0;         // :293 (moves 0, 2, 5, 7 are the diagonals)
-          if (prev_k >= 0 && pick != prev_k) nturn += 1;
-          prev_k = pick;
-          cr += (int)((0xA940u >> (2 * pick)) & 3u) - 1;            // AM_DR[pick] + 1, two bits a move
-          cc += (int)((0x9224u >> (2 * pick)) & 3u) - 1;            // AM_DC[pick] + 1
-          {
-            // a full path row (rc 3) is the exception: predicated, not a branch of its own
-            const bool ovf = n >= p.path_cap;
-            rc = ovf ? 3 : rc; done = ovf;
-            const int wi = cr * WPR + (cc >> 4);                   // = lane `pick`'s word, which it holds up to date
-            const unsigned wv = tabu_set((unsigned)gbcast8_i((int)vw, pick), epoch, cc);
-            if (k == 0 && !ovf) { out[n] = cr * C + cc; visit[wi] = wv; }
-            if (!ovf) tl.stored(wi, wv);
-            n += ovf ? 0 : 1; steps += ovf ? 0 : 1;
-          }
-        }
-      }
-    }
-#ifdef PF_WALK_PROBE
-    __builtin_amdgcn_sched_barrier(0); const unsigned long long pr_e0 = __builtin_amdgcn_s_memtime(); __builtin_amdgcn_sched_barrier(0);
-    if (pr_u0) pr_upd += pr_e0 - pr_u0;
-#endif
-    // an ant finishes in about one round of a hundred: everything that only a finished ant needs sits behind ONE wave-uniform test
-    const bool any_fin = __ballot(alive && done) != 0ull;
-    if (any_fin && alive && done) {                                 // emit, then fetch a new ant next round
-      if (rc == 0 && !(cr == tr && cc == tc)) rc = 2;               // :301-302 step cap
-      steps_tot += (unsigned long long)steps;
-      if (k == 0) {
-        p.len[a] = rc == 0 ? n : 0;
-        p.plen[a] = rc == 0 ? plen : PF_INF;
-        p.turns[a] = rc == 0 ? nturn : -1;
-        p.status[a] = rc;
-      }
-      cells_tot += rc == 0 ? n : 0; ovf_tot += rc == 3;
-    }
-#ifdef PF_WALK_PROBE
-    pr_rounds += 1; const unsigned long long pr_m0 = __builtin_amdgcn_s_memtime(); pr_emit += pr_m0 - pr_e0;
-#endif
-    if (any_fin && p.bits) {
-      // the ants that finished in this round mark their deposits: the WHOLE wave walks each finished path (64 cells a round;
-      // the other groups would only wait for a group that marked alone, 8 cells a round)
-      const bool fin = alive && done;
-      const bool good = fin && rc == 0 && n > 0 && plen > 1e-6;    // MAACO.py:307
-      if (fin && k == 0) p.dep[a] = good ? p.Q / plen : 0.0;        // :308
-      unsigned long long gm = __ballot(good && k == 0);
-      if (gm) {
-        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup"); __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");   // lane k == 0 wrote the path
-        for (; gm; gm &= gm - 1) {
-          const int l = __builtin_ctzll(gm);
-          const int aa = bcast_i(a, l), nn = bcast_i(n, l);
-          const int* oo = p.cells + (size_t)aa * p.path_cap;
-          const unsigned long long bit = 1ull << (aa & 63);
-          uint8_t* fl = p.flag + (aa >> 6);
-          for (int i = lane; i < nn; i += 256) {                    // four cell loads in flight, then their (unwaited) atomics
-            int c4[4];
-#pragma unroll
-            for (int u = 0; u < 4; ++u) c4[u] = i + 64 * u < nn ? oo[i + 64 * u] : -1;
-#pragma unroll
-            for (int u = 0; u < 4; ++u) if (c4[u] >= 0) {
-              __hip_atomic_fetch_or(&p.bits[bits_idx(c4[u], aa >> 6, p.fstride)], bit, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-              fl[(size_t)(c4[u] >> 6) * p.fstride] = 1;
-            }
-          }
-        }
-      }
-    }
-    if (any_fin) {
-      if (alive && done) fetch();                                   // the group's next ant starts in the next round
-      if (!__ballot(alive)) break;
-    }
-#ifdef PF_WALK_PROBE
-    pr_end = __builtin_amdgcn_s_memtime(); pr_mark += pr_end - pr_m0;
-#endif
-  }
-#ifdef PF_WALK_PROBE
-  // (diagnostic build: wave clocks in the counters the MAACO path leaves unused -- scripts/probe_walk_split.py)
-  if (lane == 0) { atomicAdd(&p.cnt->pops, pr_wait); atomicAdd(&p.cnt->pushes, __builtin_amdgcn_s_memtime() - pr_t0); atomicAdd(&p.cnt->nbr, pr_rounds);
-                   atomicAdd(&p.cnt->deckey, pr_mark); atomicMax(&p.cnt->pruned, __builtin_amdgcn_s_memtime() - pr_t0);
-                   atomicAdd(&p.cnt->settled, pr_sel0); atomicAdd(&p.cnt->sequential, pr_sel1);
-                   atomicAdd(&p.cnt->candidates, pr_head); atomicAdd(&p.cnt->path_cells, pr_act); (void)pr_emit; atomicAdd(&p.cnt->steps, pr_upd); atomicAdd(&p.cnt->overflow, pr_loop); }
-#endif
-  if (k == 0) {
-    p.slot_epoch[slot] = epoch;
-#ifndef PF_WALK_PROBE
-    atomicAdd(&p.cnt->candidates, cand_tot); atomicAdd(&p.cnt->path_cells, cells_tot); atomicAdd(&p.cnt->steps, steps_tot);
-    if (ovf_tot) atomicAdd(&p.cnt->overflow, ovf_tot);
-#endif
-  }
-}
+// K4 in two forms (csrc/pf_maaco_walk.h): solo, and K colonies in one walk (pf_maaco_batch_*)
+#define PF_MAACO_BATCH 0
+#define PF_WALK1 k_maaco_walk
+#define PF_WALK8 k_maaco_walk8
+#define PF_COLONIES
+#define PF_B(b, s) s
+#include "pf_maaco_walk.h"
+#undef PF_MAACO_BATCH
+#undef PF_WALK1
+#undef PF_WALK8
+#undef PF_COLONIES
+#undef PF_B
+#define PF_MAACO_BATCH 1
+#define PF_WALK1 k_maaco_walk_batch
+#define PF_WALK8 k_maaco_walk8_batch
+#define PF_COLONIES , MaacoColonies mc
+#define PF_B(b, s) b
+#include "pf_maaco_walk.h"
+#undef PF_MAACO_BATCH
+#undef PF_WALK1
+#undef PF_WALK8
+#undef PF_COLONIES
+#undef PF_B
 
 // Best ant of an iteration, MAACO.py:343-349, without the sequential loop: `L < best` only ever fires up to the first
 // occurrence p of the minimum length, which resets (idx, turns) to ant p; afterwards only ants within 1e-9 of that
@@ -1329,91 +897,58 @@ __global__ __launch_bounds__(1024) void k_maaco_best_take(int n, const double* p
   *work = 0;
   DevCounters z; memset(&z, 0, sizeof(z)); *cnt = z;
 }
+// The same for K colonies of n ants (block c = colony c, ants [c n, (c + 1) n) of the walk): the colony's scan, take-over test
+// against its own overall best (best_lt[c] = {len, turns}), 13 doubles at state / host_state + 13 c, take-over row into its own
+// best row (best_rows + c row_stride).  The overflow test reads the batch's counters: one overflowed ant anywhere skips every
+// colony's update.  The work counter and the counters go back zeroed once every block has read them (the last block out).
+__global__ __launch_bounds__(1024) void k_maaco_best_take_batch(int n, const double* plen, const int* turns, double* scan3,
+                                                               const double* best_lt, double rho, int R, int C, int* work,
+                                                               DevCounters* cnt, unsigned* ticket, double* state, double* host_state,
+                                                               const int* cells, const int* len, int path_cap, int* best_rows,
+                                                               int row_stride) {
+  __shared__ int s_take;
+  const int c = blockIdx.x;
+  const size_t a0 = (size_t)c * n;
+  scan3 += 3 * c; state += 13 * c; host_state += 13 * c;
+  maaco_best_block(n, plen + a0, turns + a0, scan3);
+  if (threadIdx.x == 0) {
+    maaco_take(scan3, best_lt[2 * c], best_lt[2 * c + 1], rho, R, C, cnt, state);
+    s_take = (state[3] != 0.0 && state[8] == 0.0 && state[2] >= 0.0) ? (int)state[2] : -1;
+  }
+  __syncthreads();
+  const int a = s_take;
+  int* best_row = best_rows + (size_t)c * row_stride;
+  if (a >= 0) {
+    const int L = len[a0 + a];
+    for (int i = threadIdx.x; i < L; i += 1024) best_row[1 + i] = cells[(a0 + a) * path_cap + i];
+    if (threadIdx.x == 0) best_row[0] = L;
+  }
+  if (threadIdx.x != 0) return;
+  for (int k = 0; k < 13; ++k) host_state[k] = state[k];
+  __threadfence();                                                 // (this block's reads of the counters are done)
+  if (atomicAdd(ticket, 1u) == gridDim.x - 1) {
+    *work = 0; *ticket = 0;
+    DevCounters z; memset(&z, 0, sizeof(z)); *cnt = z;
+  }
+}
 // The whole of MAACO.py:304-332 in ONE pass over tau: per cell t = tau * (1 - rho) (:305), then the deposits of the ants that
 // visited it in ant order (:306-311; k_tau_deposit's ordered walk of the bit matrix), then the clip (:326-332) -- the same
 // fp64 operations in the same order as the three kernels, one read and one write of tau instead of three each.  The clip
 // bounds come from `state` (k_maaco_take) or, when state is null, from the arguments.
-__global__ __launch_bounds__(1024) void k_tau_update(double* tau, const uint8_t* occ, int RC, unsigned long long* bits, int nwords,
-                                                    const double* dep, double keep, const double* state, double tmin_a, double tmax_a,
-                                                    uint8_t* flag, int fstride) {
-  extern __shared__ __attribute__((aligned(16))) double sdep[];    // [PF_UPD_CHUNK] deposits, then [PF_UPD_CHUNK] pre-scaled (dep_word_scaled)
-  double* sdeps = sdep + PF_UPD_CHUNK;
-  if (state && state[8] != 0.0) return;                            // an ant overflowed: the iteration is redone, tau stays
-  const double tmin = state ? state[6] : tmin_a, tmax = state ? state[7] : tmax_a;
-  // a wavefront owns one 64-cell stretch (512-byte word loads); the 16 wavefronts of a block take stretches gridDim.x apart, so the
-  // few busy parts of the map -- around the start, the target and the corridors every ant uses -- land on different CUs
-  const int lane = threadIdx.x & 63;
-  const int seg = (threadIdx.x >> 6) * gridDim.x + blockIdx.x;
-  const int i = seg * 64 + lane;
-  const bool live = i < RC, seg_live = seg * 64 < RC;              // (seg_live is wave-uniform)
-  double t = live ? tau[i] * keep : 0.0;                           // :305
-#if PF_TAU_PROBE == 2
-  const unsigned long long probe_t0 = __builtin_amdgcn_s_memtime();
-  int probe_dense = 0, probe_chunks = 0;
-#endif
-  uint8_t* frow = flag + (size_t)seg * fstride;
-  for (int c0 = 0; c0 < nwords; c0 += PF_UPD_CHUNK / 64) {
-    const int cw = nwords - c0 < PF_UPD_CHUNK / 64 ? nwords - c0 : PF_UPD_CHUNK / 64;
-    __syncthreads();
-    bool big = false;                                              // a deposit of 4 or more (or a NaN) would overflow its scaling by 2^1022
-    for (int k = threadIdx.x; k < cw * 64; k += blockDim.x) {
-      const double v = dep[c0 * 64 + k];
-      sdep[k] = v; sdeps[k] = __builtin_ldexp(v, 1023 - (1 << ((k & 63) % 11))); big |= !(v < 4.0);
-    }
-    const bool scaled = __syncthreads_or(big) == 0;                 // (block-uniform; Q / L is ~4e-3 with the reference's parameters)
-    if (!seg_live) continue;
-    for (int k0 = 0; k0 < cw; k0 += 64) {
-      // which of the next 64 words have anything in this stretch: one flag byte per lane -> a wave-uniform mask, walked in word
-      // (= ant) order; only those chunks are loaded at all (measured: 23 % of them at 512^2 / 16 384 ants, 14 % at 1024^2 / 8 192)
-      const int wl = c0 + k0 + lane;
-      const bool mine = k0 + lane < cw;
-      const uint8_t f = mine ? frow[wl] : (uint8_t)0;
-      if (f) frow[wl] = 0;
-      unsigned long long m = __ballot(f != 0);
-      // PF_TAU_FLY chunks in flight, the next PF_TAU_FLY requested before these are summed.  The loads are unconditional (an empty slot
-      // re-reads chunk 0 of the stretch and is masked afterwards): loads under a branch make the compiler wait for ALL of them.
-      unsigned long long* cb = bits + (size_t)seg * fstride * 64 + lane;   // bits_idx(i, w, fstride) = cb[w * 64]
-      int idx[PF_TAU_FLY], nidx[PF_TAU_FLY];
-      unsigned long long b[PF_TAU_FLY], nb[PF_TAU_FLY];
-#pragma unroll
-      for (int u = 0; u < PF_TAU_FLY; ++u) {
-        idx[u] = m ? c0 + k0 + (int)__builtin_ctzll(m) : -1; m &= m - 1;
-        b[u] = cb[(size_t)(idx[u] < 0 ? 0 : idx[u]) * 64];
-      }
-      while (idx[0] >= 0) {
-#pragma unroll
-        for (int u = 0; u < PF_TAU_FLY; ++u) {
-          nidx[u] = m ? c0 + k0 + (int)__builtin_ctzll(m) : -1; m &= m - 1;
-          nb[u] = cb[(size_t)(nidx[u] < 0 ? 0 : nidx[u]) * 64];
-        }
-#pragma unroll
-        for (int u = 0; u < PF_TAU_FLY; ++u) {
-          if (idx[u] < 0) break;                                    // (wave-uniform)
-          const unsigned long long x = live ? b[u] : 0ull;
-          // the matrix goes back zeroed; every lane stores (a store under a branch would again cost exact wait counts, and the
-          // flagged chunks are 1/4 of the matrix)
-          cb[(size_t)idx[u] * 64] = 0ull;
-#if PF_TAU_PROBE == 2
-          probe_chunks += 1; probe_dense += __any((int)__builtin_popcountll(x) > PF_DEP_DENSE) ? 1 : 0;
-#endif
-#if PF_TAU_PROBE != 1
-          t = scaled ? dep_word_scaled(t, x, sdep + (idx[u] - c0) * 64, sdeps + (idx[u] - c0) * 64) : dep_word(t, x, sdep + (idx[u] - c0) * 64);
-#else
-          t += x == 12345ull ? 1.0 : 0.0;
-#endif
-        }
-#pragma unroll
-        for (int u = 0; u < PF_TAU_FLY; ++u) { idx[u] = nidx[u]; b[u] = nb[u]; }
-      }
-    }
-  }
-#if PF_TAU_PROBE == 2
-  // (timing probe, wrong pheromone on purpose: lane 0 leaves the wave's shader clocks, lane 1 its dirty chunks, lane 2 the dense ones)
-  if (live) tau[i] = lane == 0 ? (double)(__builtin_amdgcn_s_memtime() - probe_t0) : lane == 1 ? (double)probe_chunks : lane == 2 ? (double)probe_dense : t;   // (t stays live: the sums must not be optimised away)
-  return;
-#endif
-  if (live) tau[i] = occ[i] == 1 ? 1e-9 : fmin(fmax(t, tmin), tmax);   // :326-332 (paths never cross obstacles: their words are empty)
-}
+#define PF_MAACO_BATCH 0
+#define PF_TAU_UPDATE k_tau_update
+#define PF_COLONIES
+#include "pf_tau_update.h"
+#undef PF_MAACO_BATCH
+#undef PF_TAU_UPDATE
+#undef PF_COLONIES
+#define PF_MAACO_BATCH 1
+#define PF_TAU_UPDATE k_tau_update_batch
+#define PF_COLONIES , MaacoColonies mc
+#include "pf_tau_update.h"
+#undef PF_MAACO_BATCH
+#undef PF_TAU_UPDATE
+#undef PF_COLONIES
 
 // ===========================================================================
 // K7 + K2b + K1: MPA
@@ -2278,6 +1813,25 @@ __global__ void k_selftest_targets(Grid G, unsigned long long seed, int n, int i
 // ===========================================================================
 // host side
 // ===========================================================================
+// K MAACO colonies on one handle (pf_maaco_batch_create): every table is the batch's own, at colony c's offset; the handle's
+// tabu slot pool and stream are shared with the solo state, which the batch never touches.
+struct pf_maaco_batch {
+  pf_handle* h = nullptr;
+  bool ready = false;
+  pf_maaco_params mp = {};
+  int K = 0, n = 0;                   // colonies, ants per colony
+  std::vector<int> start, target, eta_of;
+  double *d_tau = nullptr, *d_taua = nullptr, *d_eta = nullptr, *d_tep = nullptr;   // [K][RC], [K][RC] (alpha != 1), [pairs][RC][2], [K][RC][3]
+  int *d_start = nullptr, *d_target = nullptr, *d_eta_of = nullptr; unsigned long long* d_seed = nullptr;
+  size_t words = 0, bits_stride = 0, flag_stride = 0;   // per colony: 64-ant words, matrix words (words x stretches x 64), flag bytes
+  unsigned long long* d_bits = nullptr; uint8_t* d_flag = nullptr; double* d_dep = nullptr;
+  bool bits_clean = false;            // every colony's matrix and flags are zero (the update pass hands them back so)
+  char* d_ctl = nullptr; bool ctl_clean = false;   // {work counter @0, ticket @4, DevCounters @16}: zeroed by the last best/take block
+  double *d_scan3 = nullptr, *d_state = nullptr;   // [K][3], [K][13]
+  double *h_io = nullptr, *h_io_dev = nullptr;     // pinned: [K][2] overall bests in, then [K][13] out
+  int* d_best_rows = nullptr; int row_cap = 0;     // [K][row_cap]: colony c's overall best path, [0] = length
+};
+
 struct pf_handle {
   int device = 0;
   hipStream_t stream = nullptr;
@@ -2316,6 +1870,7 @@ struct pf_handle {
   unsigned* d_visit = nullptr; unsigned* d_visit_epoch = nullptr; int maaco_slots = 0; int maaco_cus = 256;
   unsigned long long* d_bits = nullptr; size_t bits_words = 0; int dep_cap = 0;
   uint8_t* d_flag = nullptr;          // chunk flags of d_bits: [(RC + 63) / 64][bits_words] bytes (MaacoArgs::flag)
+  std::vector<pf_maaco_batch*> maaco_batches;   // pf_maaco_batch_create's objects (freed by pf_destroy, invalidated by pf_update_grid)
   // MPA
   bool mpa_ready = false;
   pf_mpa_params mpp = {};
@@ -2472,9 +2027,13 @@ int pf_create(const uint8_t* grid, int32_t R, int32_t C, int32_t device, pf_hand
   return 0;
 }
 
+static void maaco_batch_free(pf_maaco_batch* b);
 void pf_destroy(pf_handle* h) {
   if (!h) return;
   (void)hipSetDevice(h->device);
+  if (h->stream) (void)hipStreamSynchronize(h->stream);
+  for (pf_maaco_batch* b : h->maaco_batches) maaco_batch_free(b);
+  h->maaco_batches.clear();
   if (h->comm && g_rccl.CommDestroy) { (void)hipStreamSynchronize(h->stream); g_rccl.CommDestroy(h->comm); h->comm = nullptr; }
   void* ptrs[] = {h->d_occ, h->d_mm_r1, h->d_mm_r0, h->d_mm_r1_nd, h->d_mm_r0_nd, h->d_d2near, h->d_rec, h->d_slot_state,
                   h->d_work, h->d_cnt, h->d_pen, h->d_tier2, h->d_tau, h->d_taua, h->d_eta, h->d_dep, h->d_tep, h->d_visit, h->d_visit_epoch,
@@ -2510,6 +2069,7 @@ int pf_update_grid(pf_handle* h, const uint8_t* grid) {
   h->wide_W = 0;                                                    // the wide distance table belongs to the old map
   h->obst_frac = -1.0;
   h->mpa_ready = false; h->maaco_ready = false;                     // their tables (initial path, bounds, tau / eta) belong to the old map
+  for (pf_maaco_batch* b : h->maaco_batches) b->ready = false;      // (so do the batches': they only accept pf_maaco_batch_destroy)
   if (h->d_ds) { (void)hipFree(h->d_ds); h->d_ds = nullptr; }
   if (h->d_dt) { (void)hipFree(h->d_dt); h->d_dt = nullptr; }
   return 0;
@@ -2997,15 +2557,11 @@ static int maaco_refresh_taua(pf_handle* h) {
   return 0;
 }
 
-int pf_maaco_setup(pf_handle* h, const pf_maaco_params* p) {
-  if (!h) return -2;
-  if (!p || p->start < 0 || p->start >= h->RC || p->target < 0 || p->target >= h->RC) return failmsg(h, "pf_maaco_setup: bad arguments");
-  CK(hipSetDevice(h->device));
-  h->mp = *p;
-  const int R = h->R, C = h->C, RC = h->RC;
+// the initial pheromone (tau[RC]) and the eta'^beta table (eta[RC][2]) of a colony from p->start to p->target
+static void maaco_tables(const pf_handle* h, const pf_maaco_params* p, double* tau, double* eta) {
+  const int R = h->R, C = h->C;
   const int sr = p->start / C, sc = p->start % C, tr = p->target / C, tc = p->target % C;
   double dsT = hdist(sr, sc, tr, tc); if (dsT < 1e-9) dsT = 1e-9;                   // MAACO.py:43-45
-  std::vector<double> tau(RC), eta((size_t)RC * 2);
   for (int r = 0; r < R; ++r) for (int c = 0; c < C; ++c) {
     const int i = r * C + c;
     // pheromone init MAACO.py:58-84
@@ -3027,25 +2583,39 @@ int pf_maaco_setup(pf_handle* h, const pf_maaco_params* p) {
       eta[(size_t)i * 2 + turn] = pow(1.0 / den, p->beta);
     }
   }
+}
+// the tabu slot pool: one packed tabu set per resident ant, shared by the solo MAACO state and every batch of the handle
+static int maaco_ensure_visit(pf_handle* h) {
+  if (h->d_visit) return 0;
+  hipDeviceProp_t prop; CK(hipGetDeviceProperties(&prop, h->device));
+  const int cus = prop.multiProcessorCount > 0 ? prop.multiProcessorCount : 256;
+  if (!h->nslots) h->nslots = cus * kSlotsPerCU;
+  // one packed tabu set (Tabu, R * ceil(C / 16) words) per resident ant: up to 128 ants per CU (16 waves x 8 ants), within 32 GiB
+  const size_t vwords = (size_t)h->R * (size_t)((h->C + 15) >> 4);
+  int vs = cus * 128;
+  while ((size_t)vs * vwords * sizeof(unsigned) > (32ull << 30) && vs > cus * 32) vs /= 2;
+  h->maaco_slots = vs; h->maaco_cus = cus;
+  CK(hipMalloc(&h->d_visit, sizeof(unsigned) * (size_t)vs * vwords));
+  CK(hipMemsetAsync(h->d_visit, 0, sizeof(unsigned) * (size_t)vs * vwords, h->stream));
+  CK(hipMalloc(&h->d_visit_epoch, sizeof(unsigned) * vs));
+  CK(hipMemsetAsync(h->d_visit_epoch, 0, sizeof(unsigned) * vs, h->stream));
+  CK(hipStreamSynchronize(h->stream));
+  return 0;
+}
+
+int pf_maaco_setup(pf_handle* h, const pf_maaco_params* p) {
+  if (!h) return -2;
+  if (!p || p->start < 0 || p->start >= h->RC || p->target < 0 || p->target >= h->RC) return failmsg(h, "pf_maaco_setup: bad arguments");
+  CK(hipSetDevice(h->device));
+  h->mp = *p;
+  const int RC = h->RC;
+  std::vector<double> tau(RC), eta((size_t)RC * 2);
+  maaco_tables(h, p, tau.data(), eta.data());
   if (!h->d_tau) { CK(hipMalloc(&h->d_tau, sizeof(double) * RC)); CK(hipMalloc(&h->d_taua, sizeof(double) * RC)); CK(hipMalloc(&h->d_eta, sizeof(double) * RC * 2)); }
   CK(hipMemcpyAsync(h->d_tau, tau.data(), sizeof(double) * RC, hipMemcpyHostToDevice, h->stream));
   CK(hipMemcpyAsync(h->d_eta, eta.data(), sizeof(double) * RC * 2, hipMemcpyHostToDevice, h->stream));
   CK(hipStreamSynchronize(h->stream));
-  if (!h->d_visit) {
-    hipDeviceProp_t prop; CK(hipGetDeviceProperties(&prop, h->device));
-    const int cus = prop.multiProcessorCount > 0 ? prop.multiProcessorCount : 256;
-    if (!h->nslots) h->nslots = cus * kSlotsPerCU;
-    // one packed tabu set (Tabu, R * ceil(C / 16) words) per resident ant: up to 128 ants per CU (16 waves x 8 ants), within 32 GiB
-    const size_t vwords = (size_t)h->R * (size_t)((h->C + 15) >> 4);
-    int vs = cus * 128;
-    while ((size_t)vs * vwords * sizeof(unsigned) > (32ull << 30) && vs > cus * 32) vs /= 2;
-    h->maaco_slots = vs; h->maaco_cus = cus;
-    CK(hipMalloc(&h->d_visit, sizeof(unsigned) * (size_t)vs * vwords));
-    CK(hipMemsetAsync(h->d_visit, 0, sizeof(unsigned) * (size_t)vs * vwords, h->stream));
-    CK(hipMalloc(&h->d_visit_epoch, sizeof(unsigned) * vs));
-    CK(hipMemsetAsync(h->d_visit_epoch, 0, sizeof(unsigned) * vs, h->stream));
-    CK(hipStreamSynchronize(h->stream));
-  }
+  if (maaco_ensure_visit(h)) return -1;
   CK(hipFuncSetAttribute((const void*)k_tau_update, hipFuncAttributeMaxDynamicSharedMemorySize, 2 * PF_UPD_CHUNK * (int)sizeof(double)));
   h->maaco_ready = true;
   if (h->d_best_row) CK(hipMemsetAsync(h->d_best_row, 0, sizeof(int), h->stream));   // a new colony has no best path yet
@@ -3325,6 +2895,235 @@ int pf_maaco_set_pheromone(pf_handle* h, const double* tau) {
   return maaco_refresh_taua(h);
 }
 void* pf_maaco_tau_dev(pf_handle* h) { return h ? (void*)h->d_tau : nullptr; }
+
+// ---------------------------------------------------------------------------
+// K MAACO colonies in one batched iteration (pf_maaco_batch_*)
+// ---------------------------------------------------------------------------
+static void maaco_batch_free(pf_maaco_batch* b) {
+  void* ptrs[] = {b->d_tau, b->d_taua, b->d_eta, b->d_tep, b->d_start, b->d_target, b->d_eta_of, b->d_seed, b->d_bits, b->d_flag,
+                  b->d_dep, b->d_ctl, b->d_scan3, b->d_state, b->d_best_rows};
+  for (void* p : ptrs) if (p) (void)hipFree(p);
+  if (b->h_io) (void)hipHostFree(b->h_io);
+  delete b;
+}
+// tau^alpha of colony c (alpha != 1: host libm pow, as maaco_refresh_taua)
+static int maaco_batch_refresh_taua(pf_maaco_batch* b, int c) {
+  pf_handle* h = b->h;
+  if (b->mp.alpha == 1.0) return 0;
+  std::vector<double> t(h->RC);
+  CK(hipMemcpyAsync(t.data(), b->d_tau + (size_t)c * h->RC, sizeof(double) * h->RC, hipMemcpyDeviceToHost, h->stream));
+  CK(hipStreamSynchronize(h->stream));
+  for (int i = 0; i < h->RC; ++i) t[i] = pow(t[i], b->mp.alpha);
+  CK(hipMemcpyAsync(b->d_taua + (size_t)c * h->RC, t.data(), sizeof(double) * h->RC, hipMemcpyHostToDevice, h->stream));
+  CK(hipStreamSynchronize(h->stream));
+  return 0;
+}
+static int maaco_batch_check(pf_maaco_batch* b, const char* what) {
+  if (!b) return failmsg(nullptr, std::string(what) + ": null batch");
+  if (!b->ready) return failmsg(b->h, std::string(what) + ": the batch belongs to a replaced grid (pf_update_grid); destroy it");
+  return 0;
+}
+
+int pf_maaco_batch_create(pf_handle* h, const pf_maaco_params* p, int32_t K, int32_t n, const int32_t* starts, const int32_t* targets,
+                          const uint64_t* seeds, pf_maaco_batch** out) {
+  if (!h) return -2;
+  if (!p || !out || K < 1 || n < 1 || !starts || !targets || !seeds) return failmsg(h, "pf_maaco_batch_create: bad arguments");
+  *out = nullptr;
+  if ((int64_t)K * n > 0x7FFFFFFF) return failmsg(h, "pf_maaco_batch_create: K * n exceeds 2^31 - 1 ants");
+  const int RC = h->RC;
+  for (int c = 0; c < K; ++c)
+    if (starts[c] < 0 || starts[c] >= RC || targets[c] < 0 || targets[c] >= RC || h->h_occ[starts[c]] == 1 || h->h_occ[targets[c]] == 1)
+      return failmsg(h, "pf_maaco_batch_create: colony " + std::to_string(c) + ": start / target out of range or on an obstacle");
+  CK(hipSetDevice(h->device));
+  // colonies with the same start / target share one eta table
+  std::vector<int> eta_of(K), pair_s, pair_t;
+  for (int c = 0; c < K; ++c) {
+    int e = 0;
+    while (e < (int)pair_s.size() && !(pair_s[e] == starts[c] && pair_t[e] == targets[c])) ++e;
+    if (e == (int)pair_s.size()) { pair_s.push_back(starts[c]); pair_t.push_back(targets[c]); }
+    eta_of[c] = e;
+  }
+  const int P = (int)pair_s.size();
+  // memory budget: per colony tau (+ tau^alpha), tep, the bit matrix, its flags, the deposits, a best row; eta per start / target pair
+  const size_t S = (size_t)(RC + 63) / 64, words = (size_t)(n + 63) / 64;
+  const size_t row_cap0 = (size_t)std::min(RC, 6 * (h->R + h->C) + 64) + 1;
+  const size_t per_colony = (size_t)RC * 8 * (p->alpha != 1.0 ? 2 : 1) + (size_t)RC * 24 + words * S * 64 * 8 + words * S + words * 64 * 8 +
+                            row_cap0 * 4 + 16 * 8;
+  const size_t need = per_colony * K + (size_t)P * RC * 16;
+  size_t free_b = 0, total_b = 0;
+  CK(hipMemGetInfo(&free_b, &total_b));
+  if (need > free_b / 10 * 9)
+    return failmsg(h, "pf_maaco_batch_create: " + std::to_string(K) + " colonies of " + std::to_string(n) + " ants need " +
+                          std::to_string(need >> 20) + " MiB of device memory, " + std::to_string(free_b >> 20) + " MiB are free");
+  if (maaco_ensure_visit(h)) return -1;
+  pf_maaco_batch* b = new pf_maaco_batch();
+  b->h = h; b->mp = *p; b->K = K; b->n = n;
+  b->start.assign(starts, starts + K); b->target.assign(targets, targets + K); b->eta_of = eta_of;
+  b->mp.start = starts[0]; b->mp.target = targets[0];
+  b->words = words; b->bits_stride = words * S * 64; b->flag_stride = words * S;
+  #define CKB(call) do { hipError_t e_ = (call); if (e_ != hipSuccess) { fail(h, #call, e_); maaco_batch_free(b); return -1; } } while (0)
+  CKB(hipMalloc(&b->d_tau, sizeof(double) * RC * (size_t)K));
+  if (p->alpha != 1.0) CKB(hipMalloc(&b->d_taua, sizeof(double) * RC * (size_t)K));
+  CKB(hipMalloc(&b->d_eta, sizeof(double) * 2 * RC * (size_t)P));
+  CKB(hipMalloc(&b->d_tep, sizeof(double) * 3 * RC * (size_t)K));
+  CKB(hipMalloc(&b->d_start, sizeof(int) * K)); CKB(hipMalloc(&b->d_target, sizeof(int) * K));
+  CKB(hipMalloc(&b->d_eta_of, sizeof(int) * K)); CKB(hipMalloc(&b->d_seed, sizeof(unsigned long long) * K));
+  CKB(hipMalloc(&b->d_bits, sizeof(unsigned long long) * b->bits_stride * K));
+  CKB(hipMalloc(&b->d_flag, b->flag_stride * K));
+  CKB(hipMalloc(&b->d_dep, sizeof(double) * words * 64 * K));
+  CKB(hipMalloc(&b->d_ctl, 16 + sizeof(DevCounters)));
+  CKB(hipMalloc(&b->d_scan3, sizeof(double) * 3 * K)); CKB(hipMalloc(&b->d_state, sizeof(double) * 13 * K));
+  CKB(hipHostMalloc((void**)&b->h_io, sizeof(double) * 15 * K, hipHostMallocMapped));
+  CKB(hipHostGetDevicePointer((void**)&b->h_io_dev, b->h_io, 0));
+  // tables, per colony as pf_maaco_setup builds them (tau from the colony's start / target; eta once per pair)
+  std::vector<double> tau((size_t)RC * K), eta((size_t)RC * 2 * P), scratch((size_t)RC * 2);
+  std::vector<bool> eta_done(P, false);
+  for (int c = 0; c < K; ++c) {
+    pf_maaco_params q = *p; q.start = starts[c]; q.target = targets[c];
+    double* e = eta_done[eta_of[c]] ? scratch.data() : eta.data() + (size_t)eta_of[c] * 2 * RC;
+    maaco_tables(h, &q, tau.data() + (size_t)c * RC, e);
+    eta_done[eta_of[c]] = true;
+  }
+  CKB(hipMemcpyAsync(b->d_tau, tau.data(), sizeof(double) * tau.size(), hipMemcpyHostToDevice, h->stream));
+  CKB(hipMemcpyAsync(b->d_eta, eta.data(), sizeof(double) * eta.size(), hipMemcpyHostToDevice, h->stream));
+  std::vector<unsigned long long> sd(seeds, seeds + K);
+  CKB(hipMemcpyAsync(b->d_start, starts, sizeof(int) * K, hipMemcpyHostToDevice, h->stream));
+  CKB(hipMemcpyAsync(b->d_target, targets, sizeof(int) * K, hipMemcpyHostToDevice, h->stream));
+  CKB(hipMemcpyAsync(b->d_eta_of, eta_of.data(), sizeof(int) * K, hipMemcpyHostToDevice, h->stream));
+  CKB(hipMemcpyAsync(b->d_seed, sd.data(), sizeof(unsigned long long) * K, hipMemcpyHostToDevice, h->stream));
+  CKB(hipMemsetAsync(b->d_dep, 0, sizeof(double) * words * 64 * K, h->stream));
+  CKB(hipStreamSynchronize(h->stream));
+  CKB(hipFuncSetAttribute((const void*)k_tau_update_batch, hipFuncAttributeMaxDynamicSharedMemorySize, 2 * PF_UPD_CHUNK * (int)sizeof(double)));
+  #undef CKB
+  b->ready = true;
+  h->maaco_batches.push_back(b);
+  for (int c = 0; c < K; ++c) if (maaco_batch_refresh_taua(b, c)) return -1;
+  *out = b;
+  return 0;
+}
+
+void pf_maaco_batch_destroy(pf_maaco_batch* b) {
+  if (!b) return;
+  pf_handle* h = b->h;
+  auto it = std::find(h->maaco_batches.begin(), h->maaco_batches.end(), b);
+  if (it == h->maaco_batches.end()) return;                        // (not this handle's: already gone)
+  h->maaco_batches.erase(it);
+  (void)hipSetDevice(h->device);
+  (void)hipStreamSynchronize(h->stream);                           // (an update pass may still be running on the batch's tables)
+  maaco_batch_free(b);
+}
+
+// One iteration of all K colonies: one walk over the K n ants, one best / take-over launch (a block per colony), one pheromone
+// pass (a block row per colony), one wait for the K x 13 doubles.  Colony c's ants are rows [c n, (c + 1) n) of the buffers.
+int pf_maaco_batch_iterate(pf_maaco_batch* b, int32_t iter, int32_t n, int32_t path_cap, int32_t* d_cells, int32_t* d_len,
+                           double* d_plen, int32_t* d_turns, int32_t* d_status, const double* best_len, const double* best_turns,
+                           double* out) {
+  if (maaco_batch_check(b, "pf_maaco_batch_iterate")) return -2;
+  pf_handle* h = b->h;
+  const int K = b->K;
+  if (n != b->n || path_cap < 2 || !d_cells || !d_len || !d_plen || !d_turns || !d_status || !best_len || !best_turns || !out)
+    return failmsg(h, "pf_maaco_batch_iterate: bad arguments (n must be the batch's ants per colony)");
+  CK(hipSetDevice(h->device));
+  const int RC = h->RC;
+  if (b->row_cap < path_cap + 1) {                                 // (longer rows keep every colony's best so far)
+    int* nb = nullptr; CK(hipMalloc(&nb, sizeof(int) * ((size_t)path_cap + 1) * K));
+    if (b->d_best_rows) {
+      CK(hipMemcpy2DAsync(nb, sizeof(int) * ((size_t)path_cap + 1), b->d_best_rows, sizeof(int) * (size_t)b->row_cap,
+                          sizeof(int) * (size_t)b->row_cap, K, hipMemcpyDeviceToDevice, h->stream));
+      CK(hipStreamSynchronize(h->stream)); CK(hipFree(b->d_best_rows));
+    } else {
+      CK(hipMemset2DAsync(nb, sizeof(int) * ((size_t)path_cap + 1), 0, sizeof(int), K, h->stream));
+    }
+    b->d_best_rows = nb; b->row_cap = path_cap + 1;
+  }
+  if (!b->bits_clean) {
+    CK(hipMemsetAsync(b->d_bits, 0, sizeof(unsigned long long) * b->bits_stride * K, h->stream));
+    CK(hipMemsetAsync(b->d_flag, 0, b->flag_stride * K, h->stream));
+  }
+  b->bits_clean = false;
+  if (!b->ctl_clean) CK(hipMemsetAsync(b->d_ctl, 0, 16 + sizeof(DevCounters), h->stream));
+  b->ctl_clean = false;
+  for (int c = 0; c < K; ++c) { b->h_io[2 * c] = best_len[c]; b->h_io[2 * c + 1] = best_turns[c]; }   // (read by the best / take launch)
+  MaacoArgs a;
+  a.G = make_grid(h, 1, 1);
+  a.tau = b->mp.alpha == 1.0 ? b->d_tau : b->d_taua; a.eta = b->d_eta; a.tep = b->d_tep;
+  a.visit = h->d_visit; a.slot_epoch = h->d_visit_epoch;
+  a.work = (int*)b->d_ctl; a.cnt = (DevCounters*)(b->d_ctl + 16);
+  a.wpr = (h->C + 15) >> 4; a.vstride = h->R * a.wpr;
+  a.start = b->mp.start; a.target = b->mp.target; a.iter = iter; a.num_iterations = b->mp.num_iterations;
+  a.q0 = maaco_q0(iter, b->mp.num_iterations, b->mp.q0_initial);
+  a.seed = 0; a.ant0 = 0; a.n = K * n; a.path_cap = path_cap;
+  a.cells = d_cells; a.len = d_len; a.plen = d_plen; a.turns = d_turns; a.status = d_status;
+  a.bits = b->d_bits; a.dep = b->d_dep; a.flag = b->d_flag; a.fstride = (int)b->words; a.Q = b->mp.Q;
+  a.groups = g_maaco_groups;
+  MaacoColonies mc;
+  mc.nper = n; mc.seed = b->d_seed; mc.start = b->d_start; mc.target = b->d_target; mc.eta_of = b->d_eta_of;
+  mc.bits_stride = b->bits_stride; mc.flag_stride = b->flag_stride; mc.dep_stride = (int)(b->words * 64);
+  // the kernel choice follows the K n ants of the walk, as for one colony of that many ants
+  const int total = K * n;
+  const bool pack8 = total >= g_maaco_pack8_min;
+  int grid = pack8 ? h->maaco_slots / 8 : (h->maaco_slots < 8192 ? h->maaco_slots : 8192);
+  const int need = pack8 ? (total + a.groups - 1) / a.groups : total; if (grid > need) grid = need;
+  if (g_tabu_epoch >= 0) {
+    CK(hipMemsetD32Async((hipDeviceptr_t)h->d_visit_epoch, g_tabu_epoch, (size_t)h->maaco_slots, h->stream));
+    g_tabu_epoch = -1;
+  }
+  if (pack8) hipLaunchKernelGGL(k_pack_tep_batch, dim3((RC + 255) / 256, K), dim3(256), 0, h->stream, RC, a.tau, (const double*)b->d_eta,
+                                (const int*)b->d_eta_of, b->d_tep);
+  CK(hipEventRecord(h->ev0, h->stream));
+  const bool ahead = g_maaco_ahead < 0 ? grid <= h->maaco_cus * 4 : g_maaco_ahead != 0;
+  if (pack8 && ahead) hipLaunchKernelGGL(k_maaco_walk8_batch<true>, dim3(grid), dim3(64), 0, h->stream, a, mc);
+  else if (pack8) hipLaunchKernelGGL(k_maaco_walk8_batch<false>, dim3(grid), dim3(64), 0, h->stream, a, mc);
+  else hipLaunchKernelGGL(k_maaco_walk_batch, dim3(grid), dim3(64), 0, h->stream, a, mc);
+  CK(hipGetLastError());
+  CK(hipEventRecord(h->ev1, h->stream));
+  double* io_out = b->h_io_dev + 2 * K;
+  hipLaunchKernelGGL(k_maaco_best_take_batch, dim3(K), dim3(1024), 0, h->stream, n, (const double*)d_plen, (const int*)d_turns, b->d_scan3,
+                     (const double*)b->h_io_dev, b->mp.rho, h->R, h->C, (int*)b->d_ctl, (DevCounters*)(b->d_ctl + 16), (unsigned*)(b->d_ctl + 4),
+                     b->d_state, io_out, (const int*)d_cells, (const int*)d_len, path_cap, b->d_best_rows, b->row_cap);
+  CK(hipEventRecord(h->ev2, h->stream));
+  hipLaunchKernelGGL(k_tau_update_batch, dim3((RC + 1023) / 1024, K), dim3(1024), 2 * PF_UPD_CHUNK * sizeof(double), h->stream, b->d_tau, h->d_occ,
+                     RC, b->d_bits, (int)b->words, b->d_dep, 1.0 - b->mp.rho, (const double*)b->d_state, 0.0, 0.0, b->d_flag, (int)b->words, mc);
+  CK(hipGetLastError());
+  CK(hipEventSynchronize(h->ev2));                                 // (the pheromone pass runs on behind the caller's bookkeeping)
+  memcpy(out, b->h_io + 2 * K, sizeof(double) * 13 * K);
+  b->ctl_clean = true;
+  h->d2h_small += 1;
+  CK(hipEventElapsedTime(&h->last_ms, h->ev0, h->ev1));
+  memset(&h->last, 0, sizeof(h->last));
+  h->last.steps = (unsigned long long)out[9]; h->last.candidates = (unsigned long long)out[10];
+  h->last.path_cells = (unsigned long long)out[11]; h->last.overflow_agents = (unsigned long long)out[12];
+  b->bits_clean = out[8] == 0.0;
+  if (out[8] == 0.0) for (int c = 0; c < K; ++c) if (maaco_batch_refresh_taua(b, c)) return -1;
+  return 0;
+}
+
+int pf_maaco_batch_best_path(pf_maaco_batch* b, int32_t k, int32_t* cells_out, int32_t cap, int32_t* len_out) {
+  if (maaco_batch_check(b, "pf_maaco_batch_best_path")) return -2;
+  pf_handle* h = b->h;
+  if (k < 0 || k >= b->K || !len_out || cap < 0 || (cap > 0 && !cells_out)) return failmsg(h, "pf_maaco_batch_best_path: bad arguments");
+  *len_out = 0;
+  if (!b->d_best_rows) return 0;
+  const int* row = b->d_best_rows + (size_t)k * b->row_cap;
+  int L = 0;
+  if (pf_d2h(h, &L, (void*)row, sizeof(int))) return -1;
+  if (L < 0 || L > b->row_cap - 1) return failmsg(h, "pf_maaco_batch_best_path: corrupt row");
+  *len_out = L;
+  if (L > cap) return failmsg(h, "pf_maaco_batch_best_path: the buffer is too small");
+  if (L > 0 && pf_d2h(h, cells_out, (void*)(row + 1), (int64_t)sizeof(int) * L)) return -1;
+  return 0;
+}
+int pf_maaco_batch_get_pheromone(pf_maaco_batch* b, int32_t k, double* tau) {
+  if (maaco_batch_check(b, "pf_maaco_batch_get_pheromone")) return -2;
+  if (k < 0 || k >= b->K || !tau) return failmsg(b->h, "pf_maaco_batch_get_pheromone: bad arguments");
+  return pf_d2h(b->h, tau, b->d_tau + (size_t)k * b->h->RC, (int64_t)sizeof(double) * b->h->RC);
+}
+int pf_maaco_batch_set_pheromone(pf_maaco_batch* b, int32_t k, const double* tau) {
+  if (maaco_batch_check(b, "pf_maaco_batch_set_pheromone")) return -2;
+  if (k < 0 || k >= b->K || !tau) return failmsg(b->h, "pf_maaco_batch_set_pheromone: bad arguments");
+  if (pf_h2d(b->h, b->d_tau + (size_t)k * b->h->RC, tau, (int64_t)sizeof(double) * b->h->RC)) return -1;
+  return maaco_batch_refresh_taua(b, k);
+}
 
 int pf_maaco_best_scan(int32_t n, const double* plen, const int32_t* turns, int32_t idx0, double* best_len,
                        double* best_turns, int32_t* best_idx) {

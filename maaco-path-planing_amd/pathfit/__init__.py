@@ -11,4 +11,5 @@ from .engine import Engine, DevBuf, score_params  # noqa: F401
 from .paths import CellPath  # noqa: F401
 from .solvers import AStarSolver, DijkstraSolver, GASolver, PSOSolver, BasePathfinder  # noqa: F401
 from .maaco import MAACO  # noqa: F401
+from .maaco_batch import MAACOBatch, MaacoColony  # noqa: F401
 from .mpa import MPA  # noqa: F401

@@ -124,6 +124,12 @@ SYMBOLS = {
     "pf_selftest_mpa_targets": (C.c_int, [_vp, _u64, _i32, _i32, _dbl, _dbl, _dbl, _vp, _vp, _vp, C.POINTER(_i64)]),
     "pf_mpa_doubts_resolved": (C.c_longlong, [_vp]),
     "pf_mpa_memory": (C.c_int, [_vp, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "pf_maaco_batch_create": (C.c_int, [_vp, C.POINTER(MaacoParams), _i32, _i32, _vp, _vp, _vp, C.POINTER(_vp)]),
+    "pf_maaco_batch_destroy": (None, [_vp]),
+    "pf_maaco_batch_iterate": (C.c_int, [_vp, _i32, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "pf_maaco_batch_best_path": (C.c_int, [_vp, _i32, _vp, _i32, C.POINTER(_i32)]),
+    "pf_maaco_batch_get_pheromone": (C.c_int, [_vp, _i32, _vp]),
+    "pf_maaco_batch_set_pheromone": (C.c_int, [_vp, _i32, _vp]),
 }
 
 
