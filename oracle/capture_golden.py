@@ -548,6 +548,236 @@ def cap_vs_reference(G):
     np.savez_compressed(os.path.join(OUT, "vs_reference.npz"), **d, **{"meta_" + k: v for k, v in META.items()})
 
 
+POLICIES = ((1, 0), (0, 1), (0, 0))      # (allow_diagonal_moves, restrict corner cutting); (1, 1) is every other fixture
+
+
+def score_walk(rnd, g, L, boundary_cuts=(61, 62, 63, 64, 125, 126, 127, 128)):
+    """A hand-built path of L cells on g: a random 8-connected walk (cells may repeat) that takes a corner-cutting diagonal
+    step, or failing that a turn, at the steps around the 64-cell chunk boundaries of score_path (pf_score.h)."""
+    R, C = g.shape
+    free = [tuple(int(v) for v in x) for x in np.argwhere(g != 1)]
+    cur, prev, path = rnd.choice(free), None, []
+    path.append(cur)
+    for k in range(L - 1):
+        moves = [(a, b) for a in (-1, 0, 1) for b in (-1, 0, 1) if (a or b)
+                 and 0 <= cur[0] + a < R and 0 <= cur[1] + b < C and g[cur[0] + a, cur[1] + b] != 1]
+        cuts = [m for m in moves if m[0] and m[1] and (g[cur[0] + m[0], cur[1]] == 1 or g[cur[0], cur[1] + m[1]] == 1)]
+        turns = [m for m in moves if m != prev]
+        if k in boundary_cuts and cuts:
+            m = rnd.choice(cuts)
+        elif k in boundary_cuts and turns:
+            m = rnd.choice(turns)
+        elif cuts and rnd.random() < 0.3:
+            m = rnd.choice(cuts)
+        elif prev in moves and rnd.random() < 0.5:
+            m = prev
+        else:
+            m = rnd.choice(moves)
+        cur, prev = (cur[0] + m[0], cur[1] + m[1]), m
+        path.append(cur)
+    return path
+
+
+def cap_policies(G):
+    """The three non-default move policies (allow_diag, restrict) = (1, 0), (0, 1), (0, 0) -> policy_cases.npz:
+    AStarSolver.solve / MPA._a_star / DijkstraSolver.solve triples (paths, heap pops / pushes), GA and PSO decodes + stats,
+    MPA._reconstruct_path_segment rebuilds + stats + draw counts, helper.calculate_path_stats / MPA._calculate_path_stats of
+    hand-built paths under both restrict values, and one GA and one MPA solve on fig7 with allow_diagonal_moves=False."""
+    import ref_e2e
+    d = {}
+    rnd = random.Random(6060)
+    # ---- connectors
+    rows = []
+    for pi, (ad, rs) in enumerate(POLICIES):
+        for name, n in (("fig7", 14), ("fig13", 10), ("img1", 10), ("img3", 10), ("g128crop", 4)):
+            g = G[name]
+            R, C = g.shape
+            solvers = (rh.RefAStar(g, allow_diagonal_moves=bool(ad), restrict_diagonal_near_obstacle_policy=bool(rs)),
+                       rh.make_mpa(g, allow_diagonal_moves=bool(ad), restrict_diagonal_near_obstacle=bool(rs)),
+                       rh.RefDijkstra(g, allow_diagonal_moves=bool(ad), restrict_diagonal_near_obstacle_policy=bool(rs)))
+            free = [tuple(int(v) for v in x) for x in np.argwhere(g != 1)]
+            obst = [tuple(int(v) for v in x) for x in np.argwhere(g == 1)]
+            for t in range(n):
+                s, e = rnd.choice(free), rnd.choice(free)
+                if R > 20:                                   # short searches on the 128 crop
+                    near = [f for f in free if abs(f[0] - s[0]) <= 12 and abs(f[1] - s[1]) <= 12]
+                    e = rnd.choice(near)
+                if t == 0 and R <= 20:
+                    s, e = st_of(g)
+                if t % 7 == 1:
+                    e = s
+                if t % 7 == 2 and obst:
+                    s = rnd.choice(obst)
+                if t % 9 == 3 and obst:
+                    e = rnd.choice(obst)
+                avoid = None
+                if t % 3 != 0:
+                    avoid = rnd.sample(free, rnd.randint(0, max(1, len(free) // 12)))
+                    if t % 6 == 1:
+                        avoid.append(e)
+                    if t % 6 == 2:
+                        avoid.append(s)
+                if t % 8 == 4:                               # target walled in by avoid cells
+                    avoid = [(e[0] + a, e[1] + b) for a in (-1, 0, 1) for b in (-1, 0, 1) if (a or b)]
+                    avoid = [a for a in avoid if 0 <= a[0] < R and 0 <= a[1] < C]
+                for variant in (0, 1, 2):
+                    if variant == 1:
+                        pc, _, cnt = rh.mpa_astar(solvers[1], s, e, avoid)
+                    else:
+                        pc, _, cnt = solvers[variant].solve(s, e, avoid)
+                    rows.append(dict(policy=pi, grid=name, variant=variant, start=s[0] * C + s[1], target=e[0] * C + e[1],
+                                     avoid=[a[0] * C + a[1] for a in avoid] if avoid is not None else [],
+                                     has_avoid=avoid is not None, path=pc, pops=cnt["pops"], pushes=cnt["pushes"]))
+    names = ["fig7", "fig13", "img1", "img3", "g128crop"]
+    d["grid_names"] = np.array(names)
+    d["policies"] = np.array(POLICIES, np.int32)
+    d["as_policy"] = np.array([r["policy"] for r in rows], np.int8)
+    d["as_grid"] = np.array([names.index(r["grid"]) for r in rows], np.int8)
+    d["as_variant"] = np.array([r["variant"] for r in rows], np.int8)
+    d["as_start"] = np.array([r["start"] for r in rows], np.int32)
+    d["as_target"] = np.array([r["target"] for r in rows], np.int32)
+    d["as_has_avoid"] = np.array([r["has_avoid"] for r in rows])
+    d["as_avoid_off"], d["as_avoid"] = csr([r["avoid"] for r in rows])
+    d["as_path_off"], d["as_path"] = csr([r["path"] for r in rows])
+    d["as_counts"] = np.array([[r["pops"], r["pushes"]] for r in rows], np.int64)
+    print("policy connector cases", len(rows), "no path", sum(len(r["path"]) == 0 for r in rows))
+
+    # ---- GA chromosome / PSO position decodes + stats
+    rows = []
+    for pi, (ad, rs) in enumerate(POLICIES):
+        for name in ("fig7", "fig13", "img1", "img3"):
+            g = G[name]
+            R, C = g.shape
+            free = [tuple(int(v) for v in x) for x in np.argwhere(g != 1)]
+            for wi, Wt in enumerate((MAIN_W, DEF_W)):
+                pk = dict(allow_diagonal_moves=bool(ad), restrict_diagonal_near_obstacle_policy=bool(rs), **Wt)
+                ga, ps = rh.make_ga(g, W=5, **pk), rh.make_pso(g, W=5, **pk)
+                for t in range(6):
+                    W = 5 if t % 3 else rnd.choice([1, 2, 3])
+                    chrom = [rnd.choice(free) if rnd.random() < 0.92 else (rnd.randint(0, R - 1), rnd.randint(0, C - 1))
+                             for _ in range(W)]
+                    pos = [[rnd.uniform(-1.5, R + 0.5), rnd.uniform(-1.5, C + 0.5)] for _ in range(W)]
+                    with rh.quiet():
+                        p = ga._reconstruct_path_from_chromosome(chrom)
+                        st = ga._calculate_stats_for_path(p)
+                        p2 = ps._reconstruct_path_from_position(pos)
+                        st2 = ps._calculate_stats_for_path(p2)
+                    rows.append(dict(policy=pi, grid=name, w=wi, kind=0, wp=[c[0] * C + c[1] for c in chrom],
+                                     path=rh.to_cells(p, C), stats=list(st[1:6])))
+                    rows.append(dict(policy=pi, grid=name, w=wi, kind=1, wp=np.array(pos, np.float64).ravel(),
+                                     path=rh.to_cells(p2, C), stats=list(st2[1:6])))
+    d["dec_policy"] = np.array([r["policy"] for r in rows], np.int8)
+    d["dec_grid"] = np.array([names.index(r["grid"]) for r in rows], np.int8)
+    d["dec_w"] = np.array([r["w"] for r in rows], np.int8)
+    d["dec_kind"] = np.array([r["kind"] for r in rows], np.int8)
+    d["dec_wp_off"], d["dec_wp"] = csr([r["wp"] for r in rows], np.float64)
+    d["dec_path_off"], d["dec_path"] = csr([r["path"] for r in rows])
+    d["dec_stats"] = np.array([r["stats"] for r in rows], np.float64)
+    d["main_w"], d["def_w"] = np.array([0.3, 0.8, 1.8, 100.0]), np.array([0.1, 0.05, 1.5, 1000.0])
+    print("policy decode cases", len(rows), "feasible", sum(len(r["path"]) > 0 for r in rows))
+
+    # ---- MPA._reconstruct_path_segment
+    rows = []
+    for pi, (ad, rs) in enumerate(POLICIES):
+        for name in ("fig7", "img1", "g128crop"):
+            g = G[name]
+            R, C = g.shape
+            for beta in (1.5, 2.0):
+                mpa = rh.make_mpa(g, levy_beta=beta, allow_diagonal_moves=bool(ad), restrict_diagonal_near_obstacle=bool(rs))
+                S, T = st_of(g)
+                base = rh.to_cells(mpa.population[0]["path"], C)
+                if R <= 20:
+                    mid = (R // 2, 0) if g[R // 2, 0] != 1 else tuple(int(v) for v in np.argwhere(g != 1)[len(np.argwhere(g != 1)) // 2])
+                else:
+                    mid = tuple(int(v) for v in np.argwhere(g[:, :40] != 1)[-1])
+                a1, _, _ = rh.mpa_astar(mpa, S, mid)
+                a2, _, _ = rh.mpa_astar(mpa, mid, T, set(rh.to_rc(a1[:-1], C)))
+                alt = np.concatenate([a1, a2[1:]]) if len(a1) and len(a2) else base
+                for t in range(12 if R <= 20 else 3):
+                    path_c, el_c = (base, alt) if t % 2 else (alt, base)
+                    idx = rnd.randint(0, len(path_c) - 1) if R <= 20 else rnd.randint(len(path_c) - 40, len(path_c) - 1)
+                    is_levy = t % 3 == 0
+                    scale = rnd.choice([0.5, 0.25, 0.05, 5.0, 40.0])
+                    pc, res, draws = rh.mpa_rebuild(mpa, rh.to_rc(path_c, C), rh.to_rc(el_c, C), idx, is_levy, scale,
+                                                    555, 7, t)
+                    rows.append(dict(policy=pi, grid=name, beta=beta, path=path_c, elite=el_c, idx=idx,
+                                     is_levy=int(is_levy), scale=scale, agent=t, out=pc, draws=draws, stats=list(res[1:6])))
+    d["reb_policy"] = np.array([r["policy"] for r in rows], np.int8)
+    d["reb_grid"] = np.array([names.index(r["grid"]) for r in rows], np.int8)
+    d["reb_beta"] = np.array([r["beta"] for r in rows])
+    d["reb_in_off"], d["reb_in"] = csr([r["path"] for r in rows])
+    d["reb_el_off"], d["reb_el"] = csr([r["elite"] for r in rows])
+    d["reb_out_off"], d["reb_out"] = csr([r["out"] for r in rows])
+    d["reb_idx"] = np.array([r["idx"] for r in rows], np.int32)
+    d["reb_is_levy"] = np.array([r["is_levy"] for r in rows], np.int8)
+    d["reb_scale"] = np.array([r["scale"] for r in rows])
+    d["reb_agent"] = np.array([r["agent"] for r in rows], np.int32)
+    d["reb_draws"] = np.array([r["draws"] for r in rows], np.int64)
+    d["reb_stats"] = np.array([r["stats"] for r in rows], np.float64)
+    d["reb_seed_it"] = np.array([555, 7])
+    d["reb_sigma"] = np.array([rh.levy_sigma(1.5), rh.levy_sigma(2.0)])
+    print("policy rebuild cases", len(rows), "changed", sum(not np.array_equal(r["out"], r["path"]) for r in rows))
+
+    # ---- scores of hand-built paths: helper.calculate_path_stats (variant 0) and MPA._calculate_path_stats (variant 1)
+    helper = rh.mods()["helper"]
+    open_map = np.zeros((24, 24), int)
+    open_map[0, 0], open_map[23, 23] = 2, 3
+    d["open_map_shape"] = np.array(open_map.shape)
+    smaps = {"g128crop": G["g128crop"], "fig13": G["fig13"], "open": open_map}
+    paths = []
+    for L in (1, 2, 3, 63, 64, 65, 66, 127, 128, 129):
+        paths.append(("g128crop", score_walk(rnd, G["g128crop"], L)))
+    for L in (2, 5, 40, 70):
+        paths.append(("fig13", score_walk(rnd, G["fig13"], L)))
+    for L in (3, 65, 130):                                   # steps of any length (pf_score.h: the sqrt branch)
+        walk = score_walk(rnd, G["g128crop"], L)
+        for k in range(1, L, 4):
+            walk[k] = (rnd.randint(0, 127), rnd.randint(0, 127))
+        paths.append(("g128crop", walk))
+    paths.append(("open", score_walk(rnd, open_map, 70)))
+    paths.append(("open", [(0, 0), (1, 1), (1, 2), (4, 7), (5, 7), (6, 8), (6, 9)]))
+    weights = ((0.3, 0.8, 1.8, 100.0), (0.1, 0.05, 1.5, 1000.0))
+    rows = []
+    for gname, p in paths:
+        g = smaps[gname]
+        R, C = g.shape
+        obst = np.argwhere(g == 1)
+        for variant in (0, 1):
+            for rs in (1, 0):
+                for wi, (wt, ws, ms, dp) in enumerate(weights):
+                    if variant == 0:
+                        res = helper.calculate_path_stats(list(p), g, R, C, obst, wt, ws, ms, bool(rs), dp)
+                    else:
+                        mpa = rh.make_mpa(g, turn_penalty_factor=wt, safety_penalty_factor=ws, min_safe_distance=ms,
+                                          restrict_diagonal_near_obstacle=bool(rs), diagonal_obstacle_penalty=dp)
+                        res = mpa._calculate_path_stats(list(p))
+                    rows.append(dict(grid=gname, path=rh.to_cells(p, C), variant=variant, rs=rs, w=wi,
+                                     stats=[float(x) for x in res[1:6]]))
+    snames = sorted(smaps)
+    d["sc_grid_names"] = np.array(snames)
+    d["sc_grid"] = np.array([snames.index(r["grid"]) for r in rows], np.int8)
+    d["sc_variant"] = np.array([r["variant"] for r in rows], np.int8)
+    d["sc_restrict"] = np.array([r["rs"] for r in rows], np.int8)
+    d["sc_w"] = np.array([r["w"] for r in rows], np.int8)
+    d["sc_weights"] = np.array(weights)
+    d["sc_path_off"], d["sc_path"] = csr([r["path"] for r in rows])
+    d["sc_stats"] = np.array([r["stats"] for r in rows], np.float64)
+    print("policy score cases", len(rows), "with corner cuts", int((d["sc_stats"][:, 3] > 0).sum()))
+
+    # ---- 4-connected end-to-end solves on fig7
+    gk = dict(num_generations=6, population_size=24, num_waypoints_per_chromosome=5, mutation_rate=0.1, crossover_rate=0.8,
+              tournament_size=3, allow_diagonal_moves=False, **MAIN_W)
+    r = ref_e2e.ga_solve(G["fig7"], 4, **gk)
+    for k in ("path", "stats", "curve", "pop_fitness"):
+        d[f"ga_{k}"] = np.asarray(r[k])
+    print("policy e2e ga fitness", r["stats"][4])
+    r = ref_e2e.mpa_solve(G["fig7"], 2, 30, 20, allow_diagonal_moves=False)
+    for k in ("path", "stats", "curve", "pop_fitness", "pop_len"):
+        d[f"mpa_{k}"] = np.asarray(r[k])
+    print("policy e2e mpa fitness", r["stats"][4])
+    np.savez_compressed(os.path.join(OUT, "policy_cases.npz"), **d, **{"meta_" + k: v for k, v in META.items()})
+
+
 if __name__ == "__main__":
     assert rh.available(), "needs /root/reference"
     os.makedirs(OUT, exist_ok=True)
@@ -565,4 +795,5 @@ if __name__ == "__main__":
     if "e2e" in which: cap_e2e(G)
     if "e2e" in which or "pso_fallback" in which: cap_e2e_pso_fallback()
     if "vs_reference" in which: cap_vs_reference(G)
+    if "policies" in which: cap_policies(G)
     print("golden fixtures written to", OUT)
