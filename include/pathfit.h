@@ -297,6 +297,55 @@ int pf_mpa_memory(pf_handle* h, int32_t n, int32_t path_cap, const int32_t* d_sl
                   const int32_t* d_cand_len, const double* d_cand_stats, int32_t* d_pop_cells, int32_t* d_pop_len,
                   double* d_pop_stats);
 
+/* ---- K7 batched: K independent MPA schools in one sweep ------------------- */
+/* A school is one MPA population with its own seed seeds[k], start starts[k] and target targets[k]; the K schools share the
+ * handle's grid, p->num_predators (N), the hyper-parameters and the score parameters (p->start / p->target are ignored).
+ * School k computes exactly what a solo run computes (pf_mpa_setup with start / target = starts[k] / targets[k], then
+ * pf_sort_order_by_key / pf_mpa_pick_elite / pf_mpa_iter_batch with seed seeds[k]): predator i of its fitness-sorted list
+ * draws the streams (seeds[k], DOM_MPA=2, iter, i) and (seeds[k], DOM_MPA_FADS=5, iter, i), and the phase-2 split
+ * (MPA.py:351) is i < N / 2 within the school.
+ * Layout of every buffer the calls below take: school k's predators are rows [k N, (k + 1) N); d_order [K N] holds, per
+ * school, the list (position -> LOCAL slot 0 .. N - 1).
+ * pf_mpa_batch_create replaces K times MPA.__init__'s device work: the K MPA._generate_initial_path() searches
+ * (_a_star(start, target), MPA.py:154; memoised for the FADs re-init branch :405) run as ONE pf_astar_batch of K and are
+ * scored by one pf_score_batch; the pruning bound tables (one host Dijkstra per DISTINCT start or target cell) are built as
+ * pf_mpa_setup builds them.  A school whose target is unreachable has initial length 0 (the caller seeds the reference's
+ * fallback population [start, target], MPA.py:235-236; the re-init branch then never fires, as in the solo run).
+ * The batch owns its school table, bound tables, initial paths, elites and sort scratch: the handle's solo MPA state
+ * (pf_mpa_setup, pf_mpa_elite_buf) is never touched and several batches may live on one handle; the search slots, the work
+ * queue and the per-call job / proposal scratch are the handle's.  Device memory (~8 RC bytes per school + 8 RC per distinct
+ * cell) is checked at creation.  pf_destroy frees every batch of the handle; after pf_update_grid a batch only accepts
+ * pf_mpa_batch_destroy (every other call fails with a message). */
+typedef struct pf_mpa_batch pf_mpa_batch;
+int pf_mpa_batch_create(pf_handle* h, const pf_mpa_params* p, const pf_score_params* sp, int32_t K, const int32_t* starts,
+                        const int32_t* targets, const uint64_t* seeds, pf_mpa_batch** out);
+void pf_mpa_batch_destroy(pf_mpa_batch* b);
+/* school k's memoised initial path (host copy; *len_out = 0: unreachable) and its 5 stats (may be null) */
+int pf_mpa_batch_init_path(pf_mpa_batch* b, int32_t k, int32_t* cells_out, int32_t cap, int32_t* len_out, double* stats5);
+/* what pf_mpa_batch_create spent, in ms of host wall time: {initial searches + scores, bound tables, whole call} */
+int pf_mpa_batch_create_ms(pf_mpa_batch* b, double* out3);
+/* list.sort(key=fitness) of every school (MPA.py:321,333,412): K stable rank sorts of N keys (d_pop_stats[row * 5 + 4]) in one
+ * launch sequence, each inside its own segment of d_order */
+int pf_mpa_batch_sort(pf_mpa_batch* b, const double* d_pop_stats, int32_t* d_order);
+/* elite = population[0].copy() of every school (MPA.py:334) into the batch's elite buffers: one block per school */
+int pf_mpa_batch_pick_elite(pf_mpa_batch* b, int32_t path_cap, const int32_t* d_pop_cells, const int32_t* d_pop_len,
+                            const double* d_pop_stats, const int32_t* d_order);
+/* MPA.py:339-410 for all K schools, as pf_mpa_iter_batch does it for one: the phase items and the FADs candidates of the
+ * K N predators share ONE longest-first work queue of 2 K N items, searched by the same kernel as the solo sweep; memory
+ * step and FADs acceptance follow.  Doubtful proposals are confirmed on the host against their own school's elite and seed.
+ * An item whose path does not fit path_cap is counted (pf_mpa_batch_counters: overflow_agents) and never truncated. */
+int pf_mpa_batch_iterate(pf_mpa_batch* b, int32_t phase, double CF, int32_t iter, int32_t path_cap, int32_t* d_pop_cells,
+                         int32_t* d_pop_len, double* d_pop_stats, const int32_t* d_order, int32_t* d_c1_cells, int32_t* d_c1_len,
+                         double* d_c1_stats, int32_t* d_c2_cells, int32_t* d_c2_len, double* d_c2_stats, int32_t* d_status);
+/* population[0] of every school after the sort (MPA.py:413) in one copy: out[6 k ...] = {local slot, length, turns, safety,
+ * diag, fitness}; the 4-level tie-break MPA.py:415-437 stays with the caller */
+int pf_mpa_batch_best_rows(pf_mpa_batch* b, const double* d_pop_stats, const int32_t* d_order, double* out);
+/* the path in local slot `slot` of school k (the caller reads it when that school's best improves, MPA.py:417) */
+int pf_mpa_batch_read_path(pf_mpa_batch* b, int32_t k, int32_t slot, int32_t path_cap, const int32_t* d_pop_cells,
+                           const int32_t* d_pop_len, int32_t* cells_out, int32_t cap, int32_t* len_out);
+/* counters of the batch's last sweep, and over its lifetime: items that overflowed, proposals the host's libm resolved */
+int pf_mpa_batch_counters(pf_mpa_batch* b, pf_counters* out, int64_t* overflow_total, int64_t* doubts_resolved);
+
 /* Tuning knobs (results never change): "maaco_pack8_min" ants per batch from which eight ants share a wavefront
  * (default 2048); "maaco_load_ahead" the packed walk kernel's load-ahead form (all of a step's loads issued together plus touches of the
  * records two steps ahead): -1 (default) for batches of at most one wavefront per SIMD, 0 never, 1 always;

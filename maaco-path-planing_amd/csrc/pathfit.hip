@@ -8,6 +8,7 @@
 #include <stdlib.h>
 #include <string.h>
 #include <algorithm>
+#include <chrono>
 #include <queue>
 #include <string>
 #include <vector>
@@ -1073,9 +1074,9 @@ PF_DEV MpaPlan mpa_plan(const MpaPhaseArgs& p, int a) {
 }
 // Proposal pass, one thread per predator: the gating draws (:343-344 etc.), the target cell, the work estimate of the
 // longest-first queue, and the list of predators whose proposal the host has to confirm (see Doubt).
-__global__ void k_mpa_propose(MpaPhaseArgs p, float* est) {
-  const int a = blockIdx.x * blockDim.x + threadIdx.x;
-  if (a >= p.n) return;
+// (the items of the small sweep kernels are device functions: the solo kernels call them on their own arguments, the batched
+// ones -- pf_mpa_batch.h -- on a school's view of theirs.  `id` is what the doubt list records: the predator's index in the launch.)
+PF_DEV void mpa_propose_item(const MpaPhaseArgs& p, int a, int id, float* est) {
   const MpaPlan q = mpa_plan(p, a);
   int idx = -1, inter = -1;
   Doubt d; d.eps_log = p.eps_log; d.eps_round = p.eps_round; d.hit = false;
@@ -1095,7 +1096,12 @@ __global__ void k_mpa_propose(MpaPhaseArgs p, float* est) {
   }
   p.prop[a] = make_int2(idx, inter);
   if (est) est[a] = idx >= 0 ? (float)(q.modL - idx) : 0.f;
-  if (d.hit && idx >= 0) { const int at = atomicAdd(p.doubt_n, 1); p.doubt_list[at] = a; }
+  if (d.hit && idx >= 0) { const int at = atomicAdd(p.doubt_n, 1); p.doubt_list[at] = id; }
+}
+__global__ void k_mpa_propose(MpaPhaseArgs p, float* est) {
+  const int a = blockIdx.x * blockDim.x + threadIdx.x;
+  if (a >= p.n) return;
+  mpa_propose_item(p, a, a, est);
 }
 
 
@@ -1339,15 +1345,10 @@ struct __attribute__((aligned(16))) MpaJob {
 };
 struct MpaRes { int n, rc; };   // cells in the item's buffer after the searches; rc 0 done, 1 FADs detour failed, 3 scratch / path overflow
 
-__global__ __launch_bounds__(64) void k_mpa_plan(MpaSweepArgs q, MpaJob* jobs, MpaRes* res) {
-  const MpaPhaseArgs& p = q.ph;
-  const MpaFadsArgs& f = q.fd;
+// item `item` of the sweep = predator a's phase item (isph) or FADs item
+PF_DEV void mpa_plan_item(const MpaPhaseArgs& p, const MpaFadsArgs& f, bool isph, int a, int item, MpaJob* jobs, MpaRes* res) {
   const Grid& G = p.c.G;
   const int lane = lane_id();
-  const int item = blockIdx.x;
-  if (item >= 2 * p.n) return;
-  const bool isph = item < p.n;
-  const int a = isph ? item : item - p.n;
   MpaJob j; j.src = nullptr; j.n0 = 0; j.astart = 0; j.g0 = -1; j.g1 = p.m.target; j.kind = 0; j.aux = isph ? 4 : 0;
   unsigned long long pruned_n = 0;
   if (isph) {
@@ -1405,6 +1406,13 @@ __global__ __launch_bounds__(64) void k_mpa_plan(MpaSweepArgs q, MpaJob* jobs, M
     MpaRes r; r.n = 0; r.rc = 1; res[item] = r;
     if (pruned_n) atomicAdd(&p.c.cnt->pruned, pruned_n);
   }
+}
+__global__ __launch_bounds__(64) void k_mpa_plan(MpaSweepArgs q, MpaJob* jobs, MpaRes* res) {
+  const MpaPhaseArgs& p = q.ph;
+  const int item = blockIdx.x;
+  if (item >= 2 * p.n) return;
+  const bool isph = item < p.n;
+  mpa_plan_item(p, q.fd, isph, isph ? item : item - p.n, item, jobs, res);
 }
 
 struct MpaSearchArgs { Common c; const MpaJob* jobs; MpaRes* res; int n_items, path_cap; int* ph_cells; int* fd_cells; int n; };
@@ -1496,15 +1504,9 @@ __global__ __launch_bounds__(PR ? 128 : 64) __attribute__((amdgpu_waves_per_eu(3
   flush_counters(p.c.cnt, tot, 0, ovf, lane);
 }
 
-__global__ __launch_bounds__(64) void k_mpa_finish(MpaSweepArgs q, const MpaJob* jobs, const MpaRes* res) {
-  const MpaPhaseArgs& p = q.ph;
-  const MpaFadsArgs& f = q.fd;
+PF_DEV void mpa_finish_item(const MpaPhaseArgs& p, const MpaFadsArgs& f, bool isph, int a, int item, const MpaJob* jobs, const MpaRes* res) {
   const Grid& G = p.c.G;
   const int lane = lane_id();
-  const int item = blockIdx.x;
-  if (item >= 2 * p.n) return;
-  const bool isph = item < p.n;
-  const int a = isph ? item : item - p.n;
   const MpaJob j = jobs[item];
   const MpaRes r = res[item];
   int n = 0;
@@ -1547,13 +1549,17 @@ __global__ __launch_bounds__(64) void k_mpa_finish(MpaSweepArgs q, const MpaJob*
   }
   if (lane == 0 && n) atomicAdd(&p.c.cnt->path_cells, (unsigned long long)n);
 }
-// memory step (MPA.py:381-384) then FADs acceptance (:402 / :408) for predator a
-__global__ __launch_bounds__(64) void k_mpa_apply(int n, int path_cap, const int* slots, const int* c1_cells, const int* c1_len,
-                                                  const double* c1_stats, const int* c2_cells, const int* c2_len,
-                                                  const double* c2_stats, int* pop_cells, int* pop_len, double* pop_stats) {
-  const int a = blockIdx.x;
-  if (a >= n) return;
-  const int slot = slots[a];
+__global__ __launch_bounds__(64) void k_mpa_finish(MpaSweepArgs q, const MpaJob* jobs, const MpaRes* res) {
+  const MpaPhaseArgs& p = q.ph;
+  const int item = blockIdx.x;
+  if (item >= 2 * p.n) return;
+  const bool isph = item < p.n;
+  mpa_finish_item(p, q.fd, isph, isph ? item : item - p.n, item, jobs, res);
+}
+// memory step (MPA.py:381-384) then FADs acceptance (:402 / :408) for predator a (candidate rows a, population row slot)
+PF_DEV void mpa_apply_item(int a, int slot, int path_cap, const int* c1_cells, const int* c1_len,
+                           const double* c1_stats, const int* c2_cells, const int* c2_len,
+                           const double* c2_stats, int* pop_cells, int* pop_len, double* pop_stats) {
   double fit = pop_stats[(size_t)slot * 5 + 4];
   int take = 0;
   if (c1_stats[(size_t)a * 5 + 4] < fit) { take = 1; fit = c1_stats[(size_t)a * 5 + 4]; }
@@ -1566,11 +1572,16 @@ __global__ __launch_bounds__(64) void k_mpa_apply(int n, int path_cap, const int
   if (threadIdx.x < 5) pop_stats[(size_t)slot * 5 + threadIdx.x] = st[(size_t)a * 5 + threadIdx.x];
   if (threadIdx.x == 0) pop_len[slot] = L;
 }
+__global__ __launch_bounds__(64) void k_mpa_apply(int n, int path_cap, const int* slots, const int* c1_cells, const int* c1_len,
+                                                  const double* c1_stats, const int* c2_cells, const int* c2_len,
+                                                  const double* c2_stats, int* pop_cells, int* pop_len, double* pop_stats) {
+  const int a = blockIdx.x;
+  if (a >= n) return;
+  mpa_apply_item(a, slots[a], path_cap, c1_cells, c1_len, c1_stats, c2_cells, c2_len, c2_stats, pop_cells, pop_len, pop_stats);
+}
 
 // work estimates of the FADs detours (the phase items' come from k_mpa_propose): replay only the gating draws
-__global__ void k_plan_mpa_fads(MpaFadsArgs p, float* est) {
-  const int a = blockIdx.x * blockDim.x + threadIdx.x;
-  if (a >= p.n) return;
+PF_DEV void mpa_fads_est_item(const MpaFadsArgs& p, int a, float* est) {
   float e = 0.f;
   Rng g; g.init(p.seed, DOM_MPA_FADS, (unsigned long long)p.iter, (unsigned long long)p.gidx[a]);
   if (g.random() < p.m.fads && g.random() < p.CF) {
@@ -1579,6 +1590,11 @@ __global__ void k_plan_mpa_fads(MpaFadsArgs p, float* est) {
     if (p.c.G.occ[node] != 1) e = cell_dist(p.c.G, p.m.start, node) + cell_dist(p.c.G, node, p.m.target);
   }
   est[a] = e;
+}
+__global__ void k_plan_mpa_fads(MpaFadsArgs p, float* est) {
+  const int a = blockIdx.x * blockDim.x + threadIdx.x;
+  if (a >= p.n) return;
+  mpa_fads_est_item(p, a, est);
 }
 
 // memory step MPA.py:381-384
@@ -1623,10 +1639,11 @@ __global__ void k_sort_prep(int n, int mode, const double* vals, int stride, int
   else { key[i] = ~key_image_f64((double)est[i]); payload[i] = i; }
   rank[i] = 0u;
 }
-__global__ __launch_bounds__(64) void k_rank_count(int n, int jsplit, int jchunk, const unsigned long long* __restrict__ key,
-                                                   unsigned* __restrict__ rank) {
+// (block `blk` of one sort: the solo kernel's blockIdx.x, the segmented kernel's block within its segment -- pf_mpa_batch.h)
+PF_DEV void rank_count_block(unsigned blk, int n, int jsplit, int jchunk, const unsigned long long* __restrict__ key,
+                             unsigned* __restrict__ rank) {
   const int lane = lane_id();
-  const int tile = (int)(blockIdx.x / (unsigned)jsplit), sp = (int)(blockIdx.x - (unsigned)tile * (unsigned)jsplit);
+  const int tile = (int)(blk / (unsigned)jsplit), sp = (int)(blk - (unsigned)tile * (unsigned)jsplit);
   const int t0 = tile * 64, i = t0 + lane;
   const unsigned long long ki = i < n ? key[i] : ~0ull;
   int j = sp * jchunk;
@@ -1647,6 +1664,10 @@ __global__ __launch_bounds__(64) void k_rank_count(int n, int jsplit, int jchunk
   PF_RANK_RUN(j1, kj < ki)                                          // later positions: only strictly smaller keys
 #undef PF_RANK_RUN
   if (i < n && cnt) atomicAdd(&rank[i], cnt);
+}
+__global__ __launch_bounds__(64) void k_rank_count(int n, int jsplit, int jchunk, const unsigned long long* __restrict__ key,
+                                                   unsigned* __restrict__ rank) {
+  rank_count_block(blockIdx.x, n, jsplit, jchunk, key, rank);
 }
 __global__ void k_rank_scatter(int n, const unsigned* rank, const int* payload, int* out) {
   const int i = blockIdx.x * blockDim.x + threadIdx.x;
@@ -1687,6 +1708,9 @@ __global__ __launch_bounds__(1024) void k_mpa_local_view(int N, const int* gorde
     __syncthreads();
   }
 }
+
+// K MPA schools in one batched sweep (pf_mpa_batch_*): the school table and the batched forms of the kernels above
+#include "pf_mpa_batch.h"
 
 // ---- GA operators on the device (ga_solver.py:136-160, 186-205) ---------------------------------------
 // Tournament selection draws from ONE stream per generation (seed, DOM_GA_SELECT, gen, 0), slot after slot, with
@@ -1832,6 +1856,26 @@ struct pf_maaco_batch {
   int* d_best_rows = nullptr; int row_cap = 0;     // [K][row_cap]: colony c's overall best path, [0] = length
 };
 
+// K MPA schools on one handle (pf_mpa_batch_create): the school table, the bound tables, the memoised initial paths, the elites
+// and the sort scratch are the batch's own; the handle's search slots, work queue, job and proposal scratch (per call, stream
+// ordered) and stream are shared with the solo state (mpp, d_ds / d_dt, d_init_cells, the elite buffer), which it never touches.
+struct pf_mpa_batch {
+  pf_handle* h = nullptr;
+  bool ready = false;
+  pf_mpa_params mp = {}; pf_score_params sp = {};
+  int K = 0, N = 0;
+  std::vector<MpaSchool> tab; MpaSchool* d_tab = nullptr;   // host copy (doubt resolution) and the device table
+  double* d_bounds = nullptr;                                // [distinct cells][RC] Dijkstra tables, or null (mpa_bounds' conditions)
+  int* d_init_cells = nullptr; double* d_init_stats = nullptr; std::vector<int> init_len;   // [K][RC], [K][5]
+  int* d_elite_cells = nullptr; int* d_elite_len = nullptr; double* d_elite_stats = nullptr;   // [K][RC], [K], [K][5]
+  int* d_gidx = nullptr;                                     // 0 .. N - 1: a predator's stream index is its position in its school's list
+  unsigned long long* d_key = nullptr; int* d_pay = nullptr; unsigned* d_rank = nullptr;   // segmented sort scratch [K N]
+  double* d_rows = nullptr;                                  // [K][6] best rows
+  pf_counters last = {};                                     // counters of the batch's last sweep
+  long long overflow_total = 0, doubts_resolved = 0;
+  double create_ms[3] = {0, 0, 0};                           // what create spent: initial paths + scores, bound tables, total
+};
+
 struct pf_handle {
   int device = 0;
   hipStream_t stream = nullptr;
@@ -1871,6 +1915,7 @@ struct pf_handle {
   unsigned long long* d_bits = nullptr; size_t bits_words = 0; int dep_cap = 0;
   uint8_t* d_flag = nullptr;          // chunk flags of d_bits: [(RC + 63) / 64][bits_words] bytes (MaacoArgs::flag)
   std::vector<pf_maaco_batch*> maaco_batches;   // pf_maaco_batch_create's objects (freed by pf_destroy, invalidated by pf_update_grid)
+  std::vector<pf_mpa_batch*> mpa_batches;       // pf_mpa_batch_create's, likewise
   // MPA
   bool mpa_ready = false;
   pf_mpa_params mpp = {};
@@ -2028,12 +2073,15 @@ int pf_create(const uint8_t* grid, int32_t R, int32_t C, int32_t device, pf_hand
 }
 
 static void maaco_batch_free(pf_maaco_batch* b);
+static void mpa_batch_free(pf_mpa_batch* b);
 void pf_destroy(pf_handle* h) {
   if (!h) return;
   (void)hipSetDevice(h->device);
   if (h->stream) (void)hipStreamSynchronize(h->stream);
   for (pf_maaco_batch* b : h->maaco_batches) maaco_batch_free(b);
   h->maaco_batches.clear();
+  for (pf_mpa_batch* b : h->mpa_batches) mpa_batch_free(b);
+  h->mpa_batches.clear();
   if (h->comm && g_rccl.CommDestroy) { (void)hipStreamSynchronize(h->stream); g_rccl.CommDestroy(h->comm); h->comm = nullptr; }
   void* ptrs[] = {h->d_occ, h->d_mm_r1, h->d_mm_r0, h->d_mm_r1_nd, h->d_mm_r0_nd, h->d_d2near, h->d_rec, h->d_slot_state,
                   h->d_work, h->d_cnt, h->d_pen, h->d_tier2, h->d_tau, h->d_taua, h->d_eta, h->d_dep, h->d_tep, h->d_visit, h->d_visit_epoch,
@@ -2070,6 +2118,7 @@ int pf_update_grid(pf_handle* h, const uint8_t* grid) {
   h->obst_frac = -1.0;
   h->mpa_ready = false; h->maaco_ready = false;                     // their tables (initial path, bounds, tau / eta) belong to the old map
   for (pf_maaco_batch* b : h->maaco_batches) b->ready = false;      // (so do the batches': they only accept pf_maaco_batch_destroy)
+  for (pf_mpa_batch* b : h->mpa_batches) b->ready = false;          // (... pf_mpa_batch_destroy)
   if (h->d_ds) { (void)hipFree(h->d_ds); h->d_ds = nullptr; }
   if (h->d_dt) { (void)hipFree(h->d_dt); h->d_dt = nullptr; }
   return 0;
@@ -3318,8 +3367,8 @@ static MpaDev mpa_dev(const pf_handle* h) {
 }
 
 // ---- proposals: k_mpa_propose, then the host confirms the (expected: zero) doubtful ones with glibc ----
-static int mpa_launch_propose(pf_handle* h, MpaPhaseArgs& a, float* est) {
-  const int n = a.n;
+// the proposal and doubt-list scratch of a sweep over n predators, and its margins
+static int mpa_prop_scratch(pf_handle* h, MpaPhaseArgs& a, int n) {
   if (n > h->prop_cap) {
     if (h->d_prop) CK(hipFree(h->d_prop));
     if (h->d_doubt) CK(hipFree(h->d_doubt));
@@ -3328,6 +3377,11 @@ static int mpa_launch_propose(pf_handle* h, MpaPhaseArgs& a, float* est) {
   }
   a.prop = h->d_prop; a.doubt_n = h->d_doubt; a.doubt_list = h->d_doubt + 1; a.eps_log = g_doubt_log; a.eps_round = g_doubt_round;
   CK(hipMemsetAsync(h->d_doubt, 0, sizeof(int), h->stream));
+  return 0;
+}
+static int mpa_launch_propose(pf_handle* h, MpaPhaseArgs& a, float* est) {
+  const int n = a.n;
+  if (mpa_prop_scratch(h, a, n)) return -1;
   if (n > 0) hipLaunchKernelGGL(k_mpa_propose, dim3((n + 255) / 256), dim3(256), 0, h->stream, a, est);
   CK(hipGetLastError());
   return 0;
@@ -3372,51 +3426,60 @@ static int host_brownian(HostRng& g, int R, int C, int cur, int elite, double sc
 }
 // Recompute the proposals the device flagged (a decision within the margin of a libm disagreement) with the host's
 // libm and patch them in.  One small D2H (the count) per sweep; the rest only when the count is not zero.
-static int mpa_resolve_doubts(pf_handle* h, const MpaPhaseArgs& a) {
+static int mpa_doubt_list(pf_handle* h, const MpaPhaseArgs& a, std::vector<int>& list) {
   int nd = 0;
+  list.clear();
   if (d2h_one(h, a.doubt_n, &nd)) return -1;
   h->d2h_small += 1;
   if (nd <= 0) return 0;
-  std::vector<int> list((size_t)nd);
+  list.resize((size_t)nd);
   CK(hipMemcpyAsync(list.data(), a.doubt_list, sizeof(int) * (size_t)nd, hipMemcpyDeviceToHost, h->stream));
   CK(hipStreamSynchronize(h->stream));
+  return 0;
+}
+// predator a_ of the sweep `a` describes (a school's view of the launch, for a batch)
+static int mpa_resolve_one(pf_handle* h, const MpaPhaseArgs& a, int a_) {
   const int R = h->R, C = h->C;
   int elite_len = a.elite_len;
   if (a.elite_len_dev && d2h_one(h, a.elite_len_dev, &elite_len)) return -1;
-  for (int a_ : list) {
-    int gi = 0, slot = a_, preyL = 0;
-    if (a.ex_idx) { if (d2h_one(h, a.ex_agent + a_, &gi)) return -1; }
-    else { if (d2h_one(h, a.gidx + a_, &gi) || d2h_one(h, a.slot + a_, &slot)) return -1; }
-    if (d2h_one(h, a.pop_len + slot, &preyL)) return -1;
-    const int* prey = a.pop_cells + (size_t)slot * a.path_cap;
-    bool is_levy; double scale; const int* mod; int modL; const int* ref; int refL;
-    if (a.ex_idx) {
-      int lv = 0; double sc = 0.0;
-      if (d2h_one(h, a.ex_levy + a_, &lv) || d2h_one(h, a.ex_scale + a_, &sc)) return -1;
-      is_levy = lv != 0; scale = sc; mod = prey; modL = preyL; ref = a.elite_cells; refL = elite_len;
-    } else if (a.phase == 1) { is_levy = false; scale = a.m.P; mod = prey; modL = preyL; ref = a.elite_cells; refL = elite_len; }
-    else if (a.phase == 2) {
-      is_levy = gi < a.m.N / 2; scale = is_levy ? a.m.P : a.m.P * a.CF;
-      mod = is_levy ? prey : a.elite_cells; modL = is_levy ? preyL : elite_len;
-      ref = is_levy ? a.elite_cells : prey; refL = is_levy ? elite_len : preyL;
-    } else { is_levy = true; scale = a.m.P * a.CF; mod = a.elite_cells; modL = elite_len; ref = prey; refL = preyL; }
-    HostRng g(a.seed, DOM_MPA, (uint64_t)a.iter, (uint64_t)gi);
-    int idx;
-    if (a.ex_idx) { if (d2h_one(h, a.ex_idx + a_, &idx)) return -1; }
-    else { idx = (int)g.randint(0, modL - 2); (void)g.random(); }   // the gate passed (no libm in it): same draws
-    int cur = 0, inter;
-    if (d2h_one(h, mod + idx, &cur)) return -1;
-    if (is_levy) inter = host_levy(g, R, C, cur, scale, a.m.levy_beta, a.m.sigma);
-    else {
-      int en = -1;
-      if (refL > 0) { const int k = (int)g.randbelow((uint64_t)refL); if (d2h_one(h, ref + k, &en)) return -1; }
-      inter = host_brownian(g, R, C, cur, en, scale);
-    }
-    const int2 v = make_int2(idx, inter);
-    CK(hipMemcpyAsync(a.prop + a_, &v, sizeof(int2), hipMemcpyHostToDevice, h->stream));
-    CK(hipStreamSynchronize(h->stream));
-    h->doubts_resolved += 1;
+  int gi = 0, slot = a_, preyL = 0;
+  if (a.ex_idx) { if (d2h_one(h, a.ex_agent + a_, &gi)) return -1; }
+  else { if (d2h_one(h, a.gidx + a_, &gi) || d2h_one(h, a.slot + a_, &slot)) return -1; }
+  if (d2h_one(h, a.pop_len + slot, &preyL)) return -1;
+  const int* prey = a.pop_cells + (size_t)slot * a.path_cap;
+  bool is_levy; double scale; const int* mod; int modL; const int* ref; int refL;
+  if (a.ex_idx) {
+    int lv = 0; double sc = 0.0;
+    if (d2h_one(h, a.ex_levy + a_, &lv) || d2h_one(h, a.ex_scale + a_, &sc)) return -1;
+    is_levy = lv != 0; scale = sc; mod = prey; modL = preyL; ref = a.elite_cells; refL = elite_len;
+  } else if (a.phase == 1) { is_levy = false; scale = a.m.P; mod = prey; modL = preyL; ref = a.elite_cells; refL = elite_len; }
+  else if (a.phase == 2) {
+    is_levy = gi < a.m.N / 2; scale = is_levy ? a.m.P : a.m.P * a.CF;
+    mod = is_levy ? prey : a.elite_cells; modL = is_levy ? preyL : elite_len;
+    ref = is_levy ? a.elite_cells : prey; refL = is_levy ? elite_len : preyL;
+  } else { is_levy = true; scale = a.m.P * a.CF; mod = a.elite_cells; modL = elite_len; ref = prey; refL = preyL; }
+  HostRng g(a.seed, DOM_MPA, (uint64_t)a.iter, (uint64_t)gi);
+  int idx;
+  if (a.ex_idx) { if (d2h_one(h, a.ex_idx + a_, &idx)) return -1; }
+  else { idx = (int)g.randint(0, modL - 2); (void)g.random(); }   // the gate passed (no libm in it): same draws
+  int cur = 0, inter;
+  if (d2h_one(h, mod + idx, &cur)) return -1;
+  if (is_levy) inter = host_levy(g, R, C, cur, scale, a.m.levy_beta, a.m.sigma);
+  else {
+    int en = -1;
+    if (refL > 0) { const int k = (int)g.randbelow((uint64_t)refL); if (d2h_one(h, ref + k, &en)) return -1; }
+    inter = host_brownian(g, R, C, cur, en, scale);
   }
+  const int2 v = make_int2(idx, inter);
+  CK(hipMemcpyAsync(a.prop + a_, &v, sizeof(int2), hipMemcpyHostToDevice, h->stream));
+  CK(hipStreamSynchronize(h->stream));
+  h->doubts_resolved += 1;
+  return 0;
+}
+static int mpa_resolve_doubts(pf_handle* h, const MpaPhaseArgs& a) {
+  std::vector<int> list;
+  if (mpa_doubt_list(h, a, list)) return -1;
+  for (int a_ : list) if (mpa_resolve_one(h, a, a_)) return -1;
   return 0;
 }
 
@@ -3570,6 +3633,325 @@ int pf_mpa_iter_batch(pf_handle* h, int32_t phase, double CF, int32_t iter, uint
   DevCounters dc;
   if (end_batch(h, &dc)) return -1;
   CK(hipEventElapsedTime(&h->last_ms, h->ev0, h->ev1));
+  return 0;
+}
+
+// ---------------------------------------------------------------------------
+// K MPA schools in one batched sweep (pf_mpa_batch_*; kernels in pf_mpa_batch.h)
+// ---------------------------------------------------------------------------
+static void mpa_batch_free(pf_mpa_batch* b) {
+  void* ptrs[] = {b->d_tab, b->d_bounds, b->d_init_cells, b->d_init_stats, b->d_elite_cells, b->d_elite_len, b->d_elite_stats, b->d_gidx,
+                  b->d_key, b->d_pay, b->d_rank, b->d_rows};
+  for (void* p : ptrs) if (p) (void)hipFree(p);
+  delete b;
+}
+static int mpa_batch_check(pf_mpa_batch* b, const char* what) {
+  if (!b) return failmsg(nullptr, std::string(what) + ": null batch");
+  if (!b->ready) return failmsg(b->h, std::string(what) + ": the batch belongs to a replaced grid (pf_update_grid); destroy it");
+  return 0;
+}
+static double ms_since(const std::chrono::steady_clock::time_point& t0) {
+  return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+}
+
+int pf_mpa_batch_create(pf_handle* h, const pf_mpa_params* p, const pf_score_params* sp, int32_t K, const int32_t* starts,
+                        const int32_t* targets, const uint64_t* seeds, pf_mpa_batch** out) {
+  if (!h) return -2;
+  if (!p || !sp || !out || K < 1 || p->num_predators < 1 || !starts || !targets || !seeds) return failmsg(h, "pf_mpa_batch_create: bad arguments");
+  *out = nullptr;
+  const int N = p->num_predators, RC = h->RC;
+  if ((int64_t)K * N > (1 << 29)) return failmsg(h, "pf_mpa_batch_create: K * num_predators exceeds 2^29");
+  for (int k = 0; k < K; ++k)
+    if (starts[k] < 0 || starts[k] >= RC || targets[k] < 0 || targets[k] >= RC || h->h_occ[starts[k]] == 1 || h->h_occ[targets[k]] == 1)
+      return failmsg(h, "pf_mpa_batch_create: school " + std::to_string(k) + ": start / target out of range or on an obstacle");
+  const auto t_all = std::chrono::steady_clock::now();
+  CK(hipSetDevice(h->device));
+  // bound tables: one per distinct start or target cell (the graph is symmetric: a table serves as ds and as dt)
+  const bool bounds = !(RC > (1 << 22) || sp->w_turn < 0.0 || sp->w_safe < 0.0 || sp->diag_pen < 0.0);   // mpa_bounds' conditions
+  std::vector<int> cells, tab_s(K), tab_t(K);
+  auto table_of = [&](int cell) {
+    size_t i = 0;
+    while (i < cells.size() && cells[i] != cell) ++i;
+    if (i == cells.size()) cells.push_back(cell);
+    return (int)i;
+  };
+  for (int k = 0; k < K; ++k) { tab_s[k] = table_of(starts[k]); tab_t[k] = table_of(targets[k]); }
+  const size_t T = bounds ? cells.size() : 0;
+  const size_t need = (size_t)K * RC * 8 + T * RC * 8 + (size_t)K * N * 16 + (size_t)K * 256;
+  size_t free_b = 0, total_b = 0;
+  CK(hipMemGetInfo(&free_b, &total_b));
+  if (need > free_b / 10 * 9)
+    return failmsg(h, "pf_mpa_batch_create: " + std::to_string(K) + " schools need " + std::to_string(need >> 20) + " MiB of device memory, " +
+                          std::to_string(free_b >> 20) + " MiB are free");
+  if (ensure_slots(h, p->allow_diag, p->restrict_corner)) return -1;
+  pf_mpa_batch* b = new pf_mpa_batch();
+  b->h = h; b->mp = *p; b->sp = *sp; b->K = K; b->N = N;
+  b->mp.start = starts[0]; b->mp.target = targets[0];
+  int* d_q = nullptr;                                               // {start, target, len, status} x K for the initial searches
+  #define CKB(call) do { hipError_t e_ = (call); if (e_ != hipSuccess) { fail(h, #call, e_); if (d_q) (void)hipFree(d_q); mpa_batch_free(b); return -1; } } while (0)
+  #define RCB(call) do { if ((call) != 0) { if (d_q) (void)hipFree(d_q); mpa_batch_free(b); return -1; } } while (0)
+  CKB(hipMalloc(&b->d_tab, sizeof(MpaSchool) * (size_t)K));
+  CKB(hipMalloc(&b->d_init_cells, sizeof(int) * (size_t)K * RC)); CKB(hipMalloc(&b->d_init_stats, sizeof(double) * 5 * (size_t)K));
+  CKB(hipMalloc(&b->d_elite_cells, sizeof(int) * (size_t)K * RC)); CKB(hipMalloc(&b->d_elite_len, sizeof(int) * (size_t)K));
+  CKB(hipMalloc(&b->d_elite_stats, sizeof(double) * 5 * (size_t)K));
+  CKB(hipMalloc(&b->d_gidx, sizeof(int) * (size_t)N));
+  CKB(hipMalloc(&b->d_key, sizeof(unsigned long long) * (size_t)K * N)); CKB(hipMalloc(&b->d_pay, sizeof(int) * (size_t)K * N));
+  CKB(hipMalloc(&b->d_rank, sizeof(unsigned) * (size_t)K * N));
+  CKB(hipMalloc(&b->d_rows, sizeof(double) * 6 * (size_t)K));
+  CKB(hipMalloc(&d_q, sizeof(int) * 4 * (size_t)K));
+  {
+    std::vector<int> gi(N);
+    for (int i = 0; i < N; ++i) gi[i] = i;
+    CKB(hipMemcpyAsync(b->d_gidx, gi.data(), sizeof(int) * (size_t)N, hipMemcpyHostToDevice, h->stream));
+    CKB(hipStreamSynchronize(h->stream));
+  }
+  // the K initial paths MPA._generate_initial_path() = _a_star(start, target) (MPA.py:154) as ONE search batch, scored as one
+  const auto t_init = std::chrono::steady_clock::now();
+  std::vector<int> hq(4 * (size_t)K, 0);
+  for (int k = 0; k < K; ++k) { hq[k] = starts[k]; hq[K + k] = targets[k]; }
+  CKB(hipMemcpyAsync(d_q, hq.data(), sizeof(int) * hq.size(), hipMemcpyHostToDevice, h->stream));
+  RCB(pf_astar_batch(h, PF_ASTAR_MPA, p->allow_diag, p->restrict_corner, K, d_q, d_q + K, nullptr, nullptr, RC, b->d_init_cells, d_q + 2 * K,
+                     d_q + 3 * K, nullptr));
+  CKB(hipMemcpyAsync(hq.data(), d_q, sizeof(int) * hq.size(), hipMemcpyDeviceToHost, h->stream));
+  CKB(hipStreamSynchronize(h->stream));
+  b->init_len.resize(K);
+  for (int k = 0; k < K; ++k) b->init_len[k] = hq[3 * K + k] == 0 ? hq[2 * K + k] : 0;
+  RCB(pf_score_batch(h, sp, K, RC, b->d_init_cells, d_q + 2 * K, b->d_init_stats));
+  CKB(hipStreamSynchronize(h->stream));
+  b->create_ms[0] = ms_since(t_init);
+  (void)hipFree(d_q); d_q = nullptr;
+  // the bound tables (host Dijkstra over the device-built move masks, as mpa_bounds)
+  const auto t_bounds = std::chrono::steady_clock::now();
+  if (T) {
+    const Grid G = make_grid(h, p->allow_diag, p->restrict_corner);
+    std::vector<uint8_t> mm(RC);
+    CKB(hipMemcpy(mm.data(), G.mm, RC, hipMemcpyDeviceToHost));
+    CKB(hipMalloc(&b->d_bounds, sizeof(double) * T * RC));
+    std::vector<double> dist;
+    for (size_t i = 0; i < T; ++i) {
+      dijkstra_host(h, mm, cells[i], dist);
+      CKB(hipMemcpy(b->d_bounds + i * RC, dist.data(), sizeof(double) * (size_t)RC, hipMemcpyHostToDevice));
+    }
+  }
+  b->create_ms[1] = ms_since(t_bounds);
+  b->tab.resize(K);
+  for (int k = 0; k < K; ++k) {
+    MpaSchool& s = b->tab[k];
+    s.seed = seeds[k]; s.start = starts[k]; s.target = targets[k];
+    s.ds = T ? b->d_bounds + (size_t)tab_s[k] * RC : nullptr; s.dt = T ? b->d_bounds + (size_t)tab_t[k] * RC : nullptr;
+    s.init_cells = b->d_init_cells + (size_t)k * RC; s.init_stats = b->d_init_stats + (size_t)k * 5; s.init_len = b->init_len[k]; s.pad_ = 0;
+    s.elite_cells = b->d_elite_cells + (size_t)k * RC; s.elite_len = b->d_elite_len + k; s.elite_stats = b->d_elite_stats + (size_t)k * 5;
+  }
+  CKB(hipMemcpyAsync(b->d_tab, b->tab.data(), sizeof(MpaSchool) * (size_t)K, hipMemcpyHostToDevice, h->stream));
+  CKB(hipMemsetAsync(b->d_elite_len, 0, sizeof(int) * (size_t)K, h->stream));
+  CKB(hipStreamSynchronize(h->stream));
+  #undef CKB
+  #undef RCB
+  b->create_ms[2] = ms_since(t_all);
+  b->ready = true;
+  h->mpa_batches.push_back(b);
+  *out = b;
+  return 0;
+}
+
+void pf_mpa_batch_destroy(pf_mpa_batch* b) {
+  if (!b) return;
+  pf_handle* h = b->h;
+  auto it = std::find(h->mpa_batches.begin(), h->mpa_batches.end(), b);
+  if (it == h->mpa_batches.end()) return;                          // (not this handle's: already gone)
+  h->mpa_batches.erase(it);
+  (void)hipSetDevice(h->device);
+  (void)hipStreamSynchronize(h->stream);
+  mpa_batch_free(b);
+}
+
+int pf_mpa_batch_init_path(pf_mpa_batch* b, int32_t k, int32_t* cells_out, int32_t cap, int32_t* len_out, double* stats5) {
+  if (mpa_batch_check(b, "pf_mpa_batch_init_path")) return -2;
+  pf_handle* h = b->h;
+  if (k < 0 || k >= b->K || !len_out || cap < 0 || (cap > 0 && !cells_out)) return failmsg(h, "pf_mpa_batch_init_path: bad arguments");
+  CK(hipSetDevice(h->device));
+  const int L = b->init_len[k];
+  *len_out = L;
+  if (L > cap) return failmsg(h, "pf_mpa_batch_init_path: the buffer is too small");
+  if (L > 0) CK(hipMemcpyAsync(cells_out, b->d_init_cells + (size_t)k * h->RC, sizeof(int) * (size_t)L, hipMemcpyDeviceToHost, h->stream));
+  if (stats5) CK(hipMemcpyAsync(stats5, b->d_init_stats + (size_t)k * 5, sizeof(double) * 5, hipMemcpyDeviceToHost, h->stream));
+  CK(hipStreamSynchronize(h->stream));
+  return 0;
+}
+
+int pf_mpa_batch_create_ms(pf_mpa_batch* b, double* out3) {
+  if (!b || !out3) return -2;
+  for (int i = 0; i < 3; ++i) out3[i] = b->create_ms[i];
+  return 0;
+}
+
+static MpaSchools mpa_batch_schools(const pf_mpa_batch* b) {
+  MpaSchools ms; ms.tab = b->d_tab; ms.K = b->K; ms.N = b->N; ms.prune = g_mpa_prune && b->d_bounds ? 1 : 0;
+  return ms;
+}
+
+int pf_mpa_batch_sort(pf_mpa_batch* b, const double* d_pop_stats, int32_t* d_order) {
+  if (mpa_batch_check(b, "pf_mpa_batch_sort")) return -2;
+  pf_handle* h = b->h;
+  if (!d_pop_stats || !d_order) return failmsg(h, "pf_mpa_batch_sort: bad arguments");
+  CK(hipSetDevice(h->device));
+  const int K = b->K, n = b->N;
+  if (n <= 1) return 0;
+  const int nb = (int)(((size_t)K * n + 255) / 256);
+  hipLaunchKernelGGL(k_sort_prep_seg<>, dim3(nb), dim3(256), 0, h->stream, K, n, d_pop_stats, 5, 4, (const int*)d_order, b->d_key, b->d_pay, b->d_rank);
+  // (rank_sort's split, with the ~8192 wavefronts shared between the K segments)
+  const int tiles = (n + 63) / 64;
+  int jsplit = 8192 / (tiles * K); const int jmax = (n + 255) / 256; if (jsplit > jmax) jsplit = jmax; if (jsplit < 1) jsplit = 1;
+  const int jchunk = (n + jsplit - 1) / jsplit;
+  const int per_seg = tiles * jsplit;
+  hipLaunchKernelGGL(k_rank_count_seg<>, dim3((unsigned)per_seg * (unsigned)K), dim3(64), 0, h->stream, n, per_seg, jsplit, jchunk,
+                     (const unsigned long long*)b->d_key, b->d_rank);
+  hipLaunchKernelGGL(k_rank_scatter_seg<>, dim3(nb), dim3(256), 0, h->stream, K, n, (const unsigned*)b->d_rank, (const int*)b->d_pay, d_order);
+  CK(hipGetLastError());
+  return 0;
+}
+
+int pf_mpa_batch_pick_elite(pf_mpa_batch* b, int32_t path_cap, const int32_t* d_pop_cells, const int32_t* d_pop_len,
+                            const double* d_pop_stats, const int32_t* d_order) {
+  if (mpa_batch_check(b, "pf_mpa_batch_pick_elite")) return -2;
+  pf_handle* h = b->h;
+  if (path_cap < 1 || path_cap > h->RC || !d_pop_cells || !d_pop_len || !d_pop_stats || !d_order) return failmsg(h, "pf_mpa_batch_pick_elite: bad arguments");
+  CK(hipSetDevice(h->device));
+  hipLaunchKernelGGL(k_mpa_pick_elite_batch<>, dim3(b->K), dim3(256), 0, h->stream, mpa_batch_schools(b), path_cap, d_pop_cells, d_pop_len,
+                     d_pop_stats, d_order);
+  CK(hipGetLastError());
+  return 0;
+}
+
+int pf_mpa_batch_best_rows(pf_mpa_batch* b, const double* d_pop_stats, const int32_t* d_order, double* out) {
+  if (mpa_batch_check(b, "pf_mpa_batch_best_rows")) return -2;
+  pf_handle* h = b->h;
+  if (!d_pop_stats || !d_order || !out) return failmsg(h, "pf_mpa_batch_best_rows: bad arguments");
+  CK(hipSetDevice(h->device));
+  hipLaunchKernelGGL(k_mpa_best_rows<>, dim3((b->K + 63) / 64), dim3(64), 0, h->stream, b->K, b->N, d_pop_stats, d_order, b->d_rows);
+  CK(hipGetLastError());
+  const size_t nb = sizeof(double) * 6 * (size_t)b->K;
+  CK(hipMemcpyAsync(out, b->d_rows, nb, hipMemcpyDeviceToHost, h->stream));
+  CK(hipStreamSynchronize(h->stream));
+  if (nb <= 128) h->d2h_small += 1; else { h->d2h_bulk += 1; h->d2h_bulk_bytes += (long long)nb; }
+  return 0;
+}
+
+int pf_mpa_batch_read_path(pf_mpa_batch* b, int32_t k, int32_t slot, int32_t path_cap, const int32_t* d_pop_cells, const int32_t* d_pop_len,
+                           int32_t* cells_out, int32_t cap, int32_t* len_out) {
+  if (mpa_batch_check(b, "pf_mpa_batch_read_path")) return -2;
+  pf_handle* h = b->h;
+  if (k < 0 || k >= b->K || slot < 0 || slot >= b->N || path_cap < 1 || !d_pop_cells || !d_pop_len || !len_out || cap < 0 || (cap > 0 && !cells_out))
+    return failmsg(h, "pf_mpa_batch_read_path: bad arguments");
+  CK(hipSetDevice(h->device));
+  const size_t row = (size_t)k * b->N + slot;
+  int L = 0;
+  if (d2h_one(h, d_pop_len + row, &L)) return -1;
+  h->d2h_small += 1;
+  if (L < 0 || L > path_cap) return failmsg(h, "pf_mpa_batch_read_path: corrupt row");
+  *len_out = L;
+  if (L > cap) return failmsg(h, "pf_mpa_batch_read_path: the buffer is too small");
+  if (L > 0 && d2h_bytes(h, d_pop_cells + row * path_cap, cells_out, sizeof(int) * (size_t)L)) return -1;
+  if (L > 0) { h->d2h_bulk += 1; h->d2h_bulk_bytes += (long long)sizeof(int) * L; }
+  return 0;
+}
+
+int pf_mpa_batch_counters(pf_mpa_batch* b, pf_counters* out, int64_t* overflow_total, int64_t* doubts_resolved) {
+  if (!b || !out) return -2;
+  *out = b->last;
+  if (overflow_total) *overflow_total = b->overflow_total;
+  if (doubts_resolved) *doubts_resolved = b->doubts_resolved;
+  return 0;
+}
+
+// One iteration's device work for all K schools (pf_mpa_iter_batch for each, in one queue): proposals and FADs estimates of the
+// K N predators, the doubtful proposals confirmed against their own school, ONE longest-first queue over the 2 K N items, plan,
+// k_mpa_search (unchanged), finish, apply.  One wait (the counters); the doubt count is the other small read.
+int pf_mpa_batch_iterate(pf_mpa_batch* b, int32_t phase, double CF, int32_t iter, int32_t path_cap, int32_t* d_pop_cells,
+                         int32_t* d_pop_len, double* d_pop_stats, const int32_t* d_order, int32_t* d_c1_cells, int32_t* d_c1_len,
+                         double* d_c1_stats, int32_t* d_c2_cells, int32_t* d_c2_len, double* d_c2_stats, int32_t* d_status) {
+  if (mpa_batch_check(b, "pf_mpa_batch_iterate")) return -2;
+  pf_handle* h = b->h;
+  if (phase < 1 || phase > 3 || path_cap < 2 || path_cap > h->RC || !d_pop_cells || !d_pop_len || !d_pop_stats || !d_order || !d_c1_cells ||
+      !d_c1_len || !d_c1_stats || !d_c2_cells || !d_c2_len || !d_c2_stats || !d_status)
+    return failmsg(h, "pf_mpa_batch_iterate: bad arguments");
+  const int K = b->K, N = b->N, KN = K * N;
+  if (ensure_slots(h, b->mp.allow_diag, b->mp.restrict_corner)) return -1;
+  const MpaSchools ms = mpa_batch_schools(b);
+  // the launch arguments every school's view starts from: row 0 of the buffers; start / target / seed / bounds / elite / initial
+  // path come from the school table (school_view)
+  MpaSweepArgs a;
+  a.ph.c = make_common(h, b->mp.allow_diag, b->mp.restrict_corner, 16, 0);
+  if (make_scorep(h, &b->sp, &a.ph.sp)) return -1;
+  MpaDev m; m.P = b->mp.P_const; m.levy_beta = b->mp.levy_beta; m.sigma = b->mp.levy_sigma; m.fads = b->mp.FADs_rate;
+  m.N = N; m.start = -1; m.target = -1; m.ds = nullptr; m.dt = nullptr;
+  a.ph.m = m; a.ph.phase = phase; a.ph.iter = iter; a.ph.CF = CF; a.ph.seed = 0; a.ph.n = N; a.ph.path_cap = path_cap;
+  a.ph.pop_cells = d_pop_cells; a.ph.pop_len = d_pop_len; a.ph.pop_stats = d_pop_stats; a.ph.gidx = b->d_gidx; a.ph.slot = d_order;
+  a.ph.elite_cells = nullptr; a.ph.elite_len = -1; a.ph.elite_stats = nullptr; a.ph.elite_len_dev = nullptr;
+  a.ph.out_cells = d_c1_cells; a.ph.out_len = d_c1_len; a.ph.out_stats = d_c1_stats; a.ph.status = d_status;
+  a.ph.ex_idx = nullptr; a.ph.ex_levy = nullptr; a.ph.ex_scale = nullptr; a.ph.ex_agent = nullptr;
+  a.fd.c = a.ph.c; a.fd.sp = a.ph.sp; a.fd.m = m; a.fd.iter = iter; a.fd.CF = CF; a.fd.seed = 0; a.fd.n = N; a.fd.path_cap = path_cap;
+  a.fd.pop_cells = d_pop_cells; a.fd.pop_len = d_pop_len; a.fd.pop_stats = d_pop_stats; a.fd.gidx = b->d_gidx; a.fd.slot = d_order;
+  a.fd.tmp_cells = nullptr; a.fd.status = d_status;
+  a.fd.init_cells = nullptr; a.fd.init_len = 0; a.fd.init_stats = nullptr;
+  a.fd.cand_cells = d_c2_cells; a.fd.cand_len = d_c2_len; a.fd.cand_stats = d_c2_stats;
+  int prc = 0;
+  if (make_queue(h, 2 * KN, [&](float* est) {
+        prc = mpa_prop_scratch(h, a.ph, KN);
+        if (prc) return;
+        hipLaunchKernelGGL(k_mpa_propose_batch<>, dim3((KN + 255) / 256), dim3(256), 0, h->stream, a.ph, ms, est);
+        hipLaunchKernelGGL(k_plan_mpa_fads_batch<>, dim3((KN + 255) / 256), dim3(256), 0, h->stream, a.fd, ms, est + KN);
+      })) return -1;
+  if (prc) return -1;
+  {
+    // doubtful proposals: predator g of the batch is predator g % N of school g / N -- its elite, its seed, its rows
+    std::vector<int> list;
+    if (mpa_doubt_list(h, a.ph, list)) return -1;
+    const long long before = h->doubts_resolved;
+    for (int g : list) {
+      const int k = g / N;
+      MpaPhaseArgs v = a.ph;
+      school_view(v, b->tab[k], ms, k);
+      if (mpa_resolve_one(h, v, g - k * N)) return -1;
+    }
+    b->doubts_resolved += h->doubts_resolved - before;
+  }
+  a.ph.c.queue = h->d_queue; a.fd.c.queue = h->d_queue;
+  const int S = kLdsS;
+  a.ph.c.S = S; a.fd.c.S = S; a.ph.c.retry = 0; a.fd.c.retry = 0;
+  if (2 * KN > h->job_cap) {
+    if (h->d_jobs) CK(hipFree(h->d_jobs));
+    if (h->d_jres) CK(hipFree(h->d_jres));
+    h->d_jobs = nullptr; h->d_jres = nullptr; h->job_cap = 0;
+    CK(hipMalloc(&h->d_jobs, sizeof(MpaJob) * 2 * (size_t)KN)); CK(hipMalloc(&h->d_jres, sizeof(MpaRes) * 2 * (size_t)KN));
+    h->job_cap = 2 * KN;
+  }
+  MpaJob* jobs = (MpaJob*)h->d_jobs; MpaRes* jres = (MpaRes*)h->d_jres;
+  MpaSearchArgs sa;
+  sa.c = a.ph.c; sa.jobs = jobs; sa.res = jres; sa.n_items = 2 * KN; sa.path_cap = path_cap; sa.ph_cells = d_c1_cells; sa.fd_cells = d_c2_cells; sa.n = KN;
+  const size_t lds = open_bytes(S);                                 // (one-wave searches: the two-wave engine is a solo experiment)
+  CK(hipFuncSetAttribute((const void*)k_mpa_search<false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+  int per_cu = (int)((160 * 1024) / lds); if (per_cu > kWavesPerCU) per_cu = kWavesPerCU; if (per_cu < 1) per_cu = 1;
+  int grid = (h->nslots / kSlotsPerCU) * per_cu; if (grid > 2 * KN) grid = 2 * KN; if (grid > h->nslots) grid = h->nslots;
+  CK(hipMemsetAsync(h->d_work, 0, sizeof(int), h->stream));
+  CK(hipMemsetAsync(h->d_cnt, 0, sizeof(DevCounters), h->stream));
+  hipLaunchKernelGGL(k_mpa_plan_batch<>, dim3(2 * KN), dim3(64), 0, h->stream, a, ms, jobs, jres);
+  CK(hipGetLastError());
+  CK(hipEventRecord(h->ev0, h->stream));
+  hipLaunchKernelGGL(k_mpa_search<false>, dim3(grid), dim3(64), lds, h->stream, sa);
+  CK(hipGetLastError());
+  CK(hipEventRecord(h->ev1, h->stream));
+  hipLaunchKernelGGL(k_mpa_finish_batch<>, dim3(2 * KN), dim3(64), 0, h->stream, a, ms, (const MpaJob*)jobs, (const MpaRes*)jres);
+  CK(hipGetLastError());
+  hipLaunchKernelGGL(k_mpa_apply_batch<>, dim3(KN), dim3(64), 0, h->stream, KN, N, path_cap, d_order, (const int*)d_c1_cells, (const int*)d_c1_len,
+                     (const double*)d_c1_stats, (const int*)d_c2_cells, (const int*)d_c2_len, (const double*)d_c2_stats, d_pop_cells, d_pop_len,
+                     d_pop_stats);
+  CK(hipGetLastError());
+  DevCounters dc;
+  if (end_batch(h, &dc)) return -1;
+  CK(hipEventElapsedTime(&h->last_ms, h->ev0, h->ev1));
+  b->last = h->last;
+  b->overflow_total += (long long)dc.overflow;
   return 0;
 }
 

@@ -13,3 +13,4 @@ from .solvers import AStarSolver, DijkstraSolver, GASolver, PSOSolver, BasePathf
 from .maaco import MAACO  # noqa: F401
 from .maaco_batch import MAACOBatch, MaacoColony  # noqa: F401
 from .mpa import MPA  # noqa: F401
+from .mpa_batch import MPABatch, MpaSchool  # noqa: F401

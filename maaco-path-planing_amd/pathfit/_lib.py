@@ -130,6 +130,16 @@ SYMBOLS = {
     "pf_maaco_batch_best_path": (C.c_int, [_vp, _i32, _vp, _i32, C.POINTER(_i32)]),
     "pf_maaco_batch_get_pheromone": (C.c_int, [_vp, _i32, _vp]),
     "pf_maaco_batch_set_pheromone": (C.c_int, [_vp, _i32, _vp]),
+    "pf_mpa_batch_create": (C.c_int, [_vp, C.POINTER(MpaParams), C.POINTER(ScoreParams), _i32, _vp, _vp, _vp, C.POINTER(_vp)]),
+    "pf_mpa_batch_destroy": (None, [_vp]),
+    "pf_mpa_batch_init_path": (C.c_int, [_vp, _i32, _vp, _i32, C.POINTER(_i32), _vp]),
+    "pf_mpa_batch_create_ms": (C.c_int, [_vp, _vp]),
+    "pf_mpa_batch_sort": (C.c_int, [_vp, _vp, _vp]),
+    "pf_mpa_batch_pick_elite": (C.c_int, [_vp, _i32, _vp, _vp, _vp, _vp]),
+    "pf_mpa_batch_iterate": (C.c_int, [_vp, _i32, _dbl, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "pf_mpa_batch_best_rows": (C.c_int, [_vp, _vp, _vp, _vp]),
+    "pf_mpa_batch_read_path": (C.c_int, [_vp, _i32, _i32, _i32, _vp, _vp, _vp, _i32, C.POINTER(_i32)]),
+    "pf_mpa_batch_counters": (C.c_int, [_vp, C.POINTER(Counters), C.POINTER(_i64), C.POINTER(_i64)]),
 }
 
 
