@@ -1948,6 +1948,17 @@ static int fail(pf_handle* h, const char* what, hipError_t e) {
 }
 static int failmsg(pf_handle* h, const std::string& m) { if (h) h->err = m; else g_create_err = m; return -2; }
 #define CK(call) do { hipError_t e_ = (call); if (e_ != hipSuccess) return fail(h, #call, e_); } while (0)
+// pf_*_batch_create: a failed step (a HIP call, or a library call that has set its own message) runs the function's undo()
+static bool failed(pf_handle* h, const char* what, hipError_t e) { if (e != hipSuccess) fail(h, what, e); return e != hipSuccess; }
+static bool failed(pf_handle*, const char*, int rc) { return rc != 0; }
+#define CKB(call) do { if (failed(h, #call, (call))) { undo(); return -1; } } while (0)
+// a batch object handed in through the C-ABI (pf_maaco_batch / pf_mpa_batch)
+template <typename Batch>
+static int batch_check(Batch* b, const char* what) {
+  if (!b) return failmsg(nullptr, std::string(what) + ": null batch");
+  if (!b->ready) return failmsg(b->h, std::string(what) + ": the batch belongs to a replaced grid (pf_update_grid); destroy it");
+  return 0;
+}
 
 // RCCL entry points, resolved from librccl on first use (see pf_comm_* at the end of the file)
 namespace {
@@ -2269,6 +2280,13 @@ static int make_queue(pf_handle* h, int n, Plan plan) {
   return rank_sort(h, n, 1, nullptr, 0, 0, nullptr, h->d_est, h->d_queue);
 }
 
+// workgroups of a search kernel that takes `lds` bytes of LDS each, for n items: what stays resident, one per search slot at most
+static int search_grid(const pf_handle* h, size_t lds, int n) {
+  int per_cu = (int)((160 * 1024) / lds); if (per_cu > kWavesPerCU) per_cu = kWavesPerCU; if (per_cu < 1) per_cu = 1;
+  int grid = (h->nslots / kSlotsPerCU) * per_cu; if (grid > n) grid = n; if (grid > h->nslots) grid = h->nslots;
+  return grid;
+}
+
 template <typename KArgs, typename Kern>
 static int launch_with_retry(pf_handle* h, Kern kern, KArgs& args, int n, bool two_wave = false) {
   if (n <= 0) return 0;
@@ -2280,8 +2298,7 @@ static int launch_with_retry(pf_handle* h, Kern kern, KArgs& args, int n, bool t
   const size_t lds = open_bytes(S);
 #endif
   CK(hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-  int per_cu = (int)((160 * 1024) / lds); if (per_cu > kWavesPerCU) per_cu = kWavesPerCU; if (per_cu < 1) per_cu = 1;
-  int grid = (h->nslots / kSlotsPerCU) * per_cu; if (grid > n) grid = n; if (grid > h->nslots) grid = h->nslots;
+  const int grid = search_grid(h, lds, n);
   CK(hipMemsetAsync(h->d_work, 0, sizeof(int), h->stream));
   CK(hipMemsetAsync(h->d_cnt, 0, sizeof(DevCounters), h->stream));
   CK(hipEventRecord(h->ev0, h->stream));
@@ -2594,15 +2611,18 @@ int pf_selftest_rng(pf_handle* h, uint64_t seed, uint64_t dom, uint64_t it, uint
 // ---------------------------------------------------------------------------
 static double hdist(int r1, int c1, int r2, int c2) { long dr = r1 - r2, dc = c1 - c2; return sqrt((double)(dr * dr + dc * dc)); }
 
-static int maaco_refresh_taua(pf_handle* h) {
+// the tau^alpha tables of K colonies laid out [K][RC]: the solo state's one, a batch's K, or one colony of a batch at its offset
+static int maaco_refresh_taua(pf_handle* h, double alpha, const double* d_tau, double* d_taua, int K = 1) {
   // alpha != 1: tau^alpha must be libm pow to match the reference (MAACO.py:238); refreshed on the host
-  if (h->mp.alpha == 1.0) return 0;
+  if (alpha == 1.0) return 0;                                       // (nothing to do, nothing waits; d_taua may be null)
   std::vector<double> t(h->RC);
-  CK(hipMemcpyAsync(t.data(), h->d_tau, sizeof(double) * h->RC, hipMemcpyDeviceToHost, h->stream));
-  CK(hipStreamSynchronize(h->stream));
-  for (int i = 0; i < h->RC; ++i) t[i] = pow(t[i], h->mp.alpha);
-  CK(hipMemcpyAsync(h->d_taua, t.data(), sizeof(double) * h->RC, hipMemcpyHostToDevice, h->stream));
-  CK(hipStreamSynchronize(h->stream));
+  for (int c = 0; c < K; ++c, d_tau += h->RC, d_taua += h->RC) {
+    CK(hipMemcpyAsync(t.data(), d_tau, sizeof(double) * h->RC, hipMemcpyDeviceToHost, h->stream));
+    CK(hipStreamSynchronize(h->stream));
+    for (int i = 0; i < h->RC; ++i) t[i] = pow(t[i], alpha);
+    CK(hipMemcpyAsync(d_taua, t.data(), sizeof(double) * h->RC, hipMemcpyHostToDevice, h->stream));
+    CK(hipStreamSynchronize(h->stream));
+  }
   return 0;
 }
 
@@ -2668,7 +2688,7 @@ int pf_maaco_setup(pf_handle* h, const pf_maaco_params* p) {
   CK(hipFuncSetAttribute((const void*)k_tau_update, hipFuncAttributeMaxDynamicSharedMemorySize, 2 * PF_UPD_CHUNK * (int)sizeof(double)));
   h->maaco_ready = true;
   if (h->d_best_row) CK(hipMemsetAsync(h->d_best_row, 0, sizeof(int), h->stream));   // a new colony has no best path yet
-  return maaco_refresh_taua(h);
+  return maaco_refresh_taua(h, h->mp.alpha, h->d_tau, h->d_taua);
 }
 
 static double maaco_q0(int it, int K, double q0_initial) {          // MAACO.py:212-226
@@ -2708,34 +2728,71 @@ static int maaco_ensure_bits(pf_handle* h, int n) {
   // one, and an entry beyond the batch is never read -- its bits are zero)
   return 0;
 }
+// the MaacoArgs fields a solo walk and a batched one fill alike: the grid, the handle's tabu slot pool, the iteration and the
+// output columns.  The caller adds its tables (tau / eta), its control block, start / target / seed / ants and its marks.
+static MaacoArgs maaco_walk_args(pf_handle* h, const pf_maaco_params& mp, int32_t iter, int32_t path_cap, int32_t* d_cells,
+                                 int32_t* d_len, double* d_plen, int32_t* d_turns, int32_t* d_status) {
+  MaacoArgs a;
+  a.G = make_grid(h, 1, 1);
+  a.visit = h->d_visit; a.slot_epoch = h->d_visit_epoch;
+  a.wpr = (h->C + 15) >> 4; a.vstride = h->R * a.wpr;
+  a.iter = iter; a.num_iterations = mp.num_iterations;
+  a.q0 = maaco_q0(iter, mp.num_iterations, mp.q0_initial);
+  a.path_cap = path_cap;
+  a.cells = d_cells; a.len = d_len; a.plen = d_plen; a.turns = d_turns; a.status = d_status;
+  a.Q = mp.Q; a.groups = g_maaco_groups;
+  return a;
+}
+// Enqueue the walk of the a.n ants `a` describes (nothing waits): one colony's, or with `mc` the ants of the a.n / mc->nper colonies
+// of a batch, whose tables lie colony after colony behind a.tau / a.eta / d_tep.  The kernel choice follows the number of ants of
+// the walk, whichever colonies they belong to.
+static int maaco_launch_walk(pf_handle* h, MaacoArgs& a, const MaacoColonies* mc, double* d_tep) {
+  a.tep = d_tep;
+  // eight ants per wavefront (k_maaco_walk8) once the batch can fill the chip that way; else one per wave
+  const bool pack8 = a.n >= g_maaco_pack8_min;
+  int grid = pack8 ? h->maaco_slots / 8 : (h->maaco_slots < 8192 ? h->maaco_slots : 8192);
+  const int need = pack8 ? (a.n + a.groups - 1) / a.groups : a.n; if (grid > need) grid = need;
+  if (g_tabu_epoch >= 0) {                                          // one-shot: later batches carry on from there
+    CK(hipMemsetD32Async((hipDeviceptr_t)h->d_visit_epoch, g_tabu_epoch, (size_t)h->maaco_slots, h->stream));
+    g_tabu_epoch = -1;
+  }
+  const int nb = (h->RC + 255) / 256;
+  if (pack8 && !mc) hipLaunchKernelGGL(k_pack_tep, dim3(nb), dim3(256), 0, h->stream, h->RC, a.tau, a.eta, d_tep);
+  else if (pack8) hipLaunchKernelGGL(k_pack_tep_batch, dim3(nb, a.n / mc->nper), dim3(256), 0, h->stream, h->RC, a.tau, a.eta, mc->eta_of, d_tep);
+  CK(hipEventRecord(h->ev0, h->stream));
+  // (the load-ahead form when the batch leaves every SIMD at most one wavefront: see k_maaco_walk8)
+  const bool ahead = g_maaco_ahead < 0 ? grid <= h->maaco_cus * 4 : g_maaco_ahead != 0;
+  if (!mc) {
+    if (pack8 && ahead) hipLaunchKernelGGL(k_maaco_walk8<true>, dim3(grid), dim3(64), 0, h->stream, a);
+    else if (pack8) hipLaunchKernelGGL(k_maaco_walk8<false>, dim3(grid), dim3(64), 0, h->stream, a);
+    else hipLaunchKernelGGL(k_maaco_walk, dim3(grid), dim3(64), 0, h->stream, a);
+  } else {
+    if (pack8 && ahead) hipLaunchKernelGGL(k_maaco_walk8_batch<true>, dim3(grid), dim3(64), 0, h->stream, a, *mc);
+    else if (pack8) hipLaunchKernelGGL(k_maaco_walk8_batch<false>, dim3(grid), dim3(64), 0, h->stream, a, *mc);
+    else hipLaunchKernelGGL(k_maaco_walk_batch, dim3(grid), dim3(64), 0, h->stream, a, *mc);
+  }
+  CK(hipGetLastError());
+  CK(hipEventRecord(h->ev1, h->stream));
+  return 0;
+}
 // enqueue the walk of ants [ant0, ant0 + n) (nothing waits); the ants mark their own deposits when g_maaco_mark is on
 static int maaco_enqueue_walk(pf_handle* h, int32_t iter, uint64_t seed, int32_t ant0, int32_t n, int32_t path_cap,
                               int32_t* d_cells, int32_t* d_len, double* d_plen, int32_t* d_turns, int32_t* d_status, bool mark,
                               bool own_ctl = false) {
   CK(hipSetDevice(h->device));
-  MaacoArgs a;
-  a.G = make_grid(h, 1, 1);
+  MaacoArgs a = maaco_walk_args(h, h->mp, iter, path_cap, d_cells, d_len, d_plen, d_turns, d_status);
   a.tau = h->mp.alpha == 1.0 ? h->d_tau : h->d_taua; a.eta = h->d_eta;
   if (!h->d_tep) CK(hipMalloc(&h->d_tep, sizeof(double) * 3 * (size_t)h->RC));
-  a.tep = h->d_tep;
-  a.visit = h->d_visit; a.slot_epoch = h->d_visit_epoch; a.work = h->d_work; a.cnt = h->d_cnt;
-  a.wpr = (h->C + 15) >> 4; a.vstride = h->R * a.wpr;
-  a.start = h->mp.start; a.target = h->mp.target; a.iter = iter; a.num_iterations = h->mp.num_iterations;
-  a.q0 = maaco_q0(iter, h->mp.num_iterations, h->mp.q0_initial);
-  a.seed = seed; a.ant0 = ant0; a.n = n; a.path_cap = path_cap;
-  a.cells = d_cells; a.len = d_len; a.plen = d_plen; a.turns = d_turns; a.status = d_status;
-  a.bits = nullptr; a.dep = nullptr; a.flag = nullptr; a.fstride = 0; a.Q = h->mp.Q;
+  a.work = h->d_work; a.cnt = h->d_cnt;
+  a.start = h->mp.start; a.target = h->mp.target;
+  a.seed = seed; a.ant0 = ant0; a.n = n;
+  a.bits = nullptr; a.dep = nullptr; a.flag = nullptr; a.fstride = 0;
   h->marks_n = 0; h->marks_cells = nullptr;
   if (mark) {
     if (maaco_ensure_bits(h, n)) return -1;
     a.bits = h->d_bits; a.dep = h->d_dep; a.flag = h->d_flag; a.fstride = (int)h->bits_words;
     h->marks_n = n; h->marks_cells = d_cells;                       // deposit_begin for exactly this batch finds its marks made
   }
-  // eight ants per wavefront (k_maaco_walk8) once the batch can fill the chip that way; else one per wave
-  const bool pack8 = n >= g_maaco_pack8_min;
-  a.groups = g_maaco_groups;
-  int grid = pack8 ? h->maaco_slots / 8 : (h->maaco_slots < 8192 ? h->maaco_slots : 8192);
-  const int need = pack8 ? (n + a.groups - 1) / a.groups : n; if (grid > need) grid = need;
   if (own_ctl) {                                                    // pf_maaco_iterate: the previous iteration's last reader left the block zeroed
     if (!h->d_mctl) { CK(hipMalloc(&h->d_mctl, 16 + sizeof(DevCounters))); h->mctl_clean = false; }
     if (!h->mctl_clean) CK(hipMemsetAsync(h->d_mctl, 0, 16 + sizeof(DevCounters), h->stream));
@@ -2745,20 +2802,7 @@ static int maaco_enqueue_walk(pf_handle* h, int32_t iter, uint64_t seed, int32_t
     CK(hipMemsetAsync(h->d_work, 0, sizeof(int), h->stream));
     CK(hipMemsetAsync(h->d_cnt, 0, sizeof(DevCounters), h->stream));
   }
-  if (g_tabu_epoch >= 0) {                                          // one-shot: later batches carry on from there
-    CK(hipMemsetD32Async((hipDeviceptr_t)h->d_visit_epoch, g_tabu_epoch, (size_t)h->maaco_slots, h->stream));
-    g_tabu_epoch = -1;
-  }
-  if (pack8) hipLaunchKernelGGL(k_pack_tep, dim3((h->RC + 255) / 256), dim3(256), 0, h->stream, h->RC, a.tau, a.eta, h->d_tep);
-  CK(hipEventRecord(h->ev0, h->stream));
-  // (the load-ahead form when the batch leaves every SIMD at most one wavefront: see k_maaco_walk8)
-  const bool ahead = g_maaco_ahead < 0 ? grid <= h->maaco_cus * 4 : g_maaco_ahead != 0;
-  if (pack8 && ahead) hipLaunchKernelGGL(k_maaco_walk8<true>, dim3(grid), dim3(64), 0, h->stream, a);
-  else if (pack8) hipLaunchKernelGGL(k_maaco_walk8<false>, dim3(grid), dim3(64), 0, h->stream, a);
-  else hipLaunchKernelGGL(k_maaco_walk, dim3(grid), dim3(64), 0, h->stream, a);
-  CK(hipGetLastError());
-  CK(hipEventRecord(h->ev1, h->stream));
-  return 0;
+  return maaco_launch_walk(h, a, nullptr, h->d_tep);
 }
 int pf_maaco_walk_batch(pf_handle* h, int32_t iter, uint64_t seed, int32_t ant0, int32_t n, int32_t path_cap,
                         int32_t* d_cells, int32_t* d_len, double* d_plen, int32_t* d_turns, int32_t* d_status) {
@@ -2769,6 +2813,54 @@ int pf_maaco_walk_batch(pf_handle* h, int32_t iter, uint64_t seed, int32_t ant0,
   if (maaco_enqueue_walk(h, iter, seed, ant0, n, path_cap, d_cells, d_len, d_plen, d_turns, d_status, g_maaco_mark != 0)) return -1;
   DevCounters dc; if (end_batch(h, &dc)) return -1;
   CK(hipEventElapsedTime(&h->last_ms, h->ev0, h->ev1));
+  return 0;
+}
+
+// The overall best paths as the iterate calls keep them in HBM: K rows of *row_cap ints, [0] = length.  Room for paths of
+// path_cap cells; longer rows keep what is there (same stream, ordered).
+static int maaco_grow_best_rows(pf_handle* h, int** d_rows, int* row_cap, int K, int path_cap) {
+  if (*row_cap >= path_cap + 1) return 0;
+  const size_t pitch = sizeof(int) * ((size_t)path_cap + 1);
+  int* nb = nullptr; CK(hipMalloc(&nb, pitch * K));
+  if (*d_rows) {
+    CK(hipMemcpy2DAsync(nb, pitch, *d_rows, sizeof(int) * (size_t)*row_cap, sizeof(int) * (size_t)*row_cap, K, hipMemcpyDeviceToDevice, h->stream));
+    CK(hipStreamSynchronize(h->stream)); CK(hipFree(*d_rows));
+  } else {
+    CK(hipMemset2DAsync(nb, pitch, 0, sizeof(int), K, h->stream));   // (no best path yet)
+  }
+  *d_rows = nb; *row_cap = path_cap + 1;
+  return 0;
+}
+// one such row -> *len_out cells (0: none yet, d_row null) into cells_out[cap]; `what` is the entry point, args_ok its own checks
+static int maaco_read_best_row(pf_handle* h, const char* what, bool args_ok, const int* d_row, int row_cap, int32_t* cells_out, int32_t cap,
+                               int32_t* len_out) {
+  if (!args_ok || !len_out || cap < 0 || (cap > 0 && !cells_out)) return failmsg(h, std::string(what) + ": bad arguments");
+  *len_out = 0;
+  if (!d_row) return 0;
+  CK(hipSetDevice(h->device));
+  int L = 0;
+  if (pf_d2h(h, &L, d_row, sizeof(int))) return -1;
+  if (L < 0 || L > row_cap - 1) return failmsg(h, std::string(what) + ": corrupt row");
+  *len_out = L;
+  if (L > cap) return failmsg(h, std::string(what) + ": the buffer is too small");
+  if (L > 0 && pf_d2h(h, cells_out, d_row + 1, (int64_t)sizeof(int) * L)) return -1;
+  return 0;
+}
+// The end of an iteration of K colonies, after its update pass is enqueued: the host needs the K x 13 doubles, not the pheromone,
+// so it waits for the take-over test (ev2) only and the update pass runs on behind the caller's bookkeeping (everything later on
+// this stream is ordered after it).  h_out13 is the pinned mirror the device wrote; the flags are the caller's control block / bit matrix.
+static int maaco_iterate_tail(pf_handle* h, int K, const double* h_out13, double* out, bool* ctl_clean, bool* bits_clean, double alpha,
+                              const double* d_tau, double* d_taua) {
+  CK(hipEventSynchronize(h->ev2));
+  memcpy(out, h_out13, sizeof(double) * 13 * K);
+  *ctl_clean = true;
+  h->d2h_small += 1;
+  CK(hipEventElapsedTime(&h->last_ms, h->ev0, h->ev1));
+  memset(&h->last, 0, sizeof(h->last));
+  h->last.steps = (unsigned long long)out[9]; h->last.candidates = (unsigned long long)out[10];
+  h->last.path_cells = (unsigned long long)out[11]; h->last.overflow_agents = (unsigned long long)out[12];
+  *bits_clean = out[8] == 0.0;                                      // the update pass read and zeroed every word (a skipped one did not)
+  if (out[8] == 0.0) return maaco_refresh_taua(h, alpha, d_tau, d_taua, K);   // (alpha == 1: nothing to do, nothing waits)
   return 0;
 }
 
@@ -2791,12 +2883,7 @@ int pf_maaco_iterate(pf_handle* h, int32_t iter, uint64_t seed, int32_t ant0, in
     CK(hipHostGetDevicePointer((void**)&h->h_mstate_dev, h->h_mstate, 0));
   }
   double* hs_dev = h->h_mstate_dev;
-  if (h->best_row_cap < path_cap + 1) {                             // (a longer row keeps the best so far: same stream, ordered)
-    int* nb = nullptr; CK(hipMalloc(&nb, sizeof(int) * ((size_t)path_cap + 1)));
-    if (h->d_best_row) { CK(hipMemcpyAsync(nb, h->d_best_row, sizeof(int) * (size_t)h->best_row_cap, hipMemcpyDeviceToDevice, h->stream)); CK(hipStreamSynchronize(h->stream)); CK(hipFree(h->d_best_row)); }
-    else CK(hipMemsetAsync(nb, 0, sizeof(int), h->stream));
-    h->d_best_row = nb; h->best_row_cap = path_cap + 1;
-  }
+  if (maaco_grow_best_rows(h, &h->d_best_row, &h->best_row_cap, 1, path_cap)) return -1;
   if (maaco_enqueue_walk(h, iter, seed, ant0, n, path_cap, d_cells, d_len, d_plen, d_turns, d_status, true, true)) return -1;   // (this path always marks)
   hipLaunchKernelGGL(k_maaco_best_take, dim3(1), dim3(1024), 0, h->stream, n, (const double*)d_plen, (const int*)d_turns, (double*)h->d_scan3,
                      best_len, best_turns, h->mp.rho, h->R, h->C, (int*)h->d_mctl, (DevCounters*)(h->d_mctl + 16), h->d_mstate, hs_dev,
@@ -2806,36 +2893,14 @@ int pf_maaco_iterate(pf_handle* h, int32_t iter, uint64_t seed, int32_t ant0, in
   hipLaunchKernelGGL(k_tau_update, dim3((h->RC + 1023) / 1024), dim3(1024), 2 * PF_UPD_CHUNK * sizeof(double), h->stream, h->d_tau, h->d_occ,
                      h->RC, h->d_bits, words, h->d_dep, 1.0 - h->mp.rho, (const double*)h->d_mstate, 0.0, 0.0, h->d_flag, (int)h->bits_words);
   CK(hipGetLastError());
-  // the host needs the 13 doubles, not the pheromone: it waits for the take-over test only, the update pass runs on behind the
-  // caller's bookkeeping (everything later on this stream is ordered after it)
-  CK(hipEventSynchronize(h->ev2));
-  memcpy(out13, h->h_mstate, 13 * sizeof(double));
-  h->mctl_clean = true;
-  h->d2h_small += 1;
-  CK(hipEventElapsedTime(&h->last_ms, h->ev0, h->ev1));
-  memset(&h->last, 0, sizeof(h->last));
-  h->last.steps = (unsigned long long)out13[9]; h->last.candidates = (unsigned long long)out13[10];
-  h->last.path_cells = (unsigned long long)out13[11]; h->last.overflow_agents = (unsigned long long)out13[12];
   h->marks_n = 0;
-  h->bits_clean = out13[8] == 0.0;                                  // the update pass read and zeroed every word (a skipped one did not)
-  if (out13[8] == 0.0) return maaco_refresh_taua(h);                // (alpha == 1: nothing to do, nothing waits)
-  return 0;
+  return maaco_iterate_tail(h, 1, h->h_mstate, out13, &h->mctl_clean, &h->bits_clean, h->mp.alpha, h->d_tau, h->d_taua);
 }
 
 // The overall best ant's path as pf_maaco_iterate keeps it in HBM: *len_out cells (0: none yet) into cells_out[cap].
 int pf_maaco_best_path(pf_handle* h, int32_t* cells_out, int32_t cap, int32_t* len_out) {
   if (!h) return -2;
-  if (!len_out || cap < 0 || (cap > 0 && !cells_out)) return failmsg(h, "pf_maaco_best_path: bad arguments");
-  *len_out = 0;
-  if (!h->d_best_row) return 0;
-  CK(hipSetDevice(h->device));
-  int L = 0;
-  if (pf_d2h(h, &L, h->d_best_row, sizeof(int))) return -1;
-  if (L < 0 || L > h->best_row_cap - 1) return failmsg(h, "pf_maaco_best_path: corrupt row");
-  *len_out = L;
-  if (L > cap) return failmsg(h, "pf_maaco_best_path: the buffer is too small");
-  if (L > 0 && pf_d2h(h, cells_out, h->d_best_row + 1, (int64_t)sizeof(int) * L)) return -1;
-  return 0;
+  return maaco_read_best_row(h, "pf_maaco_best_path", true, h->d_best_row, h->best_row_cap, cells_out, cap, len_out);
 }
 
 int pf_maaco_evaporate(pf_handle* h) {
@@ -2868,6 +2933,15 @@ int pf_maaco_deposit_begin(pf_handle* h, int32_t n, int32_t path_cap, const int3
   h->dep_words = (int)words; h->dep_done = 0;
   return 0;
 }
+// the clip bounds of a pheromone update from the overall best length so far (MAACO.py:312-323)
+static void maaco_clip_bounds(const pf_handle* h, double best_len_overall, double* tmin, double* tmax) {
+  double bl = best_len_overall;                                     // MAACO.py:312-316
+  if (bl == INFINITY) bl = (double)(h->R + h->C);
+  if (bl < 1e-6) bl = 1e-6;
+  *tmax = (1.0 / (1.0 - h->mp.rho)) * (1.0 / bl);                   // :317
+  int mx = h->C > h->R ? h->C : h->R; if (mx < 1) mx = 1;
+  *tmin = *tmax / (2.0 * mx);                                       // :323
+}
 // MAACO.py:304-332 in one pass (evaporate, ordered deposits, clip) for the paths of one batch: the single-GPU form of
 // pf_maaco_evaporate + pf_maaco_deposit + pf_maaco_clip (the sharded fold keeps those: rank 0 alone evaporates).
 int pf_maaco_update(pf_handle* h, int32_t n, int32_t path_cap, const int32_t* d_cells, const int32_t* d_len, const double* d_plen,
@@ -2875,18 +2949,13 @@ int pf_maaco_update(pf_handle* h, int32_t n, int32_t path_cap, const int32_t* d_
   if (!h || !h->maaco_ready) return failmsg(h, "pf_maaco_update: setup first");
   if (n < 0 || (n > 0 && (!d_cells || !d_len || !d_plen))) return failmsg(h, "pf_maaco_update: bad arguments");
   if (pf_maaco_deposit_begin(h, n, path_cap, d_cells, d_len, d_plen)) return -1;
-  double bl = best_len_overall;                                     // MAACO.py:312-316
-  if (bl == INFINITY) bl = (double)(h->R + h->C);
-  if (bl < 1e-6) bl = 1e-6;
-  const double tmax = (1.0 / (1.0 - h->mp.rho)) * (1.0 / bl);       // :317
-  int mx = h->C > h->R ? h->C : h->R; if (mx < 1) mx = 1;
-  const double tmin = tmax / (2.0 * mx);                            // :323
+  double tmin, tmax; maaco_clip_bounds(h, best_len_overall, &tmin, &tmax);
   hipLaunchKernelGGL(k_tau_update, dim3((h->RC + 1023) / 1024), dim3(1024), 2 * PF_UPD_CHUNK * sizeof(double), h->stream, h->d_tau, h->d_occ,
                      h->RC, h->d_bits, h->dep_words, h->d_dep, 1.0 - h->mp.rho, (const double*)nullptr, tmin, tmax, h->d_flag, (int)h->bits_words);
   CK(hipGetLastError());
   if (h->dep_words) h->bits_clean = true;
   h->dep_words = 0;
-  return maaco_refresh_taua(h);
+  return maaco_refresh_taua(h, h->mp.alpha, h->d_tau, h->d_taua);
 }
 int pf_maaco_deposit_cells(pf_handle* h, int32_t cell0, int32_t cell1) {
   if (!h || !h->maaco_ready) return failmsg(h, "pf_maaco_deposit_cells: setup first");
@@ -2923,15 +2992,10 @@ int pf_maaco_best_dev(pf_handle* h, int32_t n, const double* d_plen, const int32
 int pf_maaco_clip(pf_handle* h, double best_len_overall) {
   if (!h || !h->maaco_ready) return failmsg(h, "pf_maaco_clip: setup first");
   CK(hipSetDevice(h->device));
-  double bl = best_len_overall;                                     // MAACO.py:312-316
-  if (bl == INFINITY) bl = (double)(h->R + h->C);
-  if (bl < 1e-6) bl = 1e-6;
-  const double tmax = (1.0 / (1.0 - h->mp.rho)) * (1.0 / bl);       // :317
-  int mx = h->C > h->R ? h->C : h->R; if (mx < 1) mx = 1;
-  const double tmin = tmax / (2.0 * mx);                            // :323
+  double tmin, tmax; maaco_clip_bounds(h, best_len_overall, &tmin, &tmax);
   hipLaunchKernelGGL(k_tau_clip, dim3((h->RC + 255) / 256), dim3(256), 0, h->stream, h->d_tau, h->d_occ, h->RC, tmin, tmax);
   CK(hipGetLastError());
-  return maaco_refresh_taua(h);                                    // (alpha == 1: nothing to do, nothing waits)
+  return maaco_refresh_taua(h, h->mp.alpha, h->d_tau, h->d_taua);                                    // (alpha == 1: nothing to do, nothing waits)
 }
 
 int pf_maaco_get_pheromone(pf_handle* h, double* tau) {
@@ -2941,7 +3005,7 @@ int pf_maaco_get_pheromone(pf_handle* h, double* tau) {
 int pf_maaco_set_pheromone(pf_handle* h, const double* tau) {
   if (!h || !h->maaco_ready) return failmsg(h, "pf_maaco_set_pheromone: setup first");
   if (pf_h2d(h, h->d_tau, tau, (int64_t)sizeof(double) * h->RC)) return -1;
-  return maaco_refresh_taua(h);
+  return maaco_refresh_taua(h, h->mp.alpha, h->d_tau, h->d_taua);
 }
 void* pf_maaco_tau_dev(pf_handle* h) { return h ? (void*)h->d_tau : nullptr; }
 
@@ -2955,24 +3019,6 @@ static void maaco_batch_free(pf_maaco_batch* b) {
   if (b->h_io) (void)hipHostFree(b->h_io);
   delete b;
 }
-// tau^alpha of colony c (alpha != 1: host libm pow, as maaco_refresh_taua)
-static int maaco_batch_refresh_taua(pf_maaco_batch* b, int c) {
-  pf_handle* h = b->h;
-  if (b->mp.alpha == 1.0) return 0;
-  std::vector<double> t(h->RC);
-  CK(hipMemcpyAsync(t.data(), b->d_tau + (size_t)c * h->RC, sizeof(double) * h->RC, hipMemcpyDeviceToHost, h->stream));
-  CK(hipStreamSynchronize(h->stream));
-  for (int i = 0; i < h->RC; ++i) t[i] = pow(t[i], b->mp.alpha);
-  CK(hipMemcpyAsync(b->d_taua + (size_t)c * h->RC, t.data(), sizeof(double) * h->RC, hipMemcpyHostToDevice, h->stream));
-  CK(hipStreamSynchronize(h->stream));
-  return 0;
-}
-static int maaco_batch_check(pf_maaco_batch* b, const char* what) {
-  if (!b) return failmsg(nullptr, std::string(what) + ": null batch");
-  if (!b->ready) return failmsg(b->h, std::string(what) + ": the batch belongs to a replaced grid (pf_update_grid); destroy it");
-  return 0;
-}
-
 int pf_maaco_batch_create(pf_handle* h, const pf_maaco_params* p, int32_t K, int32_t n, const int32_t* starts, const int32_t* targets,
                           const uint64_t* seeds, pf_maaco_batch** out) {
   if (!h) return -2;
@@ -3010,7 +3056,7 @@ int pf_maaco_batch_create(pf_handle* h, const pf_maaco_params* p, int32_t K, int
   b->start.assign(starts, starts + K); b->target.assign(targets, targets + K); b->eta_of = eta_of;
   b->mp.start = starts[0]; b->mp.target = targets[0];
   b->words = words; b->bits_stride = words * S * 64; b->flag_stride = words * S;
-  #define CKB(call) do { hipError_t e_ = (call); if (e_ != hipSuccess) { fail(h, #call, e_); maaco_batch_free(b); return -1; } } while (0)
+  const auto undo = [&] { maaco_batch_free(b); };
   CKB(hipMalloc(&b->d_tau, sizeof(double) * RC * (size_t)K));
   if (p->alpha != 1.0) CKB(hipMalloc(&b->d_taua, sizeof(double) * RC * (size_t)K));
   CKB(hipMalloc(&b->d_eta, sizeof(double) * 2 * RC * (size_t)P));
@@ -3043,10 +3089,9 @@ int pf_maaco_batch_create(pf_handle* h, const pf_maaco_params* p, int32_t K, int
   CKB(hipMemsetAsync(b->d_dep, 0, sizeof(double) * words * 64 * K, h->stream));
   CKB(hipStreamSynchronize(h->stream));
   CKB(hipFuncSetAttribute((const void*)k_tau_update_batch, hipFuncAttributeMaxDynamicSharedMemorySize, 2 * PF_UPD_CHUNK * (int)sizeof(double)));
-  #undef CKB
   b->ready = true;
   h->maaco_batches.push_back(b);
-  for (int c = 0; c < K; ++c) if (maaco_batch_refresh_taua(b, c)) return -1;
+  if (maaco_refresh_taua(h, p->alpha, b->d_tau, b->d_taua, K)) return -1;
   *out = b;
   return 0;
 }
@@ -3067,24 +3112,14 @@ void pf_maaco_batch_destroy(pf_maaco_batch* b) {
 int pf_maaco_batch_iterate(pf_maaco_batch* b, int32_t iter, int32_t n, int32_t path_cap, int32_t* d_cells, int32_t* d_len,
                            double* d_plen, int32_t* d_turns, int32_t* d_status, const double* best_len, const double* best_turns,
                            double* out) {
-  if (maaco_batch_check(b, "pf_maaco_batch_iterate")) return -2;
+  if (batch_check(b, "pf_maaco_batch_iterate")) return -2;
   pf_handle* h = b->h;
   const int K = b->K;
   if (n != b->n || path_cap < 2 || !d_cells || !d_len || !d_plen || !d_turns || !d_status || !best_len || !best_turns || !out)
     return failmsg(h, "pf_maaco_batch_iterate: bad arguments (n must be the batch's ants per colony)");
   CK(hipSetDevice(h->device));
   const int RC = h->RC;
-  if (b->row_cap < path_cap + 1) {                                 // (longer rows keep every colony's best so far)
-    int* nb = nullptr; CK(hipMalloc(&nb, sizeof(int) * ((size_t)path_cap + 1) * K));
-    if (b->d_best_rows) {
-      CK(hipMemcpy2DAsync(nb, sizeof(int) * ((size_t)path_cap + 1), b->d_best_rows, sizeof(int) * (size_t)b->row_cap,
-                          sizeof(int) * (size_t)b->row_cap, K, hipMemcpyDeviceToDevice, h->stream));
-      CK(hipStreamSynchronize(h->stream)); CK(hipFree(b->d_best_rows));
-    } else {
-      CK(hipMemset2DAsync(nb, sizeof(int) * ((size_t)path_cap + 1), 0, sizeof(int), K, h->stream));
-    }
-    b->d_best_rows = nb; b->row_cap = path_cap + 1;
-  }
+  if (maaco_grow_best_rows(h, &b->d_best_rows, &b->row_cap, K, path_cap)) return -1;
   if (!b->bits_clean) {
     CK(hipMemsetAsync(b->d_bits, 0, sizeof(unsigned long long) * b->bits_stride * K, h->stream));
     CK(hipMemsetAsync(b->d_flag, 0, b->flag_stride * K, h->stream));
@@ -3093,39 +3128,16 @@ int pf_maaco_batch_iterate(pf_maaco_batch* b, int32_t iter, int32_t n, int32_t p
   if (!b->ctl_clean) CK(hipMemsetAsync(b->d_ctl, 0, 16 + sizeof(DevCounters), h->stream));
   b->ctl_clean = false;
   for (int c = 0; c < K; ++c) { b->h_io[2 * c] = best_len[c]; b->h_io[2 * c + 1] = best_turns[c]; }   // (read by the best / take launch)
-  MaacoArgs a;
-  a.G = make_grid(h, 1, 1);
-  a.tau = b->mp.alpha == 1.0 ? b->d_tau : b->d_taua; a.eta = b->d_eta; a.tep = b->d_tep;
-  a.visit = h->d_visit; a.slot_epoch = h->d_visit_epoch;
+  MaacoArgs a = maaco_walk_args(h, b->mp, iter, path_cap, d_cells, d_len, d_plen, d_turns, d_status);
+  a.tau = b->mp.alpha == 1.0 ? b->d_tau : b->d_taua; a.eta = b->d_eta;
   a.work = (int*)b->d_ctl; a.cnt = (DevCounters*)(b->d_ctl + 16);
-  a.wpr = (h->C + 15) >> 4; a.vstride = h->R * a.wpr;
-  a.start = b->mp.start; a.target = b->mp.target; a.iter = iter; a.num_iterations = b->mp.num_iterations;
-  a.q0 = maaco_q0(iter, b->mp.num_iterations, b->mp.q0_initial);
-  a.seed = 0; a.ant0 = 0; a.n = K * n; a.path_cap = path_cap;
-  a.cells = d_cells; a.len = d_len; a.plen = d_plen; a.turns = d_turns; a.status = d_status;
-  a.bits = b->d_bits; a.dep = b->d_dep; a.flag = b->d_flag; a.fstride = (int)b->words; a.Q = b->mp.Q;
-  a.groups = g_maaco_groups;
+  a.start = b->mp.start; a.target = b->mp.target;
+  a.seed = 0; a.ant0 = 0; a.n = K * n;
+  a.bits = b->d_bits; a.dep = b->d_dep; a.flag = b->d_flag; a.fstride = (int)b->words;
   MaacoColonies mc;
   mc.nper = n; mc.seed = b->d_seed; mc.start = b->d_start; mc.target = b->d_target; mc.eta_of = b->d_eta_of;
   mc.bits_stride = b->bits_stride; mc.flag_stride = b->flag_stride; mc.dep_stride = (int)(b->words * 64);
-  // the kernel choice follows the K n ants of the walk, as for one colony of that many ants
-  const int total = K * n;
-  const bool pack8 = total >= g_maaco_pack8_min;
-  int grid = pack8 ? h->maaco_slots / 8 : (h->maaco_slots < 8192 ? h->maaco_slots : 8192);
-  const int need = pack8 ? (total + a.groups - 1) / a.groups : total; if (grid > need) grid = need;
-  if (g_tabu_epoch >= 0) {
-    CK(hipMemsetD32Async((hipDeviceptr_t)h->d_visit_epoch, g_tabu_epoch, (size_t)h->maaco_slots, h->stream));
-    g_tabu_epoch = -1;
-  }
-  if (pack8) hipLaunchKernelGGL(k_pack_tep_batch, dim3((RC + 255) / 256, K), dim3(256), 0, h->stream, RC, a.tau, (const double*)b->d_eta,
-                                (const int*)b->d_eta_of, b->d_tep);
-  CK(hipEventRecord(h->ev0, h->stream));
-  const bool ahead = g_maaco_ahead < 0 ? grid <= h->maaco_cus * 4 : g_maaco_ahead != 0;
-  if (pack8 && ahead) hipLaunchKernelGGL(k_maaco_walk8_batch<true>, dim3(grid), dim3(64), 0, h->stream, a, mc);
-  else if (pack8) hipLaunchKernelGGL(k_maaco_walk8_batch<false>, dim3(grid), dim3(64), 0, h->stream, a, mc);
-  else hipLaunchKernelGGL(k_maaco_walk_batch, dim3(grid), dim3(64), 0, h->stream, a, mc);
-  CK(hipGetLastError());
-  CK(hipEventRecord(h->ev1, h->stream));
+  if (maaco_launch_walk(h, a, &mc, b->d_tep)) return -1;
   double* io_out = b->h_io_dev + 2 * K;
   hipLaunchKernelGGL(k_maaco_best_take_batch, dim3(K), dim3(1024), 0, h->stream, n, (const double*)d_plen, (const int*)d_turns, b->d_scan3,
                      (const double*)b->h_io_dev, b->mp.rho, h->R, h->C, (int*)b->d_ctl, (DevCounters*)(b->d_ctl + 16), (unsigned*)(b->d_ctl + 4),
@@ -3134,44 +3146,26 @@ int pf_maaco_batch_iterate(pf_maaco_batch* b, int32_t iter, int32_t n, int32_t p
   hipLaunchKernelGGL(k_tau_update_batch, dim3((RC + 1023) / 1024, K), dim3(1024), 2 * PF_UPD_CHUNK * sizeof(double), h->stream, b->d_tau, h->d_occ,
                      RC, b->d_bits, (int)b->words, b->d_dep, 1.0 - b->mp.rho, (const double*)b->d_state, 0.0, 0.0, b->d_flag, (int)b->words, mc);
   CK(hipGetLastError());
-  CK(hipEventSynchronize(h->ev2));                                 // (the pheromone pass runs on behind the caller's bookkeeping)
-  memcpy(out, b->h_io + 2 * K, sizeof(double) * 13 * K);
-  b->ctl_clean = true;
-  h->d2h_small += 1;
-  CK(hipEventElapsedTime(&h->last_ms, h->ev0, h->ev1));
-  memset(&h->last, 0, sizeof(h->last));
-  h->last.steps = (unsigned long long)out[9]; h->last.candidates = (unsigned long long)out[10];
-  h->last.path_cells = (unsigned long long)out[11]; h->last.overflow_agents = (unsigned long long)out[12];
-  b->bits_clean = out[8] == 0.0;
-  if (out[8] == 0.0) for (int c = 0; c < K; ++c) if (maaco_batch_refresh_taua(b, c)) return -1;
-  return 0;
+  return maaco_iterate_tail(h, K, b->h_io + 2 * K, out, &b->ctl_clean, &b->bits_clean, b->mp.alpha, b->d_tau, b->d_taua);
 }
 
 int pf_maaco_batch_best_path(pf_maaco_batch* b, int32_t k, int32_t* cells_out, int32_t cap, int32_t* len_out) {
-  if (maaco_batch_check(b, "pf_maaco_batch_best_path")) return -2;
-  pf_handle* h = b->h;
-  if (k < 0 || k >= b->K || !len_out || cap < 0 || (cap > 0 && !cells_out)) return failmsg(h, "pf_maaco_batch_best_path: bad arguments");
-  *len_out = 0;
-  if (!b->d_best_rows) return 0;
-  const int* row = b->d_best_rows + (size_t)k * b->row_cap;
-  int L = 0;
-  if (pf_d2h(h, &L, (void*)row, sizeof(int))) return -1;
-  if (L < 0 || L > b->row_cap - 1) return failmsg(h, "pf_maaco_batch_best_path: corrupt row");
-  *len_out = L;
-  if (L > cap) return failmsg(h, "pf_maaco_batch_best_path: the buffer is too small");
-  if (L > 0 && pf_d2h(h, cells_out, (void*)(row + 1), (int64_t)sizeof(int) * L)) return -1;
-  return 0;
+  if (batch_check(b, "pf_maaco_batch_best_path")) return -2;
+  const bool k_ok = k >= 0 && k < b->K;
+  return maaco_read_best_row(b->h, "pf_maaco_batch_best_path", k_ok, k_ok && b->d_best_rows ? b->d_best_rows + (size_t)k * b->row_cap : nullptr,
+                             b->row_cap, cells_out, cap, len_out);
 }
 int pf_maaco_batch_get_pheromone(pf_maaco_batch* b, int32_t k, double* tau) {
-  if (maaco_batch_check(b, "pf_maaco_batch_get_pheromone")) return -2;
+  if (batch_check(b, "pf_maaco_batch_get_pheromone")) return -2;
   if (k < 0 || k >= b->K || !tau) return failmsg(b->h, "pf_maaco_batch_get_pheromone: bad arguments");
   return pf_d2h(b->h, tau, b->d_tau + (size_t)k * b->h->RC, (int64_t)sizeof(double) * b->h->RC);
 }
 int pf_maaco_batch_set_pheromone(pf_maaco_batch* b, int32_t k, const double* tau) {
-  if (maaco_batch_check(b, "pf_maaco_batch_set_pheromone")) return -2;
+  if (batch_check(b, "pf_maaco_batch_set_pheromone")) return -2;
   if (k < 0 || k >= b->K || !tau) return failmsg(b->h, "pf_maaco_batch_set_pheromone: bad arguments");
   if (pf_h2d(b->h, b->d_tau + (size_t)k * b->h->RC, tau, (int64_t)sizeof(double) * b->h->RC)) return -1;
-  return maaco_batch_refresh_taua(b, k);
+  const size_t o = (size_t)k * b->h->RC;
+  return b->mp.alpha == 1.0 ? 0 : maaco_refresh_taua(b->h, b->mp.alpha, b->d_tau + o, b->d_taua + o);
 }
 
 int pf_maaco_best_scan(int32_t n, const double* plen, const int32_t* turns, int32_t idx0, double* best_len,
@@ -3317,44 +3311,68 @@ static int dijkstra_host(const pf_handle* h, const std::vector<uint8_t>& mm, int
   }
   return 0;
 }
+// the pruning bounds are usable: skipped for grids above 4 Mi cells or penalty weights below zero (see dijkstra_host)
+static bool mpa_bounds_usable(const pf_handle* h, const pf_score_params* sp) {
+  return !(h->RC > (1 << 22) || sp->w_turn < 0.0 || sp->w_safe < 0.0 || sp->diag_pen < 0.0);
+}
+// the device-built move masks of a move policy, on the host for dijkstra_host
+static int mpa_host_masks(pf_handle* h, const pf_mpa_params* p, std::vector<uint8_t>& mm) {
+  const Grid G = make_grid(h, p->allow_diag, p->restrict_corner);
+  mm.resize(h->RC);
+  CK(hipMemcpy(mm.data(), G.mm, h->RC, hipMemcpyDeviceToHost));
+  return 0;
+}
+// the bound table of one cell (host Dijkstra over those masks) -> d_out[RC]
+static int mpa_bound_table(pf_handle* h, const std::vector<uint8_t>& mm, int cell, double* d_out) {
+  std::vector<double> dist;
+  dijkstra_host(h, mm, cell, dist);
+  CK(hipMemcpy(d_out, dist.data(), sizeof(double) * (size_t)h->RC, hipMemcpyHostToDevice));
+  return 0;
+}
 static int mpa_bounds(pf_handle* h) {
   if (h->d_ds) { (void)hipFree(h->d_ds); h->d_ds = nullptr; }
   if (h->d_dt) { (void)hipFree(h->d_dt); h->d_dt = nullptr; }
-  if (h->RC > (1 << 22) || h->mps.w_turn < 0.0 || h->mps.w_safe < 0.0 || h->mps.diag_pen < 0.0) return 0;
-  const Grid G = make_grid(h, h->mpp.allow_diag, h->mpp.restrict_corner);
-  std::vector<uint8_t> mm(h->RC);
-  CK(hipMemcpy(mm.data(), G.mm, h->RC, hipMemcpyDeviceToHost));
-  std::vector<double> ds, dt;
-  dijkstra_host(h, mm, h->mpp.start, ds); dijkstra_host(h, mm, h->mpp.target, dt);
+  if (!mpa_bounds_usable(h, &h->mps)) return 0;
+  std::vector<uint8_t> mm;
+  if (mpa_host_masks(h, &h->mpp, mm)) return -1;
   CK(hipMalloc(&h->d_ds, sizeof(double) * (size_t)h->RC)); CK(hipMalloc(&h->d_dt, sizeof(double) * (size_t)h->RC));
-  CK(hipMemcpy(h->d_ds, ds.data(), sizeof(double) * (size_t)h->RC, hipMemcpyHostToDevice));
-  CK(hipMemcpy(h->d_dt, dt.data(), sizeof(double) * (size_t)h->RC, hipMemcpyHostToDevice));
+  if (mpa_bound_table(h, mm, h->mpp.start, h->d_ds) || mpa_bound_table(h, mm, h->mpp.target, h->d_dt)) return -1;
   return 0;
+}
+// MPA._generate_initial_path() = _a_star(start, target) (MPA.py:154) for K (start, target) pairs as ONE search batch, scored as
+// one: the paths into d_cells[K][RC], their stats into d_stats[K][5], their lengths (0: no path) into len_out[K]
+static int mpa_initial_paths(pf_handle* h, const pf_mpa_params* p, const pf_score_params* sp, int K, const int32_t* starts,
+                             const int32_t* targets, int* d_cells, double* d_stats, int* len_out) {
+  int* d_q = nullptr;                                               // {start, target, len, status} x K
+  CK(hipMalloc(&d_q, sizeof(int) * 4 * (size_t)K));
+  std::vector<int> hq(4 * (size_t)K, 0);
+  for (int k = 0; k < K; ++k) { hq[k] = starts[k]; hq[K + k] = targets[k]; }
+  const auto undo = [&] { (void)hipFree(d_q); };
+  CKB(hipMemcpyAsync(d_q, hq.data(), sizeof(int) * hq.size(), hipMemcpyHostToDevice, h->stream));
+  int rc = pf_astar_batch(h, PF_ASTAR_MPA, p->allow_diag, p->restrict_corner, K, d_q, d_q + K, nullptr, nullptr, h->RC, d_cells, d_q + 2 * K,
+                          d_q + 3 * K, nullptr);
+  if (rc == 0) {
+    CKB(hipMemcpyAsync(hq.data(), d_q, sizeof(int) * hq.size(), hipMemcpyDeviceToHost, h->stream));
+    CKB(hipStreamSynchronize(h->stream));
+    for (int k = 0; k < K; ++k) len_out[k] = hq[3 * K + k] == 0 ? hq[2 * K + k] : 0;
+    rc = pf_score_batch(h, sp, K, h->RC, d_cells, d_q + 2 * K, d_stats);
+  }
+  undo();
+  return rc;
 }
 int pf_mpa_setup(pf_handle* h, const pf_mpa_params* p, const pf_score_params* sp) {
   if (!h) return -2;
   if (!p || !sp || p->start < 0 || p->start >= h->RC || p->target < 0 || p->target >= h->RC) return failmsg(h, "pf_mpa_setup: bad arguments");
   h->mpp = *p; h->mps = *sp; h->mpa_ready = true;
   if (ensure_slots(h, p->allow_diag, p->restrict_corner)) return -1;
-  // memoise MPA._generate_initial_path() = _a_star(start, target) (MPA.py:154) and its stats
+  // memoise the initial path and its stats
   const int cap = h->RC;
   if (h->init_cap < cap) {
     if (h->d_init_cells) CK(hipFree(h->d_init_cells));
     CK(hipMalloc(&h->d_init_cells, sizeof(int) * (size_t)cap)); h->init_cap = cap;
   }
   if (!h->d_init_stats) CK(hipMalloc(&h->d_init_stats, sizeof(double) * 5));
-  int *d_s = nullptr, *d_t = nullptr, *d_l = nullptr, *d_st = nullptr;
-  CK(hipMalloc(&d_s, 4 * sizeof(int))); d_t = d_s + 1; d_l = d_s + 2; d_st = d_s + 3;
-  int hv[4] = {p->start, p->target, 0, 0};
-  CK(hipMemcpyAsync(d_s, hv, sizeof(hv), hipMemcpyHostToDevice, h->stream));
-  int rc = pf_astar_batch(h, PF_ASTAR_MPA, p->allow_diag, p->restrict_corner, 1, d_s, d_t, nullptr, nullptr, cap, h->d_init_cells, d_l, d_st, nullptr);
-  if (rc == 0) {
-    CK(hipMemcpyAsync(hv, d_s, sizeof(hv), hipMemcpyDeviceToHost, h->stream));
-    CK(hipStreamSynchronize(h->stream));
-    h->init_len = hv[3] == 0 ? hv[2] : 0;
-    rc = pf_score_batch(h, sp, 1, cap, h->d_init_cells, d_l, h->d_init_stats);
-  }
-  (void)hipFree(d_s);
+  int rc = mpa_initial_paths(h, p, sp, 1, &p->start, &p->target, h->d_init_cells, h->d_init_stats, &h->init_len);
   if (rc == 0) rc = mpa_bounds(h);
   return rc;
 }
@@ -3364,6 +3382,44 @@ static MpaDev mpa_dev(const pf_handle* h) {
   const bool on = g_mpa_prune && h->d_ds && h->d_dt;
   m.ds = on ? h->d_ds : nullptr; m.dt = on ? h->d_dt : nullptr;
   return m;
+}
+
+// ---- the sweep arguments: one place fills what every MPA entry point fills alike ----
+// search scratch, score parameters and MPA constants of a sweep: the solo state's (mpa_solo_base) or a batch's
+struct MpaBase { Common c; ScoreP sp; MpaDev m; };
+static int mpa_base(pf_handle* h, const pf_mpa_params& mp, const pf_score_params& sp, const MpaDev& m, MpaBase* o) {
+  if (ensure_slots(h, mp.allow_diag, mp.restrict_corner)) return -1;
+  o->c = make_common(h, mp.allow_diag, mp.restrict_corner, 16, 0);
+  if (make_scorep(h, &sp, &o->sp)) return -1;
+  o->m = m;
+  return 0;
+}
+static int mpa_solo_base(pf_handle* h, MpaBase* o) { return mpa_base(h, h->mpp, h->mps, mpa_dev(h), o); }
+// Phase arguments over a population: the step, who sits where, where the rebuilt paths go.  The elite and the explicit mode
+// (ex_*) are the caller's: they start out as "in HBM / none" (elite_len -1, nulls).
+static MpaPhaseArgs mpa_phase_args(const MpaBase& base, int phase, double CF, int iter, uint64_t seed, int n, int path_cap,
+                                   const int* pop_cells, const int* pop_len, const double* pop_stats, const int* gidx, const int* slot,
+                                   int* out_cells, int* out_len, double* out_stats, int* status) {
+  MpaPhaseArgs a;
+  a.c = base.c; a.sp = base.sp; a.m = base.m;
+  a.phase = phase; a.iter = iter; a.CF = CF; a.seed = seed; a.n = n; a.path_cap = path_cap;
+  a.pop_cells = pop_cells; a.pop_len = pop_len; a.pop_stats = pop_stats; a.gidx = gidx; a.slot = slot;
+  a.elite_cells = nullptr; a.elite_len = -1; a.elite_stats = nullptr; a.elite_len_dev = nullptr;
+  a.out_cells = out_cells; a.out_len = out_len; a.out_stats = out_stats; a.status = status;
+  a.ex_idx = nullptr; a.ex_levy = nullptr; a.ex_scale = nullptr; a.ex_agent = nullptr;
+  return a;
+}
+// FADs arguments over the same.  In place (tmp_cells), candidate mode (cand_*) and the memoised initial path are the caller's.
+static MpaFadsArgs mpa_fads_args(const MpaBase& base, double CF, int iter, uint64_t seed, int n, int path_cap, int* pop_cells,
+                                 int* pop_len, double* pop_stats, const int* gidx, const int* slot, int* status) {
+  MpaFadsArgs a;
+  a.c = base.c; a.sp = base.sp; a.m = base.m;
+  a.iter = iter; a.CF = CF; a.seed = seed; a.n = n; a.path_cap = path_cap;
+  a.pop_cells = pop_cells; a.pop_len = pop_len; a.pop_stats = pop_stats; a.gidx = gidx; a.slot = slot;
+  a.tmp_cells = nullptr; a.status = status;
+  a.init_cells = nullptr; a.init_len = 0; a.init_stats = nullptr;
+  a.cand_cells = nullptr; a.cand_len = nullptr; a.cand_stats = nullptr;
+  return a;
 }
 
 // ---- proposals: k_mpa_propose, then the host confirms the (expected: zero) doubtful ones with glibc ----
@@ -3492,16 +3548,11 @@ int pf_mpa_phase_batch(pf_handle* h, int32_t phase, double CF, int32_t iter, uin
   if (!h->mpa_ready) return failmsg(h, "pf_mpa_phase_batch: call pf_mpa_setup first");
   if (phase < 1 || phase > 3 || n < 0 || path_cap < 2 || !d_pop_cells || !d_pop_len || !d_pop_stats || !d_gidx || !d_slot ||
       !d_elite_cells || !d_elite_stats || !d_out_cells || !d_out_len || !d_out_stats || !d_status) return failmsg(h, "pf_mpa_phase_batch: bad arguments");
-  if (ensure_slots(h, h->mpp.allow_diag, h->mpp.restrict_corner)) return -1;
-  MpaPhaseArgs a;
-  a.c = make_common(h, h->mpp.allow_diag, h->mpp.restrict_corner, 16, 0);
-  if (make_scorep(h, &h->mps, &a.sp)) return -1;
-  a.m = mpa_dev(h); a.phase = phase; a.iter = iter; a.CF = CF; a.seed = seed; a.n = n; a.path_cap = path_cap;
-  a.pop_cells = d_pop_cells; a.pop_len = d_pop_len; a.pop_stats = d_pop_stats; a.gidx = d_gidx; a.slot = d_slot;
-  a.elite_cells = d_elite_cells; a.elite_len = elite_len; a.elite_len_dev = nullptr;
-  a.elite_stats = d_elite_stats;
-  a.out_cells = d_out_cells; a.out_len = d_out_len; a.out_stats = d_out_stats; a.status = d_status;
-  a.ex_idx = nullptr; a.ex_levy = nullptr; a.ex_scale = nullptr; a.ex_agent = nullptr;
+  MpaBase base;
+  if (mpa_solo_base(h, &base)) return -1;
+  MpaPhaseArgs a = mpa_phase_args(base, phase, CF, iter, seed, n, path_cap, d_pop_cells, d_pop_len, d_pop_stats, d_gidx, d_slot,
+                                  d_out_cells, d_out_len, d_out_stats, d_status);
+  a.elite_cells = d_elite_cells; a.elite_len = elite_len; a.elite_stats = d_elite_stats;
   int prc = 0;
   if (make_queue(h, n > 0 ? n : 1, [&](float* est) { prc = mpa_launch_propose(h, a, est); })) return -1;
   if (prc || mpa_resolve_doubts(h, a)) return -1;
@@ -3518,14 +3569,11 @@ int pf_mpa_rebuild_batch(pf_handle* h, int32_t iter, uint64_t seed, int32_t n, i
   if (!h->mpa_ready) return failmsg(h, "pf_mpa_rebuild_batch: call pf_mpa_setup first");
   if (n < 0 || path_cap < 2 || !d_pop_cells || !d_pop_len || !d_pop_stats || !d_elite_cells || !d_idx || !d_is_levy ||
       !d_scale || !d_agent || !d_out_cells || !d_out_len || !d_out_stats || !d_status) return failmsg(h, "pf_mpa_rebuild_batch: bad arguments");
-  if (ensure_slots(h, h->mpp.allow_diag, h->mpp.restrict_corner)) return -1;
-  MpaPhaseArgs a;
-  a.c = make_common(h, h->mpp.allow_diag, h->mpp.restrict_corner, 16, 0);
-  if (make_scorep(h, &h->mps, &a.sp)) return -1;
-  a.m = mpa_dev(h); a.phase = 0; a.iter = iter; a.CF = 0.0; a.seed = seed; a.n = n; a.path_cap = path_cap;
-  a.pop_cells = d_pop_cells; a.pop_len = d_pop_len; a.pop_stats = d_pop_stats; a.gidx = nullptr; a.slot = nullptr;
-  a.elite_cells = d_elite_cells; a.elite_len = elite_len; a.elite_len_dev = nullptr; a.elite_stats = d_pop_stats;
-  a.out_cells = d_out_cells; a.out_len = d_out_len; a.out_stats = d_out_stats; a.status = d_status;
+  MpaBase base;
+  if (mpa_solo_base(h, &base)) return -1;
+  MpaPhaseArgs a = mpa_phase_args(base, 0, 0.0, iter, seed, n, path_cap, d_pop_cells, d_pop_len, d_pop_stats, nullptr, nullptr,
+                                  d_out_cells, d_out_len, d_out_stats, d_status);
+  a.elite_cells = d_elite_cells; a.elite_len = elite_len; a.elite_stats = d_pop_stats;
   a.ex_idx = d_idx; a.ex_levy = d_is_levy; a.ex_scale = d_scale; a.ex_agent = d_agent;
   if (mpa_launch_propose(h, a, nullptr) || mpa_resolve_doubts(h, a)) return -1;
   return launch_with_retry(h, k_mpa_phase, a, n);
@@ -3536,26 +3584,73 @@ int pf_mpa_fads_batch(pf_handle* h, double CF, int32_t iter, uint64_t seed, int3
   if (!h) return -2;
   if (!h->mpa_ready) return failmsg(h, "pf_mpa_fads_batch: call pf_mpa_setup first");
   if (n < 0 || path_cap < 2 || !d_gidx || !d_slot || !d_pop_cells || !d_pop_len || !d_pop_stats || !d_status) return failmsg(h, "pf_mpa_fads_batch: bad arguments");
-  if (ensure_slots(h, h->mpp.allow_diag, h->mpp.restrict_corner)) return -1;
+  MpaBase base;
+  if (mpa_solo_base(h, &base)) return -1;
   if (h->tmp_cap < path_cap) {
     if (h->d_tmp) CK(hipFree(h->d_tmp));
     CK(hipMalloc(&h->d_tmp, sizeof(int) * (size_t)h->nslots * path_cap));
     h->tmp_cap = path_cap;
   }
-  MpaFadsArgs a;
-  a.c = make_common(h, h->mpp.allow_diag, h->mpp.restrict_corner, 16, 0);
-  if (make_scorep(h, &h->mps, &a.sp)) return -1;
-  a.m = mpa_dev(h); a.iter = iter; a.CF = CF; a.seed = seed; a.n = n; a.path_cap = path_cap;
-  a.pop_cells = d_pop_cells; a.pop_len = d_pop_len; a.pop_stats = d_pop_stats; a.gidx = d_gidx; a.slot = d_slot;
-  a.tmp_cells = h->d_tmp; a.status = d_status;
+  MpaFadsArgs a = mpa_fads_args(base, CF, iter, seed, n, path_cap, d_pop_cells, d_pop_len, d_pop_stats, d_gidx, d_slot, d_status);
+  a.tmp_cells = h->d_tmp;
   a.init_cells = h->d_init_cells; a.init_len = h->init_len; a.init_stats = h->d_init_stats;
-  a.cand_cells = nullptr; a.cand_len = nullptr; a.cand_stats = nullptr;
   if (n > 64) {
     if (make_queue(h, n, [&](float* est) { hipLaunchKernelGGL(k_plan_mpa_fads, dim3((n + 255) / 256), dim3(256), 0, h->stream, a, est); })) return -1;
     a.c.queue = h->d_queue;
   }
   return launch_with_retry(h, k_mpa_fads, a, n);
 }
+
+// One fused sweep from "the queue is made and the doubts are resolved" to its counters: the 2 n items of `a` (n phase items, then
+// n FADs candidates; n = K N for a batch) are planned, searched by k_mpa_search, finished and applied, back to back.  plan /
+// finish / apply enqueue the caller's kernels (solo or batched forms); two_wave picks the two-wave search engine (compiled only
+// with -DPF_TWO_WAVE).  One wait: the counters, which also come back in *dc.
+extern "C++" {
+template <typename Plan, typename Finish, typename Apply>
+static int mpa_launch_sweep(pf_handle* h, MpaSweepArgs& a, int n, bool two_wave, Plan plan, Finish finish, Apply apply, DevCounters* dc) {
+  a.ph.c.queue = h->d_queue; a.fd.c.queue = h->d_queue;
+  const int S = kLdsS;
+  a.ph.c.S = S; a.fd.c.S = S; a.ph.c.retry = 0; a.fd.c.retry = 0;
+  if (2 * n > h->job_cap) {
+    if (h->d_jobs) CK(hipFree(h->d_jobs));
+    if (h->d_jres) CK(hipFree(h->d_jres));
+    h->d_jobs = nullptr; h->d_jres = nullptr; h->job_cap = 0;       // (a failed hipMalloc leaves no dangling pointer)
+    CK(hipMalloc(&h->d_jobs, sizeof(MpaJob) * 2 * (size_t)n)); CK(hipMalloc(&h->d_jres, sizeof(MpaRes) * 2 * (size_t)n));
+    h->job_cap = 2 * n;
+  }
+  MpaJob* jobs = (MpaJob*)h->d_jobs; MpaRes* jres = (MpaRes*)h->d_jres;
+  MpaSearchArgs sa;
+  sa.c = a.ph.c; sa.jobs = jobs; sa.res = jres; sa.n_items = 2 * n; sa.path_cap = a.ph.path_cap; sa.ph_cells = a.ph.out_cells; sa.fd_cells = a.fd.cand_cells; sa.n = n;
+#ifdef PF_TWO_WAVE
+  const size_t lds = two_wave ? (size_t)PF_PR_LDS_BYTES : open_bytes(S);
+  if (two_wave) CK(hipFuncSetAttribute((const void*)k_mpa_search<true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+  else
+#else
+  const size_t lds = open_bytes(S);
+#endif
+  CK(hipFuncSetAttribute((const void*)k_mpa_search<false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+  const int grid = search_grid(h, lds, 2 * n);
+  CK(hipMemsetAsync(h->d_work, 0, sizeof(int), h->stream));
+  CK(hipMemsetAsync(h->d_cnt, 0, sizeof(DevCounters), h->stream));
+  plan(jobs, jres);
+  CK(hipGetLastError());
+  CK(hipEventRecord(h->ev0, h->stream));
+#ifdef PF_TWO_WAVE
+  if (two_wave) hipLaunchKernelGGL(k_mpa_search<true>, dim3(grid), dim3(128), lds, h->stream, sa);
+  else
+#endif
+  hipLaunchKernelGGL(k_mpa_search<false>, dim3(grid), dim3(64), lds, h->stream, sa);
+  CK(hipGetLastError());
+  CK(hipEventRecord(h->ev1, h->stream));
+  finish((const MpaJob*)jobs, (const MpaRes*)jres);
+  CK(hipGetLastError());
+  apply();
+  CK(hipGetLastError());
+  if (end_batch(h, dc)) return -1;
+  CK(hipEventElapsedTime(&h->last_ms, h->ev0, h->ev1));
+  return 0;
+}
+}  // extern "C++"
 
 int pf_mpa_iter_batch(pf_handle* h, int32_t phase, double CF, int32_t iter, uint64_t seed, int32_t n, int32_t path_cap,
                       int32_t* d_pop_cells, int32_t* d_pop_len, double* d_pop_stats, const int32_t* d_gidx,
@@ -3568,20 +3663,14 @@ int pf_mpa_iter_batch(pf_handle* h, int32_t phase, double CF, int32_t iter, uint
       !d_elite_cells || !d_elite_stats || !d_c1_cells || !d_c1_len || !d_c1_stats || !d_c2_cells || !d_c2_len || !d_c2_stats || !d_status)
     return failmsg(h, "pf_mpa_iter_batch: bad arguments");
   if (n == 0) return 0;
-  if (ensure_slots(h, h->mpp.allow_diag, h->mpp.restrict_corner)) return -1;
+  MpaBase base;
+  if (mpa_solo_base(h, &base)) return -1;
   MpaSweepArgs a;
-  a.ph.c = make_common(h, h->mpp.allow_diag, h->mpp.restrict_corner, 16, 0);
-  if (make_scorep(h, &h->mps, &a.ph.sp)) return -1;
-  a.ph.m = mpa_dev(h); a.ph.phase = phase; a.ph.iter = iter; a.ph.CF = CF; a.ph.seed = seed; a.ph.n = n; a.ph.path_cap = path_cap;
-  a.ph.pop_cells = d_pop_cells; a.ph.pop_len = d_pop_len; a.ph.pop_stats = d_pop_stats; a.ph.gidx = d_gidx; a.ph.slot = d_slot;
+  a.ph = mpa_phase_args(base, phase, CF, iter, seed, n, path_cap, d_pop_cells, d_pop_len, d_pop_stats, d_gidx, d_slot, d_c1_cells, d_c1_len,
+                        d_c1_stats, d_status);
   a.ph.elite_cells = d_elite_cells; a.ph.elite_len = elite_len; a.ph.elite_stats = d_elite_stats;
-  a.ph.elite_len_dev = nullptr;
   if (elite_len < 0) { if (ensure_elite_buf(h)) return -1; a.ph.elite_len_dev = h->d_elite_len; }   // device-resident iteration: the length stays in HBM
-  a.ph.out_cells = d_c1_cells; a.ph.out_len = d_c1_len; a.ph.out_stats = d_c1_stats; a.ph.status = d_status;
-  a.ph.ex_idx = nullptr; a.ph.ex_levy = nullptr; a.ph.ex_scale = nullptr; a.ph.ex_agent = nullptr;
-  a.fd.c = a.ph.c; a.fd.sp = a.ph.sp; a.fd.m = a.ph.m; a.fd.iter = iter; a.fd.CF = CF; a.fd.seed = seed; a.fd.n = n; a.fd.path_cap = path_cap;
-  a.fd.pop_cells = d_pop_cells; a.fd.pop_len = d_pop_len; a.fd.pop_stats = d_pop_stats; a.fd.gidx = d_gidx; a.fd.slot = d_slot;
-  a.fd.tmp_cells = nullptr; a.fd.status = d_status;
+  a.fd = mpa_fads_args(base, CF, iter, seed, n, path_cap, d_pop_cells, d_pop_len, d_pop_stats, d_gidx, d_slot, d_status);
   a.fd.init_cells = h->d_init_cells; a.fd.init_len = h->init_len; a.fd.init_stats = h->d_init_stats;
   a.fd.cand_cells = d_c2_cells; a.fd.cand_len = d_c2_len; a.fd.cand_stats = d_c2_stats;
   int prc = 0;
@@ -3590,50 +3679,18 @@ int pf_mpa_iter_batch(pf_handle* h, int32_t phase, double CF, int32_t iter, uint
         hipLaunchKernelGGL(k_plan_mpa_fads, dim3((n + 255) / 256), dim3(256), 0, h->stream, a.fd, est + n);
       })) return -1;
   if (prc || mpa_resolve_doubts(h, a.ph)) return -1;
-  a.ph.c.queue = h->d_queue; a.fd.c.queue = h->d_queue;
-  const int S = kLdsS;
-  a.ph.c.S = S; a.fd.c.S = S; a.ph.c.retry = 0; a.fd.c.retry = 0;
-  if (2 * n > h->job_cap) {
-    if (h->d_jobs) CK(hipFree(h->d_jobs));
-    if (h->d_jres) CK(hipFree(h->d_jres));
-    CK(hipMalloc(&h->d_jobs, sizeof(MpaJob) * 2 * (size_t)n)); CK(hipMalloc(&h->d_jres, sizeof(MpaRes) * 2 * (size_t)n));
-    h->job_cap = 2 * n;
-  }
-  MpaJob* jobs = (MpaJob*)h->d_jobs; MpaRes* jres = (MpaRes*)h->d_jres;
-  MpaSearchArgs sa;
-  sa.c = a.ph.c; sa.jobs = jobs; sa.res = jres; sa.n_items = 2 * n; sa.path_cap = path_cap; sa.ph_cells = d_c1_cells; sa.fd_cells = d_c2_cells; sa.n = n;
 #ifdef PF_TWO_WAVE
   const bool pr = g_two_wave != 0 && !plateau_map(h);               // two wavefronts per search (pf_astar_pr.h)
-  const size_t lds = pr ? (size_t)PF_PR_LDS_BYTES : open_bytes(S);
-  if (pr) CK(hipFuncSetAttribute((const void*)k_mpa_search<true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-  else
 #else
-  const size_t lds = open_bytes(S);
+  const bool pr = false;
 #endif
-  CK(hipFuncSetAttribute((const void*)k_mpa_search<false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-  int per_cu = (int)((160 * 1024) / lds); if (per_cu > kWavesPerCU) per_cu = kWavesPerCU; if (per_cu < 1) per_cu = 1;
-  int grid = (h->nslots / kSlotsPerCU) * per_cu; if (grid > 2 * n) grid = 2 * n; if (grid > h->nslots) grid = h->nslots;
-  CK(hipMemsetAsync(h->d_work, 0, sizeof(int), h->stream));
-  CK(hipMemsetAsync(h->d_cnt, 0, sizeof(DevCounters), h->stream));
-  hipLaunchKernelGGL(k_mpa_plan, dim3(2 * n), dim3(64), 0, h->stream, a, jobs, jres);
-  CK(hipGetLastError());
-  CK(hipEventRecord(h->ev0, h->stream));
-#ifdef PF_TWO_WAVE
-  if (pr) hipLaunchKernelGGL(k_mpa_search<true>, dim3(grid), dim3(128), lds, h->stream, sa);
-  else
-#endif
-  hipLaunchKernelGGL(k_mpa_search<false>, dim3(grid), dim3(64), lds, h->stream, sa);
-  CK(hipGetLastError());
-  CK(hipEventRecord(h->ev1, h->stream));
-  hipLaunchKernelGGL(k_mpa_finish, dim3(2 * n), dim3(64), 0, h->stream, a, (const MpaJob*)jobs, (const MpaRes*)jres);
-  CK(hipGetLastError());
-  hipLaunchKernelGGL(k_mpa_apply, dim3(n), dim3(64), 0, h->stream, n, path_cap, d_slot, d_c1_cells, d_c1_len, d_c1_stats,
-                     d_c2_cells, d_c2_len, d_c2_stats, d_pop_cells, d_pop_len, d_pop_stats);
-  CK(hipGetLastError());
   DevCounters dc;
-  if (end_batch(h, &dc)) return -1;
-  CK(hipEventElapsedTime(&h->last_ms, h->ev0, h->ev1));
-  return 0;
+  return mpa_launch_sweep(h, a, n, pr,
+      [&](MpaJob* jobs, MpaRes* jres) { hipLaunchKernelGGL(k_mpa_plan, dim3(2 * n), dim3(64), 0, h->stream, a, jobs, jres); },
+      [&](const MpaJob* jobs, const MpaRes* jres) { hipLaunchKernelGGL(k_mpa_finish, dim3(2 * n), dim3(64), 0, h->stream, a, jobs, jres); },
+      [&] { hipLaunchKernelGGL(k_mpa_apply, dim3(n), dim3(64), 0, h->stream, n, path_cap, d_slot, d_c1_cells, d_c1_len, d_c1_stats,
+                               d_c2_cells, d_c2_len, d_c2_stats, d_pop_cells, d_pop_len, d_pop_stats); },
+      &dc);
 }
 
 // ---------------------------------------------------------------------------
@@ -3644,11 +3701,6 @@ static void mpa_batch_free(pf_mpa_batch* b) {
                   b->d_key, b->d_pay, b->d_rank, b->d_rows};
   for (void* p : ptrs) if (p) (void)hipFree(p);
   delete b;
-}
-static int mpa_batch_check(pf_mpa_batch* b, const char* what) {
-  if (!b) return failmsg(nullptr, std::string(what) + ": null batch");
-  if (!b->ready) return failmsg(b->h, std::string(what) + ": the batch belongs to a replaced grid (pf_update_grid); destroy it");
-  return 0;
 }
 static double ms_since(const std::chrono::steady_clock::time_point& t0) {
   return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
@@ -3667,7 +3719,7 @@ int pf_mpa_batch_create(pf_handle* h, const pf_mpa_params* p, const pf_score_par
   const auto t_all = std::chrono::steady_clock::now();
   CK(hipSetDevice(h->device));
   // bound tables: one per distinct start or target cell (the graph is symmetric: a table serves as ds and as dt)
-  const bool bounds = !(RC > (1 << 22) || sp->w_turn < 0.0 || sp->w_safe < 0.0 || sp->diag_pen < 0.0);   // mpa_bounds' conditions
+  const bool bounds = mpa_bounds_usable(h, sp);
   std::vector<int> cells, tab_s(K), tab_t(K);
   auto table_of = [&](int cell) {
     size_t i = 0;
@@ -3687,9 +3739,7 @@ int pf_mpa_batch_create(pf_handle* h, const pf_mpa_params* p, const pf_score_par
   pf_mpa_batch* b = new pf_mpa_batch();
   b->h = h; b->mp = *p; b->sp = *sp; b->K = K; b->N = N;
   b->mp.start = starts[0]; b->mp.target = targets[0];
-  int* d_q = nullptr;                                               // {start, target, len, status} x K for the initial searches
-  #define CKB(call) do { hipError_t e_ = (call); if (e_ != hipSuccess) { fail(h, #call, e_); if (d_q) (void)hipFree(d_q); mpa_batch_free(b); return -1; } } while (0)
-  #define RCB(call) do { if ((call) != 0) { if (d_q) (void)hipFree(d_q); mpa_batch_free(b); return -1; } } while (0)
+  const auto undo = [&] { mpa_batch_free(b); };
   CKB(hipMalloc(&b->d_tab, sizeof(MpaSchool) * (size_t)K));
   CKB(hipMalloc(&b->d_init_cells, sizeof(int) * (size_t)K * RC)); CKB(hipMalloc(&b->d_init_stats, sizeof(double) * 5 * (size_t)K));
   CKB(hipMalloc(&b->d_elite_cells, sizeof(int) * (size_t)K * RC)); CKB(hipMalloc(&b->d_elite_len, sizeof(int) * (size_t)K));
@@ -3698,40 +3748,24 @@ int pf_mpa_batch_create(pf_handle* h, const pf_mpa_params* p, const pf_score_par
   CKB(hipMalloc(&b->d_key, sizeof(unsigned long long) * (size_t)K * N)); CKB(hipMalloc(&b->d_pay, sizeof(int) * (size_t)K * N));
   CKB(hipMalloc(&b->d_rank, sizeof(unsigned) * (size_t)K * N));
   CKB(hipMalloc(&b->d_rows, sizeof(double) * 6 * (size_t)K));
-  CKB(hipMalloc(&d_q, sizeof(int) * 4 * (size_t)K));
   {
     std::vector<int> gi(N);
     for (int i = 0; i < N; ++i) gi[i] = i;
     CKB(hipMemcpyAsync(b->d_gidx, gi.data(), sizeof(int) * (size_t)N, hipMemcpyHostToDevice, h->stream));
     CKB(hipStreamSynchronize(h->stream));
   }
-  // the K initial paths MPA._generate_initial_path() = _a_star(start, target) (MPA.py:154) as ONE search batch, scored as one
+  // the K initial paths
   const auto t_init = std::chrono::steady_clock::now();
-  std::vector<int> hq(4 * (size_t)K, 0);
-  for (int k = 0; k < K; ++k) { hq[k] = starts[k]; hq[K + k] = targets[k]; }
-  CKB(hipMemcpyAsync(d_q, hq.data(), sizeof(int) * hq.size(), hipMemcpyHostToDevice, h->stream));
-  RCB(pf_astar_batch(h, PF_ASTAR_MPA, p->allow_diag, p->restrict_corner, K, d_q, d_q + K, nullptr, nullptr, RC, b->d_init_cells, d_q + 2 * K,
-                     d_q + 3 * K, nullptr));
-  CKB(hipMemcpyAsync(hq.data(), d_q, sizeof(int) * hq.size(), hipMemcpyDeviceToHost, h->stream));
-  CKB(hipStreamSynchronize(h->stream));
   b->init_len.resize(K);
-  for (int k = 0; k < K; ++k) b->init_len[k] = hq[3 * K + k] == 0 ? hq[2 * K + k] : 0;
-  RCB(pf_score_batch(h, sp, K, RC, b->d_init_cells, d_q + 2 * K, b->d_init_stats));
-  CKB(hipStreamSynchronize(h->stream));
+  CKB(mpa_initial_paths(h, p, sp, K, starts, targets, b->d_init_cells, b->d_init_stats, b->init_len.data()));
   b->create_ms[0] = ms_since(t_init);
-  (void)hipFree(d_q); d_q = nullptr;
-  // the bound tables (host Dijkstra over the device-built move masks, as mpa_bounds)
+  // the bound tables
   const auto t_bounds = std::chrono::steady_clock::now();
   if (T) {
-    const Grid G = make_grid(h, p->allow_diag, p->restrict_corner);
-    std::vector<uint8_t> mm(RC);
-    CKB(hipMemcpy(mm.data(), G.mm, RC, hipMemcpyDeviceToHost));
+    std::vector<uint8_t> mm;
+    CKB(mpa_host_masks(h, p, mm));
     CKB(hipMalloc(&b->d_bounds, sizeof(double) * T * RC));
-    std::vector<double> dist;
-    for (size_t i = 0; i < T; ++i) {
-      dijkstra_host(h, mm, cells[i], dist);
-      CKB(hipMemcpy(b->d_bounds + i * RC, dist.data(), sizeof(double) * (size_t)RC, hipMemcpyHostToDevice));
-    }
+    for (size_t i = 0; i < T; ++i) CKB(mpa_bound_table(h, mm, cells[i], b->d_bounds + i * RC));
   }
   b->create_ms[1] = ms_since(t_bounds);
   b->tab.resize(K);
@@ -3745,8 +3779,6 @@ int pf_mpa_batch_create(pf_handle* h, const pf_mpa_params* p, const pf_score_par
   CKB(hipMemcpyAsync(b->d_tab, b->tab.data(), sizeof(MpaSchool) * (size_t)K, hipMemcpyHostToDevice, h->stream));
   CKB(hipMemsetAsync(b->d_elite_len, 0, sizeof(int) * (size_t)K, h->stream));
   CKB(hipStreamSynchronize(h->stream));
-  #undef CKB
-  #undef RCB
   b->create_ms[2] = ms_since(t_all);
   b->ready = true;
   h->mpa_batches.push_back(b);
@@ -3766,7 +3798,7 @@ void pf_mpa_batch_destroy(pf_mpa_batch* b) {
 }
 
 int pf_mpa_batch_init_path(pf_mpa_batch* b, int32_t k, int32_t* cells_out, int32_t cap, int32_t* len_out, double* stats5) {
-  if (mpa_batch_check(b, "pf_mpa_batch_init_path")) return -2;
+  if (batch_check(b, "pf_mpa_batch_init_path")) return -2;
   pf_handle* h = b->h;
   if (k < 0 || k >= b->K || !len_out || cap < 0 || (cap > 0 && !cells_out)) return failmsg(h, "pf_mpa_batch_init_path: bad arguments");
   CK(hipSetDevice(h->device));
@@ -3791,7 +3823,7 @@ static MpaSchools mpa_batch_schools(const pf_mpa_batch* b) {
 }
 
 int pf_mpa_batch_sort(pf_mpa_batch* b, const double* d_pop_stats, int32_t* d_order) {
-  if (mpa_batch_check(b, "pf_mpa_batch_sort")) return -2;
+  if (batch_check(b, "pf_mpa_batch_sort")) return -2;
   pf_handle* h = b->h;
   if (!d_pop_stats || !d_order) return failmsg(h, "pf_mpa_batch_sort: bad arguments");
   CK(hipSetDevice(h->device));
@@ -3813,7 +3845,7 @@ int pf_mpa_batch_sort(pf_mpa_batch* b, const double* d_pop_stats, int32_t* d_ord
 
 int pf_mpa_batch_pick_elite(pf_mpa_batch* b, int32_t path_cap, const int32_t* d_pop_cells, const int32_t* d_pop_len,
                             const double* d_pop_stats, const int32_t* d_order) {
-  if (mpa_batch_check(b, "pf_mpa_batch_pick_elite")) return -2;
+  if (batch_check(b, "pf_mpa_batch_pick_elite")) return -2;
   pf_handle* h = b->h;
   if (path_cap < 1 || path_cap > h->RC || !d_pop_cells || !d_pop_len || !d_pop_stats || !d_order) return failmsg(h, "pf_mpa_batch_pick_elite: bad arguments");
   CK(hipSetDevice(h->device));
@@ -3824,7 +3856,7 @@ int pf_mpa_batch_pick_elite(pf_mpa_batch* b, int32_t path_cap, const int32_t* d_
 }
 
 int pf_mpa_batch_best_rows(pf_mpa_batch* b, const double* d_pop_stats, const int32_t* d_order, double* out) {
-  if (mpa_batch_check(b, "pf_mpa_batch_best_rows")) return -2;
+  if (batch_check(b, "pf_mpa_batch_best_rows")) return -2;
   pf_handle* h = b->h;
   if (!d_pop_stats || !d_order || !out) return failmsg(h, "pf_mpa_batch_best_rows: bad arguments");
   CK(hipSetDevice(h->device));
@@ -3839,7 +3871,7 @@ int pf_mpa_batch_best_rows(pf_mpa_batch* b, const double* d_pop_stats, const int
 
 int pf_mpa_batch_read_path(pf_mpa_batch* b, int32_t k, int32_t slot, int32_t path_cap, const int32_t* d_pop_cells, const int32_t* d_pop_len,
                            int32_t* cells_out, int32_t cap, int32_t* len_out) {
-  if (mpa_batch_check(b, "pf_mpa_batch_read_path")) return -2;
+  if (batch_check(b, "pf_mpa_batch_read_path")) return -2;
   pf_handle* h = b->h;
   if (k < 0 || k >= b->K || slot < 0 || slot >= b->N || path_cap < 1 || !d_pop_cells || !d_pop_len || !len_out || cap < 0 || (cap > 0 && !cells_out))
     return failmsg(h, "pf_mpa_batch_read_path: bad arguments");
@@ -3870,30 +3902,23 @@ int pf_mpa_batch_counters(pf_mpa_batch* b, pf_counters* out, int64_t* overflow_t
 int pf_mpa_batch_iterate(pf_mpa_batch* b, int32_t phase, double CF, int32_t iter, int32_t path_cap, int32_t* d_pop_cells,
                          int32_t* d_pop_len, double* d_pop_stats, const int32_t* d_order, int32_t* d_c1_cells, int32_t* d_c1_len,
                          double* d_c1_stats, int32_t* d_c2_cells, int32_t* d_c2_len, double* d_c2_stats, int32_t* d_status) {
-  if (mpa_batch_check(b, "pf_mpa_batch_iterate")) return -2;
+  if (batch_check(b, "pf_mpa_batch_iterate")) return -2;
   pf_handle* h = b->h;
   if (phase < 1 || phase > 3 || path_cap < 2 || path_cap > h->RC || !d_pop_cells || !d_pop_len || !d_pop_stats || !d_order || !d_c1_cells ||
       !d_c1_len || !d_c1_stats || !d_c2_cells || !d_c2_len || !d_c2_stats || !d_status)
     return failmsg(h, "pf_mpa_batch_iterate: bad arguments");
   const int K = b->K, N = b->N, KN = K * N;
-  if (ensure_slots(h, b->mp.allow_diag, b->mp.restrict_corner)) return -1;
   const MpaSchools ms = mpa_batch_schools(b);
   // the launch arguments every school's view starts from: row 0 of the buffers; start / target / seed / bounds / elite / initial
   // path come from the school table (school_view)
-  MpaSweepArgs a;
-  a.ph.c = make_common(h, b->mp.allow_diag, b->mp.restrict_corner, 16, 0);
-  if (make_scorep(h, &b->sp, &a.ph.sp)) return -1;
   MpaDev m; m.P = b->mp.P_const; m.levy_beta = b->mp.levy_beta; m.sigma = b->mp.levy_sigma; m.fads = b->mp.FADs_rate;
   m.N = N; m.start = -1; m.target = -1; m.ds = nullptr; m.dt = nullptr;
-  a.ph.m = m; a.ph.phase = phase; a.ph.iter = iter; a.ph.CF = CF; a.ph.seed = 0; a.ph.n = N; a.ph.path_cap = path_cap;
-  a.ph.pop_cells = d_pop_cells; a.ph.pop_len = d_pop_len; a.ph.pop_stats = d_pop_stats; a.ph.gidx = b->d_gidx; a.ph.slot = d_order;
-  a.ph.elite_cells = nullptr; a.ph.elite_len = -1; a.ph.elite_stats = nullptr; a.ph.elite_len_dev = nullptr;
-  a.ph.out_cells = d_c1_cells; a.ph.out_len = d_c1_len; a.ph.out_stats = d_c1_stats; a.ph.status = d_status;
-  a.ph.ex_idx = nullptr; a.ph.ex_levy = nullptr; a.ph.ex_scale = nullptr; a.ph.ex_agent = nullptr;
-  a.fd.c = a.ph.c; a.fd.sp = a.ph.sp; a.fd.m = m; a.fd.iter = iter; a.fd.CF = CF; a.fd.seed = 0; a.fd.n = N; a.fd.path_cap = path_cap;
-  a.fd.pop_cells = d_pop_cells; a.fd.pop_len = d_pop_len; a.fd.pop_stats = d_pop_stats; a.fd.gidx = b->d_gidx; a.fd.slot = d_order;
-  a.fd.tmp_cells = nullptr; a.fd.status = d_status;
-  a.fd.init_cells = nullptr; a.fd.init_len = 0; a.fd.init_stats = nullptr;
+  MpaBase base;
+  if (mpa_base(h, b->mp, b->sp, m, &base)) return -1;
+  MpaSweepArgs a;
+  a.ph = mpa_phase_args(base, phase, CF, iter, 0, N, path_cap, d_pop_cells, d_pop_len, d_pop_stats, b->d_gidx, d_order, d_c1_cells, d_c1_len,
+                        d_c1_stats, d_status);
+  a.fd = mpa_fads_args(base, CF, iter, 0, N, path_cap, d_pop_cells, d_pop_len, d_pop_stats, b->d_gidx, d_order, d_status);
   a.fd.cand_cells = d_c2_cells; a.fd.cand_len = d_c2_len; a.fd.cand_stats = d_c2_stats;
   int prc = 0;
   if (make_queue(h, 2 * KN, [&](float* est) {
@@ -3916,40 +3941,14 @@ int pf_mpa_batch_iterate(pf_mpa_batch* b, int32_t phase, double CF, int32_t iter
     }
     b->doubts_resolved += h->doubts_resolved - before;
   }
-  a.ph.c.queue = h->d_queue; a.fd.c.queue = h->d_queue;
-  const int S = kLdsS;
-  a.ph.c.S = S; a.fd.c.S = S; a.ph.c.retry = 0; a.fd.c.retry = 0;
-  if (2 * KN > h->job_cap) {
-    if (h->d_jobs) CK(hipFree(h->d_jobs));
-    if (h->d_jres) CK(hipFree(h->d_jres));
-    h->d_jobs = nullptr; h->d_jres = nullptr; h->job_cap = 0;
-    CK(hipMalloc(&h->d_jobs, sizeof(MpaJob) * 2 * (size_t)KN)); CK(hipMalloc(&h->d_jres, sizeof(MpaRes) * 2 * (size_t)KN));
-    h->job_cap = 2 * KN;
-  }
-  MpaJob* jobs = (MpaJob*)h->d_jobs; MpaRes* jres = (MpaRes*)h->d_jres;
-  MpaSearchArgs sa;
-  sa.c = a.ph.c; sa.jobs = jobs; sa.res = jres; sa.n_items = 2 * KN; sa.path_cap = path_cap; sa.ph_cells = d_c1_cells; sa.fd_cells = d_c2_cells; sa.n = KN;
-  const size_t lds = open_bytes(S);                                 // (one-wave searches: the two-wave engine is a solo experiment)
-  CK(hipFuncSetAttribute((const void*)k_mpa_search<false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-  int per_cu = (int)((160 * 1024) / lds); if (per_cu > kWavesPerCU) per_cu = kWavesPerCU; if (per_cu < 1) per_cu = 1;
-  int grid = (h->nslots / kSlotsPerCU) * per_cu; if (grid > 2 * KN) grid = 2 * KN; if (grid > h->nslots) grid = h->nslots;
-  CK(hipMemsetAsync(h->d_work, 0, sizeof(int), h->stream));
-  CK(hipMemsetAsync(h->d_cnt, 0, sizeof(DevCounters), h->stream));
-  hipLaunchKernelGGL(k_mpa_plan_batch<>, dim3(2 * KN), dim3(64), 0, h->stream, a, ms, jobs, jres);
-  CK(hipGetLastError());
-  CK(hipEventRecord(h->ev0, h->stream));
-  hipLaunchKernelGGL(k_mpa_search<false>, dim3(grid), dim3(64), lds, h->stream, sa);
-  CK(hipGetLastError());
-  CK(hipEventRecord(h->ev1, h->stream));
-  hipLaunchKernelGGL(k_mpa_finish_batch<>, dim3(2 * KN), dim3(64), 0, h->stream, a, ms, (const MpaJob*)jobs, (const MpaRes*)jres);
-  CK(hipGetLastError());
-  hipLaunchKernelGGL(k_mpa_apply_batch<>, dim3(KN), dim3(64), 0, h->stream, KN, N, path_cap, d_order, (const int*)d_c1_cells, (const int*)d_c1_len,
-                     (const double*)d_c1_stats, (const int*)d_c2_cells, (const int*)d_c2_len, (const double*)d_c2_stats, d_pop_cells, d_pop_len,
-                     d_pop_stats);
-  CK(hipGetLastError());
-  DevCounters dc;
-  if (end_batch(h, &dc)) return -1;
-  CK(hipEventElapsedTime(&h->last_ms, h->ev0, h->ev1));
+  DevCounters dc;                                                   // (one-wave searches: the two-wave engine is a solo experiment)
+  if (mpa_launch_sweep(h, a, KN, false,
+      [&](MpaJob* jobs, MpaRes* jres) { hipLaunchKernelGGL(k_mpa_plan_batch<>, dim3(2 * KN), dim3(64), 0, h->stream, a, ms, jobs, jres); },
+      [&](const MpaJob* jobs, const MpaRes* jres) { hipLaunchKernelGGL(k_mpa_finish_batch<>, dim3(2 * KN), dim3(64), 0, h->stream, a, ms, jobs, jres); },
+      [&] { hipLaunchKernelGGL(k_mpa_apply_batch<>, dim3(KN), dim3(64), 0, h->stream, KN, N, path_cap, d_order, (const int*)d_c1_cells,
+                               (const int*)d_c1_len, (const double*)d_c1_stats, (const int*)d_c2_cells, (const int*)d_c2_len,
+                               (const double*)d_c2_stats, d_pop_cells, d_pop_len, d_pop_stats); },
+      &dc)) return -1;
   b->last = h->last;
   b->overflow_total += (long long)dc.overflow;
   return 0;

@@ -35,6 +35,8 @@ import time
 
 import numpy as np
 
+from .mpa import cf_and_phase
+
 INF = float("inf")
 
 
@@ -556,9 +558,7 @@ class ShardedMPA:
         c.broadcast(el_s, 0, 5, er)
         c.broadcast(el_c, 0, cap, er)                                 # the elite row: path_cap x 4 B
         e.mpa_local_view(self.N, self.d_gorder, lo, hi, self.d_gidx, self.d_slot)
-        ratio = it / m.num_iterations
-        CF = 0.0 if ratio >= 1.0 else ((1.0 - ratio) ** (2.0 * ratio) if ratio > 0 else 1.0)
-        phase = 1 if it <= m.num_iterations / 3 else (2 if it <= 2 * m.num_iterations / 3 else 3)
+        CF, phase = cf_and_phase(it, m.num_iterations)
         self._fresh, self._head = False, None                        # the sweep rewrites the population
         e.mpa_iter(phase, CF, it, m.seed, n, cap, m.d_cells, m.d_len, m.d_stats, self.d_gidx, self.d_slot, el_c.ptr, -1, el_s.ptr,
                    m.d_cand_cells, m.d_cand_len, m.d_cand_stats, m.d_c2_cells, m.d_c2_len, m.d_c2_stats, m.d_status)
@@ -577,45 +577,31 @@ class ShardedMPA:
         c.broadcast(self.d_hdr, 0, 5, r)
         return gid, r, slot, self.d_hdr.read(0, 5)
 
-    def _take_best(self, s, r, slot):
-        """MPA._update_best_overall on every rank: the path row comes from its owner."""
-        m, c, e = self.local, self.comm, self.local.engine
-        if getattr(self, "_row", None) is None:
-            self._row = e.buf(m.path_cap + 1, np.int32)
-        if r == c.rank:
-            self._row.copy_from(0, m.d_len, slot, 1)
-            self._row.copy_from(1, m.d_cells, slot * m.path_cap, m.path_cap)
-        c.broadcast(self._row, 0, m.path_cap + 1, r)
-        L = int(self._row.read(0, 1)[0])
-        from .paths import CellPath
-        m.best_fitness_overall = float(s[4])
-        m.best_path_overall = CellPath(self._row.read(1, L), m.cols).tolist()
-        m.best_path_length_overall, m.best_path_turns_overall = float(s[0]), int(s[1])
-        m.best_safety_penalty_overall, m.best_diag_penalty_overall = float(s[2]), float(s[3])
+    def _fetch(self, r, slot):
+        """-> the path of predator `slot` of rank r, on every rank (the row comes from its owner), for MPA._take."""
+        def fetch():
+            m, c, e = self.local, self.comm, self.local.engine
+            if getattr(self, "_row", None) is None:
+                self._row = e.buf(m.path_cap + 1, np.int32)
+            if r == c.rank:
+                self._row.copy_from(0, m.d_len, slot, 1)
+                self._row.copy_from(1, m.d_cells, slot * m.path_cap, m.path_cap)
+            c.broadcast(self._row, 0, m.path_cap + 1, r)
+            L = int(self._row.read(0, 1)[0])
+            from .paths import CellPath
+            return CellPath(self._row.read(1, L), m.cols).tolist()
+        return fetch
 
     def solve_path_planning(self):
         m = self.local
         self._resort()                                                # :321
         _, r, slot, s = self._best_row()
-        self._take_best(s, r, slot)                                   # :322-329
-        m.convergence_curve_data.append(m.best_fitness_overall if m.best_fitness_overall != INF else None)
+        m._take_first(s, self._fetch(r, slot))                        # :322-330
         for it in range(1, m.num_iterations + 1):
             self.step(it)
             _, r, slot, s = self._best_row()
-            if s[4] < m.best_fitness_overall:                         # :415-437 with the 4-level tie-break
-                self._take_best(s, r, slot)
-            elif abs(s[4] - m.best_fitness_overall) < 1e-9:
-                bl, bt, bs, bd = (m.best_path_length_overall, m.best_path_turns_overall, m.best_safety_penalty_overall,
-                                  m.best_diag_penalty_overall)
-                if s[0] < bl or (abs(s[0] - bl) < 1e-9 and s[1] < bt) or \
-                   (abs(s[0] - bl) < 1e-9 and abs(s[1] - bt) < 1e-9 and s[2] < bs) or \
-                   (abs(s[0] - bl) < 1e-9 and abs(s[1] - bt) < 1e-9 and abs(s[2] - bs) < 1e-9 and s[3] < bd):
-                    self._take_best(s, r, slot)
-            m.convergence_curve_data.append(
-                m.best_fitness_overall if m.best_fitness_overall != INF else
-                (m.convergence_curve_data[-1] if m.convergence_curve_data and m.convergence_curve_data[-1] is not None else None))
-        return (m.best_path_overall, m.best_path_length_overall, m.best_path_turns_overall, m.best_safety_penalty_overall,
-                m.best_diag_penalty_overall, m.best_fitness_overall)
+            m._take(s, self._fetch(r, slot))                          # :415-440 with the 4-level tie-break
+        return m.result()
 
 
 # ======================================================================================================================

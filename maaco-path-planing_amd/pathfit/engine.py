@@ -94,6 +94,12 @@ def score_params(variant=0, restrict_policy=True, w_turn=0.1, w_safe=0.05, min_s
                        float(diag_pen))
 
 
+def maaco_out13(out):
+    """The 13 doubles one colony's iteration leaves (pf_maaco_iterate / pf_maaco_batch_iterate), by name."""
+    return {"ib_len": float(out[0]), "ib_turns": float(out[1]), "ib_idx": int(out[2]), "took": out[3] != 0.0, "best_len": float(out[4]),
+            "best_turns": float(out[5]), "skipped": out[8] != 0.0, "overflow_agents": int(out[12])}
+
+
 class Engine:
     def __init__(self, grid, device=0):
         g = np.ascontiguousarray(np.asarray(grid), dtype=np.int64)
@@ -324,13 +330,12 @@ class Engine:
     def maaco_iterate(self, it, seed, ant0, n, path_cap, d_cells, d_len, d_plen, d_turns, d_status, best_len, best_turns):
         """One whole iteration (walks, best scan, take-over test, pheromone update) enqueued back to back; one 104-byte block back
         (mirrored by the device into pinned host memory: the call returns once the take-over test is known).
-        -> dict(ib_len, ib_turns, ib_idx, took, best_len, best_turns, skipped, overflow_agents)."""
+        -> maaco_out13 of it."""
         out = self._out13
         self._ck(self.L.pf_maaco_iterate(self.h, int(it), int(seed), int(ant0), int(n), int(path_cap), d_cells.ptr, d_len.ptr, d_plen.ptr,
                                          d_turns.ptr, d_status.ptr, float(best_len), float(best_turns), C.addressof(out)))
         self._logk("maaco_walk")
-        return {"ib_len": float(out[0]), "ib_turns": float(out[1]), "ib_idx": int(out[2]), "took": out[3] != 0.0, "best_len": float(out[4]),
-                "best_turns": float(out[5]), "skipped": out[8] != 0.0, "overflow_agents": int(out[12])}
+        return maaco_out13(out)
 
     def maaco_best_path(self, cap):
         """The overall best ant's cells as pf_maaco_iterate keeps them in HBM (empty: none yet)."""

@@ -20,6 +20,28 @@ from .paths import CellPath
 INF = float("inf")
 
 
+def grow_path_cap(obj, overflowed, fatal=True):
+    """After a walk with rows of obj.path_cap cells: -> True when ants overflowed them and the caller has to redo the walk, with
+    rows 4 x longer (no pheromone moved).  Rows that already hold the whole grid cannot grow: an error, unless not `fatal`."""
+    if overflowed and obj.path_cap < obj.rows * obj.cols:
+        obj.path_cap = min(obj.rows * obj.cols, obj.path_cap * 4)
+        return True
+    if overflowed and fatal:
+        raise RuntimeError("pathfit: path capacity overflow in a MAACO walk")
+    return False
+
+
+def take_iteration(state, r):
+    """MAACO.py:351-359 from the device's verdict r (engine.maaco_out13) on `state` (a MAACO or a MaacoColony): a new overall
+    best stays in HBM until `best_path_overall` is read (the take-over kernel copied the row there).  -> ib_len."""
+    if r["took"] and r["ib_idx"] >= 0:
+        state.best_path_length_overall = r["best_len"]
+        state._best_on_device = True
+        state.best_path_turns_overall = int(r["best_turns"]) if r["best_turns"] != INF else INF
+    state.convergence_curve_data.append(state.best_path_length_overall if state.best_path_length_overall != INF else None)
+    return r["ib_len"]
+
+
 class MAACO:
     def __init__(self, grid, num_ants, num_iterations, alpha, beta, rho, Q, a_turn_coef, wh_max, wh_min,
                  k_h_adaptive, q0_initial, C0_initial_pheromone=0.1, engine=None, device=0, seed=0, verbose=False):
@@ -89,11 +111,8 @@ class MAACO:
         while True:
             dc, dl, dp, dt, ds = self._alloc(n)
             self.engine.maaco_walk(iter_num, self.seed, ant0, n, self.path_cap, dc, dl, dp, dt, ds)
-            if self.engine.counters()["overflow_agents"] and self.path_cap < self.rows * self.cols:
-                self.path_cap = min(self.rows * self.cols, self.path_cap * 4)     # path buffer too small: redo
-                continue
-            break
-        return n
+            if not grow_path_cap(self, self.engine.counters()["overflow_agents"], fatal=False):
+                return n
 
     def walk_bufs(self):
         """(cells [n][cap], len [n], plen [n], turns [n], status [n]) device buffers of the last walk."""
@@ -131,18 +150,8 @@ class MAACO:
             dc, dl, dp, dt, ds = self._alloc(n)
             r = self.engine.maaco_iterate(iter_num, self.seed, ant0, n, self.path_cap, dc, dl, dp, dt, ds,
                                           self.best_path_length_overall, self.best_path_turns_overall)
-            if r["overflow_agents"] and self.path_cap < self.rows * self.cols:
-                self.path_cap = min(self.rows * self.cols, self.path_cap * 4)     # path rows too small: redo (tau was left untouched)
-                continue
-            if r["overflow_agents"]:
-                raise RuntimeError("pathfit: path capacity overflow in a MAACO walk")
-            break
-        if r["took"] and r["ib_idx"] >= 0:
-            self.best_path_length_overall = r["best_len"]
-            self._best_on_device = True                                    # (k_maaco_best_take copied the row on the device)
-            self.best_path_turns_overall = int(r["best_turns"]) if r["best_turns"] != INF else INF
-        self.convergence_curve_data.append(self.best_path_length_overall if self.best_path_length_overall != INF else None)
-        return r["ib_len"]
+            if not grow_path_cap(self, r["overflow_agents"]):                        # (else redo: tau was left untouched)
+                return take_iteration(self, r)
 
     def solve_path_planning(self):
         for iter_num in range(1, self.num_iterations + 1):

@@ -10,29 +10,13 @@ import ctypes as C
 
 import numpy as np
 
-from ._lib import MaacoParams, PathfitError
-from .engine import Engine
-from .env import OBSTACLE, START_NODE_VAL, TARGET_NODE_VAL, find_marker
+from ._batch import EngineOwned, cell_ids, check_endpoints, check_grid_and_seeds
+from ._lib import MaacoParams
+from .engine import Engine, maaco_out13
+from .maaco import grow_path_cap, take_iteration
 from .paths import CellPath
 
 INF = float("inf")
-
-
-def _cells(name, pts, K, R, Cc, grid):
-    out = []
-    for k, p in enumerate(pts):
-        try:
-            r, c = (int(v) for v in p)
-        except (TypeError, ValueError):
-            raise ValueError(f"MAACOBatch: {name}[{k}] must be an (r, c) pair, got {p!r}") from None
-        if not (0 <= r < R and 0 <= c < Cc):
-            raise ValueError(f"MAACOBatch: {name}[{k}] = {(r, c)} is outside the {R}x{Cc} grid")
-        if grid[r, c] == OBSTACLE:
-            raise ValueError(f"MAACOBatch: {name}[{k}] = {(r, c)} is on an obstacle")
-        out.append((r, c))
-    if len(out) != K:
-        raise ValueError(f"MAACOBatch: {len(out)} {name} for {K} seeds")
-    return out
 
 
 class MaacoColony:
@@ -77,29 +61,17 @@ class MaacoColony:
         return self.best_path_overall, self.best_path_length_overall, self.best_path_turns_overall
 
 
-class MAACOBatch:
+class MAACOBatch(EngineOwned):
+    _destroy = "pf_maaco_batch_destroy"
+
     def __init__(self, grid, num_ants, num_iterations, alpha, beta, rho, Q, a_turn_coef, wh_max, wh_min,
                  k_h_adaptive, q0_initial, C0_initial_pheromone=0.1, seeds=(), starts=None, targets=None, engine=None,
                  device=0, verbose=False):
         # every argument is checked before the device is touched
-        self.grid = np.array(grid, dtype=int)
-        if self.grid.ndim != 2:
-            raise ValueError("MAACOBatch: grid must be 2-D")
+        self.grid, self.seeds = check_grid_and_seeds("MAACOBatch", grid, seeds, "colony", "num_ants", num_ants)
         self.rows, self.cols = self.grid.shape
-        self.seeds = [int(s) for s in seeds]
         K = len(self.seeds)
-        if K == 0:
-            raise ValueError("MAACOBatch: seeds is empty (one seed per colony)")
-        if any(s < 0 or s >= 1 << 64 for s in self.seeds):
-            raise ValueError("MAACOBatch: seeds must be in [0, 2^64)")
-        if int(num_ants) < 1:
-            raise ValueError("MAACOBatch: num_ants must be >= 1")
-        if starts is None:
-            starts = [find_marker(self.grid, START_NODE_VAL, "MAACO")] * K
-        if targets is None:
-            targets = [find_marker(self.grid, TARGET_NODE_VAL, "MAACO")] * K
-        self.starts = _cells("starts", list(starts), K, self.rows, self.cols, self.grid)
-        self.targets = _cells("targets", list(targets), K, self.rows, self.cols, self.grid)
+        self.starts, self.targets = check_endpoints("MAACOBatch", "MAACO", self.grid, starts, targets, K)
         self.K = K
         self.num_ants, self.num_iterations = int(num_ants), int(num_iterations)
         self.alpha, self.beta, self.rho, self.Q = alpha, beta, rho, Q
@@ -109,10 +81,7 @@ class MAACOBatch:
         self.verbose = verbose
         self.engine = engine if engine is not None else Engine(self.grid, device)
         e = self.engine
-        if (e.R, e.C) != (self.rows, self.cols):
-            raise ValueError("MAACOBatch: the engine's grid has another shape")
-        s = np.array([r * self.cols + c for r, c in self.starts], np.int32)
-        t = np.array([r * self.cols + c for r, c in self.targets], np.int32)
+        s, t = cell_ids(e, "MAACOBatch", self.grid, self.starts, self.targets)
         sd = np.array(self.seeds, np.uint64)
         params = MaacoParams(float(alpha), float(beta), float(rho), float(Q), float(a_turn_coef), float(wh_max), float(wh_min),
                              float(k_h_adaptive), float(q0_initial), float(C0_initial_pheromone), self.num_iterations,
@@ -126,27 +95,6 @@ class MAACOBatch:
         self._bufs = None
         self._out = np.empty((K, 13), np.float64)
         self._colonies = [MaacoColony(self, k) for k in range(K)]
-
-    def _ck(self, rc):
-        if rc != 0:
-            raise PathfitError(self.engine.L.pf_last_error(self.engine.h).decode())
-
-    def _handle(self):
-        if not self._b or not getattr(self.engine, "h", None):
-            raise PathfitError("MAACOBatch: the batch is closed")
-        return self._b
-
-    def close(self):
-        # (a closed Engine has freed its batches already)
-        if getattr(self, "_b", None) and getattr(self.engine, "h", None):
-            self.engine.L.pf_maaco_batch_destroy(self._b)
-        self._b = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
 
     def colony(self, k):
         return self._colonies[k]
@@ -179,23 +127,8 @@ class MAACOBatch:
             self._ck(self.engine.L.pf_maaco_batch_iterate(self._handle(), int(iter_num), self.num_ants, self.path_cap, dc.ptr, dl.ptr,
                                                           dp.ptr, dt.ptr, ds.ptr, bl.ctypes.data, bt.ctypes.data,
                                                           self._out.ctypes.data))
-            ovf = self._out[0, 12]
-            if ovf and self.path_cap < self.rows * self.cols:
-                self.path_cap = min(self.rows * self.cols, self.path_cap * 4)     # path rows too small: redo (tau was left untouched)
-                continue
-            if ovf:
-                raise RuntimeError("pathfit: path capacity overflow in a MAACO walk")
-            break
-        ib = []
-        for k, c in enumerate(cols):
-            r = self._out[k]
-            if r[3] and r[2] >= 0:
-                c.best_path_length_overall = float(r[4])
-                c._best_on_device = True
-                c.best_path_turns_overall = int(r[5]) if r[5] != INF else INF
-            c.convergence_curve_data.append(c.best_path_length_overall if c.best_path_length_overall != INF else None)
-            ib.append(float(r[0]))
-        return ib
+            if not grow_path_cap(self, self._out[0, 12]):                            # (else redo: tau was left untouched)
+                return [take_iteration(c, maaco_out13(self._out[k])) for k, c in enumerate(cols)]
 
     def solve_path_planning(self):
         for iter_num in range(1, self.num_iterations + 1):

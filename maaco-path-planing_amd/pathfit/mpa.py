@@ -32,7 +32,66 @@ def levy_sigma(beta):
     return (num / den) ** (1 / beta) if den > 1e-9 else 1.0
 
 
-class MPA:
+def cf_and_phase(it, num_iterations):
+    """CF (MPA.py:336) and the phase (1, 2, 3: thirds of the run) of iteration `it` (1-based)."""
+    ratio = it / num_iterations
+    CF = 0.0 if ratio >= 1.0 else ((1.0 - ratio) ** (2.0 * ratio) if ratio > 0 else 1.0)
+    phase = 1 if it <= num_iterations / 3 else (2 if it <= 2 * num_iterations / 3 else 3)
+    return CF, phase
+
+
+class BestSoFar:
+    """The reference's best-so-far state of one population (MPA.py:30-36) and its rules.  `s` is the stats[5] of the best
+    predator of an iteration (length, turns, safety penalty, diagonal penalty, fitness); `fetch()` brings its path as a
+    list of (r, c) and is called only when that predator becomes the best so far."""
+
+    def _init_best(self):
+        self.best_path_overall = []
+        self.best_path_length_overall = INF
+        self.best_path_turns_overall = INF
+        self.best_safety_penalty_overall = INF
+        self.best_diag_penalty_overall = INF
+        self.best_fitness_overall = INF
+        self.convergence_curve_data = []
+
+    def _update_best(self, s, fetch):
+        self.best_fitness_overall = float(s[4])
+        self.best_path_overall = fetch()
+        self.best_path_length_overall = float(s[0])
+        self.best_path_turns_overall = int(s[1])
+        self.best_safety_penalty_overall = float(s[2])
+        self.best_diag_penalty_overall = float(s[3])
+
+    def _take_first(self, s, fetch):
+        """MPA.py:322-330: the initial population's best and the first point of the curve."""
+        self._update_best(s, fetch)
+        self.convergence_curve_data.append(self.best_fitness_overall if self.best_fitness_overall != INF else None)
+
+    def _take(self, s, fetch):
+        """MPA.py:415-440: best-so-far with the 4-level tie-break, then the iteration's point of the curve."""
+        if s[4] < self.best_fitness_overall:
+            self._update_best(s, fetch)
+        elif abs(s[4] - self.best_fitness_overall) < 1e-9:
+            bl, bt, bs, bd = (self.best_path_length_overall, self.best_path_turns_overall,
+                              self.best_safety_penalty_overall, self.best_diag_penalty_overall)
+            if s[0] < bl:
+                self._update_best(s, fetch)
+            elif abs(s[0] - bl) < 1e-9 and s[1] < bt:
+                self._update_best(s, fetch)
+            elif abs(s[0] - bl) < 1e-9 and abs(s[1] - bt) < 1e-9 and s[2] < bs:
+                self._update_best(s, fetch)
+            elif abs(s[0] - bl) < 1e-9 and abs(s[1] - bt) < 1e-9 and abs(s[2] - bs) < 1e-9 and s[3] < bd:
+                self._update_best(s, fetch)
+        c = self.convergence_curve_data
+        c.append(self.best_fitness_overall if self.best_fitness_overall != INF else
+                 (c[-1] if c and c[-1] is not None else None))
+
+    def result(self):
+        return (self.best_path_overall, self.best_path_length_overall, self.best_path_turns_overall,
+                self.best_safety_penalty_overall, self.best_diag_penalty_overall, self.best_fitness_overall)
+
+
+class MPA(BestSoFar):
     def __init__(self, grid, num_predators, num_iterations, FADs_rate=0.2, P_const=0.5, levy_beta=1.5,
                  turn_penalty_factor=0.1, safety_penalty_factor=0.05, min_safe_distance=1.5, allow_diagonal_moves=True,
                  restrict_diagonal_near_obstacle=True, diagonal_obstacle_penalty=1000.0, engine=None, device=0, seed=0,
@@ -50,13 +109,7 @@ class MPA:
         self.start_node = find_marker(self.grid, START_NODE_VAL, "MPA")
         self.target_node = find_marker(self.grid, TARGET_NODE_VAL, "MPA")
         self.obstacle_nodes = np.argwhere(self.grid == 1)
-        self.best_path_overall = []
-        self.best_path_length_overall = INF
-        self.best_path_turns_overall = INF
-        self.best_safety_penalty_overall = INF
-        self.best_diag_penalty_overall = INF
-        self.best_fitness_overall = INF
-        self.convergence_curve_data = []
+        self._init_best()
         self.seed, self.verbose = int(seed), verbose
         self.n_local = int(n_local) if n_local else int(num_predators)   # predators stored on this GPU (sharding)
         self.fused = bool(fused)   # one work queue for the phase sweep + FADs candidates (pf_mpa_iter_batch)
@@ -125,6 +178,9 @@ class MPA:
         L = int(self.d_len.read(slot, 1)[0])
         return self.d_cells.read(slot * self.path_cap, L)
 
+    def _fetch(self, slot):
+        return lambda: CellPath(self._path_of_slot(slot), self.cols).tolist()
+
     def _sort(self):
         """list.sort(key=fitness) is stable (MPA.py:321,:333,:412): device sort of the list order.  The sort at the start of an
         iteration (:333) re-sorts the list the end of the previous one (:412) left sorted on the same keys -- nothing -- and is
@@ -139,22 +195,12 @@ class MPA:
         slot = int(self.d_order.read(0, 1)[0])
         return slot, self.d_stats.read(slot * 5, 5)
 
-    def _update_best(self, s, slot):
-        self.best_fitness_overall = float(s[4])
-        self.best_path_overall = CellPath(self._path_of_slot(slot), self.cols).tolist()
-        self.best_path_length_overall = float(s[0])
-        self.best_path_turns_overall = int(s[1])
-        self.best_safety_penalty_overall = float(s[2])
-        self.best_diag_penalty_overall = float(s[3])
-
     def step(self, it):
         """One iteration of MPA.py:332-440 (it is 1-based)."""
         e, N, cap = self.engine, self.n_local, self.path_cap
         self._sort()                                                     # :333
         e.mpa_pick_elite(cap, self.d_cells, self.d_len, self.d_stats, self.d_order)   # :334 elite = population[0].copy()
-        ratio = it / self.num_iterations
-        CF = 0.0 if ratio >= 1.0 else ((1.0 - ratio) ** (2.0 * ratio) if ratio > 0 else 1.0)   # :336
-        phase = 1 if it <= self.num_iterations / 3 else (2 if it <= 2 * self.num_iterations / 3 else 3)
+        CF, phase = cf_and_phase(it, self.num_iterations)                # :336
         el_c, el_s = self._el_cells.ptr, self._el_stats.ptr
         self._sorted = False                                             # the sweep rewrites the population
         if self.fused:
@@ -173,23 +219,7 @@ class MPA:
             self._check_overflow()
         self._sort()                                                     # :412
         slot, s = self._best_row()
-        # :415-437 best-so-far with the 4-level tie-break
-        if s[4] < self.best_fitness_overall:
-            self._update_best(s, slot)
-        elif abs(s[4] - self.best_fitness_overall) < 1e-9:
-            bl, bt, bs, bd = (self.best_path_length_overall, self.best_path_turns_overall,
-                              self.best_safety_penalty_overall, self.best_diag_penalty_overall)
-            if s[0] < bl:
-                self._update_best(s, slot)
-            elif abs(s[0] - bl) < 1e-9 and s[1] < bt:
-                self._update_best(s, slot)
-            elif abs(s[0] - bl) < 1e-9 and abs(s[1] - bt) < 1e-9 and s[2] < bs:
-                self._update_best(s, slot)
-            elif abs(s[0] - bl) < 1e-9 and abs(s[1] - bt) < 1e-9 and abs(s[2] - bs) < 1e-9 and s[3] < bd:
-                self._update_best(s, slot)
-        self.convergence_curve_data.append(
-            self.best_fitness_overall if self.best_fitness_overall != INF else
-            (self.convergence_curve_data[-1] if self.convergence_curve_data and self.convergence_curve_data[-1] is not None else None))
+        self._take(s, self._fetch(slot))                                 # :415-440
         return s
 
     def _check_overflow(self):
@@ -200,11 +230,9 @@ class MPA:
     def solve_path_planning(self):
         self._sort()                                                     # :321
         slot, s0 = self._best_row()
-        self._update_best(s0, slot)                                      # :322-329
-        self.convergence_curve_data.append(self.best_fitness_overall if self.best_fitness_overall != INF else None)
+        self._take_first(s0, self._fetch(slot))                          # :322-330
         for it in range(1, self.num_iterations + 1):
             s = self.step(it)
             if self.verbose and (it % 10 == 0 or it == 1 or it == self.num_iterations):
                 print(f"MPA Iter {it}/{self.num_iterations}: IterBest Fit={s[4]:.2f}; OverallBest Fit={self.best_fitness_overall:.2f}")
-        return (self.best_path_overall, self.best_path_length_overall, self.best_path_turns_overall,
-                self.best_safety_penalty_overall, self.best_diag_penalty_overall, self.best_fitness_overall)
+        return self.result()

@@ -15,46 +15,21 @@ import ctypes as C
 
 import numpy as np
 
-from ._lib import Counters, MpaParams, PathfitError
+from ._batch import EngineOwned, cell_ids, check_endpoints, check_grid_and_seeds
+from ._lib import Counters, MpaParams
 from .engine import Engine, score_params
-from .env import OBSTACLE, START_NODE_VAL, TARGET_NODE_VAL, find_marker
-from .mpa import levy_sigma
+from .mpa import BestSoFar, cf_and_phase, levy_sigma
 from .paths import CellPath
 
-INF = float("inf")
 
-
-def _cells(name, pts, K, R, Cc, grid):
-    out = []
-    for k, p in enumerate(pts):
-        try:
-            r, c = (int(v) for v in p)
-        except (TypeError, ValueError):
-            raise ValueError(f"MPABatch: {name}[{k}] must be an (r, c) pair, got {p!r}") from None
-        if not (0 <= r < R and 0 <= c < Cc):
-            raise ValueError(f"MPABatch: {name}[{k}] = {(r, c)} is outside the {R}x{Cc} grid")
-        if grid[r, c] == OBSTACLE:
-            raise ValueError(f"MPABatch: {name}[{k}] = {(r, c)} is on an obstacle")
-        out.append((r, c))
-    if len(out) != K:
-        raise ValueError(f"MPABatch: {len(out)} {name} for {K} seeds")
-    return out
-
-
-class MpaSchool:
+class MpaSchool(BestSoFar):
     """School k of an MPABatch, with MPA's read surface (MPA.py:30-36, :320-448)."""
 
     def __init__(self, batch, k):
         self._b, self.k = batch, k
         self.start_node, self.target_node = batch.starts[k], batch.targets[k]
         self.seed = batch.seeds[k]
-        self.best_path_overall = []
-        self.best_path_length_overall = INF
-        self.best_path_turns_overall = INF
-        self.best_safety_penalty_overall = INF
-        self.best_diag_penalty_overall = INF
-        self.best_fitness_overall = INF
-        self.convergence_curve_data = []
+        self._init_best()
 
     @property
     def order(self):
@@ -77,64 +52,24 @@ class MpaSchool:
                         "fitness": float(s[4])})
         return out
 
-    def _update_best(self, s, slot):
-        self.best_fitness_overall = float(s[4])
-        self.best_path_overall = CellPath(self._b._path_of_slot(self.k, slot), self._b.cols).tolist()
-        self.best_path_length_overall = float(s[0])
-        self.best_path_turns_overall = int(s[1])
-        self.best_safety_penalty_overall = float(s[2])
-        self.best_diag_penalty_overall = float(s[3])
-
-    def _take(self, s, slot):
-        """MPA.py:415-437: best-so-far with the 4-level tie-break, on the school's best row of the iteration."""
-        if s[4] < self.best_fitness_overall:
-            self._update_best(s, slot)
-        elif abs(s[4] - self.best_fitness_overall) < 1e-9:
-            bl, bt, bs, bd = (self.best_path_length_overall, self.best_path_turns_overall,
-                              self.best_safety_penalty_overall, self.best_diag_penalty_overall)
-            if s[0] < bl:
-                self._update_best(s, slot)
-            elif abs(s[0] - bl) < 1e-9 and s[1] < bt:
-                self._update_best(s, slot)
-            elif abs(s[0] - bl) < 1e-9 and abs(s[1] - bt) < 1e-9 and s[2] < bs:
-                self._update_best(s, slot)
-            elif abs(s[0] - bl) < 1e-9 and abs(s[1] - bt) < 1e-9 and abs(s[2] - bs) < 1e-9 and s[3] < bd:
-                self._update_best(s, slot)
-        c = self.convergence_curve_data
-        c.append(self.best_fitness_overall if self.best_fitness_overall != INF else
-                 (c[-1] if c and c[-1] is not None else None))
-
-    def result(self):
-        return (self.best_path_overall, self.best_path_length_overall, self.best_path_turns_overall,
-                self.best_safety_penalty_overall, self.best_diag_penalty_overall, self.best_fitness_overall)
+    def _fetch(self, slot):
+        return lambda: CellPath(self._b._path_of_slot(self.k, slot), self._b.cols).tolist()
 
 
-class MPABatch:
+class MPABatch(EngineOwned):
+    _destroy = "pf_mpa_batch_destroy"
+
     def __init__(self, grid, num_predators, num_iterations, seeds=(), starts=None, targets=None, FADs_rate=0.2, P_const=0.5,
                  levy_beta=1.5, turn_penalty_factor=0.1, safety_penalty_factor=0.05, min_safe_distance=1.5,
                  allow_diagonal_moves=True, restrict_diagonal_near_obstacle=True, diagonal_obstacle_penalty=1000.0,
                  engine=None, device=0, verbose=False, path_cap=None):
         # every argument is checked before the device is touched
-        self.grid = np.array(grid, dtype=int)
-        if self.grid.ndim != 2:
-            raise ValueError("MPABatch: grid must be 2-D")
+        self.grid, self.seeds = check_grid_and_seeds("MPABatch", grid, seeds, "school", "num_predators", num_predators)
         self.rows, self.cols = self.grid.shape
-        self.seeds = [int(s) for s in seeds]
         K = len(self.seeds)
-        if K == 0:
-            raise ValueError("MPABatch: seeds is empty (one seed per school)")
-        if any(s < 0 or s >= 1 << 64 for s in self.seeds):
-            raise ValueError("MPABatch: seeds must be in [0, 2^64)")
-        if int(num_predators) < 1:
-            raise ValueError("MPABatch: num_predators must be >= 1")
         if path_cap is not None and int(path_cap) < 2:
             raise ValueError("MPABatch: path_cap must be >= 2")
-        if starts is None:
-            starts = [find_marker(self.grid, START_NODE_VAL, "MPA")] * K
-        if targets is None:
-            targets = [find_marker(self.grid, TARGET_NODE_VAL, "MPA")] * K
-        self.starts = _cells("starts", list(starts), K, self.rows, self.cols, self.grid)
-        self.targets = _cells("targets", list(targets), K, self.rows, self.cols, self.grid)
+        self.starts, self.targets = check_endpoints("MPABatch", "MPA", self.grid, starts, targets, K)
         self.K = K
         self.num_predators, self.num_iterations = int(num_predators), int(num_iterations)
         self.FADs_rate, self.P_const, self.levy_beta = FADs_rate, P_const, levy_beta
@@ -143,10 +78,7 @@ class MPABatch:
         self.verbose = verbose
         self.engine = engine if engine is not None else Engine(self.grid, device)
         e = self.engine
-        if (e.R, e.C) != (self.rows, self.cols):
-            raise ValueError("MPABatch: the engine's grid has another shape")
-        self._s = np.array([r * self.cols + c for r, c in self.starts], np.int32)
-        self._t = np.array([r * self.cols + c for r, c in self.targets], np.int32)
+        self._s, self._t = cell_ids(e, "MPABatch", self.grid, self.starts, self.targets)
         sd = np.array(self.seeds, np.uint64)
         self._sp = score_params(1, restrict_diagonal_near_obstacle, turn_penalty_factor, safety_penalty_factor,
                                 min_safe_distance, diagonal_obstacle_penalty)
@@ -166,27 +98,6 @@ class MPABatch:
         self._init_population()
 
     # ------------------------------------------------------------------
-    def _ck(self, rc):
-        if rc != 0:
-            raise PathfitError(self.engine.L.pf_last_error(self.engine.h).decode())
-
-    def _handle(self):
-        if not self._b or not getattr(self.engine, "h", None):
-            raise PathfitError("MPABatch: the batch is closed")
-        return self._b
-
-    def close(self):
-        # (a closed Engine has freed its batches already)
-        if getattr(self, "_b", None) and getattr(self.engine, "h", None):
-            self.engine.L.pf_mpa_batch_destroy(self._b)
-        self._b = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
     def school(self, k):
         return self._schools[k]
 
@@ -256,9 +167,7 @@ class MPABatch:
         h = self._handle()
         self._sort()                                                     # :333
         self._ck(e.L.pf_mpa_batch_pick_elite(h, cap, self.d_cells.ptr, self.d_len.ptr, self.d_stats.ptr, self.d_order.ptr))   # :334
-        ratio = it / self.num_iterations
-        CF = 0.0 if ratio >= 1.0 else ((1.0 - ratio) ** (2.0 * ratio) if ratio > 0 else 1.0)   # :336
-        phase = 1 if it <= self.num_iterations / 3 else (2 if it <= 2 * self.num_iterations / 3 else 3)
+        CF, phase = cf_and_phase(it, self.num_iterations)                # :336
         self._sorted = False                                             # the sweep rewrites the populations
         self._ck(e.L.pf_mpa_batch_iterate(h, phase, CF, int(it), cap, self.d_cells.ptr, self.d_len.ptr, self.d_stats.ptr,
                                           self.d_order.ptr, self.d_c1_cells.ptr, self.d_c1_len.ptr, self.d_c1_stats.ptr,
@@ -269,7 +178,7 @@ class MPABatch:
         self._sort()                                                     # :412
         rows = self._best_rows()
         for k, sc in enumerate(self._schools):
-            sc._take(rows[k, 1:], int(rows[k, 0]))                       # :415-437
+            sc._take(rows[k, 1:], sc._fetch(int(rows[k, 0])))            # :415-440
         return rows[:, 1:].copy()
 
     def begin(self):
@@ -277,8 +186,7 @@ class MPABatch:
         self._sort()                                                     # :321
         rows = self._best_rows()
         for k, sc in enumerate(self._schools):
-            sc._update_best(rows[k, 1:], int(rows[k, 0]))                # :322-329
-            sc.convergence_curve_data.append(sc.best_fitness_overall if sc.best_fitness_overall != INF else None)
+            sc._take_first(rows[k, 1:], sc._fetch(int(rows[k, 0])))      # :322-330
 
     def solve_path_planning(self):
         self.begin()
