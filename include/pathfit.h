@@ -135,6 +135,16 @@ int pf_decode_batch(pf_handle* h, int32_t allow_diag, int32_t restrict_corner, i
                     const int32_t* d_wp_cells, const double* d_wp_pos, int32_t start, int32_t target,
                     int32_t path_cap, int32_t* d_cells, int32_t* d_len, int32_t* d_status,
                     const pf_score_params* sp, double* d_stats);
+/* pf_decode_batch with a start and a target cell PER AGENT (d_start, d_target: int32[n] in HBM, the convention of
+ * pf_astar_batch): agent a decodes start d_start[a] -> its W waypoints -> d_target[a] exactly as pf_decode_batch(start =
+ * d_start[a], target = d_target[a]) decodes it -- ga_solver.py:58-93 / pso.py:56-94 with self.start_node / self.target_node
+ * taken per agent -- so decodes of different start / target pairs (K GA populations, pathfit.GABatch) share one launch, one
+ * longest-first queue and one tail policy.  A cell outside the grid in d_start / d_target is an argument error (-1) found by
+ * the planner before the decode is launched (one 4-byte read); a start or target ON an obstacle is legal and gives status 1. */
+int pf_decode_batch_multi(pf_handle* h, int32_t allow_diag, int32_t restrict_corner, int32_t n, int32_t W,
+                          const int32_t* d_wp_cells, const double* d_wp_pos, const int32_t* d_start, const int32_t* d_target,
+                          int32_t path_cap, int32_t* d_cells, int32_t* d_len, int32_t* d_status,
+                          const pf_score_params* sp, double* d_stats);
 
 /* ---- K6: PSO velocity/position update ------------------------------ */
 /* Replaces the inner loop pso.py:183-203 for particles agent0..agent0+n with
@@ -419,6 +429,33 @@ int pf_ga_assemble_dev(pf_handle* h, int32_t n_loc, int32_t W, int32_t path_cap,
                        const int32_t* d_chrom_old, const double* d_stats_old, const int32_t* d_cells_old, const int32_t* d_len_old,
                        int32_t old_lo, int32_t old_hi, int32_t* d_chrom_new, double* d_stats_new, int32_t* d_cells_new,
                        int32_t* d_len_new);
+
+/* ---- K independent GA populations in one batched generation (pathfit.GABatch) -----------------------------------------
+ * Population k has its own seed d_seeds[k] (uint64[K] in HBM) and, through pf_decode_batch_multi, its own start and target;
+ * the K populations share the grid, N, W and the rates.  Layout of every buffer: population k owns rows [k N, (k + 1) N);
+ * the ids inside d_gorder / d_psid are LOCAL (0 .. N - 1).  Population k computes exactly what the solo calls compute on its
+ * rows with seed d_seeds[k].  The entries are stateless (the caller owns every buffer; scratch is the handle's), stream
+ * ordered, and make no host copies except pf_best_rows_seg.
+ * pf_ga_select_batch: GASolver._selection (ga_solver.py:136-142, :181) for all K populations: K replays of the streams
+ *   (d_seeds[k], DOM_GA_SELECT, gen, 0) side by side, one wavefront each (pf_ga_select_dev for every k).
+ * pf_ga_breed_batch: _crossover + _mutate (ga_solver.py:144-160, :186-194) for all N children of all K populations, thread per
+ *   (population, pair), stream (d_seeds[k], DOM_GA, gen, pair) -> d_out [K N][W] (pf_ga_breed_dev with child0 = 0, nchild = N).
+ * pf_ga_assemble_batch: ga_solver.py:198-205 for all K N children: child or fallback parent d_psid[k N + i] of the
+ *   population's own old rows (pf_ga_assemble_dev with lo = old_lo = 0, old_hi = N: no row is ever absent).
+ * pf_sort_order_by_key_seg: K times list.sort(key=fitness) (ga_solver.py:209): segment k of d_order [K n] (position -> LOCAL
+ *   id) is re-ordered by a STABLE sort on d_vals[(k n + id) * stride + offset]; no segment sees another's keys.
+ * pf_best_rows_seg: population[0] of every population after the sort (ga_solver.py:210-213) in one copy: out[6 k ...] =
+ *   {local id at the head of segment k, the five doubles d_stats[(k N + id) * 5 ...]}. */
+int pf_ga_select_batch(pf_handle* h, const uint64_t* d_seeds, int32_t gen, int32_t K, int32_t N, int32_t tournament_size,
+                       const double* d_fit_all, const int32_t* d_gorder, int32_t* d_psid);
+int pf_ga_breed_batch(pf_handle* h, const uint64_t* d_seeds, int32_t gen, int32_t K, int32_t N, int32_t W, double crossover_rate,
+                      double mutation_rate, const int32_t* d_chrom_all, const int32_t* d_psid, int32_t* d_out);
+int pf_ga_assemble_batch(pf_handle* h, int32_t K, int32_t N, int32_t W, int32_t path_cap, const int32_t* d_kid_len,
+                         const int32_t* d_kid_chrom, const double* d_kid_stats, const int32_t* d_kid_cells, const int32_t* d_psid,
+                         const int32_t* d_chrom_old, const double* d_stats_old, const int32_t* d_cells_old, const int32_t* d_len_old,
+                         int32_t* d_chrom_new, double* d_stats_new, int32_t* d_cells_new, int32_t* d_len_new);
+int pf_sort_order_by_key_seg(pf_handle* h, int32_t K, int32_t n, const double* d_vals, int32_t stride, int32_t offset, int32_t* d_order);
+int pf_best_rows_seg(pf_handle* h, int32_t K, int32_t N, const double* d_stats, const int32_t* d_order, double* out);
 
 /* MAACO.py:306-311 in two steps (the multi-GPU fold works on row chunks): _begin marks the cells of the successful
  * ants and computes Q / L per ant, _cells adds the deposits of cells [cell0, cell1) in ant order.  pf_maaco_deposit =

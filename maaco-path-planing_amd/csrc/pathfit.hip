@@ -193,24 +193,10 @@ __global__ void k_plan_astar(Grid G, int n, const int* start, const int* target,
   const int a = blockIdx.x * blockDim.x + threadIdx.x;
   if (a < n) est[a] = cell_dist(G, start[a], target[a]);
 }
-__global__ void k_plan_decode(Grid G, int n, int W, const int* wp_cells, const double* wp_pos, int start, int target, float* est) {
-  const int a = blockIdx.x * blockDim.x + threadIdx.x;
-  if (a >= n) return;
-  int cur = start; float e = 0.f;
-  for (int k = 0; k <= W; ++k) {
-    int goal = target;
-    if (k < W) {
-      if (wp_cells) goal = wp_cells[(size_t)a * W + k];
-      else {
-        long r = (long)__builtin_rint(wp_pos[((size_t)a * W + k) * 2]), c = (long)__builtin_rint(wp_pos[((size_t)a * W + k) * 2 + 1]);
-        r = r < 0 ? 0 : (r > G.R - 1 ? G.R - 1 : r); c = c < 0 ? 0 : (c > G.C - 1 ? G.C - 1 : c);
-        goal = (int)(r * G.C + c);
-      }
-    }
-    e += cell_dist(G, cur, goal); cur = goal;
-  }
-  est[a] = e;
-}
+// k_plan_decode: the planner half of csrc/pf_decode.h in its solo form (the per-agent-endpoint forms are included at the end of the file)
+#define PF_DECODE_MULTI 0
+#define PF_DECODE_PART 1
+#include "pf_decode.h"
 
 // ===========================================================================
 // K2: A* connector batch
@@ -307,82 +293,10 @@ __global__ __launch_bounds__(64) void k_score_batch(ScoreArgs p) {
 // ===========================================================================
 // K3: chained waypoint decode (+ K1)
 // ===========================================================================
-struct DecodeArgs {
-  Common c; ScoreP sp; int do_score;
-  int n, W, path_cap, start, target;
-  const int* wp_cells; const double* wp_pos;
-  int* cells; int* len; int* status; double* stats;
-};
-template <bool PLAT>
-__global__ __launch_bounds__(64) void k_decode_batch(DecodeArgs p) {
-  extern __shared__ __attribute__((aligned(16))) char smem[];
-  const int lane = lane_id();
-  const Grid& G = p.c.G;
-  const int RC = G.R * G.C;
-  Open O = make_open(smem, p.c.S, p.c.tier2);
-  Slot s = slot_load(p.c, RC);
-  AStat tot = {0, 0, 0, 0, 0, 0};
-  unsigned long long cells = 0, ovf = 0;
-  for (;;) {
-    int qpos = 0;
-    const int a = next_agent(p.c, p.n, lane, &qpos);
-    if (a < 0) break;
-    if (p.c.retry && p.status[a] != 3) continue;
-    s.sm.astar_too = p.c.st_astar || (p.c.queue && qpos < p.c.st_top);
-    slot_begin_eval(s, RC, lane);
-    int* out = p.cells + (size_t)a * p.path_cap;
-    int n = 1, cur = p.start, rc = 0;
-    // Exact short cut.  A waypoint on an obstacle makes its segment's connector return [] at once (astar.py:37-39), and an empty
-    // segment makes the whole decode return [] (ga_solver.py:74 / pso.py:77) -- whatever the segments before it found, and they
-    // have no effect outside the call.  So the answer is known before the first search: PSO positions round onto obstacles
-    // 27 % of the time per waypoint (~80 % of a swarm on G512), and the reference spends their earlier segments for nothing.
-    for (int k = 0; k < p.W && rc == 0; ++k) {
-      int goal;
-      if (p.wp_cells) goal = p.wp_cells[(size_t)a * p.W + k];
-      else {
-        const double x = p.wp_pos[((size_t)a * p.W + k) * 2], y = p.wp_pos[((size_t)a * p.W + k) * 2 + 1];
-        long r = (long)__builtin_rint(x), c = (long)__builtin_rint(y);
-        r = r < 0 ? 0 : (r > G.R - 1 ? G.R - 1 : r);
-        c = c < 0 ? 0 : (c > G.C - 1 ? G.C - 1 : c);
-        goal = (int)(r * G.C + c);
-      }
-      if ((unsigned)goal >= (unsigned)RC || G.occ[goal] == 1) rc = 1;
-    }
-    if (lane == 0) { out[0] = p.start; s.rec[p.start].meta = s.avoid_ep << PF_AVOID_SHIFT; }   // ga_solver.py:63-65
-    for (int k = 0; k <= p.W && rc == 0; ++k) {
-      int goal = p.target;
-      if (k < p.W) {
-        if (p.wp_cells) goal = p.wp_cells[(size_t)a * p.W + k];
-        else {                                                   // pso.py:61,69-70: round-half-even then clamp
-          double x = p.wp_pos[((size_t)a * p.W + k) * 2], y = p.wp_pos[((size_t)a * p.W + k) * 2 + 1];
-          long r = (long)__builtin_rint(x), c = (long)__builtin_rint(y);
-          r = r < 0 ? 0 : (r > G.R - 1 ? G.R - 1 : r);
-          c = c < 0 ? 0 : (c > G.C - 1 ? G.C - 1 : c);
-          goal = (int)(r * G.C + c);
-        }
-      }
-      int m = 0;
-      if (p.c.st_tail > 0 && !s.sm.astar_too) {                  // the batch's tail: few agents left, the chip mostly idle -> shorten the chain
-        const unsigned long long dn = __hip_atomic_load(&p.c.cnt->done, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        if ((long long)p.n - (long long)first_u64(dn) <= (long long)p.c.st_tail) s.sm.astar_too = true;
-      }
-      rc = astar<0, PLAT>(G, s, O, cur, goal, out + n - 1, p.path_cap - (n - 1), m, tot, lane, out, n);   // ga_solver.py:68-72 (avoid = the cells visited so far)
-      if (rc != 0) break;                                        // :74 / :85 -> []
-      mark_avoid(s, out + n, m - 1, lane);                       // :76 nodes_in_path_so_far.update
-      n += m - 1;
-      cur = goal;
-    }
-    // ga_solver.py:90-93 (drop consecutive duplicates) is a no-op here: a segment's tail never starts with its head
-    if (rc != 0) n = 0;
-    double sc[5];
-    if (p.do_score) score_path(G, p.sp, out, n, lane, sc);
-    if (lane == 0) { p.len[a] = n; p.status[a] = rc; atomicAdd(&p.c.cnt->done, 1ull); }
-    if (p.do_score && lane < 5) p.stats[(size_t)a * 5 + lane] = sc[lane];
-    cells += n; ovf += rc == 3;
-  }
-  slot_store(p.c, s, lane);
-  flush_counters(p.c.cnt, tot, cells, ovf, lane);
-}
+// DecodeArgs, k_decode_batch<PLAT>: the kernel half of csrc/pf_decode.h in its solo form
+#define PF_DECODE_MULTI 0
+#define PF_DECODE_PART 2
+#include "pf_decode.h"
 
 // ===========================================================================
 // K6: PSO update + pbest
@@ -1716,8 +1630,8 @@ __global__ __launch_bounds__(1024) void k_mpa_local_view(int N, const int* gorde
 // Tournament selection draws from ONE stream per generation (seed, DOM_GA_SELECT, gen, 0), slot after slot, with
 // data-dependent draw counts (random.sample's rejection loops): inherently sequential, so one thread replays it --
 // N x k draws, microseconds -- against the fitness column in HBM.  psid[s] = storage id of the parent chosen for slot s.
-__global__ void k_ga_select(unsigned long long seed, int gen, int n, int k, const double* fit_all, const int* gorder, int* pool, int* psid) {
-  if (blockIdx.x != 0 || threadIdx.x != 0) return;
+// (the *_item functions are the kernels' bodies: the batched forms in pf_ga_batch.h call them with a population's own rows)
+PF_DEV void ga_select_item(unsigned long long seed, int gen, int n, int k, const double* fit_all, const int* gorder, int* pool, int* psid) {
   Rng r; r.init(seed, DOM_GA_SELECT, (unsigned long long)gen, 0);
   long long setsize = 21;                                            // random.sample: pool copy for small n, rejection set otherwise
   if (k > 5) { long long p4 = 1; while (p4 < (long long)k * 3) p4 *= 4; setsize += p4; }
@@ -1739,11 +1653,14 @@ __global__ void k_ga_select(unsigned long long seed, int gen, int n, int k, cons
     psid[s_] = gorder[best];
   }
 }
+__global__ void k_ga_select(unsigned long long seed, int gen, int n, int k, const double* fit_all, const int* gorder, int* pool, int* psid) {
+  if (blockIdx.x != 0 || threadIdx.x != 0) return;
+  ga_select_item(seed, gen, n, k, fit_all, gorder, pool, psid);
+}
 // crossover + mutation, one thread per pair of children (stream (seed, DOM_GA, gen, pair), ga_solver.py:144-160,186-194):
 // writes the children with index in [child0, child0 + nchild) to out[(index - child0) * W ...]
-__global__ void k_ga_breed(unsigned long long seed, int gen, int N, int W, double cx_rate, double mut_rate, const uint8_t* occ, int R, int C,
-                           const int* chrom_all, const int* psid, int child0, int nchild, int* out) {
-  const int pair = child0 / 2 + blockIdx.x * blockDim.x + threadIdx.x;
+PF_DEV void ga_breed_item(unsigned long long seed, int gen, int N, int W, double cx_rate, double mut_rate, const uint8_t* occ, int R, int C,
+                          const int* chrom_all, const int* psid, int child0, int nchild, int* out, int pair) {
   const int idx = 2 * pair;
   if (idx >= child0 + nchild) return;
   const int* p1 = chrom_all + (size_t)psid[idx % N] * W;
@@ -1766,16 +1683,18 @@ __global__ void k_ga_breed(unsigned long long seed, int gen, int N, int W, doubl
     }
   }
 }
+__global__ void k_ga_breed(unsigned long long seed, int gen, int N, int W, double cx_rate, double mut_rate, const uint8_t* occ, int R, int C,
+                           const int* chrom_all, const int* psid, int child0, int nchild, int* out) {
+  ga_breed_item(seed, gen, N, W, cx_rate, mut_rate, occ, R, C, chrom_all, psid, child0, nchild, out,
+                child0 / 2 + blockIdx.x * blockDim.x + threadIdx.x);
+}
 // new_population[i] = child i if it decoded, else the parent it falls back to (ga_solver.py:198-205: parents[i], i.e.
 // p1 for even i, p2 for odd i).  Storage id of the new individual = its child index.  A fallback parent's path is
 // copied when this rank stores it, else the row is marked absent (len -1): a path is decode(chromosome), re-derived on demand.
-__global__ __launch_bounds__(64) void k_ga_assemble(int n_loc, int W, int cap, int lo, const int* kid_len, const int* kid_chrom,
-                                                    const double* kid_stats, const int* kid_cells, const int* psid, const int* chrom_old,
-                                                    const double* stats_old, const int* cells_old, const int* len_old, int old_lo, int old_hi,
-                                                    int* chrom_new, double* stats_new, int* cells_new, int* len_new) {
-  const int i = blockIdx.x;
-  if (i >= n_loc) return;
-  const int t = threadIdx.x;
+PF_DEV void ga_assemble_item(int i, int t, int W, int cap, int lo, const int* kid_len, const int* kid_chrom,
+                             const double* kid_stats, const int* kid_cells, const int* psid, const int* chrom_old,
+                             const double* stats_old, const int* cells_old, const int* len_old, int old_lo, int old_hi,
+                             int* chrom_new, double* stats_new, int* cells_new, int* len_new) {
   if (kid_len[i] > 0) {
     for (int k = t; k < W; k += 64) chrom_new[(size_t)i * W + k] = kid_chrom[(size_t)i * W + k];
     if (t < 5) stats_new[(size_t)i * 5 + t] = kid_stats[(size_t)i * 5 + t];
@@ -1792,6 +1711,15 @@ __global__ __launch_bounds__(64) void k_ga_assemble(int n_loc, int W, int cap, i
     }
     if (t == 0) len_new[i] = L;
   }
+}
+__global__ __launch_bounds__(64) void k_ga_assemble(int n_loc, int W, int cap, int lo, const int* kid_len, const int* kid_chrom,
+                                                    const double* kid_stats, const int* kid_cells, const int* psid, const int* chrom_old,
+                                                    const double* stats_old, const int* cells_old, const int* len_old, int old_lo, int old_hi,
+                                                    int* chrom_new, double* stats_new, int* cells_new, int* len_new) {
+  const int i = blockIdx.x;
+  if (i >= n_loc) return;
+  ga_assemble_item(i, threadIdx.x, W, cap, lo, kid_len, kid_chrom, kid_stats, kid_cells, psid, chrom_old, stats_old, cells_old, len_old,
+                   old_lo, old_hi, chrom_new, stats_new, cells_new, len_new);
 }
 
 // ===========================================================================
@@ -1931,7 +1859,8 @@ struct pf_handle {
   void* d_scan = nullptr; void* d_scan3 = nullptr;   // results of the small device scans
   unsigned long long* d_okey = nullptr; int* d_opay = nullptr; unsigned* d_orank = nullptr; int okey_cap = 0;   // rank_sort scratch: key images, payloads, ranks
   int* d_elite_cells = nullptr; int* d_elite_len = nullptr;   // the elite of the iteration (MPA.py:334), device resident
-  int* d_ga_pool = nullptr; int ga_pool_cap = 0;              // random.sample's pool copy (small populations)
+  int* d_ga_pool = nullptr; int ga_pool_cap = 0;              // random.sample's pool copy (small populations; K of them for a batch)
+  double* d_seg_rows = nullptr; int seg_rows_cap = 0;         // pf_best_rows_seg: [K][6]
   unsigned long long* d_st_lab = nullptr; int* d_st_touched = nullptr; unsigned char* d_st_par = nullptr; unsigned* d_st_epoch = nullptr;   // pf_settle.h scratch
   int dep_words = 0; long long dep_done = 0;   // MAACO deposit in progress: words of the bit matrix, cells already folded
   ncclComm_t comm = nullptr; int comm_rank = 0, comm_world = 1;   // RCCL communicator over xGMI (pf_comm_init); collectives run on `stream`
@@ -2096,7 +2025,7 @@ void pf_destroy(pf_handle* h) {
   if (h->comm && g_rccl.CommDestroy) { (void)hipStreamSynchronize(h->stream); g_rccl.CommDestroy(h->comm); h->comm = nullptr; }
   void* ptrs[] = {h->d_occ, h->d_mm_r1, h->d_mm_r0, h->d_mm_r1_nd, h->d_mm_r0_nd, h->d_d2near, h->d_rec, h->d_slot_state,
                   h->d_work, h->d_cnt, h->d_pen, h->d_tier2, h->d_tau, h->d_taua, h->d_eta, h->d_dep, h->d_tep, h->d_visit, h->d_visit_epoch,
-                  h->d_bits, h->d_flag, h->d_mstate, h->d_mctl, h->d_best_row, h->d_d2wide, h->d_penw, h->d_tmp, h->d_elite_stats, h->d_init_cells, h->d_init_stats, h->d_est, h->d_queue, h->d_jobs, h->d_jres, h->d_prop, h->d_doubt, h->d_scan, h->d_scan3, h->d_okey, h->d_opay, h->d_orank, h->d_elite_cells, h->d_elite_len, h->d_ga_pool, h->d_st_lab, h->d_st_touched, h->d_st_par, h->d_st_epoch,
+                  h->d_bits, h->d_flag, h->d_mstate, h->d_mctl, h->d_best_row, h->d_d2wide, h->d_penw, h->d_tmp, h->d_elite_stats, h->d_init_cells, h->d_init_stats, h->d_est, h->d_queue, h->d_jobs, h->d_jres, h->d_prop, h->d_doubt, h->d_scan, h->d_scan3, h->d_okey, h->d_opay, h->d_orank, h->d_elite_cells, h->d_elite_len, h->d_ga_pool, h->d_seg_rows, h->d_st_lab, h->d_st_touched, h->d_st_par, h->d_st_epoch,
                   h->d_comp[0], h->d_comp[1], h->d_comp[2], h->d_comp[3], h->d_ds, h->d_dt};
   for (void* p : ptrs) if (p) (void)hipFree(p);
   for (hipEvent_t e : h->span_ev) (void)hipEventDestroy(e);
@@ -2424,14 +2353,24 @@ int pf_score_batch(pf_handle* h, const pf_score_params* sp, int32_t n, int32_t p
   return 0;
 }
 
-int pf_decode_batch(pf_handle* h, int32_t allow_diag, int32_t restrict_corner, int32_t n, int32_t W,
-                    const int32_t* d_wp_cells, const double* d_wp_pos, int32_t start, int32_t target,
-                    int32_t path_cap, int32_t* d_cells, int32_t* d_len, int32_t* d_status,
-                    const pf_score_params* sp, double* d_stats) {
-  if (!h) return -2;
+// The per-agent-endpoint decode (pf_decode_batch_multi).  Its kernels are included at the END of this file (csrc/pf_decode.h says
+// why), so the host path below reaches them through these two functions, defined behind them.
+// decode_multi_plan: k_plan_decode_multi -- the estimates of the longest-first queue (est null: none wanted) and the range check
+// of every agent's start and target; decode_multi_launch: k_decode_multi<PLAT> through launch_with_retry.
+static int decode_multi_plan(pf_handle* h, const DecodeArgs& a, const int* d_start, const int* d_target, float* est);
+static int decode_multi_bad_ends(pf_handle* h, int* bad);
+static int decode_multi_launch(pf_handle* h, const DecodeArgs& a, const int* d_start, const int* d_target, int n);
+
+// pf_decode_batch and pf_decode_batch_multi: one host path (argument checks, slots, score parameters, the longest-first queue,
+// the settle options), one solo-or-multi branch at the planner and one at the launch.  d_start non-null = per-agent endpoints.
+static int decode_batch(pf_handle* h, const char* who, int32_t allow_diag, int32_t restrict_corner, int32_t n, int32_t W,
+                        const int32_t* d_wp_cells, const double* d_wp_pos, int32_t start, int32_t target, const int32_t* d_start,
+                        const int32_t* d_target, int32_t path_cap, int32_t* d_cells, int32_t* d_len, int32_t* d_status,
+                        const pf_score_params* sp, double* d_stats) {
+  const bool multi = d_start != nullptr;
   if (n < 0 || W < 0 || W >= PF_MAX_SEARCHES_PER_EVAL || path_cap < 1 || (!d_wp_cells && !d_wp_pos && W > 0) || !d_cells || !d_len || !d_status ||
-      start < 0 || start >= h->RC || target < 0 || target >= h->RC || (sp && !d_stats))
-    return failmsg(h, "pf_decode_batch: bad arguments");
+      (sp && !d_stats))
+    return failmsg(h, std::string(who) + ": bad arguments");
   if (ensure_slots(h, allow_diag, restrict_corner)) return -1;
   DecodeArgs a;
   a.c = make_common(h, allow_diag, restrict_corner, 16, 0);
@@ -2439,8 +2378,13 @@ int pf_decode_batch(pf_handle* h, int32_t allow_diag, int32_t restrict_corner, i
   if (sp) { if (make_scorep(h, sp, &a.sp)) return -1; } else memset(&a.sp, 0, sizeof(a.sp));
   a.n = n; a.W = W; a.path_cap = path_cap; a.start = start; a.target = target;
   a.wp_cells = d_wp_cells; a.wp_pos = d_wp_pos; a.cells = d_cells; a.len = d_len; a.status = d_status; a.stats = d_stats;
+  int prc = 0;
   if (n > 64) {
-    if (make_queue(h, n, [&](float* est) { hipLaunchKernelGGL(k_plan_decode, dim3((n + 255) / 256), dim3(256), 0, h->stream, a.c.G, n, W, d_wp_cells, d_wp_pos, start, target, est); })) return -1;
+    if (make_queue(h, n, [&](float* est) {
+          if (multi) prc = decode_multi_plan(h, a, d_start, d_target, est);
+          else hipLaunchKernelGGL(k_plan_decode, dim3((n + 255) / 256), dim3(256), 0, h->stream, a.c.G, n, W, d_wp_cells, d_wp_pos, start, target, est);
+        })) return -1;
+    if (prc) return -1;
     a.c.queue = h->d_queue;
     // A decode is a chain of W + 1 closed-set searches, so a fallback costs one link, not the chain.  r02: the agents at the head
     // of the longest-first queue try the parallel settling engine from the start (ga512 121 -> 108 ms at 6 %).  r03: the TAIL
@@ -2448,12 +2392,39 @@ int pf_decode_batch(pf_handle* h, int32_t allow_diag, int32_t restrict_corner, i
     // the sequential loop, so nobody uses it while the chip is full; once the unfinished agents no longer fill 60 % of the
     // search slots, every search that starts does (one box: sequential only 117.7 ms, head 6 % 111.8, tail 60 % 102.3).
     if (g_settle < 0) a.c.st_top = (int)((long long)n * g_settle_top / 1000);
+  } else if (multi && n > 0 && decode_multi_plan(h, a, d_start, d_target, nullptr)) return -1;   // (no queue: the range check alone)
+  if (multi && n > 0) {
+    // an endpoint outside the grid is an argument error found here, before the launch: the planner never used it as an index
+    int bad = 0;
+    if (decode_multi_bad_ends(h, &bad)) return -1;
+    if (bad) return failmsg(h, std::string(who) + ": a start or target cell is outside the grid");
   }
   // ... and whatever is still running when the batch is nearly done (chains of W + 1 searches: the switch happens between
   // links, each search is certified or handed back on its own)
   // (measured against the chip, not the batch: a batch that never fills the search slots runs on the engine from its start)
   if (g_settle < 0) a.c.st_tail = (int)((long long)h->nslots * g_settle_tail / 1000);
+  if (multi) return decode_multi_launch(h, a, d_start, d_target, n);
   return plateau_map(h) ? launch_with_retry(h, k_decode_batch<true>, a, n) : launch_with_retry(h, k_decode_batch<false>, a, n);
+}
+
+int pf_decode_batch(pf_handle* h, int32_t allow_diag, int32_t restrict_corner, int32_t n, int32_t W,
+                    const int32_t* d_wp_cells, const double* d_wp_pos, int32_t start, int32_t target,
+                    int32_t path_cap, int32_t* d_cells, int32_t* d_len, int32_t* d_status,
+                    const pf_score_params* sp, double* d_stats) {
+  if (!h) return -2;
+  if (start < 0 || start >= h->RC || target < 0 || target >= h->RC) return failmsg(h, "pf_decode_batch: bad arguments");
+  return decode_batch(h, "pf_decode_batch", allow_diag, restrict_corner, n, W, d_wp_cells, d_wp_pos, start, target, nullptr, nullptr, path_cap,
+                      d_cells, d_len, d_status, sp, d_stats);
+}
+
+int pf_decode_batch_multi(pf_handle* h, int32_t allow_diag, int32_t restrict_corner, int32_t n, int32_t W,
+                          const int32_t* d_wp_cells, const double* d_wp_pos, const int32_t* d_start, const int32_t* d_target,
+                          int32_t path_cap, int32_t* d_cells, int32_t* d_len, int32_t* d_status,
+                          const pf_score_params* sp, double* d_stats) {
+  if (!h) return -2;
+  if (!d_start || !d_target) return failmsg(h, "pf_decode_batch_multi: bad arguments");
+  return decode_batch(h, "pf_decode_batch_multi", allow_diag, restrict_corner, n, W, d_wp_cells, d_wp_pos, -1, -1, d_start, d_target, path_cap,
+                      d_cells, d_len, d_status, sp, d_stats);
 }
 
 int pf_pso_update(pf_handle* h, int32_t n, int32_t W, double w, double c1, double c2, double max_vel, double* d_pos,
@@ -3822,25 +3793,31 @@ static MpaSchools mpa_batch_schools(const pf_mpa_batch* b) {
   return ms;
 }
 
-int pf_mpa_batch_sort(pf_mpa_batch* b, const double* d_pop_stats, int32_t* d_order) {
-  if (batch_check(b, "pf_mpa_batch_sort")) return -2;
-  pf_handle* h = b->h;
-  if (!d_pop_stats || !d_order) return failmsg(h, "pf_mpa_batch_sort: bad arguments");
-  CK(hipSetDevice(h->device));
-  const int K = b->K, n = b->N;
-  if (n <= 1) return 0;
+// K stable rank sorts of n keys each (k_sort_prep_seg / k_rank_count_seg / k_rank_scatter_seg, pf_mpa_batch.h), enqueued on the
+// handle's stream: segment s of d_order is re-sorted by vals[(s n + id) * stride + offset].  key / pay / rank: K n entries each.
+static int rank_sort_seg(pf_handle* h, int K, int n, const double* d_vals, int stride, int offset, int* d_order, unsigned long long* d_key,
+                         int* d_pay, unsigned* d_rank) {
   const int nb = (int)(((size_t)K * n + 255) / 256);
-  hipLaunchKernelGGL(k_sort_prep_seg<>, dim3(nb), dim3(256), 0, h->stream, K, n, d_pop_stats, 5, 4, (const int*)d_order, b->d_key, b->d_pay, b->d_rank);
+  hipLaunchKernelGGL(k_sort_prep_seg<>, dim3(nb), dim3(256), 0, h->stream, K, n, d_vals, stride, offset, (const int*)d_order, d_key, d_pay, d_rank);
   // (rank_sort's split, with the ~8192 wavefronts shared between the K segments)
   const int tiles = (n + 63) / 64;
   int jsplit = 8192 / (tiles * K); const int jmax = (n + 255) / 256; if (jsplit > jmax) jsplit = jmax; if (jsplit < 1) jsplit = 1;
   const int jchunk = (n + jsplit - 1) / jsplit;
   const int per_seg = tiles * jsplit;
   hipLaunchKernelGGL(k_rank_count_seg<>, dim3((unsigned)per_seg * (unsigned)K), dim3(64), 0, h->stream, n, per_seg, jsplit, jchunk,
-                     (const unsigned long long*)b->d_key, b->d_rank);
-  hipLaunchKernelGGL(k_rank_scatter_seg<>, dim3(nb), dim3(256), 0, h->stream, K, n, (const unsigned*)b->d_rank, (const int*)b->d_pay, d_order);
+                     (const unsigned long long*)d_key, d_rank);
+  hipLaunchKernelGGL(k_rank_scatter_seg<>, dim3(nb), dim3(256), 0, h->stream, K, n, (const unsigned*)d_rank, (const int*)d_pay, d_order);
   CK(hipGetLastError());
   return 0;
+}
+
+int pf_mpa_batch_sort(pf_mpa_batch* b, const double* d_pop_stats, int32_t* d_order) {
+  if (batch_check(b, "pf_mpa_batch_sort")) return -2;
+  pf_handle* h = b->h;
+  if (!d_pop_stats || !d_order) return failmsg(h, "pf_mpa_batch_sort: bad arguments");
+  CK(hipSetDevice(h->device));
+  if (b->N <= 1) return 0;
+  return rank_sort_seg(h, b->K, b->N, d_pop_stats, 5, 4, d_order, b->d_key, b->d_pay, b->d_rank);
 }
 
 int pf_mpa_batch_pick_elite(pf_mpa_batch* b, int32_t path_cap, const int32_t* d_pop_cells, const int32_t* d_pop_len,
@@ -3855,18 +3832,23 @@ int pf_mpa_batch_pick_elite(pf_mpa_batch* b, int32_t path_cap, const int32_t* d_
   return 0;
 }
 
+// out[6 k ...] = {local id at the head of segment k's list, its five stats}, K rows in one copy (k_mpa_best_rows)
+static int best_rows_seg(pf_handle* h, int K, int N, const double* d_stats, const int* d_order, double* d_rows, double* out) {
+  hipLaunchKernelGGL(k_mpa_best_rows<>, dim3((K + 63) / 64), dim3(64), 0, h->stream, K, N, d_stats, d_order, d_rows);
+  CK(hipGetLastError());
+  const size_t nb = sizeof(double) * 6 * (size_t)K;
+  CK(hipMemcpyAsync(out, d_rows, nb, hipMemcpyDeviceToHost, h->stream));
+  CK(hipStreamSynchronize(h->stream));
+  if (nb <= 128) h->d2h_small += 1; else { h->d2h_bulk += 1; h->d2h_bulk_bytes += (long long)nb; }
+  return 0;
+}
+
 int pf_mpa_batch_best_rows(pf_mpa_batch* b, const double* d_pop_stats, const int32_t* d_order, double* out) {
   if (batch_check(b, "pf_mpa_batch_best_rows")) return -2;
   pf_handle* h = b->h;
   if (!d_pop_stats || !d_order || !out) return failmsg(h, "pf_mpa_batch_best_rows: bad arguments");
   CK(hipSetDevice(h->device));
-  hipLaunchKernelGGL(k_mpa_best_rows<>, dim3((b->K + 63) / 64), dim3(64), 0, h->stream, b->K, b->N, d_pop_stats, d_order, b->d_rows);
-  CK(hipGetLastError());
-  const size_t nb = sizeof(double) * 6 * (size_t)b->K;
-  CK(hipMemcpyAsync(out, b->d_rows, nb, hipMemcpyDeviceToHost, h->stream));
-  CK(hipStreamSynchronize(h->stream));
-  if (nb <= 128) h->d2h_small += 1; else { h->d2h_bulk += 1; h->d2h_bulk_bytes += (long long)nb; }
-  return 0;
+  return best_rows_seg(h, b->K, b->N, d_pop_stats, d_order, b->d_rows, out);
 }
 
 int pf_mpa_batch_read_path(pf_mpa_batch* b, int32_t k, int32_t slot, int32_t path_cap, const int32_t* d_pop_cells, const int32_t* d_pop_len,
@@ -4245,4 +4227,103 @@ int pf_span_total(pf_handle* h, double* ms_out, int64_t* count_out, int32_t rese
 int pf_comm_rank(pf_handle* h) { return h ? h->comm_rank : 0; }
 int pf_comm_world(pf_handle* h) { return h && h->comm ? h->comm_world : 1; }
 
+// the batched forms of k_ga_select / k_ga_breed / k_ga_assemble
 }  // extern "C"
+#include "pf_ga_batch.h"
+extern "C" {
+
+// ---------------------------------------------------------------------------
+// K GA populations in one batched generation (pathfit.GABatch): the per-agent-endpoint decode and the batched small kernels.
+// The entries are stateless: the caller owns every population buffer; the handle lends its search slots, queue and sort / pool
+// / best-row scratch (stream ordered, grown on demand, freed by pf_destroy).  Nothing here depends on the map's contents, so
+// pf_update_grid has nothing to invalidate.
+// ---------------------------------------------------------------------------
+int pf_ga_select_batch(pf_handle* h, const uint64_t* d_seeds, int32_t gen, int32_t K, int32_t N, int32_t tournament_size,
+                       const double* d_fit_all, const int32_t* d_gorder, int32_t* d_psid) {
+  if (!h) return -2;
+  if (K <= 0 || N <= 0 || (int64_t)K * N > (1 << 29) || tournament_size <= 0 || tournament_size > 64 || !d_seeds || !d_fit_all || !d_gorder || !d_psid)
+    return failmsg(h, "pf_ga_select_batch: bad arguments (1 <= tournament_size <= 64, K * N <= 2^29)");
+  CK(hipSetDevice(h->device));
+  const int k = tournament_size < N ? tournament_size : N;
+  const int KN = K * N;
+  if (KN > h->ga_pool_cap) { if (h->d_ga_pool) CK(hipFree(h->d_ga_pool)); h->d_ga_pool = nullptr; h->ga_pool_cap = 0; CK(hipMalloc(&h->d_ga_pool, sizeof(int) * (size_t)KN)); h->ga_pool_cap = KN; }
+  hipLaunchKernelGGL(k_ga_select_batch<>, dim3(K), dim3(64), 0, h->stream, (const unsigned long long*)d_seeds, gen, K, N, k, d_fit_all, d_gorder,
+                     h->d_ga_pool, d_psid);
+  CK(hipGetLastError());
+  return 0;
+}
+int pf_ga_breed_batch(pf_handle* h, const uint64_t* d_seeds, int32_t gen, int32_t K, int32_t N, int32_t W, double crossover_rate,
+                      double mutation_rate, const int32_t* d_chrom_all, const int32_t* d_psid, int32_t* d_out) {
+  if (!h) return -2;
+  if (K <= 0 || N <= 0 || (int64_t)K * N > (1 << 29) || W <= 0 || !d_seeds || !d_chrom_all || !d_psid || !d_out) return failmsg(h, "pf_ga_breed_batch: bad arguments");
+  CK(hipSetDevice(h->device));
+  const int items = K * ((N + 1) / 2);
+  hipLaunchKernelGGL(k_ga_breed_batch<>, dim3((items + 63) / 64), dim3(64), 0, h->stream, (const unsigned long long*)d_seeds, gen, K, N, W,
+                     crossover_rate, mutation_rate, h->d_occ, h->R, h->C, d_chrom_all, d_psid, d_out);
+  CK(hipGetLastError());
+  return 0;
+}
+int pf_ga_assemble_batch(pf_handle* h, int32_t K, int32_t N, int32_t W, int32_t path_cap, const int32_t* d_kid_len,
+                         const int32_t* d_kid_chrom, const double* d_kid_stats, const int32_t* d_kid_cells, const int32_t* d_psid,
+                         const int32_t* d_chrom_old, const double* d_stats_old, const int32_t* d_cells_old, const int32_t* d_len_old,
+                         int32_t* d_chrom_new, double* d_stats_new, int32_t* d_cells_new, int32_t* d_len_new) {
+  if (!h) return -2;
+  if (K <= 0 || N <= 0 || (int64_t)K * N > (1 << 29) || W <= 0 || path_cap < 1 || !d_kid_len || !d_kid_chrom || !d_kid_stats || !d_kid_cells || !d_psid ||
+      !d_chrom_old || !d_stats_old || !d_cells_old || !d_len_old || !d_chrom_new || !d_stats_new || !d_cells_new || !d_len_new)
+    return failmsg(h, "pf_ga_assemble_batch: bad arguments");
+  CK(hipSetDevice(h->device));
+  hipLaunchKernelGGL(k_ga_assemble_batch<>, dim3(K * N), dim3(64), 0, h->stream, K, N, W, path_cap, d_kid_len, d_kid_chrom, d_kid_stats, d_kid_cells,
+                     d_psid, d_chrom_old, d_stats_old, d_cells_old, d_len_old, d_chrom_new, d_stats_new, d_cells_new, d_len_new);
+  CK(hipGetLastError());
+  return 0;
+}
+int pf_sort_order_by_key_seg(pf_handle* h, int32_t K, int32_t n, const double* d_vals, int32_t stride, int32_t offset, int32_t* d_order) {
+  if (!h) return -2;
+  if (K < 1 || n < 0 || (int64_t)K * n > (1 << 29) || !d_vals || !d_order || stride < 1 || offset < 0 || offset >= stride)
+    return failmsg(h, "pf_sort_order_by_key_seg: bad arguments");
+  if (n <= 1) return 0;
+  CK(hipSetDevice(h->device));
+  const int KN = K * n;
+  if (KN > h->okey_cap) {                                           // (rank_sort's scratch: the calls are stream ordered)
+    for (void* q : {(void*)h->d_okey, (void*)h->d_opay, (void*)h->d_orank}) if (q) CK(hipFree(q));
+    h->d_okey = nullptr; h->d_opay = nullptr; h->d_orank = nullptr; h->okey_cap = 0;
+    CK(hipMalloc(&h->d_okey, sizeof(unsigned long long) * (size_t)KN)); CK(hipMalloc(&h->d_opay, sizeof(int) * (size_t)KN));
+    CK(hipMalloc(&h->d_orank, sizeof(unsigned) * (size_t)KN));
+    h->okey_cap = KN;
+  }
+  return rank_sort_seg(h, K, n, d_vals, stride, offset, d_order, h->d_okey, h->d_opay, h->d_orank);
+}
+int pf_best_rows_seg(pf_handle* h, int32_t K, int32_t N, const double* d_stats, const int32_t* d_order, double* out) {
+  if (!h) return -2;
+  if (K < 1 || N < 1 || !d_stats || !d_order || !out) return failmsg(h, "pf_best_rows_seg: bad arguments");
+  CK(hipSetDevice(h->device));
+  if (K > h->seg_rows_cap) { if (h->d_seg_rows) CK(hipFree(h->d_seg_rows)); h->d_seg_rows = nullptr; h->seg_rows_cap = 0; CK(hipMalloc(&h->d_seg_rows, sizeof(double) * 6 * (size_t)K)); h->seg_rows_cap = K; }
+  return best_rows_seg(h, K, N, d_stats, d_order, h->d_seg_rows, out);
+}
+
+}  // extern "C"
+
+// ---- the per-agent-endpoint decode: k_plan_decode_multi, DecodeMultiArgs, k_decode_multi<PLAT> (behind every other kernel) ----
+#define PF_DECODE_MULTI 1
+#define PF_DECODE_PART 3
+#include "pf_decode.h"
+
+static int decode_multi_plan(pf_handle* h, const DecodeArgs& a, const int* d_start, const int* d_target, float* est) {
+  if (!h->d_scan3) CK(hipMalloc(&h->d_scan3, 24));
+  CK(hipMemsetAsync(h->d_scan3, 0, sizeof(int), h->stream));
+  hipLaunchKernelGGL(k_plan_decode_multi<>, dim3((a.n + 255) / 256), dim3(256), 0, h->stream, a.c.G, a.n, a.W, a.wp_cells, a.wp_pos, d_start, d_target,
+                     est, (int*)h->d_scan3);
+  CK(hipGetLastError());
+  return 0;
+}
+static int decode_multi_bad_ends(pf_handle* h, int* bad) {
+  if (d2h_one(h, (const int*)h->d_scan3, bad)) return -1;
+  h->d2h_small += 1;
+  return 0;
+}
+static int decode_multi_launch(pf_handle* h, const DecodeArgs& a, const int* d_start, const int* d_target, int n) {
+  DecodeMultiArgs m;
+  m.c = a.c; m.sp = a.sp; m.do_score = a.do_score; m.n = a.n; m.W = a.W; m.path_cap = a.path_cap; m.start = d_start; m.target = d_target;
+  m.wp_cells = a.wp_cells; m.wp_pos = a.wp_pos; m.cells = a.cells; m.len = a.len; m.status = a.status; m.stats = a.stats;
+  return plateau_map(h) ? launch_with_retry(h, k_decode_multi<true>, m, n) : launch_with_retry(h, k_decode_multi<false>, m, n);
+}

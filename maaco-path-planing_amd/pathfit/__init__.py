@@ -14,3 +14,4 @@ from .maaco import MAACO  # noqa: F401
 from .maaco_batch import MAACOBatch, MaacoColony  # noqa: F401
 from .mpa import MPA  # noqa: F401
 from .mpa_batch import MPABatch, MpaSchool  # noqa: F401
+from .ga_batch import GABatch, GaPopulation  # noqa: F401

@@ -1,4 +1,4 @@
-"""What MAACOBatch and MPABatch share: the argument checks of their constructors (all of them run before the device is touched;
+"""What MAACOBatch, MPABatch and GABatch share: the argument checks of their constructors (all of them run before the device is touched;
 `who` is the class name every message starts with) and the ownership of an object the library keeps on an Engine."""
 import numpy as np
 

@@ -140,6 +140,13 @@ SYMBOLS = {
     "pf_mpa_batch_best_rows": (C.c_int, [_vp, _vp, _vp, _vp]),
     "pf_mpa_batch_read_path": (C.c_int, [_vp, _i32, _i32, _i32, _vp, _vp, _vp, _i32, C.POINTER(_i32)]),
     "pf_mpa_batch_counters": (C.c_int, [_vp, C.POINTER(Counters), C.POINTER(_i64), C.POINTER(_i64)]),
+    "pf_decode_batch_multi": (C.c_int, [_vp, _i32, _i32, _i32, _i32, _vp, _vp, _vp, _vp, _i32, _vp, _vp, _vp,
+                                        C.POINTER(ScoreParams), _vp]),
+    "pf_ga_select_batch": (C.c_int, [_vp, _vp, _i32, _i32, _i32, _i32, _vp, _vp, _vp]),
+    "pf_ga_breed_batch": (C.c_int, [_vp, _vp, _i32, _i32, _i32, _i32, _dbl, _dbl, _vp, _vp, _vp]),
+    "pf_ga_assemble_batch": (C.c_int, [_vp, _i32, _i32, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "pf_sort_order_by_key_seg": (C.c_int, [_vp, _i32, _i32, _vp, _i32, _i32, _vp]),
+    "pf_best_rows_seg": (C.c_int, [_vp, _i32, _i32, _vp, _vp, _vp]),
 }
 
 

@@ -242,6 +242,39 @@ class Engine:
         paths = [cells[i, :lens[i]].copy() for i in range(n)]
         return paths, st, (dstat.download() if dstat is not None else None)
 
+    def decode_multi(self, n, W, d_start, d_target, path_cap, d_cells, d_len, d_status, d_wp_cells=None, d_wp_pos=None,
+                     sp=None, d_stats=None, allow_diag=True, restrict_corner=True):
+        """decode_batch with a start and a target cell per agent (d_start, d_target: int32[n] buffers)."""
+        self._ck(self.L.pf_decode_batch_multi(self.h, int(allow_diag), int(restrict_corner), n, W,
+                                              d_wp_cells.ptr if d_wp_cells else None, d_wp_pos.ptr if d_wp_pos else None,
+                                              d_start.ptr, d_target.ptr, path_cap, d_cells.ptr, d_len.ptr, d_status.ptr,
+                                              C.byref(sp) if sp is not None else None, d_stats.ptr if d_stats else None))
+        self._logk("decode")
+
+    def decode_multi_host(self, starts, targets, wp_cells=None, wp_pos=None, sp=None, path_cap=None, allow_diag=True,
+                          restrict_corner=True):
+        """decode_host with per-agent endpoints: starts / targets int[n] -> (paths, status, stats or None)."""
+        if wp_cells is not None:
+            wp = np.ascontiguousarray(wp_cells, np.int32)
+            n, W = wp.shape
+            dwc, dwp = self.put(wp.reshape(-1) if wp.size else np.zeros(1, np.int32)), None
+        else:
+            wp = np.ascontiguousarray(wp_pos, np.float64)
+            n, W = wp.shape[0], wp.shape[1]
+            dwc, dwp = None, self.put(wp.reshape(-1) if wp.size else np.zeros(1))
+        st_, tg_ = np.ascontiguousarray(starts, np.int32), np.ascontiguousarray(targets, np.int32)
+        if st_.shape != (n,) or tg_.shape != (n,):
+            raise ValueError("decode_multi_host: one start and one target per agent")
+        cap = int(path_cap or self.default_path_cap())
+        m = max(n, 1)
+        ds, dt = self.put(st_ if n else np.zeros(1, np.int32)), self.put(tg_ if n else np.zeros(1, np.int32))
+        dc, dl, dst = self.buf((m, cap), np.int32), self.buf(m, np.int32), self.buf(m, np.int32)
+        dstat = self.buf((m, 5), np.float64) if sp is not None else None
+        self.decode_multi(n, W, ds, dt, cap, dc, dl, dst, dwc, dwp, sp, dstat, allow_diag, restrict_corner)
+        cells, lens, st = dc.download(), dl.download(), dst.download()
+        paths = [cells[i, :lens[i]].copy() for i in range(n)]
+        return paths, st[:n], (dstat.download()[:n] if dstat is not None else None)
+
     # ------------------------------------------------------------------ K6
     def pso_update(self, n, W, w, c1, c2, max_vel, d_pos, d_vel, d_pbest, d_gbest, seed, it, agent0=0):
         self._ck(self.L.pf_pso_update(self.h, n, W, w, c1, c2, max_vel, d_pos.ptr, d_vel.ptr, d_pbest.ptr,
@@ -425,6 +458,29 @@ class Engine:
         self._ck(self.L.pf_ga_assemble_dev(self.h, int(n_loc), int(W), int(cap), int(lo), kid_len.ptr, kid_chrom.ptr, kid_stats.ptr,
                                            kid_cells.ptr, psid.ptr, chrom_old.ptr, stats_old.ptr, cells_old.ptr, len_old.ptr,
                                            int(old_lo), int(old_hi), chrom_new.ptr, stats_new.ptr, cells_new.ptr, len_new.ptr))
+
+    # ------------------------------------------------------------------ K GA populations in one generation (GABatch)
+    def ga_select_batch(self, d_seeds, gen, K, N, k, d_fit_all, d_gorder, d_psid):
+        self._ck(self.L.pf_ga_select_batch(self.h, d_seeds.ptr, int(gen), int(K), int(N), int(k), d_fit_all.ptr, d_gorder.ptr, d_psid.ptr))
+
+    def ga_breed_batch(self, d_seeds, gen, K, N, W, cx, mut, d_chrom_all, d_psid, d_out):
+        self._ck(self.L.pf_ga_breed_batch(self.h, d_seeds.ptr, int(gen), int(K), int(N), int(W), float(cx), float(mut), d_chrom_all.ptr,
+                                          d_psid.ptr, d_out.ptr))
+
+    def ga_assemble_batch(self, K, N, W, cap, kid_len, kid_chrom, kid_stats, kid_cells, psid, chrom_old, stats_old, cells_old, len_old,
+                          chrom_new, stats_new, cells_new, len_new):
+        self._ck(self.L.pf_ga_assemble_batch(self.h, int(K), int(N), int(W), int(cap), kid_len.ptr, kid_chrom.ptr, kid_stats.ptr,
+                                             kid_cells.ptr, psid.ptr, chrom_old.ptr, stats_old.ptr, cells_old.ptr, len_old.ptr,
+                                             chrom_new.ptr, stats_new.ptr, cells_new.ptr, len_new.ptr))
+
+    def sort_order_by_key_seg(self, K, n, d_vals, stride, offset, d_order):
+        """K stable sorts of n keys each: segment k of d_order (position -> local id) by d_vals[(k n + id) * stride + offset]."""
+        self._ck(self.L.pf_sort_order_by_key_seg(self.h, int(K), int(n), d_vals.ptr, int(stride), int(offset), d_order.ptr))
+
+    def best_rows_seg(self, K, N, d_stats, d_order, out):
+        """out [K][6] = (local id at the head of segment k, its five stats): one copy."""
+        self._ck(self.L.pf_best_rows_seg(self.h, int(K), int(N), d_stats.ptr, d_order.ptr, out.ctypes.data))
+        return out
 
     def sort_order_by_key(self, n, d_vals, stride, offset, d_order):
         self._ck(self.L.pf_sort_order_by_key(self.h, int(n), d_vals.ptr, int(stride), int(offset), d_order.ptr))

@@ -50,6 +50,49 @@ def ga_breed_native(seed, gen, crossover_rate, mutation_rate, occ, parent_cells)
 INF = float("inf")
 
 
+# ---- what GASolver and GABatch (pathfit/ga_batch.py) both need ----------------------------------------------------------
+def ga_attempt_round(N, have, k):
+    """Initialisation (ga_solver.py:95-133) runs in rounds: how many attempts the next round makes for a population that has
+    `have` of its N individuals after k of at most 20 N attempts.  Attempt j draws from its own stream (seed, DOM_INIT, 0, j) and
+    the population is the first N feasible attempts in attempt order, so the grouping into rounds never changes the result."""
+    return min(20 * N - k, max(N - have, 32) * 2)
+
+
+def ga_individuals(chroms, cps, stats):
+    """The reference's individual dicts (ga_solver.py:110-113) from chromosomes, paths and stats rows."""
+    return [{"chromosome": c, "path": p, "fitness": float(s[4]), "length": float(s[0]), "turns": int(s[1]),
+             "safety_penalty": float(s[2]), "diag_penalty": float(s[3])} for c, p, s in zip(chroms, cps, stats)]
+
+
+def ga_take_feasible(pop, N, wp, cps, stats, feas, cols):
+    """ga_solver.py:104-114 for one round: the feasible attempts join `pop` in attempt order until it holds N."""
+    chroms = [[(c // cols, c % cols) for c in row] for row in wp.tolist()]
+    for j, (ind, ok) in enumerate(zip(ga_individuals(chroms, cps, stats), feas)):
+        if ok and len(pop) < N:
+            ind["_cells"] = wp[j]
+            pop.append(ind)
+
+
+def ga_pad_and_sort(pop, N, seed):
+    """ga_solver.py:130-132: random copies (stream (seed, DOM_INIT, 1, 0)) up to N individuals, then the first sort."""
+    r = pfrng.AgentRandom(seed, pfrng.DOM_INIT, 1, 0)
+    while len(pop) < N:
+        pop.append(r.choice(pop).copy())
+    pop.sort(key=lambda x: x["fitness"])
+
+
+def ga_row_individual(ch, path, s5, cols):
+    """An individual dict from device rows: chromosome cells, a CellPath and the five stats."""
+    return {"chromosome": [(int(x) // cols, int(x) % cols) for x in ch], "path": path, "fitness": float(s5[4]),
+            "length": float(s5[0]), "turns": int(s5[1]), "safety_penalty": float(s5[2]), "diag_penalty": float(s5[3]), "_cells": ch}
+
+
+def ga_result_tuple(res):
+    """solve()'s return value from best_solution_overall (ga_solver.py:216-218)."""
+    path = res["path"].tolist() if isinstance(res["path"], CellPath) else res["path"]
+    return (path, res["length"], res["turns"], res["safety_penalty"], res["diag_penalty"], res["fitness"])
+
+
 class BasePathfinder:
     """helper.BasePathfinder (helper.py:115-161) minus the matplotlib half."""
 
@@ -256,15 +299,7 @@ class GASolver(_WaypointSolver):
                 missing.append(sid)
         for sid, cp in zip(missing, self._decode_rows(chrom[missing]) if missing else []):
             paths[sid] = cp
-        C_ = self.cols
-        out = []
-        for sid in gorder:
-            sid = int(sid)
-            s = stats[sid]
-            out.append({"chromosome": [(int(c) // C_, int(c) % C_) for c in chrom[sid]], "path": paths[sid], "fitness": float(s[4]),
-                        "length": float(s[0]), "turns": int(s[1]), "safety_penalty": float(s[2]), "diag_penalty": float(s[3]),
-                        "_cells": chrom[sid].copy()})
-        return out
+        return [ga_row_individual(chrom[int(sid)].copy(), paths[int(sid)], stats[int(sid)], self.cols) for sid in gorder]
 
     def _solve_device(self):
         """ga_solver.py:178-213 with the population in HBM: selection, crossover + mutation, decode + stitch + score,
@@ -341,13 +376,8 @@ class GASolver(_WaypointSolver):
         if best is not None:
             gid, ch, s5 = best
             row = self._best_row if self._best_row is not None else self._decode_rows(ch[None, :])[0].cells
-            C_ = self.cols
-            self.best_solution_overall = {"chromosome": [(int(x) // C_, int(x) % C_) for x in ch], "path": CellPath(row, self.cols),
-                                          "fitness": float(s5[4]), "length": float(s5[0]), "turns": int(s5[1]),
-                                          "safety_penalty": float(s5[2]), "diag_penalty": float(s5[3]), "_cells": ch}
-        res = self.best_solution_overall
-        path = res["path"].tolist() if isinstance(res["path"], CellPath) else res["path"]
-        return (path, res["length"], res["turns"], res["safety_penalty"], res["diag_penalty"], res["fitness"])
+            self.best_solution_overall = ga_row_individual(ch, CellPath(row, self.cols), s5, self.cols)
+        return ga_result_tuple(self.best_solution_overall)
 
     # ---- host-side genetic operators (ga_solver.py:48-56,136-160), per-agent streams ----
     def _generate_random_waypoint(self, r):
@@ -368,8 +398,7 @@ class GASolver(_WaypointSolver):
         return self._evaluate(wp_cells=wp)[0][0].tolist()
 
     def _individuals(self, chroms, cps, stats):
-        return [{"chromosome": c, "path": p, "fitness": float(s[4]), "length": float(s[0]), "turns": int(s[1]),
-                 "safety_penalty": float(s[2]), "diag_penalty": float(s[3])} for c, p, s in zip(chroms, cps, stats)]
+        return ga_individuals(chroms, cps, stats)
 
     def _chrom_cells(self, ind):
         """int32 cells of an individual's chromosome (cached on the individual)."""
@@ -384,19 +413,14 @@ class GASolver(_WaypointSolver):
         max_total_attempts = self.population_size * 20
         k = 0
         while len(self.population) < self.population_size and k < max_total_attempts:
-            batch = min(max_total_attempts - k, max(self.population_size - len(self.population), 32) * 2)
+            batch = ga_attempt_round(self.population_size, len(self.population), k)
             if self.native_operators and self.num_waypoints > 0:
                 wp = ga_random_chromosomes_native(self.seed, k, batch, self.num_waypoints, self.grid == 1)
-                C_ = self.cols
-                chroms = [[(c // C_, c % C_) for c in row] for row in wp.tolist()]
             else:
                 chroms = [self._create_chromosome(pfrng.AgentRandom(self.seed, pfrng.DOM_INIT, 0, k + i)) for i in range(batch)]
                 wp = np.array([[self._cell(w) for w in c] for c in chroms], np.int32).reshape(batch, self.num_waypoints)
             cps, stats, feas = self._evaluate(wp_cells=wp)
-            for j, (ind, ok) in enumerate(zip(self._individuals(chroms, cps, stats), feas)):
-                if ok and len(self.population) < self.population_size:
-                    ind["_cells"] = wp[j]
-                    self.population.append(ind)
+            ga_take_feasible(self.population, self.population_size, wp, cps, stats, feas, self.cols)
             k += batch
         if not self.population and self.num_waypoints > 0:
             path_direct = self._reconstruct_path_from_chromosome([])
@@ -408,10 +432,7 @@ class GASolver(_WaypointSolver):
             self.population = [{"chromosome": [], "path": [], "fitness": INF, "length": INF, "turns": 0,
                                 "safety_penalty": 0, "diag_penalty": 0}] * self.population_size
             return False
-        r = pfrng.AgentRandom(self.seed, pfrng.DOM_INIT, 1, 0)
-        while len(self.population) < self.population_size:
-            self.population.append(r.choice(self.population).copy())
-        self.population.sort(key=lambda x: x["fitness"])
+        ga_pad_and_sort(self.population, self.population_size, self.seed)
         return True
 
     def _selection(self, gen):
@@ -515,9 +536,7 @@ class GASolver(_WaypointSolver):
             if self.verbose and ((gen + 1) % 10 == 0 or gen == 0 or gen == self.num_generations - 1):
                 b = self.best_solution_overall
                 print(f"GA Gen {gen + 1}/{self.num_generations}: BestFit={b['fitness']:.2f} (L:{b['length']:.1f}, T:{b['turns']})")
-        res = self.best_solution_overall
-        path = res["path"].tolist() if isinstance(res["path"], CellPath) else res["path"]
-        return (path, res["length"], res["turns"], res["safety_penalty"], res["diag_penalty"], res["fitness"])
+        return ga_result_tuple(self.best_solution_overall)
 
 
 class PSOSolver(_WaypointSolver):
