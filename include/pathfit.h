@@ -294,6 +294,32 @@ int pf_mpa_iter_batch(pf_handle* h, int32_t phase, double CF, int32_t iter, uint
                       const int32_t* d_slot, const int32_t* d_elite_cells, int32_t elite_len, const double* d_elite_stats,
                       int32_t* d_c1_cells, int32_t* d_c1_len, double* d_c1_stats, int32_t* d_c2_cells, int32_t* d_c2_len,
                       double* d_c2_stats, int32_t* d_status);
+/* Exact look-ahead for the fused sweep.  An iteration that accepts no candidate leaves the population, the
+ * list order and the elite untouched, so the next iteration's sweep can run in the same work queue.
+ * pf_mpa_iter_ahead: iterations iters[0 .. depth) (1 <= depth <= 16; phases[d], CFs[d] are level d's) of the population as
+ *   ONE sweep of 2 * depth * n items.  depth == 1 is pf_mpa_iter_batch whose apply also counts.  With depth > 1 the candidate
+ *   rows of all levels live in buffers the handle owns (allocated on first use, freed by pf_destroy; the d_c1 / d_c2 / d_status
+ *   arguments are then not written); level 0 is applied, the others wait.  *accepted = predators level 0 changed.
+ *   pf_get_counters() after a merged sweep: the search counters of the whole sweep, overflow_agents of level 0 alone.
+ * pf_mpa_ahead_take: the device work of iteration `iter` from the waiting levels, if the level is still that iteration's (all
+ *   levels before it accepted nothing, none overflowed, same buffers, no other MPA call or pf_update_grid since): its
+ *   candidates are applied -- no search runs -- and *accepted = predators changed; pf_get_counters() then reads zero.
+ *   Otherwise *accepted = -1, the waiting levels are dropped, and the caller sweeps the iteration itself.
+ * pf_mpa_ahead_level_bufs: where the candidate rows of the level applied last are: out7 = {c1 cells, c1 len, c1 stats,
+ *   c2 cells, c2 len, c2 stats, status}, all null after a single-level sweep (the caller's own rows).
+ * pf_mpa_ahead_drop: forget the waiting levels (the caller changes the population by other means).
+ * pf_mpa_ahead_stats: out6 = {option "mpa_lookahead", option "mpa_lookahead_always", merged sweeps, levels swept ahead,
+ *   iterations served from a level, times a waiting level was found stale}. */
+int pf_mpa_iter_ahead(pf_handle* h, int32_t depth, const int32_t* phases, const double* CFs, const int32_t* iters, uint64_t seed, int32_t n,
+                      int32_t path_cap, int32_t* d_pop_cells, int32_t* d_pop_len, double* d_pop_stats, const int32_t* d_gidx,
+                      const int32_t* d_slot, const int32_t* d_elite_cells, int32_t elite_len, const double* d_elite_stats,
+                      int32_t* d_c1_cells, int32_t* d_c1_len, double* d_c1_stats, int32_t* d_c2_cells, int32_t* d_c2_len,
+                      double* d_c2_stats, int32_t* d_status, int32_t* accepted);
+int pf_mpa_ahead_take(pf_handle* h, int32_t iter, const int32_t* d_slot, int32_t* d_pop_cells, int32_t* d_pop_len, double* d_pop_stats,
+                      int32_t* accepted);
+int pf_mpa_ahead_level_bufs(pf_handle* h, void** out7);
+int pf_mpa_ahead_drop(pf_handle* h);
+int pf_mpa_ahead_stats(pf_handle* h, int64_t* out6);
 /* MPA._reconstruct_path_segment (MPA.py:284-318) called directly: predator a
  * modifies population path a against the given elite path with explicit
  * idx / is_levy / scale and stream (seed, DOM_MPA, iter, d_agent[a]). */
@@ -359,7 +385,9 @@ int pf_mpa_batch_counters(pf_mpa_batch* b, pf_counters* out, int64_t* overflow_t
 /* Tuning knobs (results never change): "maaco_pack8_min" ants per batch from which eight ants share a wavefront
  * (default 2048); "maaco_load_ahead" the packed walk kernel's load-ahead form (all of a step's loads issued together plus touches of the
  * records two steps ahead): -1 (default) for batches of at most one wavefront per SIMD, 0 never, 1 always;
- * "mpa_prune" 0/1 exact bound pruning of MPA rebuilds (default 1); "two_wave" 0/1 MPA._a_star searches (pf_mpa_iter_batch,
+ * "mpa_prune" 0/1 exact bound pruning of MPA rebuilds (default 1); "mpa_lookahead" how many iterations one MPA sweep may cover
+ * after an iteration that accepted nothing (pf_mpa_iter_ahead; at most 16, 0 = off: exactly pf_mpa_iter_batch's
+ * launches; default 8, or the environment's PF_MPA_LOOKAHEAD; < 0 restores the default); test hook "mpa_lookahead_always" 0/1: look ahead after any iteration, so that levels do go stale; "two_wave" 0/1 MPA._a_star searches (pf_mpa_iter_batch,
  * pf_astar_batch variant 1) on two-wavefront workgroups -- a pop wave and a pool wave, csrc/pf_astar_pr.h -- default 0:
  * identical pops, measured 0.9x; compiled only with -DPF_TWO_WAVE (PF_EXTRA_FLAGS of build.py), otherwise
  * setting it to 1 is an error; "astar_settle" 0/1 closed-set searches (AStarSolver

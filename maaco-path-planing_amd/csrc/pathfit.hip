@@ -33,6 +33,8 @@ using namespace pf;
 struct DevCounters {
   unsigned long long pops, pushes, nbr, path_cells, steps, candidates, deckey, overflow, pruned, settled, sequential;
   unsigned long long done;   // agents of the running batch that have finished (k_decode_batch: the tail policy of the parallel engine)
+                             // -- and, in an MPA sweep, whose searches never touch it: predators the sweep's apply changed
+                             // (k_mpa_apply_count, pf_mpa_ahead.h), so that the count comes back with the counter block
 };
 
 struct Common {
@@ -1866,6 +1868,7 @@ struct pf_handle {
   ncclComm_t comm = nullptr; int comm_rank = 0, comm_world = 1;   // RCCL communicator over xGMI (pf_comm_init); collectives run on `stream`
   std::vector<hipEvent_t> span_ev; int span_n = 0; bool span_open = false; double span_ms = 0.0; long long span_cnt = 0;   // pf_span_*: HIP-event timed spans on `stream`
   long long d2h_small = 0, d2h_bulk = 0, d2h_bulk_bytes = 0;   // device-to-host copies the library made (f1/f2 accounting): <= 128 B / larger
+  struct MpaAhead* ahead = nullptr;   // pf_mpa_iter_ahead: level buffers and the levels still to be taken (end of this file)
 };
 
 static long long g_step_cap = 0;   // > 0: lowers the connectors' step cap (pf_set_option "astar_step_cap": tests of the cap path)
@@ -2014,10 +2017,13 @@ int pf_create(const uint8_t* grid, int32_t R, int32_t C, int32_t device, pf_hand
 
 static void maaco_batch_free(pf_maaco_batch* b);
 static void mpa_batch_free(pf_mpa_batch* b);
+static void mpa_ahead_free(pf_handle* h);
+static void mpa_ahead_drop(pf_handle* h);   // forget the look-ahead levels not yet taken: the population or the map is about to change
 void pf_destroy(pf_handle* h) {
   if (!h) return;
   (void)hipSetDevice(h->device);
   if (h->stream) (void)hipStreamSynchronize(h->stream);
+  mpa_ahead_free(h);
   for (pf_maaco_batch* b : h->maaco_batches) maaco_batch_free(b);
   h->maaco_batches.clear();
   for (pf_mpa_batch* b : h->mpa_batches) mpa_batch_free(b);
@@ -2057,6 +2063,7 @@ int pf_update_grid(pf_handle* h, const uint8_t* grid) {
   h->wide_W = 0;                                                    // the wide distance table belongs to the old map
   h->obst_frac = -1.0;
   h->mpa_ready = false; h->maaco_ready = false;                     // their tables (initial path, bounds, tau / eta) belong to the old map
+  mpa_ahead_drop(h);                                                // (so do the look-ahead levels of an MPA run)
   for (pf_maaco_batch* b : h->maaco_batches) b->ready = false;      // (so do the batches': they only accept pf_maaco_batch_destroy)
   for (pf_mpa_batch* b : h->mpa_batches) b->ready = false;          // (... pf_mpa_batch_destroy)
   if (h->d_ds) { (void)hipFree(h->d_ds); h->d_ds = nullptr; }
@@ -2086,6 +2093,10 @@ static int g_two_wave = env_int("PF_TWO_WAVE", 0);   // MPA searches on two-wave
                                                      // pop loop's speed depends on what else its kernel carries)
 static const int kWavesPerCU = env_int("PF_WAVES_PER_CU", kSlotsPerCU);   // resident one-agent waves per CU (LDS permitting)
 static int g_mpa_prune = 1;   // exact bound pruning of MPA rebuilds (pf_set_option "mpa_prune")
+static int clamp_lookahead(int v) { return v < 0 ? 8 : (v > 16 ? 16 : v); }   // (16 = PF_AHEAD_MAX, pf_mpa_ahead.h)
+static const int kMpaLookahead = clamp_lookahead(env_int("PF_MPA_LOOKAHEAD", 8));
+static int g_mpa_lookahead = kMpaLookahead;   // most iterations one MPA sweep may cover after a quiet iteration (pf_set_option "mpa_lookahead"; 0: off)
+static int g_mpa_lookahead_always = 0;   // test hook ("mpa_lookahead_always"): look ahead after ANY iteration, so that levels do go stale
 static int g_settle_top = env_int("PF_SETTLE_TOP", 0);  // auto mode ("astar_settle" -1): per mille of a DECODE batch, from the head of the longest-first queue, whose A* searches
                                                          // also try the engine (pf_set_option "astar_settle_top")
 static int g_settle_tail = env_int("PF_SETTLE_TAIL", 400);   // (r03: 600; re-measured after the r04 trip cuts: 200 / 400 / 600 / 800 -> ga512 23.9 / 23.8 / 23.6 / 23.1 k, pso512 13.2 / 13.4 / 12.9 / 12.9 k) auto mode: per mille of the SEARCH SLOTS; once no more agents of a decode batch than this are unfinished, every search that starts
@@ -2545,6 +2556,8 @@ int pf_set_option(pf_handle* h, const char* name, int64_t value) {
   if (!strcmp(name, "maaco_load_ahead")) { g_maaco_ahead = value < 0 ? -1 : (value ? 1 : 0); return 0; }
   if (!strcmp(name, "maaco_ants_per_wave")) { g_maaco_groups = value < 1 ? 1 : (value > 8 ? 8 : (int)value); return 0; }
   if (!strcmp(name, "mpa_prune")) { g_mpa_prune = value != 0; return 0; }
+  if (!strcmp(name, "mpa_lookahead")) { g_mpa_lookahead = value < 0 ? kMpaLookahead : clamp_lookahead((int)value); return 0; }
+  if (!strcmp(name, "mpa_lookahead_always")) { g_mpa_lookahead_always = value != 0; return 0; }
 #ifdef PF_TWO_WAVE
   if (!strcmp(name, "two_wave")) { g_two_wave = value != 0; return 0; }
 #else
@@ -3335,6 +3348,7 @@ int pf_mpa_setup(pf_handle* h, const pf_mpa_params* p, const pf_score_params* sp
   if (!h) return -2;
   if (!p || !sp || p->start < 0 || p->start >= h->RC || p->target < 0 || p->target >= h->RC) return failmsg(h, "pf_mpa_setup: bad arguments");
   h->mpp = *p; h->mps = *sp; h->mpa_ready = true;
+  mpa_ahead_drop(h);
   if (ensure_slots(h, p->allow_diag, p->restrict_corner)) return -1;
   // memoise the initial path and its stats
   const int cap = h->RC;
@@ -3555,6 +3569,7 @@ int pf_mpa_fads_batch(pf_handle* h, double CF, int32_t iter, uint64_t seed, int3
   if (!h) return -2;
   if (!h->mpa_ready) return failmsg(h, "pf_mpa_fads_batch: call pf_mpa_setup first");
   if (n < 0 || path_cap < 2 || !d_gidx || !d_slot || !d_pop_cells || !d_pop_len || !d_pop_stats || !d_status) return failmsg(h, "pf_mpa_fads_batch: bad arguments");
+  mpa_ahead_drop(h);
   MpaBase base;
   if (mpa_solo_base(h, &base)) return -1;
   if (h->tmp_cap < path_cap) {
@@ -3634,6 +3649,7 @@ int pf_mpa_iter_batch(pf_handle* h, int32_t phase, double CF, int32_t iter, uint
       !d_elite_cells || !d_elite_stats || !d_c1_cells || !d_c1_len || !d_c1_stats || !d_c2_cells || !d_c2_len || !d_c2_stats || !d_status)
     return failmsg(h, "pf_mpa_iter_batch: bad arguments");
   if (n == 0) return 0;
+  mpa_ahead_drop(h);
   MpaBase base;
   if (mpa_solo_base(h, &base)) return -1;
   MpaSweepArgs a;
@@ -4061,6 +4077,7 @@ int pf_mpa_memory(pf_handle* h, int32_t n, int32_t path_cap, const int32_t* d_sl
   if (!h) return -2;
   if (n <= 0) return 0;
   CK(hipSetDevice(h->device));
+  mpa_ahead_drop(h);
   hipLaunchKernelGGL(k_mpa_memory, dim3(n), dim3(64), 0, h->stream, n, path_cap, d_slot, d_cand_cells, d_cand_len,
                      d_cand_stats, d_pop_cells, d_pop_len, d_pop_stats);
   CK(hipGetLastError());
@@ -4327,3 +4344,222 @@ static int decode_multi_launch(pf_handle* h, const DecodeArgs& a, const int* d_s
   m.wp_cells = a.wp_cells; m.wp_pos = a.wp_pos; m.cells = a.cells; m.len = a.len; m.status = a.status; m.stats = a.stats;
   return plateau_map(h) ? launch_with_retry(h, k_decode_multi<true>, m, n) : launch_with_retry(h, k_decode_multi<false>, m, n);
 }
+
+// ---------------------------------------------------------------------------
+// MPA look-ahead: D consecutive iterations of one population in one sweep (pf_mpa_iter_ahead / pf_mpa_ahead_take; kernels in
+// pf_mpa_ahead.h)
+// ---------------------------------------------------------------------------
+#include "pf_mpa_ahead.h"
+
+struct MpaAhead {
+  // candidate rows of the levels of a merged sweep, level d in rows [d n, (d + 1) n): allocated on the first merged sweep, grown on demand
+  int *c1_cells = nullptr, *c1_len = nullptr, *c2_cells = nullptr, *c2_len = nullptr, *status = nullptr;
+  double *c1_stats = nullptr, *c2_stats = nullptr;
+  size_t rows_cap = 0; int row_cells = 0;
+  unsigned long long* d_ctl = nullptr;        // [0] acceptances of a level taken later, [1 + d] overflowed items of level d of a merged sweep
+  // the levels of the last merged sweep that are still to be taken
+  int planned = 0, valid = 0, next = 0;       // levels swept / of them usable (none overflowed before) / the next one to take
+  int prev_accepted = 0;                      // acceptances of the level applied last: the next one is current only if 0
+  int iters[PF_AHEAD_MAX] = {};
+  int n = 0, path_cap = 0;
+  const int* slot = nullptr; int* pop_cells = nullptr; int* pop_len = nullptr; double* pop_stats = nullptr;
+  int last_level = -1;                        // the level applied last (pf_mpa_ahead_level_bufs), -1: the caller's own rows
+  long long sweeps = 0, levels = 0, served = 0, stale = 0;
+};
+static void mpa_ahead_drop(pf_handle* h) {
+  MpaAhead* S = h->ahead;
+  if (!S) return;
+  S->planned = S->valid = S->next = 0; S->last_level = -1;
+}
+static void mpa_ahead_free(pf_handle* h) {
+  MpaAhead* S = h->ahead;
+  if (!S) return;
+  void* ptrs[] = {S->c1_cells, S->c1_len, S->c1_stats, S->c2_cells, S->c2_len, S->c2_stats, S->status, S->d_ctl};
+  for (void* q : ptrs) if (q) (void)hipFree(q);
+  delete S;
+  h->ahead = nullptr;
+}
+static int mpa_ahead_state(pf_handle* h) {
+  if (!h->ahead) h->ahead = new MpaAhead();
+  if (!h->ahead->d_ctl) CK(hipMalloc(&h->ahead->d_ctl, sizeof(unsigned long long) * (1 + PF_AHEAD_MAX)));
+  return 0;
+}
+static int mpa_ahead_rows(pf_handle* h, size_t rows, int path_cap) {
+  MpaAhead* S = h->ahead;
+  if (rows <= S->rows_cap && path_cap == S->row_cells) return 0;
+  CK(hipStreamSynchronize(h->stream));
+  void** slots[] = {(void**)&S->c1_cells, (void**)&S->c1_len, (void**)&S->c1_stats, (void**)&S->c2_cells, (void**)&S->c2_len,
+                    (void**)&S->c2_stats, (void**)&S->status};
+  for (void** q : slots) if (*q) { (void)hipFree(*q); *q = nullptr; }
+  S->rows_cap = 0;
+  CK(hipMalloc(&S->c1_cells, sizeof(int) * rows * path_cap)); CK(hipMalloc(&S->c2_cells, sizeof(int) * rows * path_cap));
+  CK(hipMalloc(&S->c1_len, sizeof(int) * rows)); CK(hipMalloc(&S->c2_len, sizeof(int) * rows)); CK(hipMalloc(&S->status, sizeof(int) * rows));
+  CK(hipMalloc(&S->c1_stats, sizeof(double) * 5 * rows)); CK(hipMalloc(&S->c2_stats, sizeof(double) * 5 * rows));
+  S->rows_cap = rows; S->row_cells = path_cap;
+  return 0;
+}
+
+extern "C" {
+
+// Iterations iters[0 .. depth) of one population as ONE sweep.  depth == 1 is pf_mpa_iter_batch with an apply that counts; with
+// depth > 1 the candidates of all levels go to the handle's level buffers, level 0 is applied, and the others wait for
+// pf_mpa_ahead_take.  *accepted = predators level 0 changed.
+int pf_mpa_iter_ahead(pf_handle* h, int32_t depth, const int32_t* phases, const double* CFs, const int32_t* iters, uint64_t seed, int32_t n,
+                      int32_t path_cap, int32_t* d_pop_cells, int32_t* d_pop_len, double* d_pop_stats, const int32_t* d_gidx,
+                      const int32_t* d_slot, const int32_t* d_elite_cells, int32_t elite_len, const double* d_elite_stats,
+                      int32_t* d_c1_cells, int32_t* d_c1_len, double* d_c1_stats, int32_t* d_c2_cells, int32_t* d_c2_len,
+                      double* d_c2_stats, int32_t* d_status, int32_t* accepted) {
+  if (!h) return -2;
+  if (!h->mpa_ready) return failmsg(h, "pf_mpa_iter_ahead: call pf_mpa_setup first");
+  if (depth < 1 || depth > PF_AHEAD_MAX || !phases || !CFs || !iters || n <= 0 || (int64_t)depth * n > (1 << 28) || path_cap < 2 || !d_pop_cells ||
+      !d_pop_len || !d_pop_stats || !d_gidx || !d_slot || !d_elite_cells || !d_elite_stats || !d_c1_cells || !d_c1_len || !d_c1_stats ||
+      !d_c2_cells || !d_c2_len || !d_c2_stats || !d_status || !accepted)
+    return failmsg(h, "pf_mpa_iter_ahead: bad arguments");
+  for (int d = 0; d < depth; ++d) if (phases[d] < 1 || phases[d] > 3) return failmsg(h, "pf_mpa_iter_ahead: bad arguments");
+  MpaBase base;
+  if (mpa_solo_base(h, &base) || mpa_ahead_state(h)) return -1;
+  mpa_ahead_drop(h);
+  MpaAhead* S = h->ahead;
+  const int D = depth, DN = D * n;
+  if (D > 1) {                                                      // the levels' own rows; a single level keeps the caller's
+    if (mpa_ahead_rows(h, (size_t)DN, path_cap)) return -1;
+    d_c1_cells = S->c1_cells; d_c1_len = S->c1_len; d_c1_stats = S->c1_stats;
+    d_c2_cells = S->c2_cells; d_c2_len = S->c2_len; d_c2_stats = S->c2_stats; d_status = S->status;
+  }
+  MpaLevels ls; ls.D = D; ls.N = n;
+  for (int d = 0; d < PF_AHEAD_MAX; ++d) { const int e = d < D ? d : 0; ls.lv[d].phase = phases[e]; ls.lv[d].iter = iters[e]; ls.lv[d].CF = CFs[e]; }
+  // the launch arguments every level's view starts from: level 0's
+  MpaSweepArgs a;
+  a.ph = mpa_phase_args(base, phases[0], CFs[0], iters[0], seed, n, path_cap, d_pop_cells, d_pop_len, d_pop_stats, d_gidx, d_slot, d_c1_cells,
+                        d_c1_len, d_c1_stats, d_status);
+  a.ph.elite_cells = d_elite_cells; a.ph.elite_len = elite_len; a.ph.elite_stats = d_elite_stats;
+  if (elite_len < 0) { if (ensure_elite_buf(h)) return -1; a.ph.elite_len_dev = h->d_elite_len; }
+  a.fd = mpa_fads_args(base, CFs[0], iters[0], seed, n, path_cap, d_pop_cells, d_pop_len, d_pop_stats, d_gidx, d_slot, d_status);
+  a.fd.init_cells = h->d_init_cells; a.fd.init_len = h->init_len; a.fd.init_stats = h->d_init_stats;
+  a.fd.cand_cells = d_c2_cells; a.fd.cand_len = d_c2_len; a.fd.cand_stats = d_c2_stats;
+  int prc = 0;
+  if (make_queue(h, 2 * DN, [&](float* est) {
+        if (D == 1) {
+          prc = mpa_launch_propose(h, a.ph, est);
+          hipLaunchKernelGGL(k_plan_mpa_fads, dim3((n + 255) / 256), dim3(256), 0, h->stream, a.fd, est + n);
+          return;
+        }
+        prc = mpa_prop_scratch(h, a.ph, DN);
+        if (prc) return;
+        hipLaunchKernelGGL(k_mpa_estimates_ahead<>, dim3((2 * DN + 255) / 256), dim3(256), 0, h->stream, a.ph, a.fd, ls, est);
+      })) return -1;
+  if (prc) return -1;
+  {
+    // doubtful proposals: item g of the launch is predator g % n of level g / n -- its iteration, its CF, its phase
+    std::vector<int> list;
+    if (mpa_doubt_list(h, a.ph, list)) return -1;
+    for (int g : list) {
+      const int d = g / n;
+      MpaPhaseArgs v = a.ph;
+      level_view(v, ls, d);
+      if (mpa_resolve_one(h, v, g - d * n)) return -1;
+    }
+  }
+#ifdef PF_TWO_WAVE
+  const bool pr = g_two_wave != 0 && !plateau_map(h);
+#else
+  const bool pr = false;
+#endif
+  unsigned long long* const ctl = S->d_ctl;
+  if (D > 1) CK(hipMemsetAsync(ctl, 0, sizeof(unsigned long long) * (1 + PF_AHEAD_MAX), h->stream));
+  DevCounters dc;
+  if (mpa_launch_sweep(h, a, DN, pr,
+      [&](MpaJob* jobs, MpaRes* jres) {
+        if (D == 1) hipLaunchKernelGGL(k_mpa_plan, dim3(2 * n), dim3(64), 0, h->stream, a, jobs, jres);
+        else hipLaunchKernelGGL(k_mpa_plan_ahead<>, dim3(2 * DN), dim3(64), 0, h->stream, a, ls, jobs, jres);
+      },
+      [&](const MpaJob* jobs, const MpaRes* jres) {
+        if (D == 1) hipLaunchKernelGGL(k_mpa_finish, dim3(2 * n), dim3(64), 0, h->stream, a, jobs, jres);
+        else hipLaunchKernelGGL(k_mpa_finish_ahead<>, dim3(2 * DN), dim3(64), 0, h->stream, a, ls, jobs, jres, ctl + 1);
+      },
+      [&] { hipLaunchKernelGGL(k_mpa_apply_count<>, dim3(n), dim3(64), 0, h->stream, n, path_cap, d_slot, (const int*)d_c1_cells, (const int*)d_c1_len,
+                               (const double*)d_c1_stats, (const int*)d_c2_cells, (const int*)d_c2_len, (const double*)d_c2_stats, d_pop_cells,
+                               d_pop_len, d_pop_stats, &h->d_cnt->done); },   // (DevCounters::done: the count comes back with the counter block)
+      &dc)) return -1;
+  *accepted = (int32_t)dc.done;
+  if (D == 1) return 0;
+  unsigned long long hc[1 + PF_AHEAD_MAX];                          // the levels' overflow counts: one more small read per MERGED sweep
+  if (d2h_bytes(h, ctl, hc, sizeof(unsigned long long) * (size_t)(1 + D))) return -1;
+  h->d2h_small += 1;
+  // The merged launch is the leader's: its time and its search counters stay with this step.  Overflow is per level -- this
+  // step reports level 0's, and a later level that overflowed (or follows one that did) is not kept: it runs again as an
+  // iteration of its own and reports there.
+  h->last.overflow_agents = (long long)hc[1];
+  S->sweeps += 1; S->levels += D - 1;
+  S->planned = D; S->valid = D; S->next = 1; S->prev_accepted = (int)dc.done; S->last_level = 0;
+  for (int d = D - 1; d >= 1; --d) if (hc[1 + d] > 0) S->valid = d;
+  if (hc[1] > 0) S->valid = 1;
+  for (int d = 0; d < D; ++d) S->iters[d] = iters[d];
+  S->n = n; S->path_cap = path_cap; S->slot = d_slot; S->pop_cells = d_pop_cells; S->pop_len = d_pop_len; S->pop_stats = d_pop_stats;
+  return 0;
+}
+
+// The device work of iteration `iter` from the levels of the last merged sweep, if it is still that iteration's: every level
+// before it accepted nothing, none overflowed, and nothing else touched the population since.  Then the level's candidates
+// are applied (one small kernel, one 4-byte read) and *accepted = predators changed.  Otherwise *accepted = -1, the remaining
+// levels are dropped and the caller sweeps the iteration as usual.
+int pf_mpa_ahead_take(pf_handle* h, int32_t iter, const int32_t* d_slot, int32_t* d_pop_cells, int32_t* d_pop_len, double* d_pop_stats,
+                      int32_t* accepted) {
+  if (!h) return -2;
+  if (!accepted) return failmsg(h, "pf_mpa_ahead_take: bad arguments");
+  *accepted = -1;
+  MpaAhead* S = h->ahead;
+  if (!S || S->next >= S->planned) return 0;                        // nothing is waiting
+  const int d = S->next;
+  if (d >= S->valid || S->prev_accepted != 0 || S->iters[d] != iter || d_slot != S->slot || d_pop_cells != S->pop_cells ||
+      d_pop_len != S->pop_len || d_pop_stats != S->pop_stats) {
+    S->stale += 1;
+    mpa_ahead_drop(h);
+    return 0;
+  }
+  CK(hipSetDevice(h->device));
+  const size_t o = (size_t)d * (size_t)S->n;
+  const int n = S->n, cap = S->path_cap;
+  CK(hipMemsetAsync(S->d_ctl, 0, sizeof(unsigned long long), h->stream));
+  hipLaunchKernelGGL(k_mpa_apply_count<>, dim3(n), dim3(64), 0, h->stream, n, cap, d_slot, (const int*)(S->c1_cells + o * cap),
+                     (const int*)(S->c1_len + o), (const double*)(S->c1_stats + o * 5), (const int*)(S->c2_cells + o * cap), (const int*)(S->c2_len + o),
+                     (const double*)(S->c2_stats + o * 5), d_pop_cells, d_pop_len, d_pop_stats, S->d_ctl);
+  CK(hipGetLastError());
+  unsigned long long acc64 = 0;
+  if (d2h_one(h, S->d_ctl, &acc64)) return -1;
+  h->d2h_small += 1;
+  const int acc = (int)acc64;
+  S->prev_accepted = acc; S->next = d + 1; S->last_level = d; S->served += 1;
+  h->last = pf_counters{}; h->last_ms = 0.f;                        // no search ran for this step: the leader's step carries the sweep
+  *accepted = acc;
+  return 0;
+}
+
+// the candidate rows of the level applied last: {c1 cells, c1 len, c1 stats, c2 cells, c2 len, c2 stats, status}; all null when
+// that was a single-level sweep (the rows are then the caller's own)
+int pf_mpa_ahead_level_bufs(pf_handle* h, void** out7) {
+  if (!h) return -2;
+  if (!out7) return failmsg(h, "pf_mpa_ahead_level_bufs: bad arguments");
+  for (int i = 0; i < 7; ++i) out7[i] = nullptr;
+  const MpaAhead* S = h->ahead;
+  if (!S || S->last_level < 0) return 0;
+  const size_t o = (size_t)S->last_level * (size_t)S->n;
+  out7[0] = S->c1_cells + o * S->path_cap; out7[1] = S->c1_len + o; out7[2] = S->c1_stats + o * 5;
+  out7[3] = S->c2_cells + o * S->path_cap; out7[4] = S->c2_len + o; out7[5] = S->c2_stats + o * 5; out7[6] = S->status + o;
+  return 0;
+}
+
+// forget the levels not yet taken (the caller is about to change the population by other means)
+int pf_mpa_ahead_drop(pf_handle* h) { if (!h) return -2; mpa_ahead_drop(h); return 0; }
+
+// out6 = {"mpa_lookahead", "mpa_lookahead_always", merged sweeps, levels swept ahead, steps served from a level, levels found stale}
+int pf_mpa_ahead_stats(pf_handle* h, int64_t* out6) {
+  if (!h) return -2;
+  if (!out6) return failmsg(h, "pf_mpa_ahead_stats: bad arguments");
+  const MpaAhead* S = h->ahead;
+  out6[0] = g_mpa_lookahead; out6[1] = g_mpa_lookahead_always;
+  out6[2] = S ? S->sweeps : 0; out6[3] = S ? S->levels : 0; out6[4] = S ? S->served : 0; out6[5] = S ? S->stale : 0;
+  return 0;
+}
+
+}  // extern "C"

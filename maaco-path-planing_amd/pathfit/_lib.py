@@ -86,6 +86,12 @@ SYMBOLS = {
     "pf_mpa_fads_batch": (C.c_int, [_vp, _dbl, _i32, _u64, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _vp]),
     "pf_mpa_iter_batch": (C.c_int, [_vp, _i32, _dbl, _i32, _u64, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _i32, _vp,
                                     _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "pf_mpa_iter_ahead": (C.c_int, [_vp, _i32, _vp, _vp, _vp, _u64, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _i32, _vp,
+                                    _vp, _vp, _vp, _vp, _vp, _vp, _vp, C.POINTER(_i32)]),
+    "pf_mpa_ahead_take": (C.c_int, [_vp, _i32, _vp, _vp, _vp, _vp, C.POINTER(_i32)]),
+    "pf_mpa_ahead_level_bufs": (C.c_int, [_vp, _vp]),
+    "pf_mpa_ahead_drop": (C.c_int, [_vp]),
+    "pf_mpa_ahead_stats": (C.c_int, [_vp, _vp]),
     "pf_mpa_rebuild_batch": (C.c_int, [_vp, _i32, _u64, _i32, _i32, _vp, _vp, _vp, _vp, _i32, _vp, _vp, _vp, _vp, _vp,
                                        _vp, _vp, _vp]),
     "pf_set_option": (C.c_int, [_vp, C.c_char_p, _i64]),

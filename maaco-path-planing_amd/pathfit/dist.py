@@ -35,7 +35,6 @@ import time
 
 import numpy as np
 
-from .mpa import cf_and_phase
 
 INF = float("inf")
 
@@ -558,10 +557,8 @@ class ShardedMPA:
         c.broadcast(el_s, 0, 5, er)
         c.broadcast(el_c, 0, cap, er)                                 # the elite row: path_cap x 4 B
         e.mpa_local_view(self.N, self.d_gorder, lo, hi, self.d_gidx, self.d_slot)
-        CF, phase = cf_and_phase(it, m.num_iterations)
         self._fresh, self._head = False, None                        # the sweep rewrites the population
-        e.mpa_iter(phase, CF, it, m.seed, n, cap, m.d_cells, m.d_len, m.d_stats, self.d_gidx, self.d_slot, el_c.ptr, -1, el_s.ptr,
-                   m.d_cand_cells, m.d_cand_len, m.d_cand_stats, m.d_c2_cells, m.d_c2_len, m.d_c2_stats, m.d_status)
+        m._sweep(it, n, self.d_gidx, self.d_slot, c.world)           # (look-ahead on one rank only: see MPA._sweep)
         m._check_overflow()
         self._resort()                                                # :412
         return self._first()[1]

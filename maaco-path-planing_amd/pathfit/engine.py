@@ -445,6 +445,52 @@ class Engine:
                                           d_status.ptr))
         self._logk("mpa_sweep")
 
+    def mpa_iter_ahead(self, levels, seed, n, path_cap, d_pop_cells, d_pop_len, d_pop_stats, d_gidx, d_slot, elite_cells_ptr,
+                       elite_len, elite_stats_ptr, d_c1_cells, d_c1_len, d_c1_stats, d_c2_cells, d_c2_len, d_c2_stats, d_status):
+        """mpa_iter for the iterations `levels` = [(phase, CF, it), ...] in one sweep (pf_mpa_iter_ahead): the first is applied,
+        the others wait for mpa_ahead_take.  -> predators the first one changed."""
+        D = len(levels)
+        ph = (C.c_int32 * D)(*[int(l[0]) for l in levels])
+        cf = (C.c_double * D)(*[float(l[1]) for l in levels])
+        its = (C.c_int32 * D)(*[int(l[2]) for l in levels])
+        acc = C.c_int32(0)
+        self._ck(self.L.pf_mpa_iter_ahead(self.h, D, C.addressof(ph), C.addressof(cf), C.addressof(its), int(seed), n, path_cap,
+                                          d_pop_cells.ptr, d_pop_len.ptr, d_pop_stats.ptr, d_gidx.ptr, d_slot.ptr,
+                                          elite_cells_ptr, int(elite_len), elite_stats_ptr, d_c1_cells.ptr, d_c1_len.ptr,
+                                          d_c1_stats.ptr, d_c2_cells.ptr, d_c2_len.ptr, d_c2_stats.ptr, d_status.ptr, C.byref(acc)))
+        self._logk("mpa_sweep")
+        return acc.value
+
+    def mpa_ahead_take(self, it, d_slot, d_pop_cells, d_pop_len, d_pop_stats):
+        """Iteration `it` from a level of the last merged sweep -> predators changed, or -1 when the level is not (or no longer)
+        that iteration's.  No search runs, so nothing is logged."""
+        acc = C.c_int32(-1)
+        self._ck(self.L.pf_mpa_ahead_take(self.h, int(it), d_slot.ptr, d_pop_cells.ptr, d_pop_len.ptr, d_pop_stats.ptr, C.byref(acc)))
+        return acc.value
+
+    def mpa_ahead_level_bufs(self, n, path_cap):
+        """Views of the candidate rows of the level applied last (c1 cells / len / stats, c2 cells / len / stats, status), or None
+        after a single-level sweep."""
+        out = (C.c_void_p * 7)()
+        self._ck(self.L.pf_mpa_ahead_level_bufs(self.h, C.addressof(out)))
+        if not out[0]:
+            return None
+        shapes = [((n, path_cap), np.int32), ((n,), np.int32), ((n, 5), np.float64)] * 2 + [((n,), np.int32)]
+        views = []
+        for p, (shape, dt) in zip(out, shapes):
+            v = _View(self, p, int(np.prod(shape)), dt)
+            v.shape = shape
+            views.append(v)
+        return views
+
+    def mpa_ahead_drop(self):
+        self._ck(self.L.pf_mpa_ahead_drop(self.h))
+
+    def mpa_ahead_stats(self):
+        out = (C.c_int64 * 6)()
+        self._ck(self.L.pf_mpa_ahead_stats(self.h, C.addressof(out)))
+        return dict(zip(("cap", "always", "merged_sweeps", "levels_ahead", "served", "stale"), (int(v) for v in out)))
+
     # ------------------------------------------------------------------ GA generation in HBM
     def ga_select(self, seed, gen, n, k, d_fit_all, d_gorder, d_psid):
         self._ck(self.L.pf_ga_select_dev(self.h, int(seed), int(gen), int(n), int(k), d_fit_all.ptr, d_gorder.ptr, d_psid.ptr))

@@ -40,6 +40,27 @@ def cf_and_phase(it, num_iterations):
     return CF, phase
 
 
+STALE = -1      # in an acceptance history: the level waiting for the iteration that follows was found stale
+
+
+def lookahead_depth(history, cap, left, always=False):
+    """How many consecutive iterations the next sweep covers (pf_mpa_iter_ahead): a pure function of the acceptance history
+    (predators changed by each iteration so far, oldest first, with STALE before an iteration whose waiting level had to be
+    thrown away), the option "mpa_lookahead" (`cap`, 0 = off) and the iterations left in the run, this one included.
+    0: off -- the plain sweep.  1: this iteration alone.  An iteration that accepted nothing left the population, the list
+    order and the elite as they were, so the iterations after it can be swept with it, up to `cap` and never past the run's
+    end; after a stale level the run goes back to single sweeps until the next quiet iteration.  `always` (test hook
+    "mpa_lookahead_always") treats every iteration as quiet."""
+    if cap <= 0:
+        return 0
+    if left <= 1:
+        return 1
+    if history and history[-1] == STALE:
+        return 1
+    quiet = always or (len(history) > 0 and history[-1] == 0)
+    return min(int(cap), int(left)) if quiet else 1
+
+
 class BestSoFar:
     """The reference's best-so-far state of one population (MPA.py:30-36) and its rules.  `s` is the stats[5] of the best
     predator of an iteration (length, turns, safety penalty, diagonal penalty, fitness); `fetch()` brings its path as a
@@ -151,6 +172,9 @@ class MPA(BestSoFar):
         self.d_order = e.put(np.arange(N, dtype=np.int32))               # the list: sorted position -> storage slot
         self._sorted = False                                             # (see _sort)
         self.d_gidx = e.put(np.arange(N, dtype=np.int32))                # single GPU: every predator is local
+        self._own_rows = (self.d_cand_cells, self.d_cand_len, self.d_cand_stats, self.d_c2_cells, self.d_c2_len, self.d_c2_stats,
+                          self.d_status)
+        self.drop_lookahead()
         self._el_cells, self._el_len, self._el_stats = e.mpa_elite_bufs()
 
     @property
@@ -204,9 +228,7 @@ class MPA(BestSoFar):
         el_c, el_s = self._el_cells.ptr, self._el_stats.ptr
         self._sorted = False                                             # the sweep rewrites the population
         if self.fused:
-            e.mpa_iter(phase, CF, it, self.seed, N, cap, self.d_cells, self.d_len, self.d_stats, self.d_gidx, self.d_order,
-                       el_c, -1, el_s, self.d_cand_cells, self.d_cand_len, self.d_cand_stats,
-                       self.d_c2_cells, self.d_c2_len, self.d_c2_stats, self.d_status)     # :339-410 in one queue
+            self._sweep(it, N, self.d_gidx, self.d_order)                # :339-410 in one queue
             self._check_overflow()
         else:
             elite_len = int(self._el_len.read(0, 1)[0])
@@ -221,6 +243,48 @@ class MPA(BestSoFar):
         slot, s = self._best_row()
         self._take(s, self._fetch(slot))                                 # :415-440
         return s
+
+    def drop_lookahead(self):
+        """Forget the iterations swept ahead and the acceptance history: the population has been (re)built or changed by
+        something other than step()."""
+        self.accept_history = []         # predators changed by every iteration so far (STALE marks a discarded level)
+        self._ahead_left = 0             # levels of the last merged sweep still waiting
+        if hasattr(self.engine, "mpa_ahead_drop"):
+            self.engine.mpa_ahead_drop()
+
+    def _sweep(self, it, n, d_gidx, d_slot, world=1):
+        """The fused device work of iteration `it` for the n predators stored here (MPA.step and ShardedMPA.step).  With the
+        look-ahead on (one rank only: another rank's acceptance changes the global list) an iteration that follows a quiet
+        one is served from the sweep that already covered it, or sweeps the iterations after it along with its own."""
+        e, cap, K = self.engine, self.path_cap, self.num_iterations
+        own = self._own_rows
+        st = e.mpa_ahead_stats() if world == 1 else {"cap": 0, "always": 0}
+        el_c, el_s = self._el_cells.ptr, self._el_stats.ptr
+        CF, phase = cf_and_phase(it, K)
+        acc, rows = -1, own                              # (rows: where this iteration's candidate rows end up)
+        if st["cap"] > 0 and self._ahead_left > 0:
+            acc = e.mpa_ahead_take(it, d_slot, self.d_cells, self.d_len, self.d_stats)
+            self._ahead_left = self._ahead_left - 1 if acc >= 0 else 0
+            if acc < 0:
+                self.accept_history.append(STALE)
+            else:
+                rows = None                              # a level's
+        if acc < 0:
+            depth = lookahead_depth(self.accept_history, st["cap"], K - it + 1, bool(st["always"]))
+            if depth == 0:                               # off: exactly the plain sweep
+                self._ahead_left = 0
+                e.mpa_iter(phase, CF, it, self.seed, n, cap, self.d_cells, self.d_len, self.d_stats, d_gidx, d_slot, el_c, -1, el_s, *own)
+            else:
+                levels = [(cf_and_phase(it + d, K)[1], cf_and_phase(it + d, K)[0], it + d) for d in range(depth)]
+                acc = e.mpa_iter_ahead(levels, self.seed, n, cap, self.d_cells, self.d_len, self.d_stats, d_gidx, d_slot, el_c, -1,
+                                       el_s, *own)
+                self._ahead_left = depth - 1
+                if depth > 1:
+                    rows = None
+        if acc >= 0:
+            self.accept_history.append(acc)
+        (self.d_cand_cells, self.d_cand_len, self.d_cand_stats, self.d_c2_cells, self.d_c2_len, self.d_c2_stats,
+         self.d_status) = rows or e.mpa_ahead_level_bufs(n, cap)
 
     def _check_overflow(self):
         n = self.engine.counters()["overflow_agents"]      # counted on the device: no status column leaves HBM
