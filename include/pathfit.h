@@ -485,6 +485,42 @@ int pf_ga_assemble_batch(pf_handle* h, int32_t K, int32_t N, int32_t W, int32_t 
 int pf_sort_order_by_key_seg(pf_handle* h, int32_t K, int32_t n, const double* d_vals, int32_t stride, int32_t offset, int32_t* d_order);
 int pf_best_rows_seg(pf_handle* h, int32_t K, int32_t N, const double* d_stats, const int32_t* d_order, double* out);
 
+/* ---- K independent PSO swarms in one batched sweep (pathfit.PSOBatch) --------------------------------------------------
+ * Swarm k has its own seed d_seeds[k] (uint64[K] in HBM), start cell d_starts[k] and target cell d_targets[k]; the K swarms
+ * share the grid, N, W and the coefficients.  Layout: particle a (LOCAL, 0 .. N - 1) of swarm k is row k N + a of d_pos /
+ * d_vel / d_pbest [K N][W][2], d_pbest_fit / d_len / d_pb_len [K N], d_stats [K N][5], d_cells / d_pb_cells [K N][path_cap];
+ * swarm k owns row k of d_gbest [K][W][2], d_gbest_stats [K][5], d_gbest_path [K][path_cap + 1] ([0] = length) and d_gfit [K].
+ * A round of the asynchronous sweep evaluates the particles [cur[k], N) of every swarm, cur[k] being its first particle that
+ * is not final yet; these segments back to back are the round's n ITEMS.  d_tab, int32 [2 K + 1], is the round's table:
+ * off[0 .. K] (off[k] = first item of swarm k, off[K] = n), then cur[0 .. K).  The d_s_* buffers are STAGING rows, one per
+ * item ([K N] rows at most): the new position and velocity, the item's start and target cell, its row k N + a, and -- written
+ * by pf_decode_batch_multi(n, W, wp_pos = d_s_pos, d_s_start, d_s_target, ...) between the update and the scan -- its path
+ * row, length, status and stats.  Swarm k computes exactly what the solo calls compute on its rows with seed d_seeds[k].  The
+ * entries are stateless (the caller owns every buffer) and stream ordered; only pf_pso_scan_batch copies to the host.
+ * pf_pso_update_batch: pso.py:186-202 for every item, stream (d_seeds[k], DOM_PSO, iter, a) with waypoint d at draw 4 d and
+ *   gbest row k (pf_pso_update per swarm).  Reads the swarms' rows, writes staging only: an item that turns out not to be final
+ *   leaves nothing to roll back.
+ * pf_pso_scan_batch: the decision of pso.py:216-229 per swarm (pf_pso_scan on its segment with gbest_fit = d_gfit[k]): d_rec[k]
+ *   = {int32 index INSIDE the segment of the first item that is feasible with fitness below its own pbest and below d_gfit[k]
+ *   -- sync_mode != 0: of the first item holding the smallest such fitness --, or -1; int32 number of items with status
+ *   PF_ST_OVERFLOW; double its fitness or inf}, 16 bytes; the K records are copied to out in ONE device-to-host copy.
+ * pf_pso_commit_batch: the writes of pso.py:216-229.  Final items are, asynchronously, those at or before their swarm's
+ *   improver (the whole segment if d_rec[k] has none), synchronously all: their staging rows become the particle's position,
+ *   velocity, path row, length and stats; pso.py:216-220 (strict < against the OLD pbest: position, fitness, path row);
+ *   the improver: pso.py:222-229 into gbest row k, d_gbest_stats, d_gbest_path (length first) and d_gfit[k].  Nothing is
+ *   written for the other items. */
+int pf_pso_update_batch(pf_handle* h, int32_t n, int32_t K, int32_t N, int32_t W, double w, double c1, double c2, double max_vel, uint64_t iter,
+                        const uint64_t* d_seeds, const int32_t* d_tab, const int32_t* d_starts, const int32_t* d_targets, const double* d_pos,
+                        const double* d_vel, const double* d_pbest, const double* d_gbest, double* d_s_pos, double* d_s_vel, int32_t* d_s_start,
+                        int32_t* d_s_target, int32_t* d_s_row);
+int pf_pso_scan_batch(pf_handle* h, int32_t K, int32_t N, int32_t sync_mode, const int32_t* d_tab, const double* d_s_stats, const int32_t* d_s_len,
+                      const int32_t* d_s_status, const double* d_pbest_fit, const double* d_gfit, void* d_rec, void* out);
+int pf_pso_commit_batch(pf_handle* h, int32_t n, int32_t K, int32_t N, int32_t W, int32_t path_cap, int32_t sync_mode, const int32_t* d_tab,
+                        const void* d_rec, const int32_t* d_s_row, const double* d_s_pos, const double* d_s_vel, const double* d_s_stats,
+                        const int32_t* d_s_len, const int32_t* d_s_cells, double* d_pos, double* d_vel, double* d_stats, int32_t* d_len,
+                        int32_t* d_cells, double* d_pbest, double* d_pbest_fit, int32_t* d_pb_cells, int32_t* d_pb_len, double* d_gbest,
+                        double* d_gbest_stats, int32_t* d_gbest_path, double* d_gfit);
+
 /* MAACO.py:306-311 in two steps (the multi-GPU fold works on row chunks): _begin marks the cells of the successful
  * ants and computes Q / L per ant, _cells adds the deposits of cells [cell0, cell1) in ant order.  pf_maaco_deposit =
  * _begin + _cells(0, R*C).  All stream ordered. */

@@ -309,26 +309,35 @@ struct PsoArgs {
   unsigned long long seed, iter, agent0;
   double* pos_keep; double* vel_keep;   // non-null: the pre-update values are left here (the asynchronous sweep's roll-back copy)
 };
+// (the *_item functions are the kernels' bodies: the batched forms in pf_pso_batch.h call them with a swarm's own rows, seed and gbest)
+// Waypoint d of one particle (pso.py:186-202).  ri = the element index of the waypoint in p.pos / p.vel / p.pbest (read) and in
+// p.pos_keep / p.vel_keep (which, when non-null, get the pre-update values); the new position and velocity go to nxs / nvs at
+// element index ro: the same rows in the solo sweep, a staging row in a batch.
+PF_DEV void pso_update_item(const PsoArgs& p, unsigned long long seed, unsigned long long agent, int d, const double* gbest, size_t ri,
+                            double* nxs, double* nvs, size_t ro) {
+  Rng g; g.init(seed, DOM_PSO, p.iter, agent);
+  g.set_ctr(4ull * (unsigned long long)d);
+  for (int ax = 0; ax < 2; ++ax) {
+    const size_t i = ri + ax;
+    const double hi = ax == 0 ? (double)(p.R - 1) : (double)(p.C - 1);
+    const double r1 = g.random(), r2 = g.random();
+    const double x = p.pos[i], v0 = p.vel[i];
+    if (p.pos_keep) { p.pos_keep[i] = x; p.vel_keep[i] = v0; }
+    double v = p.w * v0 + p.c1 * r1 * (p.pbest[i] - x) + p.c2 * r2 * (gbest[d * 2 + ax] - x);
+    v = fmin(fmax(v, -p.max_vel), p.max_vel);                     // np.clip pso.py:192-193
+    double nx = x + v;
+    nx = fmin(fmax(nx, 0.0), hi);                                 // np.clip pso.py:201-202
+    nvs[ro + ax] = v; nxs[ro + ax] = nx;
+  }
+}
 // one thread per (particle, waypoint): the counter RNG is random access, so
 // waypoint d starts at draw 4*d of the particle's stream (pso.py:186-190 order).
 __global__ void k_pso_update(PsoArgs p) {
   const int t = blockIdx.x * blockDim.x + threadIdx.x;
   if (t >= p.n * p.W) return;
   const int part = t / p.W, d = t - part * p.W;
-  Rng g; g.init(p.seed, DOM_PSO, p.iter, p.agent0 + (unsigned long long)part);
-  g.set_ctr(4ull * (unsigned long long)d);
-  for (int ax = 0; ax < 2; ++ax) {
-    const size_t i = ((size_t)part * p.W + d) * 2 + ax;
-    const double hi = ax == 0 ? (double)(p.R - 1) : (double)(p.C - 1);
-    const double r1 = g.random(), r2 = g.random();
-    const double x = p.pos[i], v0 = p.vel[i];
-    if (p.pos_keep) { p.pos_keep[i] = x; p.vel_keep[i] = v0; }
-    double v = p.w * v0 + p.c1 * r1 * (p.pbest[i] - x) + p.c2 * r2 * (p.gbest[d * 2 + ax] - x);
-    v = fmin(fmax(v, -p.max_vel), p.max_vel);                     // np.clip pso.py:192-193
-    double nx = x + v;
-    nx = fmin(fmax(nx, 0.0), hi);                                 // np.clip pso.py:201-202
-    p.vel[i] = v; p.pos[i] = nx;
-  }
+  const size_t i = ((size_t)part * p.W + d) * 2;
+  pso_update_item(p, p.seed, p.agent0 + (unsigned long long)part, d, p.gbest, i, p.pos, p.vel, i);
 }
 __global__ void k_pso_pbest(int n, int W, const double* pos, const double* stats, const int* len, double* pbest,
                             double* pbest_fit, int* improved) {
@@ -350,6 +359,26 @@ __global__ __launch_bounds__(64) void k_pso_pbest_paths(int n, int path_cap, con
   for (int i = threadIdx.x; i < L; i += 64) pb_cells[(size_t)a * path_cap + i] = cells[(size_t)a * path_cap + i];
   if (threadIdx.x == 0) pb_len[a] = L;
 }
+// A final particle of a round (the body of k_pso_commit behind its roll-back): t = the thread of its 64-thread block, L / fit
+// its path length and fitness, ppos / pstats / pcells its evaluated position [W][2], five stats and path row, pb / pbf / pbc / pbl
+// its pbest position, fitness, path row and length.  pso.py:216-220 -- fitness below its pbest (strict) -> position, fitness and
+// path row become the pbest; improver: pso.py:222-229 -- its position, five stats and path row (length first) go to gb / gstats /
+// gpath.  Every thread of the block calls it (the barrier is reached by all of them or by none: `better` is the same for all).
+PF_DEV void pso_commit_item(int t, int W, bool improver, int L, double fit, const double* ppos, const double* pstats, const int* pcells,
+                            double* pb, double* pbf, int* pbc, int* pbl, double* gb, double* gstats, int* gpath) {
+  if (improver) {                                                 // the gbest moves here (decided by k_pso_scan against the OLD pbest: read before it changes)
+    for (int i = t; i < W * 2; i += 64) gb[i] = ppos[i];
+    if (t < 5) gstats[t] = pstats[t];
+    for (int i = t; i < L; i += 64) gpath[1 + i] = pcells[i];
+    if (t == 0) gpath[0] = L;
+  }
+  const bool better = L > 0 && fit < pbf[0];                      // pso.py:210,216
+  if (!better) return;
+  for (int i = t; i < W * 2; i += 64) pb[i] = ppos[i];
+  for (int i = t; i < L; i += 64) pbc[i] = pcells[i];
+  __syncthreads();                                                // (every thread has read the pbest fitness before it changes)
+  if (t == 0) { pbf[0] = fit; pbl[0] = L; }
+}
 // One round of the asynchronous sweep committed in ONE launch (it was pbest + pbest paths + two / four device-to-device copies
 // + two small reads, each behind a stream synchronisation).  Block a = particle a of the evaluated batch [0, m):
 //   a <  k   final: pso.py:216-220 -- fitness below its pbest (strict) -> position, fitness and path row become the pbest;
@@ -367,28 +396,16 @@ __global__ __launch_bounds__(64) void k_pso_commit(int m, int W, int path_cap, i
     for (int i = t; i < W * 2; i += 64) { pos[w0 + i] = pos_keep[w0 + i]; vel[w0 + i] = vel_keep[w0 + i]; }
     return;
   }
-  const int L = len[a];
-  const double fit = stats[(size_t)a * 5 + 4];
-  if (a == j) {                                                   // the gbest moves here (decided by k_pso_scan against the OLD pbest: read before it changes)
-    for (int i = t; i < W * 2; i += 64) gb[i] = pos[w0 + i];
-    if (t < 5) gstats[t] = stats[(size_t)a * 5 + t];
-    for (int i = t; i < L; i += 64) gpath[1 + i] = cells[(size_t)a * path_cap + i];
-    if (t == 0) gpath[0] = L;
-  }
-  const bool better = L > 0 && fit < pbest_fit[a];               // pso.py:210,216
-  if (!better) return;
-  for (int i = t; i < W * 2; i += 64) pbest[w0 + i] = pos[w0 + i];
-  for (int i = t; i < L; i += 64) pb_cells[(size_t)a * path_cap + i] = cells[(size_t)a * path_cap + i];
-  __syncthreads();                                                // (every thread has read pbest_fit[a] before it changes)
-  if (t == 0) { pbest_fit[a] = fit; pb_len[a] = L; }
+  pso_commit_item(t, W, a == j, len[a], stats[(size_t)a * 5 + 4], pos + w0, stats + (size_t)a * 5, cells + (size_t)a * path_cap, pbest + w0,
+                  pbest_fit + a, pb_cells + (size_t)a * path_cap, pb_len + a, gb, gstats, gpath);
 }
 // pbest -> gbest scan over particles [0, n) of one evaluated batch (pso.py:216-229), one block.  A particle improves
 // the gbest when its path is feasible and its fitness is below both its own pbest (:216) and the gbest (:222).
 // Asynchronous mode: the FIRST improver (everything before it is final, everything after it has to be re-evaluated
 // with the moved gbest); synchronous mode: the first particle with the smallest improving fitness.
 // out[0] = index or -1, out[1] = number of particles with status 3 (scratch / path capacity overflow).
-__global__ __launch_bounds__(256) void k_pso_scan(int n, const double* stats, const int* len, const int* status, const double* pbf,
-                                                  double gbest_fit, int sync_mode, int* out, double* out_fit) {
+PF_DEV void pso_scan_item(int n, const double* stats, const int* len, const int* status, const double* pbf, double gbest_fit, int sync_mode,
+                          int* out, double* out_fit) {
   __shared__ unsigned long long best[256];
   __shared__ int ovf[256];
   unsigned long long b = ~0ull; int o = 0;
@@ -430,6 +447,10 @@ __global__ __launch_bounds__(256) void k_pso_scan(int n, const double* stats, co
     out[1] = novf;
     out_fit[0] = idx == ~0ull ? PF_INF : stats[(size_t)idx * 5 + 4];
   }
+}
+__global__ __launch_bounds__(256) void k_pso_scan(int n, const double* stats, const int* len, const int* status, const double* pbf,
+                                                  double gbest_fit, int sync_mode, int* out, double* out_fit) {
+  pso_scan_item(n, stats, len, status, pbf, gbest_fit, sync_mode, out, out_fit);
 }
 
 // ===========================================================================
@@ -4559,6 +4580,76 @@ int pf_mpa_ahead_stats(pf_handle* h, int64_t* out6) {
   const MpaAhead* S = h->ahead;
   out6[0] = g_mpa_lookahead; out6[1] = g_mpa_lookahead_always;
   out6[2] = S ? S->sweeps : 0; out6[3] = S ? S->levels : 0; out6[4] = S ? S->served : 0; out6[5] = S ? S->stale : 0;
+  return 0;
+}
+
+}  // extern "C"
+
+// ---------------------------------------------------------------------------
+// K PSO swarms in one batched sweep (pathfit.PSOBatch): the three small kernels around the per-agent-endpoint decode, in their
+// batched forms (pf_pso_batch.h).  The entries are stateless, like pf_ga_*_batch: the caller owns every swarm
+// and staging buffer, the handle lends its stream.  Nothing here depends on the map's contents, so pf_update_grid has nothing
+// to invalidate.
+// ---------------------------------------------------------------------------
+#include "pf_pso_batch.h"
+extern "C" {
+
+// pso.py:186-202 for the n items of a round (k_pso_update in its batched form); stream ordered
+int pf_pso_update_batch(pf_handle* h, int32_t n, int32_t K, int32_t N, int32_t W, double w, double c1, double c2, double max_vel, uint64_t iter,
+                        const uint64_t* d_seeds, const int32_t* d_tab, const int32_t* d_starts, const int32_t* d_targets, const double* d_pos,
+                        const double* d_vel, const double* d_pbest, const double* d_gbest, double* d_s_pos, double* d_s_vel, int32_t* d_s_start,
+                        int32_t* d_s_target, int32_t* d_s_row) {
+  if (!h) return -2;
+  if (n < 0 || K < 1 || N < 1 || (int64_t)K * N > (1 << 29) || n > K * N || W < 1 || (int64_t)n * W > (1ll << 31) - 256 || !d_seeds || !d_tab || !d_starts ||
+      !d_targets || !d_pos || !d_vel || !d_pbest || !d_gbest || !d_s_pos || !d_s_vel || !d_s_start || !d_s_target || !d_s_row)
+    return failmsg(h, "pf_pso_update_batch: bad arguments (0 <= n <= K * N <= 2^29)");
+  if (n == 0) return 0;
+  CK(hipSetDevice(h->device));
+  PsoArgs a{n, W, h->R, h->C, w, c1, c2, max_vel, const_cast<double*>(d_pos), const_cast<double*>(d_vel), d_pbest, d_gbest, 0ull, iter, 0ull, nullptr, nullptr};
+  const int threads = 256, blocks = (n * W + threads - 1) / threads;
+  hipLaunchKernelGGL(k_pso_update_batch<>, dim3(blocks), dim3(threads), 0, h->stream, a, K, N, (const unsigned long long*)d_seeds, d_tab, d_starts, d_targets,
+                     d_s_pos, d_s_vel, d_s_start, d_s_target, d_s_row);
+  CK(hipGetLastError());
+  return 0;
+}
+
+// pso.py:216-229, the decision: every swarm's improver of the round (k_pso_scan per segment) -> d_rec [K] x 16 B, then ONE
+// device-to-host copy of the K records into out (the round's only read besides the decode's own)
+int pf_pso_scan_batch(pf_handle* h, int32_t K, int32_t N, int32_t sync_mode, const int32_t* d_tab, const double* d_s_stats, const int32_t* d_s_len,
+                      const int32_t* d_s_status, const double* d_pbest_fit, const double* d_gfit, void* d_rec, void* out) {
+  if (!h) return -2;
+  if (K < 1 || N < 1 || (int64_t)K * N > (1 << 29) || !d_tab || !d_s_stats || !d_s_len || !d_s_status || !d_pbest_fit || !d_gfit || !d_rec || !out)
+    return failmsg(h, "pf_pso_scan_batch: bad arguments");
+  CK(hipSetDevice(h->device));
+  static_assert(sizeof(PsoScanRec) == 16, "the scan record is 16 bytes");
+  hipLaunchKernelGGL(k_pso_scan_batch<>, dim3(K), dim3(256), 0, h->stream, K, N, sync_mode, d_tab, d_s_stats, d_s_len, d_s_status, d_pbest_fit, d_gfit,
+                     (PsoScanRec*)d_rec);
+  CK(hipGetLastError());
+  const size_t nb = sizeof(PsoScanRec) * (size_t)K;
+  CK(hipMemcpyAsync(out, d_rec, nb, hipMemcpyDeviceToHost, h->stream));
+  CK(hipStreamSynchronize(h->stream));
+  if (nb <= 128) h->d2h_small += 1; else { h->d2h_bulk += 1; h->d2h_bulk_bytes += (long long)nb; }
+  return 0;
+}
+
+// pso.py:216-229, the writes: the final items of the round into their swarms' rows (k_pso_commit in its batched form; the block
+// reads its swarm's scan record, so the host passes nothing per swarm); stream ordered
+int pf_pso_commit_batch(pf_handle* h, int32_t n, int32_t K, int32_t N, int32_t W, int32_t path_cap, int32_t sync_mode, const int32_t* d_tab,
+                        const void* d_rec, const int32_t* d_s_row, const double* d_s_pos, const double* d_s_vel, const double* d_s_stats,
+                        const int32_t* d_s_len, const int32_t* d_s_cells, double* d_pos, double* d_vel, double* d_stats, int32_t* d_len,
+                        int32_t* d_cells, double* d_pbest, double* d_pbest_fit, int32_t* d_pb_cells, int32_t* d_pb_len, double* d_gbest,
+                        double* d_gbest_stats, int32_t* d_gbest_path, double* d_gfit) {
+  if (!h) return -2;
+  if (n < 0 || K < 1 || N < 1 || (int64_t)K * N > (1 << 29) || n > K * N || W < 1 || path_cap < 1 || !d_tab || !d_rec || !d_s_row || !d_s_pos || !d_s_vel ||
+      !d_s_stats || !d_s_len || !d_s_cells || !d_pos || !d_vel || !d_stats || !d_len || !d_cells || !d_pbest || !d_pbest_fit || !d_pb_cells ||
+      !d_pb_len || !d_gbest || !d_gbest_stats || !d_gbest_path || !d_gfit)
+    return failmsg(h, "pf_pso_commit_batch: bad arguments (0 <= n <= K * N <= 2^29)");
+  if (n == 0) return 0;
+  CK(hipSetDevice(h->device));
+  hipLaunchKernelGGL(k_pso_commit_batch<>, dim3(n), dim3(64), 0, h->stream, n, K, N, W, path_cap, sync_mode, d_tab, (const PsoScanRec*)d_rec, d_s_row,
+                     d_s_pos, d_s_vel, d_s_stats, d_s_len, d_s_cells, d_pos, d_vel, d_stats, d_len, d_cells, d_pbest, d_pbest_fit, d_pb_cells,
+                     d_pb_len, d_gbest, d_gbest_stats, d_gbest_path, d_gfit);
+  CK(hipGetLastError());
   return 0;
 }
 

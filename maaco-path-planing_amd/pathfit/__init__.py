@@ -15,3 +15,4 @@ from .maaco_batch import MAACOBatch, MaacoColony  # noqa: F401
 from .mpa import MPA  # noqa: F401
 from .mpa_batch import MPABatch, MpaSchool  # noqa: F401
 from .ga_batch import GABatch, GaPopulation  # noqa: F401
+from .pso_batch import PSOBatch, PsoSwarm  # noqa: F401

@@ -153,6 +153,9 @@ SYMBOLS = {
     "pf_ga_assemble_batch": (C.c_int, [_vp, _i32, _i32, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "pf_sort_order_by_key_seg": (C.c_int, [_vp, _i32, _i32, _vp, _i32, _i32, _vp]),
     "pf_best_rows_seg": (C.c_int, [_vp, _i32, _i32, _vp, _vp, _vp]),
+    "pf_pso_update_batch": (C.c_int, [_vp, _i32, _i32, _i32, _i32, _dbl, _dbl, _dbl, _dbl, _u64] + [_vp] * 13),
+    "pf_pso_scan_batch": (C.c_int, [_vp, _i32, _i32, _i32] + [_vp] * 8),
+    "pf_pso_commit_batch": (C.c_int, [_vp, _i32, _i32, _i32, _i32, _i32, _i32] + [_vp] * 21),
 }
 
 

@@ -519,6 +519,26 @@ class Engine:
                                              kid_cells.ptr, psid.ptr, chrom_old.ptr, stats_old.ptr, cells_old.ptr, len_old.ptr,
                                              chrom_new.ptr, stats_new.ptr, cells_new.ptr, len_new.ptr))
 
+    # ------------------------------------------------------------------ K PSO swarms in one batched sweep (pathfit.PSOBatch)
+    def pso_update_batch(self, n, K, N, W, w, c1, c2, max_vel, it, d_seeds, d_tab, d_starts, d_targets, d_pos, d_vel, d_pbest, d_gbest,
+                         s_pos, s_vel, s_start, s_target, s_row):
+        self._ck(self.L.pf_pso_update_batch(self.h, int(n), int(K), int(N), int(W), w, c1, c2, max_vel, int(it), d_seeds.ptr, d_tab.ptr,
+                                            d_starts.ptr, d_targets.ptr, d_pos.ptr, d_vel.ptr, d_pbest.ptr, d_gbest.ptr, s_pos.ptr, s_vel.ptr,
+                                            s_start.ptr, s_target.ptr, s_row.ptr))
+
+    def pso_scan_batch(self, K, N, sync_mode, d_tab, s_stats, s_len, s_status, d_pbf, d_gfit, d_rec, out):
+        """-> out, a structured array [K] of (idx, ovf, fit): every swarm's improver of the round; ONE copy of 16 K bytes."""
+        self._ck(self.L.pf_pso_scan_batch(self.h, int(K), int(N), int(sync_mode), d_tab.ptr, s_stats.ptr, s_len.ptr, s_status.ptr, d_pbf.ptr,
+                                          d_gfit.ptr, d_rec.ptr, out.ctypes.data))
+        return out
+
+    def pso_commit_batch(self, n, K, N, W, cap, sync_mode, d_tab, d_rec, s_row, s_pos, s_vel, s_stats, s_len, s_cells, d_pos, d_vel, d_stats,
+                         d_len, d_cells, d_pbest, d_pbf, d_pb_cells, d_pb_len, d_gbest, d_gstats, d_gpath, d_gfit):
+        self._ck(self.L.pf_pso_commit_batch(self.h, int(n), int(K), int(N), int(W), int(cap), int(sync_mode), d_tab.ptr, d_rec.ptr, s_row.ptr,
+                                            s_pos.ptr, s_vel.ptr, s_stats.ptr, s_len.ptr, s_cells.ptr, d_pos.ptr, d_vel.ptr, d_stats.ptr,
+                                            d_len.ptr, d_cells.ptr, d_pbest.ptr, d_pbf.ptr, d_pb_cells.ptr, d_pb_len.ptr, d_gbest.ptr,
+                                            d_gstats.ptr, d_gpath.ptr, d_gfit.ptr))
+
     def sort_order_by_key_seg(self, K, n, d_vals, stride, offset, d_order):
         """K stable sorts of n keys each: segment k of d_order (position -> local id) by d_vals[(k n + id) * stride + offset]."""
         self._ck(self.L.pf_sort_order_by_key_seg(self.h, int(K), int(n), d_vals.ptr, int(stride), int(offset), d_order.ptr))

@@ -93,6 +93,56 @@ def ga_result_tuple(res):
     return (path, res["length"], res["turns"], res["safety_penalty"], res["diag_penalty"], res["fitness"])
 
 
+# ---- what PSOSolver and PSOBatch (pathfit/pso_batch.py) both need --------------------------------------------------------
+def pso_attempt_draws(seed, k0, n, W, rows, cols, max_vel):
+    """Attempts k0 .. k0 + n - 1 of the initialisation (pso.py:97-117): attempt k draws its position, then its velocity, from
+    the stream (seed, DOM_INIT, 0, k) -> (positions, velocities), float64 [n][W][2] each.  The swarm is the first N feasible
+    attempts in attempt order, so the grouping into rounds (ga_attempt_round) never changes the result."""
+    P = np.zeros((n, W, 2)); V = np.zeros((n, W, 2))
+    for i in range(n):
+        r = pfrng.AgentRandom(seed, pfrng.DOM_INIT, 0, k0 + i)
+        P[i] = [[r.uniform(0, rows - 1), r.uniform(0, cols - 1)] for _ in range(W)]                   # :50-51
+        V[i] = [[r.uniform(-max_vel / 5, max_vel / 5) for _ in range(2)] for _ in range(W)]           # :105
+    return P, V
+
+
+def pso_take_feasible(swarm, N, P, V, cps, stats, feas):
+    """pso.py:107-119 for one round: the feasible attempts join `swarm` = (pos, vel, cps, stats) in attempt order until it holds N."""
+    pos, vel, paths, st = swarm
+    for i in range(len(P)):
+        if feas[i] and len(pos) < N:
+            pos.append(P[i]); vel.append(V[i]); paths.append(cps[i]); st.append(stats[i])
+
+
+def pso_pad(swarm, N, seed):
+    """pso.py:159-160: random copies (stream (seed, DOM_INIT, 1, 0)) up to N particles."""
+    pos, vel, paths, st = swarm
+    r = pfrng.AgentRandom(seed, pfrng.DOM_INIT, 1, 0)
+    while len(pos) < N:
+        j = r.randrange(len(pos))
+        pos.append(pos[j].copy()); vel.append(vel[j].copy()); paths.append(paths[j]); st.append(st[j])
+
+
+def pso_gbest_record(position, path, st):
+    """The reference's gbest dict (pso.py:121-126, :222-229) from a position [W][2], a path and the five stats."""
+    return {"fitness": float(st[4]), "path": path, "position": [list(p) for p in position], "length": float(st[0]),
+            "turns": int(st[1]), "safety_penalty": float(st[2]), "diag_penalty": float(st[3])}
+
+
+def pso_particle_dicts(pos, vel, pbest, pbest_fit, pbest_path, cur_path, cur_stats):
+    """The reference's particle dicts (pso.py:111-117) from the swarm's columns."""
+    return [{"position": pos[i].tolist(), "velocity": vel[i].tolist(), "pbest_position": pbest[i].tolist(),
+             "pbest_fitness": float(pbest_fit[i]), "pbest_path": pbest_path[i], "current_path": cur_path[i],
+             "current_fitness": float(cur_stats[i][4])} for i in range(len(pos))]
+
+
+def pso_result_tuple(res):
+    """solve()'s return value from the gbest dict (pso.py:238-240); the dict's path becomes the list it returns."""
+    path = res["path"].tolist() if isinstance(res["path"], CellPath) else res["path"]
+    res["path"] = path
+    return (path, res.get("length", INF), res.get("turns", INF), res.get("safety_penalty", INF), res.get("diag_penalty", INF), res["fitness"])
+
+
 class BasePathfinder:
     """helper.BasePathfinder (helper.py:115-161) minus the matplotlib half."""
 
@@ -580,19 +630,13 @@ class PSOSolver(_WaypointSolver):
     def _initialize_particles(self):
         """pso.py:97-161: attempt k draws position then velocity from stream (seed, DOM_INIT, 0, k)."""
         W, N = self.num_waypoints, self.num_particles
-        pos, vel, cps, stats = [], [], [], []
+        pos, vel, cps, stats = swarm = [], [], [], []
         k, max_total = 0, N * 20
         while len(pos) < N and k < max_total:
-            batch = min(max_total - k, max(N - len(pos), 32) * 2)
-            P = np.zeros((batch, W, 2)); V = np.zeros((batch, W, 2))
-            for i in range(batch):
-                r = pfrng.AgentRandom(self.seed, pfrng.DOM_INIT, 0, k + i)
-                P[i] = [[r.uniform(0, self.rows - 1), r.uniform(0, self.cols - 1)] for _ in range(W)]     # :50-51
-                V[i] = [[r.uniform(-self.max_vel / 5, self.max_vel / 5) for _ in range(2)] for _ in range(W)]   # :105
+            batch = ga_attempt_round(N, len(pos), k)
+            P, V = pso_attempt_draws(self.seed, k, batch, W, self.rows, self.cols, self.max_vel)
             a, b, feas = self._evaluate(wp_pos=P)
-            for i in range(batch):
-                if feas[i] and len(pos) < N:
-                    pos.append(P[i]); vel.append(V[i]); cps.append(a[i]); stats.append(b[i])
+            pso_take_feasible(swarm, N, P, V, a, b, feas)
             k += batch
         if not pos and W > 0:                                            # :126-143 fallback: the direct A* path as one particle
             direct = self._reconstruct_path_from_position([])
@@ -603,10 +647,7 @@ class PSOSolver(_WaypointSolver):
                 cps.append(CellPath(cells, self.cols)); stats.append(st)
         if not pos:
             return False
-        r = pfrng.AgentRandom(self.seed, pfrng.DOM_INIT, 1, 0)
-        while len(pos) < N:                                              # :159-160 random copies
-            j = r.randrange(len(pos))
-            pos.append(pos[j].copy()); vel.append(vel[j].copy()); cps.append(cps[j]); stats.append(stats[j])
+        pso_pad(swarm, N, self.seed)                                     # :159-160 random copies
         self._pos, self._vel = np.array(pos), np.array(vel)
         self._pbest, self._pbest_fit = self._pos.copy(), np.array([s[4] for s in stats])
         self._pbest_path, self._pbest_stats = list(cps), [np.array(s) for s in stats]
@@ -617,9 +658,7 @@ class PSOSolver(_WaypointSolver):
         return True
 
     def _set_gbest(self, idx, position, path, st):
-        self._gbest = {"fitness": float(st[4]), "path": path, "position": [list(p) for p in position],
-                       "length": float(st[0]), "turns": int(st[1]), "safety_penalty": float(st[2]),
-                       "diag_penalty": float(st[3])}
+        self._gbest = pso_gbest_record(position, path, st)
         self._gbest_dev = None
 
     # gbest_particle_data / particles are the reference's public attributes (pso.py:37-38); while a solve is running
@@ -675,10 +714,7 @@ class PSOSolver(_WaypointSolver):
         self._particles = v
 
     def _sync_particles(self):
-        self._particles = [{"position": self._pos[i].tolist(), "velocity": self._vel[i].tolist(),
-                            "pbest_position": self._pbest[i].tolist(), "pbest_fitness": float(self._pbest_fit[i]),
-                            "pbest_path": self._pbest_path[i], "current_path": self._cur_path[i],
-                            "current_fitness": float(self._cur_stats[i][4])} for i in range(len(self._pos))]
+        self._particles = pso_particle_dicts(self._pos, self._vel, self._pbest, self._pbest_fit, self._pbest_path, self._cur_path, self._cur_stats)
 
     def _download_state(self):
         """HBM -> the host mirrors behind `particles` (bulk copies; only on demand and at the end of solve()).  A sharded
@@ -832,8 +868,4 @@ class PSOSolver(_WaypointSolver):
         self._sync_particles()
         self._particles_stale = False
         self.fetch_gbest()
-        res = self.gbest_particle_data
-        path = res["path"].tolist() if isinstance(res["path"], CellPath) else res["path"]
-        res["path"] = path
-        return (path, res.get("length", INF), res.get("turns", INF), res.get("safety_penalty", INF),
-                res.get("diag_penalty", INF), res["fitness"])
+        return pso_result_tuple(self.gbest_particle_data)
