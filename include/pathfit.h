@@ -167,10 +167,6 @@ int pf_pso_commit(pf_handle* h, int32_t m, int32_t W, int32_t path_cap, int32_t 
                   double* d_vel, const double* d_pos_keep, const double* d_vel_keep, const double* d_stats, const int32_t* d_len,
                   const int32_t* d_cells, double* d_pbest, double* d_pbest_fit, int32_t* d_pb_cells, int32_t* d_pb_len,
                   double* d_gbest, double* d_gbest_stats, int32_t* d_gbest_path);
-/* pbest bookkeeping pso.py:216-220: where stats fitness < pbest_fit (strict),
- * copy pos -> pbest and fitness -> pbest_fit.  d_improved int32[n] out. */
-int pf_pso_pbest(pf_handle* h, int32_t n, int32_t W, const double* d_pos, const double* d_stats,
-                 const int32_t* d_len, double* d_pbest, double* d_pbest_fit, int32_t* d_improved);
 
 /* ---- K4/K5: MAACO --------------------------------------------------- */
 /* Replaces MAACO.__init__ state (pheromone_matrix :58-84, dist table :86-91)
@@ -554,10 +550,6 @@ int pf_comm_recv(pf_handle* h, void* d_buf, int64_t bytes, int32_t peer);
 int pf_comm_sendrecv(pf_handle* h, const void* d_send, int64_t send_bytes, int32_t to, void* d_recv, int64_t recv_bytes,
                      int32_t from);
 
-/* pso.py:218-219 for the paths: rows of the particles pf_pso_pbest marked improved are copied into the pbest path
- * store (both strided [n][path_cap]); asynchronous (stream ordered). */
-int pf_pso_pbest_paths(pf_handle* h, int32_t n, int32_t path_cap, const int32_t* d_cells, const int32_t* d_len,
-                       const int32_t* d_improved, int32_t* d_pb_cells, int32_t* d_pb_len);
 /* pbest -> gbest scan of one evaluated batch of n particles (pso.py:216-229): *idx_out = the first particle that
  * improves the gbest (feasible, fitness below its pbest AND below gbest_fit), or with sync_mode != 0 the first particle
  * with the smallest such fitness; -1 if none.  *fit_out its fitness, *overflow_out the number of particles whose

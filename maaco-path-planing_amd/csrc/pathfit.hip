@@ -339,26 +339,6 @@ __global__ void k_pso_update(PsoArgs p) {
   const size_t i = ((size_t)part * p.W + d) * 2;
   pso_update_item(p, p.seed, p.agent0 + (unsigned long long)part, d, p.gbest, i, p.pos, p.vel, i);
 }
-__global__ void k_pso_pbest(int n, int W, const double* pos, const double* stats, const int* len, double* pbest,
-                            double* pbest_fit, int* improved) {
-  const int a = blockIdx.x;
-  if (a >= n) return;
-  const bool better = len[a] > 0 && stats[(size_t)a * 5 + 4] < pbest_fit[a];   // pso.py:210,216
-  for (int i = threadIdx.x; i < W * 2; i += blockDim.x)
-    if (better) pbest[(size_t)a * W * 2 + i] = pos[(size_t)a * W * 2 + i];
-  __syncthreads();
-  if (threadIdx.x == 0) { improved[a] = better; if (better) pbest_fit[a] = stats[(size_t)a * 5 + 4]; }
-}
-
-// pbest paths stay in HBM too: rows of the particles k_pso_pbest marked as improved are copied over (pso.py:218-219)
-__global__ __launch_bounds__(64) void k_pso_pbest_paths(int n, int path_cap, const int* cells, const int* len, const int* improved,
-                                                        int* pb_cells, int* pb_len) {
-  const int a = blockIdx.x;
-  if (a >= n || !improved[a]) return;
-  const int L = len[a];
-  for (int i = threadIdx.x; i < L; i += 64) pb_cells[(size_t)a * path_cap + i] = cells[(size_t)a * path_cap + i];
-  if (threadIdx.x == 0) pb_len[a] = L;
-}
 // A final particle of a round (the body of k_pso_commit behind its roll-back): t = the thread of its 64-thread block, L / fit
 // its path length and fitness, ppos / pstats / pcells its evaluated position [W][2], five stats and path row, pb / pbf / pbc / pbl
 // its pbest position, fitness, path row and length.  pso.py:216-220 -- fitness below its pbest (strict) -> position, fitness and
@@ -2204,16 +2184,32 @@ static int end_batch(pf_handle* h, DevCounters* dc) {
   return 0;
 }
 
+// The rank sort's scratch (key images, payloads, ranks) for n elements.  The calls that use it are stream ordered; the pointers are
+// nulled before the re-allocation, so a failed growth leaves nothing that pf_destroy would free a second time.
+static int ensure_sort_scratch(pf_handle* h, int n) {
+  if (n <= h->okey_cap) return 0;
+  for (void* q : {(void*)h->d_okey, (void*)h->d_opay, (void*)h->d_orank}) if (q) CK(hipFree(q));
+  h->d_okey = nullptr; h->d_opay = nullptr; h->d_orank = nullptr; h->okey_cap = 0;
+  CK(hipMalloc(&h->d_okey, sizeof(unsigned long long) * (size_t)n)); CK(hipMalloc(&h->d_opay, sizeof(int) * (size_t)n));
+  CK(hipMalloc(&h->d_orank, sizeof(unsigned) * (size_t)n));
+  h->okey_cap = n;
+  return 0;
+}
+// random.sample's pool copy of the GA selection, n ints (grown like the sort scratch)
+static int ensure_ga_pool(pf_handle* h, int n) {
+  if (n <= h->ga_pool_cap) return 0;
+  if (h->d_ga_pool) CK(hipFree(h->d_ga_pool));
+  h->d_ga_pool = nullptr; h->ga_pool_cap = 0;
+  CK(hipMalloc(&h->d_ga_pool, sizeof(int) * (size_t)n));
+  h->ga_pool_cap = n;
+  return 0;
+}
+
 // The stable rank sort (K8: k_sort_prep / k_rank_count / k_rank_scatter) of n elements, enqueued on the handle's stream.
 // mode 0: d_out[] = the list order d_order[] re-sorted by vals[id * stride + offset] ascending (d_out may be d_order itself: the
 // payload is saved before anything is written); mode 1: d_out[] = indices 0..n-1 by est[] descending.
 static int rank_sort(pf_handle* h, int n, int mode, const double* d_vals, int stride, int offset, const int* d_order, const float* d_est, int* d_out) {
-  if (n > h->okey_cap) {
-    for (void* q : {(void*)h->d_okey, (void*)h->d_opay, (void*)h->d_orank}) if (q) CK(hipFree(q));
-    CK(hipMalloc(&h->d_okey, sizeof(unsigned long long) * (size_t)n)); CK(hipMalloc(&h->d_opay, sizeof(int) * (size_t)n));
-    CK(hipMalloc(&h->d_orank, sizeof(unsigned) * (size_t)n));
-    h->okey_cap = n;
-  }
+  if (ensure_sort_scratch(h, n)) return -1;
   const int nb = (n + 255) / 256;
   hipLaunchKernelGGL(k_sort_prep, dim3(nb), dim3(256), 0, h->stream, n, mode, d_vals, stride, offset, d_order, d_est, h->d_okey, h->d_opay, h->d_orank);
   // ~8192 wavefronts per launch when there is that much work; a slice of the other keys is never shorter than 256
@@ -2459,6 +2455,17 @@ int pf_decode_batch_multi(pf_handle* h, int32_t allow_diag, int32_t restrict_cor
                       d_cells, d_len, d_status, sp, d_stats);
 }
 
+// k_pso_update over particles [0, n), enqueued on the handle's stream (d_pos_keep / d_vel_keep may be null)
+static int pso_update_launch(pf_handle* h, int n, int W, double w, double c1, double c2, double max_vel, double* d_pos, double* d_vel,
+                             const double* d_pbest, const double* d_gbest, uint64_t seed, uint64_t iter, uint64_t agent0, double* d_pos_keep,
+                             double* d_vel_keep) {
+  PsoArgs a{n, W, h->R, h->C, w, c1, c2, max_vel, d_pos, d_vel, d_pbest, d_gbest, seed, iter, agent0, d_pos_keep, d_vel_keep};
+  const int threads = 256, blocks = (n * W + threads - 1) / threads;
+  hipLaunchKernelGGL(k_pso_update, dim3(blocks), dim3(threads), 0, h->stream, a);
+  CK(hipGetLastError());
+  return 0;
+}
+
 int pf_pso_update(pf_handle* h, int32_t n, int32_t W, double w, double c1, double c2, double max_vel, double* d_pos,
                   double* d_vel, const double* d_pbest, const double* d_gbest, uint64_t seed, uint64_t iter,
                   uint64_t agent0) {
@@ -2466,11 +2473,8 @@ int pf_pso_update(pf_handle* h, int32_t n, int32_t W, double w, double c1, doubl
   if (n < 0 || W < 1 || !d_pos || !d_vel || !d_pbest || !d_gbest) return failmsg(h, "pf_pso_update: bad arguments");
   if (n == 0) return 0;
   CK(hipSetDevice(h->device));
-  PsoArgs a{n, W, h->R, h->C, w, c1, c2, max_vel, d_pos, d_vel, d_pbest, d_gbest, seed, iter, agent0, nullptr, nullptr};
-  const int threads = 256, blocks = (n * W + threads - 1) / threads;
   CK(hipEventRecord(h->ev0, h->stream));
-  hipLaunchKernelGGL(k_pso_update, dim3(blocks), dim3(threads), 0, h->stream, a);
-  CK(hipGetLastError());
+  if (pso_update_launch(h, n, W, w, c1, c2, max_vel, d_pos, d_vel, d_pbest, d_gbest, seed, iter, agent0, nullptr, nullptr)) return -1;
   CK(hipEventRecord(h->ev1, h->stream));
   CK(hipStreamSynchronize(h->stream));
   CK(hipEventElapsedTime(&h->last_ms, h->ev0, h->ev1));
@@ -2485,11 +2489,7 @@ int pf_pso_update_keep(pf_handle* h, int32_t n, int32_t W, double w, double c1, 
   if (n < 0 || W < 1 || !d_pos || !d_vel || !d_pbest || !d_gbest || !d_pos_keep || !d_vel_keep) return failmsg(h, "pf_pso_update_keep: bad arguments");
   if (n == 0) return 0;
   CK(hipSetDevice(h->device));
-  PsoArgs a{n, W, h->R, h->C, w, c1, c2, max_vel, d_pos, d_vel, d_pbest, d_gbest, seed, iter, agent0, d_pos_keep, d_vel_keep};
-  const int threads = 256, blocks = (n * W + threads - 1) / threads;
-  hipLaunchKernelGGL(k_pso_update, dim3(blocks), dim3(threads), 0, h->stream, a);
-  CK(hipGetLastError());
-  return 0;
+  return pso_update_launch(h, n, W, w, c1, c2, max_vel, d_pos, d_vel, d_pbest, d_gbest, seed, iter, agent0, d_pos_keep, d_vel_keep);
 }
 // one round of the asynchronous sweep committed in one launch (k_pso_commit); asynchronous (stream ordered)
 int pf_pso_commit(pf_handle* h, int32_t m, int32_t W, int32_t path_cap, int32_t n_final, int32_t improver, double* d_pos,
@@ -2504,28 +2504,6 @@ int pf_pso_commit(pf_handle* h, int32_t m, int32_t W, int32_t path_cap, int32_t 
   CK(hipSetDevice(h->device));
   hipLaunchKernelGGL(k_pso_commit, dim3(m), dim3(64), 0, h->stream, m, W, path_cap, n_final, improver, d_pos, d_vel, d_pos_keep, d_vel_keep,
                      d_stats, d_len, d_cells, d_pbest, d_pbest_fit, d_pb_cells, d_pb_len, d_gbest, d_gbest_stats, d_gbest_path);
-  CK(hipGetLastError());
-  return 0;
-}
-
-int pf_pso_pbest(pf_handle* h, int32_t n, int32_t W, const double* d_pos, const double* d_stats, const int32_t* d_len,
-                 double* d_pbest, double* d_pbest_fit, int32_t* d_improved) {
-  if (!h) return -2;
-  if (n <= 0) return 0;
-  CK(hipSetDevice(h->device));
-  hipLaunchKernelGGL(k_pso_pbest, dim3(n), dim3(64), 0, h->stream, n, W, d_pos, d_stats, d_len, d_pbest, d_pbest_fit, d_improved);
-  CK(hipGetLastError());
-  CK(hipStreamSynchronize(h->stream));
-  return 0;
-}
-
-int pf_pso_pbest_paths(pf_handle* h, int32_t n, int32_t path_cap, const int32_t* d_cells, const int32_t* d_len,
-                       const int32_t* d_improved, int32_t* d_pb_cells, int32_t* d_pb_len) {
-  if (!h) return -2;
-  if (n < 0 || path_cap < 1 || !d_cells || !d_len || !d_improved || !d_pb_cells || !d_pb_len) return failmsg(h, "pf_pso_pbest_paths: bad arguments");
-  if (n == 0) return 0;
-  CK(hipSetDevice(h->device));
-  hipLaunchKernelGGL(k_pso_pbest_paths, dim3(n), dim3(64), 0, h->stream, n, path_cap, d_cells, d_len, d_improved, d_pb_cells, d_pb_len);
   CK(hipGetLastError());
   return 0;
 }
@@ -3980,7 +3958,7 @@ int pf_ga_select_dev(pf_handle* h, uint64_t seed, int32_t gen, int32_t n, int32_
   if (n <= 0 || tournament_size <= 0 || tournament_size > 64 || !d_fit_all || !d_gorder || !d_psid) return failmsg(h, "pf_ga_select_dev: bad arguments (1 <= tournament_size <= 64)");
   CK(hipSetDevice(h->device));
   const int k = tournament_size < n ? tournament_size : n;
-  if (n > h->ga_pool_cap) { if (h->d_ga_pool) CK(hipFree(h->d_ga_pool)); CK(hipMalloc(&h->d_ga_pool, sizeof(int) * (size_t)n)); h->ga_pool_cap = n; }
+  if (ensure_ga_pool(h, n)) return -1;
   hipLaunchKernelGGL(k_ga_select, dim3(1), dim3(1), 0, h->stream, (unsigned long long)seed, gen, n, k, d_fit_all, d_gorder, h->d_ga_pool, d_psid);
   CK(hipGetLastError());
   return 0;
@@ -4284,7 +4262,7 @@ int pf_ga_select_batch(pf_handle* h, const uint64_t* d_seeds, int32_t gen, int32
   CK(hipSetDevice(h->device));
   const int k = tournament_size < N ? tournament_size : N;
   const int KN = K * N;
-  if (KN > h->ga_pool_cap) { if (h->d_ga_pool) CK(hipFree(h->d_ga_pool)); h->d_ga_pool = nullptr; h->ga_pool_cap = 0; CK(hipMalloc(&h->d_ga_pool, sizeof(int) * (size_t)KN)); h->ga_pool_cap = KN; }
+  if (ensure_ga_pool(h, KN)) return -1;
   hipLaunchKernelGGL(k_ga_select_batch<>, dim3(K), dim3(64), 0, h->stream, (const unsigned long long*)d_seeds, gen, K, N, k, d_fit_all, d_gorder,
                      h->d_ga_pool, d_psid);
   CK(hipGetLastError());
@@ -4321,14 +4299,7 @@ int pf_sort_order_by_key_seg(pf_handle* h, int32_t K, int32_t n, const double* d
     return failmsg(h, "pf_sort_order_by_key_seg: bad arguments");
   if (n <= 1) return 0;
   CK(hipSetDevice(h->device));
-  const int KN = K * n;
-  if (KN > h->okey_cap) {                                           // (rank_sort's scratch: the calls are stream ordered)
-    for (void* q : {(void*)h->d_okey, (void*)h->d_opay, (void*)h->d_orank}) if (q) CK(hipFree(q));
-    h->d_okey = nullptr; h->d_opay = nullptr; h->d_orank = nullptr; h->okey_cap = 0;
-    CK(hipMalloc(&h->d_okey, sizeof(unsigned long long) * (size_t)KN)); CK(hipMalloc(&h->d_opay, sizeof(int) * (size_t)KN));
-    CK(hipMalloc(&h->d_orank, sizeof(unsigned) * (size_t)KN));
-    h->okey_cap = KN;
-  }
+  if (ensure_sort_scratch(h, K * n)) return -1;
   return rank_sort_seg(h, K, n, d_vals, stride, offset, d_order, h->d_okey, h->d_opay, h->d_orank);
 }
 int pf_best_rows_seg(pf_handle* h, int32_t K, int32_t N, const double* d_stats, const int32_t* d_order, double* out) {

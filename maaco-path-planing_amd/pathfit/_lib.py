@@ -62,7 +62,6 @@ SYMBOLS = {
     "pf_decode_batch": (C.c_int, [_vp, _i32, _i32, _i32, _i32, _vp, _vp, _i32, _i32, _i32, _vp, _vp, _vp,
                                   C.POINTER(ScoreParams), _vp]),
     "pf_pso_update": (C.c_int, [_vp, _i32, _i32, _dbl, _dbl, _dbl, _dbl, _vp, _vp, _vp, _vp, _u64, _u64, _u64]),
-    "pf_pso_pbest": (C.c_int, [_vp, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _vp]),
     "pf_pso_update_keep": (C.c_int, [_vp, _i32, _i32, _dbl, _dbl, _dbl, _dbl, _vp, _vp, _vp, _vp, _u64, _u64, _u64, _vp, _vp]),
     "pf_pso_commit": (C.c_int, [_vp, _i32, _i32, _i32, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "pf_maaco_setup": (C.c_int, [_vp, C.POINTER(MaacoParams)]),
@@ -121,7 +120,6 @@ SYMBOLS = {
     "pf_comm_send": (C.c_int, [_vp, _vp, _i64, _i32]),
     "pf_comm_recv": (C.c_int, [_vp, _vp, _i64, _i32]),
     "pf_comm_sendrecv": (C.c_int, [_vp, _vp, _i64, _i32, _vp, _i64, _i32]),
-    "pf_pso_pbest_paths": (C.c_int, [_vp, _i32, _i32, _vp, _vp, _vp, _vp, _vp]),
     "pf_pso_scan": (C.c_int, [_vp, _i32, _vp, _vp, _vp, _vp, _dbl, _i32, C.POINTER(_i32), C.POINTER(_dbl), C.POINTER(_i32)]),
     "pf_d2h_counts": (C.c_int, [_vp, C.POINTER(_i64), C.POINTER(_i64), C.POINTER(_i64)]),
     "pf_span_begin": (C.c_int, [_vp]),

@@ -225,7 +225,8 @@ class Engine:
 
     def decode_host(self, start, target, wp_cells=None, wp_pos=None, sp=None, path_cap=None, allow_diag=True,
                     restrict_corner=True):
-        """wp_cells int[n, W] or wp_pos float[n, W, 2] -> (paths, status, stats or None)."""
+        """wp_cells int[n, W] or wp_pos float[n, W, 2] -> (paths, status, stats or None).  start / target: one cell each for the
+        whole batch, or int[n] arrays with one start and one target per agent (decode_multi)."""
         if wp_cells is not None:
             wp = np.ascontiguousarray(wp_cells, np.int32)
             n, W = wp.shape
@@ -235,12 +236,20 @@ class Engine:
             n, W = wp.shape[0], wp.shape[1]
             dwc, dwp = None, self.put(wp.reshape(-1) if wp.size else np.zeros(1))
         cap = int(path_cap or self.default_path_cap())
-        dc, dl, dst = self.buf((n, cap), np.int32), self.buf(n, np.int32), self.buf(n, np.int32)
-        dstat = self.buf((n, 5), np.float64) if sp is not None else None
-        self.decode_batch(n, W, start, target, cap, dc, dl, dst, dwc, dwp, sp, dstat, allow_diag, restrict_corner)
+        m = max(n, 1)
+        dc, dl, dst = self.buf((m, cap), np.int32), self.buf(m, np.int32), self.buf(m, np.int32)
+        dstat = self.buf((m, 5), np.float64) if sp is not None else None
+        if np.ndim(start) or np.ndim(target):
+            st_, tg_ = np.ascontiguousarray(start, np.int32), np.ascontiguousarray(target, np.int32)
+            if st_.shape != (n,) or tg_.shape != (n,):
+                raise ValueError("decode_multi_host: one start and one target per agent")
+            ds, dt = self.put(st_ if n else np.zeros(1, np.int32)), self.put(tg_ if n else np.zeros(1, np.int32))
+            self.decode_multi(n, W, ds, dt, cap, dc, dl, dst, dwc, dwp, sp, dstat, allow_diag, restrict_corner)
+        else:
+            self.decode_batch(n, W, start, target, cap, dc, dl, dst, dwc, dwp, sp, dstat, allow_diag, restrict_corner)
         cells, lens, st = dc.download(), dl.download(), dst.download()
         paths = [cells[i, :lens[i]].copy() for i in range(n)]
-        return paths, st, (dstat.download() if dstat is not None else None)
+        return paths, st[:n], (dstat.download()[:n] if dstat is not None else None)
 
     def decode_multi(self, n, W, d_start, d_target, path_cap, d_cells, d_len, d_status, d_wp_cells=None, d_wp_pos=None,
                      sp=None, d_stats=None, allow_diag=True, restrict_corner=True):
@@ -251,41 +260,17 @@ class Engine:
                                               C.byref(sp) if sp is not None else None, d_stats.ptr if d_stats else None))
         self._logk("decode")
 
-    def decode_multi_host(self, starts, targets, wp_cells=None, wp_pos=None, sp=None, path_cap=None, allow_diag=True,
-                          restrict_corner=True):
-        """decode_host with per-agent endpoints: starts / targets int[n] -> (paths, status, stats or None)."""
-        if wp_cells is not None:
-            wp = np.ascontiguousarray(wp_cells, np.int32)
-            n, W = wp.shape
-            dwc, dwp = self.put(wp.reshape(-1) if wp.size else np.zeros(1, np.int32)), None
-        else:
-            wp = np.ascontiguousarray(wp_pos, np.float64)
-            n, W = wp.shape[0], wp.shape[1]
-            dwc, dwp = None, self.put(wp.reshape(-1) if wp.size else np.zeros(1))
-        st_, tg_ = np.ascontiguousarray(starts, np.int32), np.ascontiguousarray(targets, np.int32)
-        if st_.shape != (n,) or tg_.shape != (n,):
-            raise ValueError("decode_multi_host: one start and one target per agent")
-        cap = int(path_cap or self.default_path_cap())
-        m = max(n, 1)
-        ds, dt = self.put(st_ if n else np.zeros(1, np.int32)), self.put(tg_ if n else np.zeros(1, np.int32))
-        dc, dl, dst = self.buf((m, cap), np.int32), self.buf(m, np.int32), self.buf(m, np.int32)
-        dstat = self.buf((m, 5), np.float64) if sp is not None else None
-        self.decode_multi(n, W, ds, dt, cap, dc, dl, dst, dwc, dwp, sp, dstat, allow_diag, restrict_corner)
-        cells, lens, st = dc.download(), dl.download(), dst.download()
-        paths = [cells[i, :lens[i]].copy() for i in range(n)]
-        return paths, st[:n], (dstat.download()[:n] if dstat is not None else None)
+    def decode_multi_host(self, starts, targets, **kw):
+        """decode_host with per-agent endpoints: starts / targets int[n]."""
+        return self.decode_host(np.atleast_1d(starts), np.atleast_1d(targets), **kw)
 
     # ------------------------------------------------------------------ K6
     def pso_update(self, n, W, w, c1, c2, max_vel, d_pos, d_vel, d_pbest, d_gbest, seed, it, agent0=0):
         self._ck(self.L.pf_pso_update(self.h, n, W, w, c1, c2, max_vel, d_pos.ptr, d_vel.ptr, d_pbest.ptr,
                                       d_gbest.ptr, int(seed), int(it), int(agent0)))
 
-    def pso_update_raw(self, n, W, w, c1, c2, max_vel, pos_ptr, vel_ptr, pbest_ptr, gbest_ptr, seed, it, agent0):
-        self._ck(self.L.pf_pso_update(self.h, n, W, w, c1, c2, max_vel, pos_ptr, vel_ptr, pbest_ptr, gbest_ptr,
-                                      int(seed), int(it), int(agent0)))
-
     def pso_update_keep_raw(self, n, W, w, c1, c2, max_vel, pos_ptr, vel_ptr, pbest_ptr, gbest_ptr, seed, it, agent0, pos_keep_ptr, vel_keep_ptr):
-        """pso_update_raw + the pre-update position / velocity kept for the roll-back; nothing synchronises."""
+        """pso_update on raw pointers + the pre-update position / velocity kept for the roll-back; nothing synchronises."""
         self._ck(self.L.pf_pso_update_keep(self.h, n, W, w, c1, c2, max_vel, pos_ptr, vel_ptr, pbest_ptr, gbest_ptr,
                                            int(seed), int(it), int(agent0), pos_keep_ptr, vel_keep_ptr))
 
@@ -303,18 +288,12 @@ class Engine:
                                         C.byref(sp), stats_ptr))
         self._logk("decode")
 
-    def pso_pbest_raw(self, n, W, pos_ptr, stats_ptr, len_ptr, pbest_ptr, pbf_ptr, imp_ptr):
-        self._ck(self.L.pf_pso_pbest(self.h, n, W, pos_ptr, stats_ptr, len_ptr, pbest_ptr, pbf_ptr, imp_ptr))
-
     def pso_scan(self, n, stats_ptr, len_ptr, status_ptr, pbf_ptr, gbest_fit, sync_mode):
         """-> (index of the gbest improver in the batch or -1, its fitness, overflowed particles); one 16-byte D2H."""
         i, f, o = C.c_int32(-1), C.c_double(INF), C.c_int32(0)
         self._ck(self.L.pf_pso_scan(self.h, n, stats_ptr, len_ptr, status_ptr, pbf_ptr, float(gbest_fit), int(sync_mode),
                                     C.byref(i), C.byref(f), C.byref(o)))
         return i.value, f.value, o.value
-
-    def pso_pbest_paths_raw(self, n, path_cap, cells_ptr, len_ptr, imp_ptr, pb_cells_ptr, pb_len_ptr):
-        self._ck(self.L.pf_pso_pbest_paths(self.h, n, path_cap, cells_ptr, len_ptr, imp_ptr, pb_cells_ptr, pb_len_ptr))
 
     def d2h_counts(self):
         """(small copies <= 64 B, bulk copies, bulk bytes) this handle has made device -> host."""
@@ -341,10 +320,6 @@ class Engine:
         if out.nbytes:
             self._ck(self.L.pf_d2h(self.h, out.ctypes.data, ptr, out.nbytes))
         return out
-
-    def pso_pbest(self, n, W, d_pos, d_stats, d_len, d_pbest, d_pbest_fit, d_improved):
-        self._ck(self.L.pf_pso_pbest(self.h, n, W, d_pos.ptr, d_stats.ptr, d_len.ptr, d_pbest.ptr, d_pbest_fit.ptr,
-                                     d_improved.ptr))
 
     # ------------------------------------------------------------------ K4/K5
     def maaco_setup(self, params):

@@ -32,13 +32,12 @@ every particle that is not final (no `max_speculation`).
 """
 import numpy as np
 
-from ._batch import cell_ids, check_endpoints, check_grid_and_seeds
-from ._lib import PathfitError
-from .engine import Engine, score_params
+from ._batch import WaypointBatch
+from .engine import Engine
 from .env import mark
-from .paths import CellPath, cells_of
-from .solvers import (INF, PSOSolver, ga_attempt_round, pso_attempt_draws, pso_gbest_record, pso_pad, pso_particle_dicts,
-                      pso_result_tuple, pso_take_feasible)
+from .paths import CellPath
+from .solvers import (INF, PSOSolver, pack_path_rows, pso_attempt_draws, pso_gbest_record, pso_pad, pso_particle_dicts, pso_result_tuple,
+                      pso_take_feasible)
 
 SCAN_REC = np.dtype([("idx", "<i4"), ("ovf", "<i4"), ("fit", "<f8")])       # PsoScanRec (csrc/pf_pso_batch.h)
 
@@ -53,6 +52,7 @@ class PsoSwarm:
         self.convergence_curve = []
         self.rounds = []                    # per sweep: the rounds in which the swarm had particles to evaluate
         self.attempts = 0                   # initial attempts made (pso.py:99-103)
+        self._init = ([], [], [], [])       # the particles begin() has collected: positions, velocities, paths, stats
         self._gbest = {"fitness": INF, "path": [], "position": []}
         self._gdev = None                   # the gbest has moved on the device: {"idx", "fitness", "host": the record was read}
         self._solo = None                   # a degenerate swarm: the solo PSOSolver that ran it (PSOBatch docstring)
@@ -73,126 +73,45 @@ class PsoSwarm:
         return self._result if self._solo is not None else pso_result_tuple(self.gbest_particle_data)
 
 
-class PSOBatch:
+class PSOBatch(WaypointBatch):
+    _solver, _unit, _wp, _mirror = "PSO", "swarm", "wp_pos", ("convergence_curve",)
+
     def __init__(self, grid, num_iterations, num_particles, num_waypoints_per_particle, w, c1, c2, seeds=(), starts=None, targets=None,
                  turn_penalty_factor=0.1, safety_penalty_factor=0.05, min_safe_distance=1.5, allow_diagonal_moves=True,
                  restrict_diagonal_near_obstacle_policy=True, diagonal_obstacle_penalty_value=1000.0, asynchronous=True, engine=None,
                  device=0, verbose=False):
         # every argument is checked before the device is touched
-        self.grid, self.seeds = check_grid_and_seeds("PSOBatch", grid, seeds, "swarm", "num_particles", num_particles)
-        if int(num_waypoints_per_particle) < 1:
-            raise ValueError("PSOBatch: num_waypoints_per_particle must be >= 1 (a PSO without waypoints is one A* call: AStarSolver)")
-        if int(num_iterations) < 0:
-            raise ValueError("PSOBatch: num_iterations must be >= 0")
-        self.rows, self.cols = self.grid.shape
-        K = len(self.seeds)
-        try:
-            self.starts, self.targets = check_endpoints("PSOBatch", "PSO", self.grid, starts, targets, K)
-        except ValueError as ex:                                       # (a missing marker is reported in the solo class's words)
-            raise ValueError(str(ex) if str(ex).startswith("PSOBatch:") else f"PSOBatch: {ex}") from None
-        self.K = K
-        self.num_iterations, self.num_particles = int(num_iterations), int(num_particles)
-        self.num_waypoints = int(num_waypoints_per_particle)
+        self._check_sizes(grid, seeds, "num_particles", num_particles, "num_waypoints_per_particle", num_waypoints_per_particle,
+                          "num_iterations", num_iterations)
+        self.num_iterations, self.num_particles = int(num_iterations), self._N
         self.w, self.c1, self.c2 = w, c1, c2
         self.max_vel = max(1.0, 0.15 * max(self.rows, self.cols))      # pso.py:34
         self.asynchronous = bool(asynchronous)
-        self.allow_diagonal_moves = allow_diagonal_moves
-        self.restrict_diagonal_near_obstacle_policy = restrict_diagonal_near_obstacle_policy
-        self._weights = dict(turn_penalty_factor=turn_penalty_factor, safety_penalty_factor=safety_penalty_factor,
-                             min_safe_distance=min_safe_distance, diagonal_obstacle_penalty_value=diagonal_obstacle_penalty_value)
-        self.verbose = verbose
-        self.engine = engine if engine is not None else Engine(self.grid, device)
-        self._s, self._t = cell_ids(self.engine, "PSOBatch", self.grid, self.starts, self.targets)
-        self._sp = score_params(0, restrict_diagonal_near_obstacle_policy, turn_penalty_factor, safety_penalty_factor,
-                                min_safe_distance, diagonal_obstacle_penalty_value)
-        self.path_cap = min(self.rows * self.cols, 16 * (self.rows + self.cols) + 64)      # _WaypointSolver._path_cap
-        self._swarms = [PsoSwarm(self, k) for k in range(K)]
-        self.live = []                      # the swarms that run batched, in batch order (begin() fills it)
-        self._d = None                      # the device state (begin())
         self._it = 0                        # sweeps made
-        self._closed = False
-        self.init_launches = 0              # multi-endpoint launches begin() made
+        self._open(starts, targets, allow_diagonal_moves, restrict_diagonal_near_obstacle_policy,
+                   dict(turn_penalty_factor=turn_penalty_factor, safety_penalty_factor=safety_penalty_factor,
+                        min_safe_distance=min_safe_distance, diagonal_obstacle_penalty_value=diagonal_obstacle_penalty_value),
+                   engine, lambda: Engine(self.grid, device), PsoSwarm, verbose)          # (Engine: this module's name for it)
 
-    # ------------------------------------------------------------------
     def swarm(self, k):
-        return self._swarms[k]
+        return self._units[k]
 
-    def _check_open(self):
-        if self._closed or not getattr(self.engine, "h", None):
-            raise PathfitError("PSOBatch: the batch is closed")
-
-    def _check_begun(self):
-        self._check_open()
-        if self._d is None:
-            raise PathfitError("PSOBatch: begin() has not run")
-
-    def close(self):
-        d, self._d = self._d, None
-        self._closed = True
-        if d:
-            for b in d.values():
-                if hasattr(b, "free"):
-                    b.free()
-
-    # ------------------------------------------------------------------ initialisation
-    def _decode(self, wp_pos, s_cells, t_cells):
-        """_WaypointSolver._evaluate with per-agent endpoints: retry once with the full R * C capacity, then raise."""
-        e = self.engine
-        kw = dict(wp_pos=wp_pos, sp=self._sp, allow_diag=self.allow_diagonal_moves, restrict_corner=self.restrict_diagonal_near_obstacle_policy)
-        paths, st, stats = e.decode_multi_host(s_cells, t_cells, path_cap=self.path_cap, **kw)
-        self.init_launches += 1
-        if (st == 3).any():
-            paths, st, stats = e.decode_multi_host(s_cells, t_cells, path_cap=self.rows * self.cols, **kw)
-            self.init_launches += 1
-            if (st == 3).any():
-                raise RuntimeError("pathfit: open-list scratch overflow on %d agents" % int((st == 3).sum()))
-        return [CellPath(p, self.cols) for p in paths], stats, np.array([len(p) > 0 for p in paths])
-
+    # ------------------------------------------------------------------ initialisation (WaypointBatch.begin)
     def _solo_solver(self, k):
         return PSOSolver(mark(self.grid, self.starts[k], self.targets[k]), self.num_iterations, self.num_particles, self.num_waypoints,
                          self.w, self.c1, self.c2, allow_diagonal_moves=self.allow_diagonal_moves,
                          restrict_diagonal_near_obstacle_policy=self.restrict_diagonal_near_obstacle_policy, engine=self.engine,
                          seed=self.seeds[k], verbose=self.verbose, asynchronous=self.asynchronous, **self._weights)
 
-    def begin(self):
-        """PSOSolver._initialize_particles (pso.py:97-161) for every swarm, then the move into HBM."""
-        self._check_open()
-        if self._d is not None:
-            raise PathfitError("PSOBatch: begin() has already run")
-        K, N, W = self.K, self.num_particles, self.num_waypoints
-        sw = [([], [], [], []) for _ in range(K)]                      # (positions, velocities, paths, stats) per swarm
-        while True:
-            short = [k for k in range(K) if len(sw[k][0]) < N and self._swarms[k].attempts < 20 * N]
-            if not short:
-                break
-            # one round: the next attempts of every swarm that is still short, decoded in ONE launch
-            sizes = [ga_attempt_round(N, len(sw[k][0]), self._swarms[k].attempts) for k in short]
-            draws = [pso_attempt_draws(self.seeds[k], self._swarms[k].attempts, n, W, self.rows, self.cols, self.max_vel)
-                     for k, n in zip(short, sizes)]
-            P = np.concatenate([p for p, _ in draws])
-            cps, stats, feas = self._decode(P, np.repeat(self._s[short], sizes), np.repeat(self._t[short], sizes))
-            o = 0
-            for k, n, (Pk, Vk) in zip(short, sizes, draws):
-                pso_take_feasible(sw[k], N, Pk, Vk, cps[o:o + n], stats[o:o + n], feas[o:o + n])
-                self._swarms[k].attempts += n
-                o += n
-        self.live = [k for k in range(K) if sw[k][0]]
-        for k in range(K):
-            p = self._swarms[k]
-            if not sw[k][0]:                                           # degenerate: the solo class runs it whole
-                p._solo = self._solo_solver(k)
-                p._result = p._solo.solve()
-                p.convergence_curve = p._solo.convergence_curve
-                continue
-            pso_pad(sw[k], N, self.seeds[k])                           # :159-160
-            pos, _, cps, stats = sw[k]
-            g = int(np.argmin([s[4] for s in stats]))                  # first minimum == the sequential :121 scan
-            p._gbest = pso_gbest_record(pos[g], cps[g], stats[g])
-            p.convergence_curve.append(p._gbest["fitness"])
-        self._to_device(sw)
+    def _draw(self, p, n):
+        return pso_attempt_draws(p.seed, p.attempts, n, self.num_waypoints, self.rows, self.cols, self.max_vel)
 
-    def _to_device(self, sw):
-        """The live swarms into HBM, back to back in batch order: row j N + a = particle a of live swarm j."""
+    def _take(self, p, draw, cps, stats, feas):
+        pso_take_feasible(p._init, self.num_particles, draw[0], draw[1], cps, stats, feas)
+
+    def _to_device(self):
+        """pso.py:159-160 and the :121 gbest scan for the live swarms, and their move into HBM, back to back in batch order:
+        row j N + a = particle a of live swarm j."""
         e, N, W, cap, live = self.engine, self.num_particles, self.num_waypoints, self.path_cap, self.live
         Kb = len(live)
         d = {}
@@ -200,19 +119,21 @@ class PSOBatch:
         if not Kb:
             return
         KN = Kb * N
-        pos = np.array([x for k in live for x in sw[k][0]], np.float64).reshape(KN, W, 2)
-        vel = np.array([x for k in live for x in sw[k][1]], np.float64).reshape(KN, W, 2)
-        stats = np.array([x for k in live for x in sw[k][3]], np.float64).reshape(KN, 5)
-        cells, lens = np.zeros((KN, cap), np.int32), np.zeros(KN, np.int32)
-        for i, cp in enumerate(x for k in live for x in sw[k][2]):
-            cc = cells_of(cp, self.cols)
-            if len(cc) > cap:
-                raise RuntimeError("pathfit: path capacity overflow in PSO initialisation")
-            cells[i, :len(cc)] = cc; lens[i] = len(cc)
+        sw = ([], [], [], [])                                          # (positions, velocities, paths, stats) of all of them
+        for p in (self._units[k] for k in live):
+            pso_pad(p._init, N, p.seed)                                # :159-160
+            for all_, own in zip(sw, p._init):
+                all_ += own
+            p._init = None
+        pos, vel = np.array(sw[0], np.float64).reshape(KN, W, 2), np.array(sw[1], np.float64).reshape(KN, W, 2)
+        stats = np.array(sw[3], np.float64).reshape(KN, 5)
+        cells, lens = pack_path_rows(sw[2], self.cols, cap, "PSO")
         gb, gstats, gpath = np.zeros((Kb, W, 2)), np.zeros((Kb, 5)), np.zeros((Kb, cap + 1), np.int32)
-        for j in range(Kb):
-            g = j * N + int(np.argmin(stats[j * N:(j + 1) * N, 4]))
+        for j, p in enumerate(self._units[k] for k in live):
+            g = j * N + int(np.argmin(stats[j * N:(j + 1) * N, 4]))    # first minimum == the sequential :121 scan
             gb[j], gstats[j], gpath[j, 0], gpath[j, 1:] = pos[g], stats[g], lens[g], cells[g]
+            p._gbest = pso_gbest_record(pos[g], sw[2][g], stats[g])
+            p.convergence_curve.append(p._gbest["fitness"])
         d["seeds"] = e.put(np.array([self.seeds[k] for k in live], np.uint64))
         d["start"], d["target"] = e.put(self._s[live]), e.put(self._t[live])                                  # per SWARM
         d["pos"], d["vel"], d["pb"], d["pbf"] = e.put(pos), e.put(vel), e.put(pos), e.put(stats[:, 4].copy())   # pso.py:111-117
@@ -288,11 +209,11 @@ class PSOBatch:
                 idx = int(rec["idx"][j])
                 if idx >= 0:                                           # pso.py:222-229: the swarm's gbest moves to particle cur + idx
                     self._gfit[j] = float(rec["fit"][j])
-                    self._swarms[live[j]]._gdev = {"idx": int(cur[j]) + idx, "fitness": self._gfit[j], "host": False}
+                    self._units[live[j]]._gdev = {"idx": int(cur[j]) + idx, "fitness": self._gfit[j], "host": False}
                 cur[j] = cur[j] + idx + 1 if (idx >= 0 and self.asynchronous) else N
         it = self._it = self._it + 1
         out = []
-        for k, p in enumerate(self._swarms):
+        for k, p in enumerate(self._units):
             if p._solo is not None:                                    # ran whole in begin(): its curve is reported
                 c = p.convergence_curve
                 out.append(c[min(it, len(c) - 1)] if c else INF)
@@ -310,10 +231,4 @@ class PSOBatch:
         self.begin()
         for _ in range(self.num_iterations):
             self.sweep()
-        return [p.result() for p in self._swarms]
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
+        return [p.result() for p in self._units]

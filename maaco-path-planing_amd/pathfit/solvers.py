@@ -50,6 +50,33 @@ def ga_breed_native(seed, gen, crossover_rate, mutation_rate, occ, parent_cells)
 INF = float("inf")
 
 
+# ---- what the waypoint solvers and their batches (pathfit/_batch.py) both need -----------------------------------------
+def path_capacity(rows, cols):
+    """The cells a path row of GA / PSO holds; decode_retry falls back to the full R * C."""
+    return min(rows * cols, 16 * (rows + cols) + 64)
+
+
+def decode_retry(engine, start, target, rows, cols, **kw):
+    """Engine.decode_host (start / target: one cell each, or one per agent) with path_capacity, and once more with the full
+    R * C capacity if a path outgrows it -> (list[CellPath], stats ndarray[n,5], feasible mask, launches made)."""
+    for launches, cap in enumerate((path_capacity(rows, cols), rows * cols), 1):
+        paths, st, stats = engine.decode_host(start, target, path_cap=cap, **kw)
+        if not (st == 3).any():
+            return [CellPath(p, cols) for p in paths], stats, np.array([len(p) > 0 for p in paths]), launches
+    raise RuntimeError("pathfit: open-list scratch overflow on %d agents" % int((st == 3).sum()))
+
+
+def pack_path_rows(paths, cols, cap, what, rows=0):
+    """Paths as device rows -> (cells int32 [max(len(paths), rows)][cap], lengths int32); `what` names the solver in the error."""
+    cells, lens = np.zeros((max(len(paths), rows), cap), np.int32), np.zeros(max(len(paths), rows), np.int32)
+    for i, p in enumerate(paths):
+        cc = cells_of(p, cols)
+        if len(cc) > cap:
+            raise RuntimeError(f"pathfit: path capacity overflow in {what} initialisation")
+        cells[i, :len(cc)] = cc; lens[i] = len(cc)
+    return cells, lens
+
+
 # ---- what GASolver and GABatch (pathfit/ga_batch.py) both need ----------------------------------------------------------
 def ga_attempt_round(N, have, k):
     """Initialisation (ga_solver.py:95-133) runs in rounds: how many attempts the next round makes for a population that has
@@ -62,6 +89,12 @@ def ga_individuals(chroms, cps, stats):
     """The reference's individual dicts (ga_solver.py:110-113) from chromosomes, paths and stats rows."""
     return [{"chromosome": c, "path": p, "fitness": float(s[4]), "length": float(s[0]), "turns": int(s[1]),
              "safety_penalty": float(s[2]), "diag_penalty": float(s[3])} for c, p, s in zip(chroms, cps, stats)]
+
+
+def ga_direct_individual(st):
+    """An individual without waypoints from a (path, length, turns, safety, diag, fitness) tuple (ga_solver.py:116-127, :164-166)."""
+    return {"chromosome": [], "path": st[0], "fitness": st[5], "length": st[1], "turns": st[2], "safety_penalty": st[3],
+            "diag_penalty": st[4]}
 
 
 def ga_take_feasible(pop, N, wp, cps, stats, feas, cols):
@@ -183,100 +216,62 @@ class BasePathfinder:
         return path, float(st[0]), int(st[1]), float(st[2]), float(st[3]), float(st[4])
 
 
-class AStarSolver(BasePathfinder):
+class _ConnectorSolver(BasePathfinder):
+    """AStarSolver / DijkstraSolver: one query of Engine.astar_host in the class's variant."""
+    _variant, _label, _strict = None, None, None      # astar_host's variant, find_marker's label, the corner-policy attribute
+
     def __init__(self, grid, turn_penalty_factor=0.1, safety_penalty_factor=0.05, min_safe_distance=1.5,
                  allow_diagonal_moves=True, restrict_diagonal_near_obstacle_policy=True,
                  diagonal_obstacle_penalty_value=1000.0, engine=None, device=0, seed=0):
         g = np.asarray(grid)
-        start_node = find_marker(g, START_NODE_VAL, "AStar")
-        target_node = find_marker(g, TARGET_NODE_VAL, "AStar")
+        start_node = find_marker(g, START_NODE_VAL, self._label)
+        target_node = find_marker(g, TARGET_NODE_VAL, self._label)
         super().__init__(grid, start_node, target_node, turn_penalty_factor, safety_penalty_factor, min_safe_distance,
                          allow_diagonal_moves, restrict_diagonal_near_obstacle_policy, diagonal_obstacle_penalty_value,
                          engine, device, seed)
-        self.astar_strictly_restricts_corners = self.restrict_diagonal_near_obstacle_policy
+        setattr(self, self._strict, self.restrict_diagonal_near_obstacle_policy)
 
     def solve(self, start_node_override=None, target_node_override=None, nodes_to_avoid=None):
-        """astar.py:33-101 for one query (batched form: Engine.astar_host)."""
+        """astar.py:33-101 / dijkstra.py:32-97 for one query (Dijkstra: A*'s loop with heap entries (g, node))."""
         s = start_node_override if start_node_override else self.start_node
         t = target_node_override if target_node_override else self.target_node
         inb = lambda n: 0 <= n[0] < self.rows and 0 <= n[1] < self.cols
         if not inb(s) or not inb(t):
             return self._calculate_stats_for_path([])
         avoid = [np.array([self._cell(a) for a in nodes_to_avoid if inb(a)], np.int32)] if nodes_to_avoid else None
-        paths, st = self.engine.astar_host(0, [self._cell(s)], [self._cell(t)], avoid,
-                                           path_cap=self.rows * self.cols if self.rows * self.cols <= 1 << 16 else None,
-                                           allow_diag=self.allow_diagonal_moves,
-                                           restrict_corner=self.astar_strictly_restricts_corners)
-        if st[0] == 3:
-            paths, st = self.engine.astar_host(0, [self._cell(s)], [self._cell(t)], avoid, path_cap=self.rows * self.cols,
-                                               allow_diag=self.allow_diagonal_moves,
-                                               restrict_corner=self.astar_strictly_restricts_corners)
+        full = self.rows * self.cols
+        for cap in (full if full <= 1 << 16 else None, full):          # the engine's default capacity on a large map, then R * C
+            paths, st = self.engine.astar_host(self._variant, [self._cell(s)], [self._cell(t)], avoid, path_cap=cap,
+                                               allow_diag=self.allow_diagonal_moves, restrict_corner=getattr(self, self._strict))
+            if st[0] != 3:
+                break
         path = CellPath(paths[0], self.cols).tolist()
         res = self._calculate_stats_for_path(path)
         if len(path) > 1:
-            self.convergence_curve.append(res[1])      # astar.py:70: g of the goal == path length
+            self.convergence_curve.append(res[1])      # astar.py:70, dijkstra.py:67: g of the goal == path length
         return res
 
 
-class DijkstraSolver(BasePathfinder):
-    def __init__(self, grid, turn_penalty_factor=0.1, safety_penalty_factor=0.05, min_safe_distance=1.5,
-                 allow_diagonal_moves=True, restrict_diagonal_near_obstacle_policy=True,
-                 diagonal_obstacle_penalty_value=1000.0, engine=None, device=0, seed=0):
-        g = np.asarray(grid)
-        start_node = find_marker(g, START_NODE_VAL, "Dijkstra")
-        target_node = find_marker(g, TARGET_NODE_VAL, "Dijkstra")
-        super().__init__(grid, start_node, target_node, turn_penalty_factor, safety_penalty_factor, min_safe_distance,
-                         allow_diagonal_moves, restrict_diagonal_near_obstacle_policy, diagonal_obstacle_penalty_value,
-                         engine, device, seed)
-        self.dijkstra_strictly_restricts_corners = self.restrict_diagonal_near_obstacle_policy
+class AStarSolver(_ConnectorSolver):
+    _variant, _label, _strict = 0, "AStar", "astar_strictly_restricts_corners"
 
-    def solve(self, start_node_override=None, target_node_override=None, nodes_to_avoid=None):
-        """dijkstra.py:32-97 for one query: AStarSolver's loop with heap entries (g, node) (batched form: Engine.astar_host, variant 2)."""
-        s = start_node_override if start_node_override else self.start_node
-        t = target_node_override if target_node_override else self.target_node
-        inb = lambda n: 0 <= n[0] < self.rows and 0 <= n[1] < self.cols
-        if not inb(s) or not inb(t):
-            return self._calculate_stats_for_path([])
-        avoid = [np.array([self._cell(a) for a in nodes_to_avoid if inb(a)], np.int32)] if nodes_to_avoid else None
-        paths, st = self.engine.astar_host(2, [self._cell(s)], [self._cell(t)], avoid,
-                                           path_cap=self.rows * self.cols if self.rows * self.cols <= 1 << 16 else None,
-                                           allow_diag=self.allow_diagonal_moves,
-                                           restrict_corner=self.dijkstra_strictly_restricts_corners)
-        if st[0] == 3:
-            paths, st = self.engine.astar_host(2, [self._cell(s)], [self._cell(t)], avoid, path_cap=self.rows * self.cols,
-                                               allow_diag=self.allow_diagonal_moves,
-                                               restrict_corner=self.dijkstra_strictly_restricts_corners)
-        path = CellPath(paths[0], self.cols).tolist()
-        res = self._calculate_stats_for_path(path)
-        if len(path) > 1:
-            self.convergence_curve.append(res[1])      # dijkstra.py:67: g of the goal == path length
-        return res
+
+class DijkstraSolver(_ConnectorSolver):
+    _variant, _label, _strict = 2, "Dijkstra", "dijkstra_strictly_restricts_corners"
 
 
 class _WaypointSolver(BasePathfinder):
     """Shared decode + score batch for GA / PSO."""
 
     def _path_cap(self):
-        return min(self.rows * self.cols, 16 * (self.rows + self.cols) + 64)
+        return path_capacity(self.rows, self.cols)
 
     def _evaluate(self, wp_cells=None, wp_pos=None):
         """-> (list[CellPath], stats ndarray[n,5], feasible mask).  Retries with the full R*C capacity if a
         path outgrows the default buffer."""
-        cap = self._path_cap()
-        paths, st, stats = self.engine.decode_host(self._cell(self.start_node), self._cell(self.target_node),
-                                                   wp_cells=wp_cells, wp_pos=wp_pos, sp=self._sp, path_cap=cap,
-                                                   allow_diag=self.allow_diagonal_moves,
-                                                   restrict_corner=self.restrict_diagonal_near_obstacle_policy)
-        if (st == 3).any():
-            cap = self.rows * self.cols
-            paths, st, stats = self.engine.decode_host(self._cell(self.start_node), self._cell(self.target_node),
-                                                       wp_cells=wp_cells, wp_pos=wp_pos, sp=self._sp, path_cap=cap,
-                                                       allow_diag=self.allow_diagonal_moves,
-                                                       restrict_corner=self.restrict_diagonal_near_obstacle_policy)
-            if (st == 3).any():
-                raise RuntimeError("pathfit: open-list scratch overflow on %d agents" % int((st == 3).sum()))
-        cps = [CellPath(p, self.cols) for p in paths]
-        return cps, stats, np.array([len(p) > 0 for p in paths])
+        return decode_retry(self.engine, self._cell(self.start_node), self._cell(self.target_node), self.rows, self.cols,
+                            wp_cells=wp_cells, wp_pos=wp_pos, sp=self._sp, allow_diag=self.allow_diagonal_moves,
+                            restrict_corner=self.restrict_diagonal_near_obstacle_policy)[:3]
 
 
 class GASolver(_WaypointSolver):
@@ -377,12 +372,7 @@ class GASolver(_WaypointSolver):
         d["cells"] = [e.buf((m, cap), np.int32), e.buf((m, cap), np.int32)]
         d["len"] = [e.buf(m, np.int32), e.buf(m, np.int32)]
         d["chrom_loc"], d["stats_loc"] = e.buf((m, W), np.int32), e.buf((m, 5), np.float64)
-        cur_cells = np.zeros((m, cap), np.int32); cur_len = np.zeros(m, np.int32)
-        for i in range(n):
-            cc = cells_of(pop[lo + i]["path"], self.cols)
-            if len(cc) > cap:
-                raise RuntimeError("pathfit: path capacity overflow in GA initialisation")
-            cur_cells[i, :len(cc)] = cc; cur_len[i] = len(cc)
+        cur_cells, cur_len = pack_path_rows([x["path"] for x in pop[lo:hi]], self.cols, cap, "GA", rows=m)
         d["cells"][0].upload(cur_cells); d["len"][0].upload(cur_len)
         self._gd = d
         s_cell, t_cell = self._cell(self.start_node), self._cell(self.target_node)
@@ -475,12 +465,9 @@ class GASolver(_WaypointSolver):
         if not self.population and self.num_waypoints > 0:
             path_direct = self._reconstruct_path_from_chromosome([])
             if path_direct and path_direct[0] == self.start_node and path_direct[-1] == self.target_node:
-                _, l, t, sp, dp, f = self._calculate_stats_for_path(path_direct)
-                self.population.append({"chromosome": [], "path": path_direct, "fitness": f, "length": l, "turns": t,
-                                        "safety_penalty": sp, "diag_penalty": dp})
+                self.population.append(ga_direct_individual(self._calculate_stats_for_path(path_direct)))
         if not self.population:
-            self.population = [{"chromosome": [], "path": [], "fitness": INF, "length": INF, "turns": 0,
-                                "safety_penalty": 0, "diag_penalty": 0}] * self.population_size
+            self.population = [ga_direct_individual(([], INF, 0, 0, 0, INF))] * self.population_size
             return False
         ga_pad_and_sort(self.population, self.population_size, self.seed)
         return True
@@ -514,8 +501,7 @@ class GASolver(_WaypointSolver):
         if self.num_waypoints == 0:
             path = self._reconstruct_path_from_chromosome([])
             stats = self._calculate_stats_for_path(path)
-            self.best_solution_overall = {"path": stats[0], "fitness": stats[5], "length": stats[1], "turns": stats[2],
-                                          "safety_penalty": stats[3], "diag_penalty": stats[4]}
+            self.best_solution_overall = ga_direct_individual(stats)
             self.convergence_curve.append(stats[5])
             return stats
         if not self._initialize_population():
@@ -566,10 +552,8 @@ class GASolver(_WaypointSolver):
                 if kids[i] == [] :
                     path = self._reconstruct_path_from_chromosome([])
                     ok = bool(path) and path[0] == self.start_node and path[-1] == self.target_node
-                    st = self._calculate_stats_for_path(path) if ok else None
                     if ok:
-                        new_pop.append({"chromosome": [], "path": path, "fitness": st[5], "length": st[1], "turns": st[2],
-                                        "safety_penalty": st[3], "diag_penalty": st[4]})
+                        new_pop.append(ga_direct_individual(self._calculate_stats_for_path(path)))
                         continue
                 elif feas[i]:
                     new_pop.append(self._individuals([kids[i]], [cps[i]], [stats[i]])[0])
@@ -762,12 +746,7 @@ class PSOSolver(_WaypointSolver):
         if n:
             d["pos"].upload(self._pos); d["vel"].upload(self._vel); d["pb"].upload(self._pbest); d["pbf"].upload(self._pbest_fit)
             # current / pbest paths start as the initial paths (pso.py:111-117)
-            cur = np.zeros((n, cap), np.int32); ln = np.zeros(n, np.int32)
-            for i, cp in enumerate(self._cur_path):
-                cc = cells_of(cp, self.cols)
-                if len(cc) > cap:
-                    raise RuntimeError("pathfit: path capacity overflow in PSO initialisation")
-                cur[i, :len(cc)] = cc; ln[i] = len(cc)
+            cur, ln = pack_path_rows(self._cur_path, self.cols, cap, "PSO")
             d["cells"].upload(cur); d["len"].upload(ln)
             d["stats"].upload(np.array(self._cur_stats, np.float64).reshape(n, 5))
             d["pb_cells"].upload(cur); d["pb_len"].upload(ln)
