@@ -396,7 +396,13 @@ int pf_mpa_batch_counters(pf_mpa_batch* b, pf_counters* out, int64_t* overflow_t
  * lowers the connectors' step cap below the reference's 3RC / 2RC (astar.py:58, MPA.py:118) so that the cap path
  * (PF_ST_STEP_CAP) can be exercised; 0 restores the reference's value.  "mpa_doubt_log_e15" / "mpa_doubt_round_e15":
  * margins (in 1e-15; < 0 = default) inside which an MPA proposal is handed to the host's libm (tests widen them to
- * force that route). */
+ * force that route).  Test hooks "astar_slot_tag" (24 bit) / "astar_slot_avoid_epoch" (14 bit): before the next search launch
+ * (A* batch, decode, MPA sweep) every search slot's solve tag / avoid epoch is moved FORWARD to the value, so that the wipes
+ * that precede a wrap (avoid epoch 0x3FF0, tag 0xFFFFFF - 2 * 0x8000) can be reached in a test; one-shot (later launches carry
+ * on from there), < 0 withdraws a value not yet applied, and that launch fails with a message if the value lies below a
+ * slot's current one (stale stamps would look current).  Like every option the pending value is process-wide, not per handle:
+ * it goes to the slots of whichever handle launches a search next, so a test sets it right in front of the launch it is meant
+ * for.  pf_selftest_slot_state reads the counters back. */
 int pf_set_option(pf_handle* h, const char* name, int64_t value);
 
 /* ---- device self-tests (used by tests/ to pin device arithmetic) ----- */
@@ -568,6 +574,11 @@ int pf_d2h_counts(pf_handle* h, int64_t* small_copies, int64_t* bulk_copies, int
 int pf_span_begin(pf_handle* h);
 int pf_span_end(pf_handle* h);
 int pf_span_total(pf_handle* h, double* ms_out, int64_t* count_out, int32_t reset);
+
+/* The epoch counters of search slot `slot` (0 <= slot < the handle's slot count; workgroup b of a search launch owns slot b, so
+ * a batch of one search runs on slot 0): out3 = {24-bit solve tag, 14-bit avoid epoch, label epoch of the parallel settling
+ * engine (-1: the engine has no scratch on this handle)}.  The slots exist from the first search launch on. */
+int pf_selftest_slot_state(pf_handle* h, int32_t slot, int64_t* out3);
 
 /* Target-cell proposals of MPA._get_levy_target_node / _get_brownian_target_node (MPA.py:250-282) for n keyed streams
  * (seed, DOM_MPA, 0, i) from cells d_cur[i] (and elite cells d_elite[i], < 0 = None): the device arithmetic, with the

@@ -2113,6 +2113,9 @@ static int g_maaco_ahead = env_int("PF_MAACO_TOUCH", -1);   // load-ahead form o
 static int g_maaco_groups = env_int("PF_MAACO_GROUPS", 8);   // ants per wavefront of k_maaco_walk8 (pf_set_option "maaco_ants_per_wave": 1..8)
 static int g_maaco_mark = env_int("PF_MAACO_MARK", 1);   // successful ants mark their deposits in the walk kernel (pf_set_option "maaco_mark_in_walk")
 static int g_tabu_epoch = -1;                      // test hook ("maaco_tabu_epoch"): >= 0 -> the next walk batch starts its tabu slots from this epoch (wrap coverage)
+static long long g_slot_tag = -1, g_slot_avoid_epoch = -1;   // test hooks ("astar_slot_tag" / "astar_slot_avoid_epoch"): >= 0 -> before the next search launch every
+                                                              // search slot's 24-bit tag / 14-bit avoid epoch moves FORWARD to this value (wrap coverage; one-shot)
+                                                              // process-wide like the other hooks: the value goes to the slots of WHICHEVER handle launches a search next
 static const int kLdsS = 16;
 static int ensure_slots(pf_handle* h, int allow_diag = 1, int restrict_corner = 1) {
   CK(hipSetDevice(h->device));
@@ -2146,6 +2149,23 @@ static int ensure_slots(pf_handle* h, int allow_diag = 1, int restrict_corner = 
     CK(hipMemcpyAsync(h->d_slot_state, init.data(), sizeof(uint32_t) * init.size(), hipMemcpyHostToDevice, h->stream));
     CK(hipStreamSynchronize(h->stream));
     h->rec_policy = policy;
+  }
+  if (g_slot_tag >= 0 || g_slot_avoid_epoch >= 0) {
+    // Forward only: every stamp a record carries is then older than the slot's counters, as after any number of real
+    // evaluations.  A value below a slot's current one would make stale stamps look current, so it is refused.
+    const long long tag = g_slot_tag, av = g_slot_avoid_epoch;
+    g_slot_tag = -1; g_slot_avoid_epoch = -1;                     // one-shot: later launches carry on from there
+    std::vector<uint32_t> st(2 * (size_t)h->nslots);
+    CK(hipMemcpyAsync(st.data(), h->d_slot_state, sizeof(uint32_t) * st.size(), hipMemcpyDeviceToHost, h->stream));
+    CK(hipStreamSynchronize(h->stream));
+    for (int i = 0; i < h->nslots; ++i) {
+      if ((tag >= 0 && tag < (long long)st[2 * i]) || (av >= 0 && av < (long long)st[2 * i + 1]))
+        return failmsg(h, "pf_set_option: astar_slot_tag / astar_slot_avoid_epoch may only move a slot's counters forward");
+      if (tag >= 0) st[2 * i] = (uint32_t)tag;
+      if (av >= 0) st[2 * i + 1] = (uint32_t)av;
+    }
+    CK(hipMemcpyAsync(h->d_slot_state, st.data(), sizeof(uint32_t) * st.size(), hipMemcpyHostToDevice, h->stream));
+    CK(hipStreamSynchronize(h->stream));
   }
   return 0;
 }
@@ -2568,6 +2588,14 @@ int pf_set_option(pf_handle* h, const char* name, int64_t value) {
   if (!strcmp(name, "astar_settle_top")) { g_settle_top = value < 0 ? 0 : (value > 1000 ? 1000 : (int)value); return 0; }
   if (!strcmp(name, "plateau_kernels")) { g_plateau_mode = (int)value; return 0; }
   if (!strcmp(name, "maaco_tabu_epoch")) { g_tabu_epoch = (int)value; return 0; }
+  if (!strcmp(name, "astar_slot_tag")) {
+    if (value > 0xFFFFFF) return failmsg(h, "pf_set_option: astar_slot_tag is a 24-bit value");
+    g_slot_tag = value < 0 ? -1 : (long long)value; return 0;
+  }
+  if (!strcmp(name, "astar_slot_avoid_epoch")) {
+    if (value > 0x3FFF) return failmsg(h, "pf_set_option: astar_slot_avoid_epoch is a 14-bit value");
+    g_slot_avoid_epoch = value < 0 ? -1 : (long long)value; return 0;
+  }
   if (!strcmp(name, "mpa_doubt_log_e15")) { g_doubt_log = value < 0 ? 1.0 / 8589934592.0 : (double)value * 1e-15; return 0; }
   if (!strcmp(name, "mpa_doubt_round_e15")) { g_doubt_round = value < 0 ? 1e-7 : (double)value * 1e-15; return 0; }
   return failmsg(h, std::string("pf_set_option: unknown option ") + name);
@@ -2578,6 +2606,18 @@ int pf_selftest_sqrt(pf_handle* h, int32_t n, const int64_t* d_in, double* d_out
   CK(hipSetDevice(h->device));
   hipLaunchKernelGGL(k_selftest_sqrt, dim3((n + 255) / 256), dim3(256), 0, h->stream, n, (const long long*)d_in, d_out);
   CK(hipGetLastError()); CK(hipStreamSynchronize(h->stream));
+  return 0;
+}
+int pf_selftest_slot_state(pf_handle* h, int32_t slot, int64_t* out3) {
+  if (!h || !out3) return failmsg(h, "pf_selftest_slot_state: bad arguments");
+  if (!h->d_slot_state) return failmsg(h, "pf_selftest_slot_state: the search slots do not exist before the first search launch");
+  if (slot < 0 || slot >= h->nslots) return failmsg(h, "pf_selftest_slot_state: no such slot");
+  CK(hipSetDevice(h->device));
+  uint32_t st[2] = {0, 0}; unsigned ep = 0;
+  CK(hipMemcpyAsync(st, h->d_slot_state + 2 * (size_t)slot, sizeof(st), hipMemcpyDeviceToHost, h->stream));
+  if (h->d_st_epoch) CK(hipMemcpyAsync(&ep, h->d_st_epoch + slot, sizeof(ep), hipMemcpyDeviceToHost, h->stream));
+  CK(hipStreamSynchronize(h->stream));
+  out3[0] = st[0]; out3[1] = st[1]; out3[2] = h->d_st_epoch ? (int64_t)ep : -1;
   return 0;
 }
 int pf_selftest_rng(pf_handle* h, uint64_t seed, uint64_t dom, uint64_t it, uint64_t agent, uint64_t* d_u64,

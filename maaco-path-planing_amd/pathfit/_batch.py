@@ -120,7 +120,7 @@ class WaypointBatch:
         self._s, self._t = cell_ids(self.engine, who, self.grid, self.starts, self.targets)
         self._sp = score_params(0, restrict_diagonal_near_obstacle_policy, weights["turn_penalty_factor"], weights["safety_penalty_factor"],
                                 weights["min_safe_distance"], weights["diagonal_obstacle_penalty_value"])
-        self.path_cap = path_capacity(self.rows, self.cols)
+        self.path_cap = path_capacity(self.rows, self.cols, self.num_waypoints)
         self._units = [unit_cls(self, k) for k in range(self.K)]
         self.live = []                      # the units that run batched, in batch order (begin() fills it)
         self._d = None                      # the device state (begin())

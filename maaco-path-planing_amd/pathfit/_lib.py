@@ -96,6 +96,7 @@ SYMBOLS = {
     "pf_set_option": (C.c_int, [_vp, C.c_char_p, _i64]),
     "pf_selftest_sqrt": (C.c_int, [_vp, _i32, _vp, _vp]),
     "pf_selftest_rng": (C.c_int, [_vp, _u64, _u64, _u64, _u64, _vp, _vp, _vp]),
+    "pf_selftest_slot_state": (C.c_int, [_vp, _i32, _vp]),
     "pf_ga_select_dev": (C.c_int, [_vp, _u64, _i32, _i32, _i32, _vp, _vp, _vp]),
     "pf_ga_breed_dev": (C.c_int, [_vp, _u64, _i32, _i32, _i32, _dbl, _dbl, _vp, _vp, _i32, _i32, _vp]),
     "pf_ga_assemble_dev": (C.c_int, [_vp, _i32, _i32, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i32, _i32, _vp, _vp, _vp, _vp]),

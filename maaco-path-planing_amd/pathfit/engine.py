@@ -158,6 +158,12 @@ class Engine:
     def set_option(self, name, value):
         self._ck(self.L.pf_set_option(self.h, name.encode(), int(value)))
 
+    def slot_state(self, slot=0):
+        """(solve tag, avoid epoch, settle label epoch) of one search slot (pf_selftest_slot_state; tests of the epoch wraps)."""
+        out = (C.c_int64 * 3)()
+        self._ck(self.L.pf_selftest_slot_state(self.h, int(slot), out))
+        return int(out[0]), int(out[1]), int(out[2])
+
     def counters(self):
         c = Counters()
         self._ck(self.L.pf_get_counters(self.h, C.byref(c)))
@@ -166,8 +172,10 @@ class Engine:
     def last_kernel_ms(self):
         return float(self.L.pf_last_kernel_ms(self.h))
 
-    def default_path_cap(self):
-        return min(self.R * self.C, 8 * (self.R + self.C) + 64)
+    def default_path_cap(self, W=None):
+        """Cells per path row when the caller names none: a search's path visits a cell once (at most R * C cells); a decode of W
+        waypoints may end each of its W + 1 segments on a visited cell (astar.py:55-56), so it holds up to R * C + W + 1."""
+        return min(self.R * self.C + (0 if W is None else int(W) + 1), 8 * (self.R + self.C) + 64)
 
     # ------------------------------------------------------------------ K2
     def astar_batch(self, variant, d_start, d_target, n, path_cap, d_cells, d_len, d_status, d_avoid_off=None,
@@ -235,7 +243,7 @@ class Engine:
             wp = np.ascontiguousarray(wp_pos, np.float64)
             n, W = wp.shape[0], wp.shape[1]
             dwc, dwp = None, self.put(wp.reshape(-1) if wp.size else np.zeros(1))
-        cap = int(path_cap or self.default_path_cap())
+        cap = int(path_cap or self.default_path_cap(W))
         m = max(n, 1)
         dc, dl, dst = self.buf((m, cap), np.int32), self.buf(m, np.int32), self.buf(m, np.int32)
         dstat = self.buf((m, 5), np.float64) if sp is not None else None

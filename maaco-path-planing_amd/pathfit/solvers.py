@@ -51,15 +51,24 @@ INF = float("inf")
 
 
 # ---- what the waypoint solvers and their batches (pathfit/_batch.py) both need -----------------------------------------
-def path_capacity(rows, cols):
-    """The cells a path row of GA / PSO holds; decode_retry falls back to the full R * C."""
-    return min(rows * cols, 16 * (rows + cols) + 64)
+def decode_bound(rows, cols, W):
+    """The longest path a chain of W waypoints can decode to.  A segment never enters a cell the chain has visited, EXCEPT its own
+    goal (astar.py:55-56 exempts start and target from the avoid set): each of the W + 1 segments may end on a visited cell, so
+    the path holds at most R * C fresh cells, one revisited goal per segment, and the start -- not R * C."""
+    return rows * cols + int(W) + 1
+
+
+def path_capacity(rows, cols, W):
+    """The cells a path row of GA / PSO with W waypoints holds; decode_retry falls back to the full decode_bound."""
+    return min(decode_bound(rows, cols, W), 16 * (rows + cols) + 64)
 
 
 def decode_retry(engine, start, target, rows, cols, **kw):
     """Engine.decode_host (start / target: one cell each, or one per agent) with path_capacity, and once more with the full
-    R * C capacity if a path outgrows it -> (list[CellPath], stats ndarray[n,5], feasible mask, launches made)."""
-    for launches, cap in enumerate((path_capacity(rows, cols), rows * cols), 1):
+    decode_bound capacity if a path outgrows it -> (list[CellPath], stats ndarray[n,5], feasible mask, launches made)."""
+    wp = kw["wp_cells"] if kw.get("wp_cells") is not None else kw["wp_pos"]
+    W = np.shape(wp)[1]
+    for launches, cap in enumerate((path_capacity(rows, cols, W), decode_bound(rows, cols, W)), 1):
         paths, st, stats = engine.decode_host(start, target, path_cap=cap, **kw)
         if not (st == 3).any():
             return [CellPath(p, cols) for p in paths], stats, np.array([len(p) > 0 for p in paths]), launches
@@ -264,10 +273,10 @@ class _WaypointSolver(BasePathfinder):
     """Shared decode + score batch for GA / PSO."""
 
     def _path_cap(self):
-        return path_capacity(self.rows, self.cols)
+        return path_capacity(self.rows, self.cols, self.num_waypoints)
 
     def _evaluate(self, wp_cells=None, wp_pos=None):
-        """-> (list[CellPath], stats ndarray[n,5], feasible mask).  Retries with the full R*C capacity if a
+        """-> (list[CellPath], stats ndarray[n,5], feasible mask).  Retries with the full decode_bound capacity if a
         path outgrows the default buffer."""
         return decode_retry(self.engine, self._cell(self.start_node), self._cell(self.target_node), self.rows, self.cols,
                             wp_cells=wp_cells, wp_pos=wp_pos, sp=self._sp, allow_diag=self.allow_diagonal_moves,

@@ -778,6 +778,236 @@ def cap_policies(G):
     np.savez_compressed(os.path.join(OUT, "policy_cases.npz"), **d, **{"meta_" + k: v for k, v in META.items()})
 
 
+WIDE_W = dict(turn_penalty_factor=0.3, safety_penalty_factor=0.8, min_safe_distance=20.0,
+              diagonal_obstacle_penalty_value=100.0)            # a safety window wider than the short side of a thin map
+
+
+def csr_delta(list_of_arrays):
+    """csr of int32 paths, each stored as its first cell followed by first differences (a path's steps repeat: a 4096-cell
+    corridor run compresses to a few bytes).  tests/golden_io.csr_get_delta undoes it."""
+    return csr([np.concatenate([a[:1], np.diff(a)]) if len(a) else a for a in (np.asarray(x, np.int64) for x in list_of_arrays)])
+
+
+def cap_thin():
+    """Grids with a side of 1, 2 or 3 cells (tests/thin_maps.py: empty, and with 13 % obstacles) -> thin_cases.npz: the three
+    connectors with avoid sets, GA / PSO decodes + stats (with the two decodes that are LONGER than the grid, astar.py:55-56),
+    MAACO iterations with the pheromone after every update, MPA segment rebuilds."""
+    sys.path.insert(0, os.path.join(ROOT, "tests"))
+    import thin_maps as tm
+    d = {}
+    rnd = random.Random(3131)
+    names = [tm.name_of(*m) for m in tm.all_maps()]
+    d["grid_names"] = np.array(names)
+    maps = {}
+    for (R, C, ob), name in zip(tm.all_maps(), names):
+        g0, s, t = tm.thin_map(R, C, ob)
+        g = rh.mark_grid((g0 == 1).astype(int), (s // C, s % C), (t // C, t % C))
+        assert np.array_equal(g, g0)                           # the numpy recipe IS the reference's marked grid
+        maps[name] = (g, s, t)
+        d[name + "_bits"] = np.packbits((g == 1).astype(np.uint8))
+        d[name + "_dims"] = np.array([R, C, s, t], np.int32)
+
+    # ---- connectors: AStarSolver.solve, MPA._a_star, DijkstraSolver.solve
+    rows = []
+    for name in names:
+        g, S, T = maps[name]
+        R, C = g.shape
+        L, along_cols = max(R, C), C >= R
+        solvers = (rh.RefAStar(g, **MAIN_W), rh.make_mpa(g), rh.RefDijkstra(g, **MAIN_W))
+        free = [tuple(int(v) for v in x) for x in np.argwhere(g != 1)]
+        obst = [tuple(int(v) for v in x) for x in np.argwhere(g == 1)]
+        axis = 1 if along_cols else 0
+        n = 22 if L < 300 else 12
+        got = []
+        for k in range(n):
+            s, e = rnd.choice(free), rnd.choice(free)
+            if L >= 300 and k % 2:                              # a nearby pair
+                near = [f for f in free if abs(f[axis] - s[axis]) <= 14]
+                e = rnd.choice(near)
+            if k == 0:
+                s, e = (S // C, S % C), (T // C, T % C)
+            if k == 1:                                          # end to end: row / column 0 <-> the last one
+                s, e = free[0], free[-1]
+            if k == 2:
+                s, e = free[-1], free[0]
+            if k % 7 == 3:
+                e = s
+            if k % 7 == 4:                                      # adjacent cells
+                nb = [f for f in free if f != s and abs(f[0] - s[0]) <= 1 and abs(f[1] - s[1]) <= 1]
+                e = rnd.choice(nb) if nb else s
+            if k % 11 == 5 and obst:
+                s = rnd.choice(obst)
+            if k % 11 == 6 and obst:
+                e = rnd.choice(obst)
+            avoid = None
+            if k % 3 == 1:
+                avoid = rnd.sample(free, rnd.randint(0, max(1, len(free) // 12)))
+                if k % 6 == 1:
+                    avoid.append(e)
+                if k % 6 == 4:
+                    avoid.append(s)
+            if k % 5 == 2 and abs(s[axis] - e[axis]) >= 2:      # an avoid set that cuts the corridor between the two
+                mid = (s[axis] + e[axis]) // 2
+                avoid = [f for f in free if f[axis] == mid]
+            for variant in (0, 1, 2):
+                if variant == 1:
+                    pc, _, cnt = rh.mpa_astar(solvers[1], s, e, avoid)
+                    st = [0.0] * 5
+                else:
+                    pc, res, cnt = solvers[variant].solve(s, e, avoid)
+                    st = [float(x) for x in res[1:6]]
+                rows.append(dict(grid=names.index(name), variant=variant, start=s[0] * C + s[1], target=e[0] * C + e[1],
+                                 avoid=[a[0] * C + a[1] for a in avoid] if avoid is not None else [],
+                                 has_avoid=avoid is not None, path=pc, pops=cnt["pops"], pushes=cnt["pushes"], stats=st))
+                got.append(len(pc))
+        assert max(got) >= L / 2, (name, max(got))              # not all of one kind: a long feasible path ...
+        assert not obst or min(got) == 0, name                  # ... and, where there are obstacles, an infeasible result
+    d["as_grid"] = np.array([r["grid"] for r in rows], np.int8)
+    d["as_variant"] = np.array([r["variant"] for r in rows], np.int8)
+    d["as_start"] = np.array([r["start"] for r in rows], np.int32)
+    d["as_target"] = np.array([r["target"] for r in rows], np.int32)
+    d["as_has_avoid"] = np.array([r["has_avoid"] for r in rows])
+    d["as_avoid_off"], d["as_avoid"] = csr([r["avoid"] for r in rows])
+    d["as_path_off"], d["as_path_d"] = csr_delta([r["path"] for r in rows])
+    d["as_counts"] = np.array([[r["pops"], r["pushes"]] for r in rows], np.int64)
+    d["as_stats"] = np.array([r["stats"] for r in rows], np.float64)
+    print("thin connector cases", len(rows), "no path", sum(len(r["path"]) == 0 for r in rows))
+
+    # ---- GA / PSO decodes + stats
+    weights = (MAIN_W, WIDE_W)
+    d["dec_weights"] = np.array([[w["turn_penalty_factor"], w["safety_penalty_factor"], w["min_safe_distance"],
+                                  w["diagonal_obstacle_penalty_value"]] for w in weights])
+    rows = []
+    for name in names:
+        g, S, T = maps[name]
+        R, C = g.shape
+        L = max(R, C)
+        free = [tuple(int(v) for v in x) for x in np.argwhere(g != 1)]
+        near_s = [f for f in free if abs(f[0] - S // C) + abs(f[1] - S % C) <= max(20, (T // C - S // C) + (T % C - S % C))]
+        got = []
+        for wi, Wt in enumerate(weights):
+            if wi == 1 and name not in ("3x200o", "200x3o", "2x17o", "1x9o"):
+                continue
+            ga, ps = rh.make_ga(g, W=5, **Wt), rh.make_pso(g, W=5, **Wt)
+            for k in range(8 if L < 300 else 4):
+                W = 1 + (k % 5)
+                pool = near_s if k % 2 else free
+                chrom = [rnd.choice(pool) if rnd.random() < 0.9 else (rnd.randint(0, R - 1), rnd.randint(0, C - 1)) for _ in range(W)]
+                pos = [[rnd.uniform(-1.5, R + 0.5), rnd.uniform(-1.5, C + 0.5)] for _ in range(W)]
+                if k % 4 == 1:                                  # exact .5 ties (round half to even) and positions outside the grid
+                    pos[0] = [0.5, min(C - 1, 2) + 0.5]
+                    pos[-1] = [R - 0.5, -0.5] if k % 8 == 1 else [-7.0, C + 30.25]
+                if k % 4 == 3:
+                    pos = [[rnd.choice(near_s)[0] + rnd.choice([-0.5, 0.5, 0.0]), rnd.choice(near_s)[1] + rnd.choice([-0.5, 0.5, 1.5])]
+                           for _ in range(W)]
+                with rh.quiet():
+                    p = ga._reconstruct_path_from_chromosome(chrom)
+                    st = ga._calculate_stats_for_path(p)
+                    p2 = ps._reconstruct_path_from_position(pos)
+                    st2 = ps._calculate_stats_for_path(p2)
+                rows.append(dict(grid=names.index(name), w=wi, kind=0, wp=[c[0] * C + c[1] for c in chrom], path=rh.to_cells(p, C),
+                                 stats=list(st[1:6])))
+                rows.append(dict(grid=names.index(name), w=wi, kind=1, wp=np.array(pos, np.float64).ravel(), path=rh.to_cells(p2, C),
+                                 stats=list(st2[1:6])))
+                got += [len(p), len(p2)]
+        assert max(got) >= L / 2 or R * C < 9, (name, max(got))     # not all of one kind: a decode as long as half the map ...
+        assert "o" not in name[-1] or L < 9 or min(got) == 0, name  # ... and, on a map with an obstacle zone, one that fails
+    # the two decodes that are longer than their grid: every waypoint is a cell the chain has already visited
+    for name, chrom in (("1x2e", [(0, 1), (0, 0), (0, 1)]), ("2x2e", [(0, 1), (1, 1), (1, 0), (0, 0), (1, 1)])):
+        g, S, T = maps[name]
+        R, C = g.shape
+        ga, ps = rh.make_ga(g, W=len(chrom), **MAIN_W), rh.make_pso(g, W=len(chrom), **MAIN_W)
+        with rh.quiet():
+            p = ga._reconstruct_path_from_chromosome(chrom)
+            st = ga._calculate_stats_for_path(p)
+            p2 = ps._reconstruct_path_from_position([[float(a), float(b)] for a, b in chrom])
+            st2 = ps._calculate_stats_for_path(p2)
+        assert len(p) > R * C and p == p2, (name, p)
+        rows.append(dict(grid=names.index(name), w=0, kind=0, wp=[c[0] * C + c[1] for c in chrom], path=rh.to_cells(p, C), stats=list(st[1:6])))
+        rows.append(dict(grid=names.index(name), w=0, kind=1, wp=np.array(chrom, np.float64).ravel(), path=rh.to_cells(p2, C), stats=list(st2[1:6])))
+    d["dec_long"] = np.array([len(rows) - 4, len(rows) - 2], np.int32)        # the GA rows of the two long examples
+    d["dec_grid"] = np.array([r["grid"] for r in rows], np.int8)
+    d["dec_w"] = np.array([r["w"] for r in rows], np.int8)
+    d["dec_kind"] = np.array([r["kind"] for r in rows], np.int8)
+    d["dec_wp_off"], d["dec_wp"] = csr([r["wp"] for r in rows], np.float64)
+    d["dec_path_off"], d["dec_path_d"] = csr_delta([r["path"] for r in rows])
+    d["dec_stats"] = np.array([r["stats"] for r in rows], np.float64)
+    print("thin decode cases", len(rows), "feasible", sum(len(r["path"]) > 0 for r in rows),
+          "longer than the grid", sum(len(r["path"]) > maps[names[r["grid"]]][0].size for r in rows))
+
+    # ---- MAACO: 6 ants, 3 iterations, beta 7 and 2
+    base = dict(alpha=1.0, rho=0.1, Q=2.5, a_turn_coef=1.0, wh_max=0.9, wh_min=0.2, k_h_adaptive=0.9,
+                q0_initial=0.5, C0_initial_pheromone=0.1)
+    d["maaco_base_params"] = np.array([base[k] for k in ("alpha", "rho", "Q", "a_turn_coef", "wh_max", "wh_min", "k_h_adaptive",
+                                                         "q0_initial", "C0_initial_pheromone")])
+    runs = []
+    plan = [(name, beta, None) for name in ("1x9e", "1x9o", "2x17e", "2x17o", "17x2o", "3x200e", "3x200o") for beta in (7.0, 2.0)]
+    # On these maps nearly every walk arrives.  Two more runs with seeds picked (with the CPU oracle) so that several ants of
+    # the 18 end in a pocket: the failed walk (no path, no deposit) is then a covered case -- asserted below.
+    plan += [("2x17o", 7.0, 695), ("17x2o", 7.0, 609)]
+    for name, beta, mixed_seed in plan:
+        g, S, T = maps[name]
+        R, C = g.shape
+        ri, seed, n_ants, n_it, K = len(runs), 500 + len(runs), 6, 3, 10
+        if mixed_seed is not None:
+            seed = mixed_seed
+        ma = rh.make_maaco(g, num_ants=n_ants, num_iterations=K, beta=beta, **base)
+        d[f"maaco{ri}_tau0"] = ma.pheromone_matrix.copy()
+        paths, LT, taus, best = [], [], [], float("inf")
+        for it in range(1, n_it + 1):
+            it_paths = []
+            for ant in range(n_ants):
+                pc, Lp, Tn, _ = rh.maaco_walk(ma, it, seed, ant)
+                paths.append(pc); LT.append([Lp, Tn if Tn != float("inf") else -1]); best = min(best, Lp)
+                it_paths.append((rh.to_rc(pc, C), Lp, Tn))
+            ma.best_path_length_overall = best              # MAACO.py:351-352 precedes :359
+            ma._update_pheromone_trails_maaco(it_paths, None)
+            taus.append(ma.pheromone_matrix.copy())
+        d[f"maaco{ri}_path_off"], d[f"maaco{ri}_path_d"] = csr_delta(paths)
+        d[f"maaco{ri}_len_turns"], d[f"maaco{ri}_tau"] = np.array(LT, np.float64), np.array(taus)
+        runs.append((names.index(name), beta, n_ants, n_it, K, seed))
+        arrived = sum(len(p) > 0 for p in paths)
+        print("thin maaco run", ri, name, beta, "arrived", arrived, "/", len(paths))
+        assert arrived > 0, (name, beta)                    # not all of one kind: walks that arrive ...
+        assert mixed_seed is None or arrived <= len(paths) - 3, (name, beta, arrived)     # ... and, in the picked runs, walks that fail
+    d["maaco_runs"] = np.array(runs, np.float64)
+
+    # ---- MPA._reconstruct_path_segment, Levy and Brownian
+    rows = []
+    for name in ("2x17e", "2x17o", "3x200e", "3x200o"):
+        g, S, T = maps[name]
+        R, C = g.shape
+        for beta in (1.5, 2.0):
+            mpa = rh.make_mpa(g, levy_beta=beta)
+            base_p = rh.to_cells(mpa.population[0]["path"], C)
+            mid = (R - 1, (T % C) // 2)
+            a1, _, _ = rh.mpa_astar(mpa, (S // C, S % C), mid)
+            a2, _, _ = rh.mpa_astar(mpa, mid, (T // C, T % C), set(rh.to_rc(a1[:-1], C)))
+            alt = np.concatenate([a1, a2[1:]]) if len(a1) and len(a2) else base_p
+            for k in range(14):
+                path_c, el_c = (base_p, alt) if k % 2 else (alt, base_p)
+                idx = rnd.randint(0, len(path_c) - 1)
+                is_levy, scale = k % 3 == 0, rnd.choice([0.5, 0.25, 0.05, 5.0, 40.0])
+                pc, res, draws = rh.mpa_rebuild(mpa, rh.to_rc(path_c, C), rh.to_rc(el_c, C), idx, is_levy, scale, 555, 7, k)
+                rows.append(dict(grid=names.index(name), beta=beta, path=path_c, elite=el_c, idx=idx, is_levy=int(is_levy), scale=scale,
+                                 agent=k, out=pc, draws=draws, stats=list(res[1:6])))
+    d["reb_grid"] = np.array([r["grid"] for r in rows], np.int8)
+    d["reb_beta"] = np.array([r["beta"] for r in rows])
+    d["reb_in_off"], d["reb_in_d"] = csr_delta([r["path"] for r in rows])
+    d["reb_el_off"], d["reb_el_d"] = csr_delta([r["elite"] for r in rows])
+    d["reb_out_off"], d["reb_out_d"] = csr_delta([r["out"] for r in rows])
+    d["reb_idx"] = np.array([r["idx"] for r in rows], np.int32)
+    d["reb_is_levy"] = np.array([r["is_levy"] for r in rows], np.int8)
+    d["reb_scale"] = np.array([r["scale"] for r in rows])
+    d["reb_agent"] = np.array([r["agent"] for r in rows], np.int32)
+    d["reb_draws"] = np.array([r["draws"] for r in rows], np.int64)
+    d["reb_stats"] = np.array([r["stats"] for r in rows], np.float64)
+    d["reb_seed_it"] = np.array([555, 7])
+    d["reb_sigma"] = np.array([rh.levy_sigma(1.5), rh.levy_sigma(2.0)])
+    print("thin rebuild cases", len(rows), "changed", sum(not np.array_equal(r["out"], r["path"]) for r in rows))
+    np.savez_compressed(os.path.join(OUT, "thin_cases.npz"), **d, **{"meta_" + k: v for k, v in META.items()})
+
+
 if __name__ == "__main__":
     assert rh.available(), "needs /root/reference"
     os.makedirs(OUT, exist_ok=True)
@@ -796,4 +1026,5 @@ if __name__ == "__main__":
     if "e2e" in which or "pso_fallback" in which: cap_e2e_pso_fallback()
     if "vs_reference" in which: cap_vs_reference(G)
     if "policies" in which: cap_policies(G)
+    if "thin" in which: cap_thin()
     print("golden fixtures written to", OUT)

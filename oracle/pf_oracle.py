@@ -154,10 +154,12 @@ class Oracle:
     def decode(self, start, target, wps):
         wps = np.ascontiguousarray(wps, np.int32)
         st = np.zeros(6, np.int64)
+        # each of the W + 1 segments may end on a cell the chain has visited (astar.py:55-56): up to R * C + W + 1 cells
+        buf = np.empty(self.R * self.C + wps.size + 1, np.int32)
         n = self.L.orc_decode(self.ws, _p(self.occ), self.R, self.C, self.allow_diag, self.restrict, int(start),
-                              int(target), _p(wps), wps.size, _p(self._scratch), _p(self._buf), self._buf.size, _p(st))
+                              int(target), _p(wps), wps.size, _p(self._scratch), _p(buf), buf.size, _p(st))
         assert n >= 0
-        return self._buf[:n].copy(), st
+        return buf[:n].copy(), st
 
     def pso_update(self, pos, vel, pbest, gbest, w, c1, c2, max_vel, seed, it, agent0=0):
         pos = np.array(pos, np.float64, order="C"); vel = np.array(vel, np.float64, order="C")

@@ -34,3 +34,17 @@ def upsample(g, k):
 
 def csr_get(off, flat, i):
     return flat[int(off[i]): int(off[i + 1])]
+
+
+def csr_get_delta(off, flat, i):
+    """csr_get for paths stored as their first cell followed by first differences (thin_cases.npz)."""
+    return np.cumsum(flat[int(off[i]): int(off[i + 1])], dtype=np.int64).astype(np.int32)
+
+
+def thin_grid(z, name):
+    """-> (uint8 grid with cell values 0/1/2/3, start_cell, target_cell) of a map stored in thin_cases.npz"""
+    R, C, s, t = (int(v) for v in z[name + "_dims"])
+    g = np.unpackbits(z[name + "_bits"])[: R * C].reshape(R, C).astype(np.uint8)
+    g.reshape(-1)[s] = 2
+    g.reshape(-1)[t] = 3
+    return g, s, t
