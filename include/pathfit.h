@@ -383,10 +383,8 @@ int pf_mpa_batch_counters(pf_mpa_batch* b, pf_counters* out, int64_t* overflow_t
  * records two steps ahead): -1 (default) for batches of at most one wavefront per SIMD, 0 never, 1 always;
  * "mpa_prune" 0/1 exact bound pruning of MPA rebuilds (default 1); "mpa_lookahead" how many iterations one MPA sweep may cover
  * after an iteration that accepted nothing (pf_mpa_iter_ahead; at most 16, 0 = off: exactly pf_mpa_iter_batch's
- * launches; default 8, or the environment's PF_MPA_LOOKAHEAD; < 0 restores the default); test hook "mpa_lookahead_always" 0/1: look ahead after any iteration, so that levels do go stale; "two_wave" 0/1 MPA._a_star searches (pf_mpa_iter_batch,
- * pf_astar_batch variant 1) on two-wavefront workgroups -- a pop wave and a pool wave, csrc/pf_astar_pr.h -- default 0:
- * identical pops, measured 0.9x; compiled only with -DPF_TWO_WAVE (PF_EXTRA_FLAGS of build.py), otherwise
- * setting it to 1 is an error; "astar_settle" 0/1 closed-set searches (AStarSolver
+ * launches; default 8, or the environment's PF_MPA_LOOKAHEAD; < 0 restores the default); test hook "mpa_lookahead_always" 0/1: look ahead after any iteration, so that levels do go stale;
+ * "astar_settle" 0/1 closed-set searches (AStarSolver
  * / Dijkstra / GA / PSO decodes) try the parallel label-settling engine first: -1 (default) the Dijkstra variant
  * always (it is always certified) and the A* searches of the decodes at the head of a batch's longest-first queue
  * ("astar_settle_top", per mille of the batch, default 0 since r03; a decode is a chain of W + 1 searches, so a fallback costs

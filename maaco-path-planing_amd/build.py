@@ -3,8 +3,7 @@
     python maaco-path-planing_amd/build.py [--force]
 
 hipcc cross-compiles gfx950 without a GPU; the .so travels to the GPU box with
-the repo snapshot.  PF_EXTRA_FLAGS adds compiler flags: -DPF_TWO_WAVE compiles the
-two-wavefronts-per-search engine (csrc/pf_astar_pr.h; off by default, measured 0.90x),
+the repo snapshot.  PF_EXTRA_FLAGS adds compiler flags:
 -DPF_TRACE / -DPF_STAMPS / -DPF_WALK_PROBE the diagnostic builds of scripts/.  -ffp-contract=off: the reference's arithmetic is unfused
 IEEE double and bit-exact path parity depends on it.
 """

@@ -211,28 +211,11 @@ struct AstarArgs {
   int* cells; int* len; int* status; long long* counters;
 };
 
-template <int VARIANT, bool PLAT, bool PR = false>
-__global__ __launch_bounds__(PR ? 128 : 64) __attribute__((amdgpu_waves_per_eu(PR ? 3 : 1, 8))) void k_astar_batch(AstarArgs p) {
+template <int VARIANT, bool PLAT>
+__global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(1, 8))) void k_astar_batch(AstarArgs p) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
   const int lane = lane_id();
   const int RC = p.c.G.R * p.c.G.C;
-#ifdef PF_TWO_WAVE
-  if (PR) {                                                       // two wavefronts per search (pf_astar_pr.h): wave 1 owns the bucket pool
-    const int wave = (int)(threadIdx.x >> 6);
-    if (wave == 0) pr_init_ctl(smem, lane);
-    __syncthreads();
-    if (wave == 1) {
-      pool_wave<VARIANT>(smem, p.c.tier2 + (size_t)blockIdx.x * PF_POOL_STRIDE, p.c.rec + (size_t)blockIdx.x * RC, p.c.G.C, lane);
-      return;
-    }
-  }
-  PrLink link = {};
-  if (PR) link = pr_link(smem);                                   // (single-wave kernels never touch the link's LDS block: it lies beyond their allocation)
-#else
-  static_assert(!PR, "two-wave searches need -DPF_TWO_WAVE");
-  PrLink link = {};
-#endif
-  PrLink* const L = &link;
   Open O = make_open(smem, p.c.S, p.c.tier2);
   Slot s = slot_load(p.c, RC);
   AStat tot = {0, 0, 0, 0, 0, 0};
@@ -255,8 +238,8 @@ __global__ __launch_bounds__(PR ? 128 : 64) __attribute__((amdgpu_waves_per_eu(P
     const int sa = p.start[a], ta = p.target[a];
     const long long ab = p.avoid_off ? p.avoid_off[a] : 0, ae = p.avoid_off ? p.avoid_off[a + 1] : 0;
     const int rc = ((unsigned)sa >= (unsigned)RC || (unsigned)ta >= (unsigned)RC) ? 1 :
-                   astar<VARIANT, PLAT, PR>(p.c.G, s, O, sa, ta, p.cells + (size_t)a * p.path_cap, p.path_cap, n, st, lane,
-                                  p.avoid_off ? p.avoid_cells + ab : nullptr, (int)(ae - ab), L);
+                   astar<VARIANT, PLAT>(p.c.G, s, O, sa, ta, p.cells + (size_t)a * p.path_cap, p.path_cap, n, st, lane,
+                                  p.avoid_off ? p.avoid_cells + ab : nullptr, (int)(ae - ab));
     if (lane == 0) {
       p.len[a] = rc == 0 ? n : 0;
       p.status[a] = rc;
@@ -269,9 +252,6 @@ __global__ __launch_bounds__(PR ? 128 : 64) __attribute__((amdgpu_waves_per_eu(P
     tot.settled += st.settled; tot.sequential += st.sequential;
     cells += rc == 0 ? n : 0; ovf += rc == 3;
   }
-#ifdef PF_TWO_WAVE
-  if (PR) pr_exit(smem, lane);
-#endif
   slot_store(p.c, s, lane);
   flush_counters(p.c.cnt, tot, cells, ovf, lane);
 }
@@ -1334,30 +1314,11 @@ __global__ __launch_bounds__(64) void k_mpa_plan(MpaSweepArgs q, MpaJob* jobs, M
 
 struct MpaSearchArgs { Common c; const MpaJob* jobs; MpaRes* res; int n_items, path_cap; int* ph_cells; int* fd_cells; int n; };
 
-// PR = two wavefronts per search (pf_astar_pr.h): wave 0 pops, wave 1 owns the bucket pool.  128-thread workgroups, one per slot.
-template <bool PR>
-__global__ __launch_bounds__(PR ? 128 : 64) __attribute__((amdgpu_waves_per_eu(3, 8))) void k_mpa_search(MpaSearchArgs p) {
+__global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(3, 8))) void k_mpa_search(MpaSearchArgs p) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
   const int lane = lane_id();
   const Grid& G = p.c.G;
   const int RC = G.R * G.C;
-#ifdef PF_TWO_WAVE
-  if (PR) {
-    const int wave = (int)(threadIdx.x >> 6);
-    if (wave == 0) pr_init_ctl(smem, lane);
-    __syncthreads();
-    if (wave == 1) {
-      pool_wave<1>(smem, p.c.tier2 + (size_t)blockIdx.x * PF_POOL_STRIDE, p.c.rec + (size_t)blockIdx.x * RC, G.C, lane);
-      return;
-    }
-  }
-  PrLink link = {};
-  if (PR) link = pr_link(smem);
-#else
-  static_assert(!PR, "two-wave searches need -DPF_TWO_WAVE");
-  PrLink link = {};
-#endif
-  PrLink* const L = &link;
   Open O = make_open(smem, p.c.S, p.c.tier2);
   Slot s = slot_load(p.c, RC);
   AStat tot = {0, 0, 0, 0, 0, 0};
@@ -1390,7 +1351,7 @@ __global__ __launch_bounds__(PR ? 128 : 64) __attribute__((amdgpu_waves_per_eu(3
       const unsigned long long pq0 = tot.pops;
       if (!isph && seg == 0 && lane == 0 && item < 16384) { g_trace3[4 * item] = 1; g_trace3[4 * item + 1] = g0; }
 #endif
-      const int r2 = astar<1, false, PR>(G, s, O, astart, seg == 0 ? g0 : g1, buf + n - 1, cap - (n - 1), mlen, tot, lane, nullptr, 0, L);
+      const int r2 = astar<1, false>(G, s, O, astart, seg == 0 ? g0 : g1, buf + n - 1, cap - (n - 1), mlen, tot, lane);
 #ifdef PF_TRACE
       if (lane == 0 && item < 16384) { g_trace2[4 * item + 2 * seg] = tot.pops - pq0; g_trace2[4 * item + 2 * seg + 1] = 100 + r2; }
 #endif
@@ -1414,9 +1375,6 @@ __global__ __launch_bounds__(PR ? 128 : 64) __attribute__((amdgpu_waves_per_eu(3
     }
 #endif
   }
-#ifdef PF_TWO_WAVE
-  if (PR) pr_exit(smem, lane);
-#endif
   slot_store(p.c, s, lane);
   flush_counters(p.c.cnt, tot, 0, ovf, lane);
 }
@@ -2088,10 +2046,6 @@ float pf_last_kernel_ms(pf_handle* h) { return h ? h->last_ms : 0.0f; }
 // resident agent slots per CU and LDS bin capacity; PF_SLOTS_PER_CU / PF_LDS_S override for experiments
 static int env_int(const char* name, int dflt) { const char* v = getenv(name); return v && *v ? atoi(v) : dflt; }
 static const int kSlotsPerCU = env_int("PF_SLOTS_PER_CU", 8);   // search slots (record / pool scratch) per CU = resident one-agent waves per CU at most
-#ifdef PF_TWO_WAVE
-static int g_two_wave = env_int("PF_TWO_WAVE", 0);   // MPA searches on two-wave workgroups: pop wave + pool wave (pf_astar_pr.h; pf_set_option "two_wave")
-#endif                                               // (the two-wave engine is compiled only with -DPF_TWO_WAVE: measured 0.90x, DESIGN.md 4.2 -- and the
-                                                     // pop loop's speed depends on what else its kernel carries)
 static const int kWavesPerCU = env_int("PF_WAVES_PER_CU", kSlotsPerCU);   // resident one-agent waves per CU (LDS permitting)
 static int g_mpa_prune = 1;   // exact bound pruning of MPA rebuilds (pf_set_option "mpa_prune")
 static int clamp_lookahead(int v) { return v < 0 ? 8 : (v > 16 ? 16 : v); }   // (16 = PF_AHEAD_MAX, pf_mpa_ahead.h)
@@ -2265,21 +2219,17 @@ static int search_grid(const pf_handle* h, size_t lds, int n) {
 }
 
 template <typename KArgs, typename Kern>
-static int launch_with_retry(pf_handle* h, Kern kern, KArgs& args, int n, bool two_wave = false) {
+static int launch_with_retry(pf_handle* h, Kern kern, KArgs& args, int n) {
   if (n <= 0) return 0;
   const int S = kLdsS;
   args.c.S = S; args.c.retry = 0;
-#ifdef PF_TWO_WAVE
-  const size_t lds = two_wave ? (size_t)PF_PR_LDS_BYTES : open_bytes(S);
-#else
   const size_t lds = open_bytes(S);
-#endif
   CK(hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
   const int grid = search_grid(h, lds, n);
   CK(hipMemsetAsync(h->d_work, 0, sizeof(int), h->stream));
   CK(hipMemsetAsync(h->d_cnt, 0, sizeof(DevCounters), h->stream));
   CK(hipEventRecord(h->ev0, h->stream));
-  hipLaunchKernelGGL(kern, dim3(grid), dim3(two_wave ? 128 : 64), lds, h->stream, args);
+  hipLaunchKernelGGL(kern, dim3(grid), dim3(64), lds, h->stream, args);
   CK(hipGetLastError());
   CK(hipEventRecord(h->ev1, h->stream));
   DevCounters dc;
@@ -2370,13 +2320,7 @@ int pf_astar_batch(pf_handle* h, int32_t variant, int32_t allow_diag, int32_t re
   // sparse maps (plateaus of equal f along open runs) go to the separately compiled kernels with the plateau refills
   const bool plat = plateau_map(h);
   if (variant == PF_ASTAR_REF) return plat ? launch_with_retry(h, k_astar_batch<0, true>, a, n) : launch_with_retry(h, k_astar_batch<0, false>, a, n);
-  if (variant == PF_ASTAR_MPA) {
-    if (plat) return launch_with_retry(h, k_astar_batch<1, true>, a, n);
-#ifdef PF_TWO_WAVE
-    if (g_two_wave) return launch_with_retry(h, k_astar_batch<1, false, true>, a, n, true);
-#endif
-    return launch_with_retry(h, k_astar_batch<1, false>, a, n);
-  }
+  if (variant == PF_ASTAR_MPA) return plat ? launch_with_retry(h, k_astar_batch<1, true>, a, n) : launch_with_retry(h, k_astar_batch<1, false>, a, n);
   if (variant == PF_ASTAR_DIJKSTRA) return plat ? launch_with_retry(h, k_astar_batch<2, true>, a, n) : launch_with_retry(h, k_astar_batch<2, false>, a, n);
   return failmsg(h, "pf_astar_batch: unknown variant");
 }
@@ -2577,11 +2521,6 @@ int pf_set_option(pf_handle* h, const char* name, int64_t value) {
   if (!strcmp(name, "mpa_prune")) { g_mpa_prune = value != 0; return 0; }
   if (!strcmp(name, "mpa_lookahead")) { g_mpa_lookahead = value < 0 ? kMpaLookahead : clamp_lookahead((int)value); return 0; }
   if (!strcmp(name, "mpa_lookahead_always")) { g_mpa_lookahead_always = value != 0; return 0; }
-#ifdef PF_TWO_WAVE
-  if (!strcmp(name, "two_wave")) { g_two_wave = value != 0; return 0; }
-#else
-  if (!strcmp(name, "two_wave")) { if (value == 0) return 0; return failmsg(h, "pf_set_option: two_wave is not built in (compile with -DPF_TWO_WAVE)"); }
-#endif
   if (!strcmp(name, "maaco_mark_in_walk")) { g_maaco_mark = value != 0; return 0; }
   if (!strcmp(name, "astar_settle")) { g_settle = value < 0 ? -1 : (value != 0); return 0; }
   if (!strcmp(name, "astar_settle_tail")) { g_settle_tail = value < 0 ? 0 : (value > 1000 ? 1000 : (int)value); return 0; }
@@ -3628,11 +3567,10 @@ int pf_mpa_fads_batch(pf_handle* h, double CF, int32_t iter, uint64_t seed, int3
 
 // One fused sweep from "the queue is made and the doubts are resolved" to its counters: the 2 n items of `a` (n phase items, then
 // n FADs candidates; n = K N for a batch) are planned, searched by k_mpa_search, finished and applied, back to back.  plan /
-// finish / apply enqueue the caller's kernels (solo or batched forms); two_wave picks the two-wave search engine (compiled only
-// with -DPF_TWO_WAVE).  One wait: the counters, which also come back in *dc.
+// finish / apply enqueue the caller's kernels (solo or batched forms).  One wait: the counters, which also come back in *dc.
 extern "C++" {
 template <typename Plan, typename Finish, typename Apply>
-static int mpa_launch_sweep(pf_handle* h, MpaSweepArgs& a, int n, bool two_wave, Plan plan, Finish finish, Apply apply, DevCounters* dc) {
+static int mpa_launch_sweep(pf_handle* h, MpaSweepArgs& a, int n, Plan plan, Finish finish, Apply apply, DevCounters* dc) {
   a.ph.c.queue = h->d_queue; a.fd.c.queue = h->d_queue;
   const int S = kLdsS;
   a.ph.c.S = S; a.fd.c.S = S; a.ph.c.retry = 0; a.fd.c.retry = 0;
@@ -3646,25 +3584,15 @@ static int mpa_launch_sweep(pf_handle* h, MpaSweepArgs& a, int n, bool two_wave,
   MpaJob* jobs = (MpaJob*)h->d_jobs; MpaRes* jres = (MpaRes*)h->d_jres;
   MpaSearchArgs sa;
   sa.c = a.ph.c; sa.jobs = jobs; sa.res = jres; sa.n_items = 2 * n; sa.path_cap = a.ph.path_cap; sa.ph_cells = a.ph.out_cells; sa.fd_cells = a.fd.cand_cells; sa.n = n;
-#ifdef PF_TWO_WAVE
-  const size_t lds = two_wave ? (size_t)PF_PR_LDS_BYTES : open_bytes(S);
-  if (two_wave) CK(hipFuncSetAttribute((const void*)k_mpa_search<true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-  else
-#else
   const size_t lds = open_bytes(S);
-#endif
-  CK(hipFuncSetAttribute((const void*)k_mpa_search<false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+  CK(hipFuncSetAttribute((const void*)k_mpa_search, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
   const int grid = search_grid(h, lds, 2 * n);
   CK(hipMemsetAsync(h->d_work, 0, sizeof(int), h->stream));
   CK(hipMemsetAsync(h->d_cnt, 0, sizeof(DevCounters), h->stream));
   plan(jobs, jres);
   CK(hipGetLastError());
   CK(hipEventRecord(h->ev0, h->stream));
-#ifdef PF_TWO_WAVE
-  if (two_wave) hipLaunchKernelGGL(k_mpa_search<true>, dim3(grid), dim3(128), lds, h->stream, sa);
-  else
-#endif
-  hipLaunchKernelGGL(k_mpa_search<false>, dim3(grid), dim3(64), lds, h->stream, sa);
+  hipLaunchKernelGGL(k_mpa_search, dim3(grid), dim3(64), lds, h->stream, sa);
   CK(hipGetLastError());
   CK(hipEventRecord(h->ev1, h->stream));
   finish((const MpaJob*)jobs, (const MpaRes*)jres);
@@ -3705,13 +3633,8 @@ int pf_mpa_iter_batch(pf_handle* h, int32_t phase, double CF, int32_t iter, uint
         hipLaunchKernelGGL(k_plan_mpa_fads, dim3((n + 255) / 256), dim3(256), 0, h->stream, a.fd, est + n);
       })) return -1;
   if (prc || mpa_resolve_doubts(h, a.ph)) return -1;
-#ifdef PF_TWO_WAVE
-  const bool pr = g_two_wave != 0 && !plateau_map(h);               // two wavefronts per search (pf_astar_pr.h)
-#else
-  const bool pr = false;
-#endif
   DevCounters dc;
-  return mpa_launch_sweep(h, a, n, pr,
+  return mpa_launch_sweep(h, a, n,
       [&](MpaJob* jobs, MpaRes* jres) { hipLaunchKernelGGL(k_mpa_plan, dim3(2 * n), dim3(64), 0, h->stream, a, jobs, jres); },
       [&](const MpaJob* jobs, const MpaRes* jres) { hipLaunchKernelGGL(k_mpa_finish, dim3(2 * n), dim3(64), 0, h->stream, a, jobs, jres); },
       [&] { hipLaunchKernelGGL(k_mpa_apply, dim3(n), dim3(64), 0, h->stream, n, path_cap, d_slot, d_c1_cells, d_c1_len, d_c1_stats,
@@ -3978,8 +3901,8 @@ int pf_mpa_batch_iterate(pf_mpa_batch* b, int32_t phase, double CF, int32_t iter
     }
     b->doubts_resolved += h->doubts_resolved - before;
   }
-  DevCounters dc;                                                   // (one-wave searches: the two-wave engine is a solo experiment)
-  if (mpa_launch_sweep(h, a, KN, false,
+  DevCounters dc;
+  if (mpa_launch_sweep(h, a, KN,
       [&](MpaJob* jobs, MpaRes* jres) { hipLaunchKernelGGL(k_mpa_plan_batch<>, dim3(2 * KN), dim3(64), 0, h->stream, a, ms, jobs, jres); },
       [&](const MpaJob* jobs, const MpaRes* jres) { hipLaunchKernelGGL(k_mpa_finish_batch<>, dim3(2 * KN), dim3(64), 0, h->stream, a, ms, jobs, jres); },
       [&] { hipLaunchKernelGGL(k_mpa_apply_batch<>, dim3(KN), dim3(64), 0, h->stream, KN, N, path_cap, d_order, (const int*)d_c1_cells,
@@ -4492,15 +4415,10 @@ int pf_mpa_iter_ahead(pf_handle* h, int32_t depth, const int32_t* phases, const 
       if (mpa_resolve_one(h, v, g - d * n)) return -1;
     }
   }
-#ifdef PF_TWO_WAVE
-  const bool pr = g_two_wave != 0 && !plateau_map(h);
-#else
-  const bool pr = false;
-#endif
   unsigned long long* const ctl = S->d_ctl;
   if (D > 1) CK(hipMemsetAsync(ctl, 0, sizeof(unsigned long long) * (1 + PF_AHEAD_MAX), h->stream));
   DevCounters dc;
-  if (mpa_launch_sweep(h, a, DN, pr,
+  if (mpa_launch_sweep(h, a, DN,
       [&](MpaJob* jobs, MpaRes* jres) {
         if (D == 1) hipLaunchKernelGGL(k_mpa_plan, dim3(2 * n), dim3(64), 0, h->stream, a, jobs, jres);
         else hipLaunchKernelGGL(k_mpa_plan_ahead<>, dim3(2 * DN), dim3(64), 0, h->stream, a, ls, jobs, jres);

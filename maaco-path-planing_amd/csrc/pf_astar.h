@@ -76,19 +76,6 @@ PF_DEV int move_dc(int d) { return (int)((0x2252u >> (2 * d)) & 3u) - 1; }   // 
 
 }  // namespace pf
 #include "pf_astar_sw.h"
-#ifdef PF_TWO_WAVE
-#include "pf_astar_pr.h"     // two wavefronts per search (off by default and measured 0.90x: compiled only on request)
-#else
-namespace pf {               // PR is false in every instantiation of this build: the pop wave's link functions are never called
-PF_DEV void pr_search_start(PrLink&, int, int, int, bool, int) {}
-PF_DEV bool pr_search_stop(PrLink&, unsigned&, bool&, int) { return true; }
-PF_DEV void pr_request(PrLink&, int, int) {}
-PF_DEV int pr_take(PrLink&, SwWin&, int) { return 0; }
-PF_DEV void pr_publish(PrLink&, int) {}
-PF_DEV bool pr_wait_room(PrLink&) { return true; }
-PF_DEV int pr_ld(const int*) { return 0; }
-}  // namespace pf
-#endif
 #include "pf_settle.h"
 namespace pf {
 
@@ -106,8 +93,7 @@ namespace pf {
 #define PF_FLOOD_K 512
 #define PF_FLOOD_TAB 2048
 // (One wave runs the flood.  Its LDS instructions execute in order, so the hand-over points between the lanes need the
-// stores to have been ISSUED, not a workgroup barrier -- which, in the two-wave workgroups of pf_astar_pr.h, the pool wave
-// would never join.)
+// stores to have been ISSUED, not a workgroup barrier.)
 #define PF_WAVE_SYNC() do { __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup"); __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup"); } while (0)
 PF_DEV int pocket_flood(const Grid& G, const Slot& s, int* lds, int from, int to, int exempt, int lane) {
   int* tab = lds;                    // [PF_FLOOD_TAB] visited cells (open addressing), -1 = empty
@@ -161,9 +147,9 @@ PF_DEV int pocket_flood(const Grid& G, const Slot& s, int* lds, int from, int to
 // (r*C+c) start..target.  out_cap is the room available at `out`.
 // av_list / av_n: the cells of this search's avoid set as a list (the same cells mark_avoid has stamped into the
 // records); only the closed-set variants use it, to re-mark them under the parallel engine's label epoch.
-template <int VARIANT, bool PLAT = false, bool PR = false>
+template <int VARIANT, bool PLAT = false>
 __device__ __forceinline__ int astar(const Grid& G, Slot& s, const Open& O, int start, int target, int* out, int out_cap,
-                     int& out_n, AStat& st, int lane, const int* av_list = nullptr, int av_n = 0, PrLink* L = nullptr) {
+                     int& out_n, AStat& st, int lane, const int* av_list = nullptr, int av_n = 0) {
   // VARIANT 0 AStarSolver.solve (astar.py:33-101), 1 MPA._a_star (MPA.py:106-151), 2 DijkstraSolver.solve
   // (dijkstra.py:32-97: the loop of variant 0 with heap entries (g, node), i.e. h == 0 and key (g, g, node))
   constexpr int SEM = VARIANT == 1 ? 1 : 0;
@@ -226,7 +212,7 @@ __device__ __forceinline__ int astar(const Grid& G, Slot& s, const Open& O, int 
   long long cap_steps = (long long)G.R * C * (SEM == 0 ? 3 : 2);   // astar.py:58 / MPA.py:118 (R,C <= 4096)
   if (G.step_cap > 0 && G.step_cap < cap_steps) cap_steps = G.step_cap;   // test hook, see pf_set_option("astar_step_cap")
   const int max_steps = (int)cap_steps;
-  const int status4 = pop_loop_sw<VARIANT, PLAT, PR>(G, rec, O, tag, avm, start, target, tr, tc, max_steps, h0, (sr << 16) | sc_, st, lane, L);
+  const int status4 = pop_loop_sw<VARIANT, PLAT>(G, rec, O, tag, avm, start, target, tr, tc, max_steps, h0, (sr << 16) | sc_, st, lane);
   if (status4 != 0) return status4;
 
   // ---- walk parents target -> start (astar.py:65-69 / MPA.py:124-130), then reverse in place ----
