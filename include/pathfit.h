@@ -378,10 +378,25 @@ int pf_mpa_batch_read_path(pf_mpa_batch* b, int32_t k, int32_t slot, int32_t pat
 /* counters of the batch's last sweep, and over its lifetime: items that overflowed, proposals the host's libm resolved */
 int pf_mpa_batch_counters(pf_mpa_batch* b, pf_counters* out, int64_t* overflow_total, int64_t* doubts_resolved);
 
+/* ---- distance fields: exact one-to-all path lengths from K sources (pathfit.DistanceField) ----------------------------
+ * Exact shortest-path lengths from K source cells to every cell (one-to-all Dijkstra, dijkstra.py's relaxation with no target):
+ * d_out[k*RC + v] = the least fixed point of D[src[k]] = 0, D[v] = min over legal moves u -> v of fl(D[u] + w) (w = 1 for the
+ * four straight moves, sqrt(2) for the diagonals, the call's move policy) -- bit for bit what a heap Dijkstra leaves; +inf for
+ * obstacles and unreachable cells; a source ON an obstacle gives an all-inf row (legal); a source outside the grid, K < 1 or a
+ * null pointer is an argument error (-1) found on the host before anything is launched.  src is a HOST array.  d_info: int64[K*4]
+ * {levels that held at least one live cell, cells with a finite label, relaxations offered, list appends} or NULL.
+ * One workgroup per source, min(K, CUs) of them; their level lists (12 RC bytes per workgroup) are the
+ * handle's, allocated on first use.  Time grows with the number of levels, floor(largest length) + 1: a corridor map with
+ * paths of ~RC / 2 steps serialises.  Synchronous, ordered on the handle's stream; pf_last_kernel_ms reports the kernel. */
+int pf_dist_field_batch(pf_handle* h, int32_t allow_diag, int32_t restrict_corner, int32_t K, const int32_t* src,
+                        double* d_out, int64_t* d_info);
+
 /* Tuning knobs (results never change): "maaco_pack8_min" ants per batch from which eight ants share a wavefront
  * (default 2048); "maaco_load_ahead" the packed walk kernel's load-ahead form (all of a step's loads issued together plus touches of the
  * records two steps ahead): -1 (default) for batches of at most one wavefront per SIMD, 0 never, 1 always;
- * "mpa_prune" 0/1 exact bound pruning of MPA rebuilds (default 1); "mpa_lookahead" how many iterations one MPA sweep may cover
+ * "mpa_prune" 0/1 exact bound pruning of MPA rebuilds (default 1); "mpa_bounds_device" 0/1 the bound tables of pf_mpa_setup /
+ * pf_mpa_batch_create come from one pf_dist_field_batch launch instead of one host Dijkstra per distinct cell (default 0: the
+ * launch serialises on corridor maps; the tables are bit-identical either way); "mpa_lookahead" how many iterations one MPA sweep may cover
  * after an iteration that accepted nothing (pf_mpa_iter_ahead; at most 16, 0 = off: exactly pf_mpa_iter_batch's
  * launches; default 8, or the environment's PF_MPA_LOOKAHEAD; < 0 restores the default); test hook "mpa_lookahead_always" 0/1: look ahead after any iteration, so that levels do go stale;
  * "astar_settle" 0/1 closed-set searches (AStarSolver

@@ -1828,6 +1828,7 @@ struct pf_handle {
   std::vector<hipEvent_t> span_ev; int span_n = 0; bool span_open = false; double span_ms = 0.0; long long span_cnt = 0;   // pf_span_*: HIP-event timed spans on `stream`
   long long d2h_small = 0, d2h_bulk = 0, d2h_bulk_bytes = 0;   // device-to-host copies the library made (f1/f2 accounting): <= 128 B / larger
   struct MpaAhead* ahead = nullptr;   // pf_mpa_iter_ahead: level buffers and the levels still to be taken (end of this file)
+  int* d_df_lists = nullptr; int df_slots = 0; int* d_df_ctl = nullptr; int df_ctl_cap = 0; int df_cus = 0;   // pf_dist_field_batch: [slots][3][RC] rolling lists; {error word, K sources}
 };
 
 static long long g_step_cap = 0;   // > 0: lowers the connectors' step cap (pf_set_option "astar_step_cap": tests of the cap path)
@@ -1991,7 +1992,7 @@ void pf_destroy(pf_handle* h) {
   void* ptrs[] = {h->d_occ, h->d_mm_r1, h->d_mm_r0, h->d_mm_r1_nd, h->d_mm_r0_nd, h->d_d2near, h->d_rec, h->d_slot_state,
                   h->d_work, h->d_cnt, h->d_pen, h->d_tier2, h->d_tau, h->d_taua, h->d_eta, h->d_dep, h->d_tep, h->d_visit, h->d_visit_epoch,
                   h->d_bits, h->d_flag, h->d_mstate, h->d_mctl, h->d_best_row, h->d_d2wide, h->d_penw, h->d_tmp, h->d_elite_stats, h->d_init_cells, h->d_init_stats, h->d_est, h->d_queue, h->d_jobs, h->d_jres, h->d_prop, h->d_doubt, h->d_scan, h->d_scan3, h->d_okey, h->d_opay, h->d_orank, h->d_elite_cells, h->d_elite_len, h->d_ga_pool, h->d_seg_rows, h->d_st_lab, h->d_st_touched, h->d_st_par, h->d_st_epoch,
-                  h->d_comp[0], h->d_comp[1], h->d_comp[2], h->d_comp[3], h->d_ds, h->d_dt};
+                  h->d_comp[0], h->d_comp[1], h->d_comp[2], h->d_comp[3], h->d_ds, h->d_dt, h->d_df_lists, h->d_df_ctl};
   for (void* p : ptrs) if (p) (void)hipFree(p);
   for (hipEvent_t e : h->span_ev) (void)hipEventDestroy(e);
   if (h->ev0) (void)hipEventDestroy(h->ev0);
@@ -2047,6 +2048,7 @@ float pf_last_kernel_ms(pf_handle* h) { return h ? h->last_ms : 0.0f; }
 static int env_int(const char* name, int dflt) { const char* v = getenv(name); return v && *v ? atoi(v) : dflt; }
 static const int kSlotsPerCU = env_int("PF_SLOTS_PER_CU", 8);   // search slots (record / pool scratch) per CU = resident one-agent waves per CU at most
 static const int kWavesPerCU = env_int("PF_WAVES_PER_CU", kSlotsPerCU);   // resident one-agent waves per CU (LDS permitting)
+static int g_mpa_bounds_device = 0;   // the MPA bound tables come from pf_dist_field_batch instead of dijkstra_host (pf_set_option "mpa_bounds_device")
 static int g_mpa_prune = 1;   // exact bound pruning of MPA rebuilds (pf_set_option "mpa_prune")
 static int clamp_lookahead(int v) { return v < 0 ? 8 : (v > 16 ? 16 : v); }   // (16 = PF_AHEAD_MAX, pf_mpa_ahead.h)
 static const int kMpaLookahead = clamp_lookahead(env_int("PF_MPA_LOOKAHEAD", 8));
@@ -2519,6 +2521,7 @@ int pf_set_option(pf_handle* h, const char* name, int64_t value) {
   if (!strcmp(name, "maaco_load_ahead")) { g_maaco_ahead = value < 0 ? -1 : (value ? 1 : 0); return 0; }
   if (!strcmp(name, "maaco_ants_per_wave")) { g_maaco_groups = value < 1 ? 1 : (value > 8 ? 8 : (int)value); return 0; }
   if (!strcmp(name, "mpa_prune")) { g_mpa_prune = value != 0; return 0; }
+  if (!strcmp(name, "mpa_bounds_device")) { g_mpa_bounds_device = value != 0; return 0; }
   if (!strcmp(name, "mpa_lookahead")) { g_mpa_lookahead = value < 0 ? kMpaLookahead : clamp_lookahead((int)value); return 0; }
   if (!strcmp(name, "mpa_lookahead_always")) { g_mpa_lookahead_always = value != 0; return 0; }
   if (!strcmp(name, "maaco_mark_in_walk")) { g_maaco_mark = value != 0; return 0; }
@@ -3291,10 +3294,24 @@ static int mpa_bound_table(pf_handle* h, const std::vector<uint8_t>& mm, int cel
   CK(hipMemcpy(d_out, dist.data(), sizeof(double) * (size_t)h->RC, hipMemcpyHostToDevice));
   return 0;
 }
+// the same tables built on the device (end of this file): rows d_out[k][RC] for the K host cells src[k]
+static int dist_field_run(pf_handle* h, const char* who, int allow_diag, int restrict_corner, int K, const int32_t* src, double* d_out, int64_t* d_info);
 static int mpa_bounds(pf_handle* h) {
   if (h->d_ds) { (void)hipFree(h->d_ds); h->d_ds = nullptr; }
   if (h->d_dt) { (void)hipFree(h->d_dt); h->d_dt = nullptr; }
   if (!mpa_bounds_usable(h, &h->mps)) return 0;
+  if (g_mpa_bounds_device) {                                        // both tables in one launch, then a device copy each
+    const size_t nb = sizeof(double) * (size_t)h->RC;
+    const int32_t src[2] = {h->mpp.start, h->mpp.target};
+    double* d_two = nullptr;
+    CK(hipMalloc(&h->d_ds, nb)); CK(hipMalloc(&h->d_dt, nb)); CK(hipMalloc(&d_two, 2 * nb));
+    int rc = dist_field_run(h, "pf_mpa_setup", h->mpp.allow_diag, h->mpp.restrict_corner, 2, src, d_two, nullptr);
+    if (rc == 0 && (failed(h, "hipMemcpyAsync", hipMemcpyAsync(h->d_ds, d_two, nb, hipMemcpyDeviceToDevice, h->stream)) ||
+                    failed(h, "hipMemcpyAsync", hipMemcpyAsync(h->d_dt, d_two + h->RC, nb, hipMemcpyDeviceToDevice, h->stream)) ||
+                    failed(h, "hipStreamSynchronize", hipStreamSynchronize(h->stream)))) rc = -1;
+    (void)hipFree(d_two);
+    return rc;
+  }
   std::vector<uint8_t> mm;
   if (mpa_host_masks(h, &h->mpp, mm)) return -1;
   CK(hipMalloc(&h->d_ds, sizeof(double) * (size_t)h->RC)); CK(hipMalloc(&h->d_dt, sizeof(double) * (size_t)h->RC));
@@ -3710,7 +3727,10 @@ int pf_mpa_batch_create(pf_handle* h, const pf_mpa_params* p, const pf_score_par
   b->create_ms[0] = ms_since(t_init);
   // the bound tables
   const auto t_bounds = std::chrono::steady_clock::now();
-  if (T) {
+  if (T && g_mpa_bounds_device) {                                   // all T tables in one launch, straight into the batch's rows
+    CKB(hipMalloc(&b->d_bounds, sizeof(double) * T * RC));
+    CKB(dist_field_run(h, "pf_mpa_batch_create", p->allow_diag, p->restrict_corner, (int)T, cells.data(), b->d_bounds, nullptr));
+  } else if (T) {
     std::vector<uint8_t> mm;
     CKB(mpa_host_masks(h, p, mm));
     CKB(hipMalloc(&b->d_bounds, sizeof(double) * T * RC));
@@ -4580,6 +4600,82 @@ int pf_pso_commit_batch(pf_handle* h, int32_t n, int32_t K, int32_t N, int32_t W
                      d_pb_len, d_gbest, d_gbest_stats, d_gbest_path, d_gfit);
   CK(hipGetLastError());
   return 0;
+}
+
+}  // extern "C"
+
+// ---------------------------------------------------------------------------
+// Distance fields: exact one-to-all path lengths from K sources (pf_dist_field.h).  One workgroup per source,
+// min(K, CUs) of them looping over the sources; each owns one slot of three rolling cell lists in HBM.  The slots are the
+// handle's (allocated on first use, grown when a call needs more, freed by pf_destroy); nothing in them outlives a call, so
+// pf_update_grid has nothing to invalidate.
+// ---------------------------------------------------------------------------
+#include "pf_dist_field.h"
+
+static int dist_field_run(pf_handle* h, const char* who, int allow_diag, int restrict_corner, int K, const int32_t* src, double* d_out, int64_t* d_info) {
+  const std::string me(who);
+  if (K < 1 || !src || !d_out) return failmsg(h, me + ": bad arguments (K >= 1, sources and rows must not be null)");
+  for (int k = 0; k < K; ++k)
+    if (src[k] < 0 || src[k] >= h->RC) return failmsg(h, me + ": source " + std::to_string(k) + " lies outside the grid");
+  CK(hipSetDevice(h->device));
+  if (h->df_cus < 1) {
+    int cus = 0;
+    if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, h->device) != hipSuccess || cus < 1) cus = 256;
+    h->df_cus = cus;
+  }
+  const size_t slot_bytes = sizeof(int) * 3 * (size_t)h->RC;
+  int G = K < h->df_cus ? K : h->df_cus;
+  if (G > h->df_slots) {                                            // grow the slots (a workgroup's lists: 12 RC bytes)
+    CK(hipStreamSynchronize(h->stream));
+    if (h->d_df_lists) { (void)hipFree(h->d_df_lists); h->d_df_lists = nullptr; h->df_slots = 0; }
+    size_t free_b = 0, total_b = 0;
+    CK(hipMemGetInfo(&free_b, &total_b));
+    const size_t fit = free_b / 2 / slot_bytes;                     // on a large map fewer workgroups loop over more sources each
+    if (fit < (size_t)G) G = (int)fit;
+    if (G < 1 || hipMalloc(&h->d_df_lists, slot_bytes * (size_t)G) != hipSuccess) {
+      (void)hipGetLastError();
+      h->d_df_lists = nullptr;
+      return failmsg(h, me + ": no device memory for the level lists (" + std::to_string(slot_bytes >> 20) + " MiB per workgroup, " +
+                            std::to_string(free_b >> 20) + " MiB are free)");
+    }
+    h->df_slots = G;
+  }
+  if (K + 1 > h->df_ctl_cap) {
+    if (h->d_df_ctl) { (void)hipFree(h->d_df_ctl); h->d_df_ctl = nullptr; h->df_ctl_cap = 0; }
+    const int cap = K + 1 < 64 ? 64 : K + 1;
+    if (hipMalloc(&h->d_df_ctl, sizeof(int) * (size_t)cap) != hipSuccess) {
+      (void)hipGetLastError();
+      h->d_df_ctl = nullptr;
+      return failmsg(h, me + ": no device memory for the source table");
+    }
+    h->df_ctl_cap = cap;
+  }
+  std::vector<int> ctl((size_t)K + 1);
+  ctl[0] = 0;
+  for (int k = 0; k < K; ++k) ctl[(size_t)k + 1] = src[k];
+  CK(hipMemcpyAsync(h->d_df_ctl, ctl.data(), sizeof(int) * ctl.size(), hipMemcpyHostToDevice, h->stream));
+  CK(hipStreamSynchronize(h->stream));                              // (ctl is pageable and leaves scope)
+  const uint8_t* mm = allow_diag ? (restrict_corner ? h->d_mm_r1 : h->d_mm_r0) : (restrict_corner ? h->d_mm_r1_nd : h->d_mm_r0_nd);
+  CK(hipEventRecord(h->ev0, h->stream));
+  hipLaunchKernelGGL(k_dist_field_level_synchronous<>, dim3(G), dim3(PF_DF_THREADS), 0, h->stream, (const uint8_t*)h->d_occ, mm, h->RC, h->C, K,
+                     (const int*)(h->d_df_ctl + 1), d_out, h->d_df_lists, (long long*)d_info, h->d_df_ctl);
+  CK(hipGetLastError());
+  CK(hipEventRecord(h->ev1, h->stream));
+  int err = 0;
+  CK(hipMemcpyAsync(&err, h->d_df_ctl, sizeof(int), hipMemcpyDeviceToHost, h->stream));
+  CK(hipStreamSynchronize(h->stream));
+  CK(hipEventElapsedTime(&h->last_ms, h->ev0, h->ev1));
+  h->d2h_small += 1;
+  if (err == PF_DF_ERR_LEVELS) return failmsg(h, me + ": internal: level bound");
+  if (err) return failmsg(h, me + ": internal: list bound");
+  return 0;
+}
+
+extern "C" {
+
+int pf_dist_field_batch(pf_handle* h, int32_t allow_diag, int32_t restrict_corner, int32_t K, const int32_t* src, double* d_out, int64_t* d_info) {
+  if (!h) return -2;
+  return dist_field_run(h, "pf_dist_field_batch", allow_diag, restrict_corner, K, src, d_out, d_info) ? -1 : 0;
 }
 
 }  // extern "C"

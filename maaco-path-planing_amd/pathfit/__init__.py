@@ -16,3 +16,4 @@ from .mpa import MPA  # noqa: F401
 from .mpa_batch import MPABatch, MpaSchool  # noqa: F401
 from .ga_batch import GABatch, GaPopulation  # noqa: F401
 from .pso_batch import PSOBatch, PsoSwarm  # noqa: F401
+from .dist_field import DistanceField  # noqa: F401

@@ -155,6 +155,7 @@ SYMBOLS = {
     "pf_pso_update_batch": (C.c_int, [_vp, _i32, _i32, _i32, _i32, _dbl, _dbl, _dbl, _dbl, _u64] + [_vp] * 13),
     "pf_pso_scan_batch": (C.c_int, [_vp, _i32, _i32, _i32] + [_vp] * 8),
     "pf_pso_commit_batch": (C.c_int, [_vp, _i32, _i32, _i32, _i32, _i32, _i32] + [_vp] * 21),
+    "pf_dist_field_batch": (C.c_int, [_vp, _i32, _i32, _i32, _vp, _vp, _vp]),
 }
 
 

@@ -209,6 +209,30 @@ class Engine:
             return paths, st[:n], dcnt.download()[:n]
         return paths, st[:n]
 
+    # ------------------------------------------------------------------ distance fields
+    def dist_field_batch(self, sources, d_out, allow_diag=True, restrict_corner=True, d_info=None):
+        """Exact path lengths from the K cells `sources` (host int32 ids) to every cell -> d_out [K, R * C] doubles in HBM; d_info
+        [K, 4] int64 = (levels, cells reached, relaxations offered, list appends) per source."""
+        src = np.ascontiguousarray(sources, np.int32).reshape(-1)
+        self._ck(self.L.pf_dist_field_batch(self.h, int(allow_diag), int(restrict_corner), int(src.size), src.ctypes.data if src.size else None,
+                                            d_out.ptr, d_info.ptr if d_info else None))
+        self._logk("dist_field")
+
+    def dist_fields_host(self, sources, allow_diag=True, restrict_corner=True, want_info=False):
+        """-> float64 [K, R, C] (and int64 [K, 4] when want_info)."""
+        src = np.ascontiguousarray(sources, np.int32).reshape(-1)
+        K = max(int(src.size), 1)
+        out = self.buf((K, self.R, self.C), np.float64)
+        info = self.buf((K, 4), np.int64) if want_info else None
+        try:
+            self.dist_field_batch(src, out, allow_diag, restrict_corner, info)
+            res = out.download()[:src.size]
+            return (res, info.download()[:src.size]) if want_info else res
+        finally:
+            out.free()
+            if info is not None:
+                info.free()
+
     # ------------------------------------------------------------------ K1
     def score_host(self, paths, sp):
         n = len(paths)

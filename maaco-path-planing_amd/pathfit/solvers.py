@@ -268,6 +268,14 @@ class AStarSolver(_ConnectorSolver):
 class DijkstraSolver(_ConnectorSolver):
     _variant, _label, _strict = 2, "Dijkstra", "dijkstra_strictly_restricts_corners"
 
+    def distance_field(self, source=None):
+        """float64 [R, C]: the length of the shortest path from `source` (default: the start node) to every cell under the solver's
+        move policy -- solve()'s relaxation with no target (inf: an obstacle, or out of reach)."""
+        s = source if source is not None else self.start_node
+        if not (0 <= s[0] < self.rows and 0 <= s[1] < self.cols):
+            raise ValueError(f"Dijkstra: source {tuple(s)} is outside the {self.rows}x{self.cols} grid")
+        return self.engine.dist_fields_host([self._cell(s)], self.allow_diagonal_moves, getattr(self, self._strict))[0]
+
 
 class _WaypointSolver(BasePathfinder):
     """Shared decode + score batch for GA / PSO."""
