@@ -391,6 +391,32 @@ int pf_mpa_batch_counters(pf_mpa_batch* b, pf_counters* out, int64_t* overflow_t
 int pf_dist_field_batch(pf_handle* h, int32_t allow_diag, int32_t restrict_corner, int32_t K, const int32_t* src,
                         double* d_out, int64_t* d_info);
 
+/* ---- routing trees: DijkstraSolver's paths to many targets from one field (pathfit.DistanceField.paths) ----------------
+ * pf_dist_field_parents: d_parents[k*RC + v] (uint8) = the last step of DijkstraSolver.solve()'s path from source k into v, from
+ * the K fields d_fields [K][RC] that pf_dist_field_batch left under the SAME move policy: 0..7 the move index (helper.py:30-36
+ * order) with v = parent + move, 8 at the source (D == 0), 255 for an obstacle or a cell out of reach (D == +inf).  The parent is
+ * the u with the smallest (D[u], u) among the cells with a legal move u -> v and fl(D[u] + w) == D[v]: dijkstra.py:59-96 pops
+ * in (g, (r, c)) order, every weight is >= 1, so that is its pop order, and came_from (:84) keeps the earliest-popped cell that
+ * offers the final label -- the traced paths are the reference's cell for cell, not merely as short.  Fields that
+ * are no fixed point of the handle's grid under the policy (a finite non-source cell without such a u) fail the call with a message;
+ * every byte is written all the same.  K < 1 or a null pointer is an argument error (-1) found before anything is launched.
+ * pf_dist_field_paths: n queries (d_field_idx[q], d_target[q]) -> row q of d_cells [n][path_cap], d_len, d_status, laid out as
+ * pf_astar_batch's rows (pf_score_batch scores them unchanged): the path source -> target (reverse = 0, solve()'s order) or
+ * target -> source (reverse != 0, the order an agent walks to the goal); target == source is the one-cell path (dijkstra.py:40-41).
+ * PF_ST_INFEASIBLE, length 0: the target's code is 255, the target id lies outside [0, RC) or the field index outside [0, K)
+ * (nothing is read or written out of range).  PF_ST_OVERFLOW, length 0, row untouched: more than path_cap cells -- or a map that
+ * is no tree (a code other than 0..8 on the way, a step off the grid, more than RC cells): the walk is bounded whatever the
+ * bytes hold.  d_field_idx NULL: each query takes the field with the smallest d_fields[k][target], the lowest k on a tie (the
+ * nearest source; d_fields is needed only then); d_chosen (or NULL) takes the field each query used, -1 where the target id or
+ * the field index was out of range.  K < 1, n < 0, path_cap < 1 or a missing pointer is an argument error (-1) found before any
+ * launch; n == 0 returns 0 and launches nothing.  One lane per query, a step is one dependent byte load.
+ * Both calls are synchronous and ordered on the handle's stream; pf_last_kernel_ms reports the kernel. */
+int pf_dist_field_parents(pf_handle* h, int32_t allow_diag, int32_t restrict_corner, int32_t K, const double* d_fields,
+                          uint8_t* d_parents);
+int pf_dist_field_paths(pf_handle* h, int32_t K, const uint8_t* d_parents, const double* d_fields, int32_t n,
+                        const int32_t* d_field_idx, const int32_t* d_target, int32_t reverse, int32_t path_cap, int32_t* d_cells,
+                        int32_t* d_len, int32_t* d_status, int32_t* d_chosen);
+
 /* Tuning knobs (results never change): "maaco_pack8_min" ants per batch from which eight ants share a wavefront
  * (default 2048); "maaco_load_ahead" the packed walk kernel's load-ahead form (all of a step's loads issued together plus touches of the
  * records two steps ahead): -1 (default) for batches of at most one wavefront per SIMD, 0 never, 1 always;

@@ -4679,3 +4679,72 @@ int pf_dist_field_batch(pf_handle* h, int32_t allow_diag, int32_t restrict_corne
 }
 
 }  // extern "C"
+
+// ---------------------------------------------------------------------------
+// Routing trees: DijkstraSolver's paths from a distance field (pf_field_paths.h).  pf_dist_field_parents turns K
+// fields into K parent maps (one byte per cell) by the field-only rule; pf_dist_field_paths chases n (field, target) queries
+// through them into path rows laid out as pf_astar_batch's.  Both keep nothing on the handle but the error word of the
+// distance-field control block.
+// ---------------------------------------------------------------------------
+#include "pf_field_paths.h"
+
+extern "C" {
+
+int pf_dist_field_parents(pf_handle* h, int32_t allow_diag, int32_t restrict_corner, int32_t K, const double* d_fields, uint8_t* d_parents) {
+  if (!h) return -2;
+  if (K < 1 || !d_fields || !d_parents) { failmsg(h, "pf_dist_field_parents: bad arguments (K >= 1, fields and parents must not be null)"); return -1; }
+  auto run = [&]() -> int {
+    CK(hipSetDevice(h->device));
+    if (!h->d_df_ctl) {                                             // (fields computed elsewhere: no control block yet)
+      if (hipMalloc(&h->d_df_ctl, sizeof(int) * 64) != hipSuccess) {
+        (void)hipGetLastError();
+        h->d_df_ctl = nullptr;
+        return failmsg(h, "pf_dist_field_parents: no device memory for the error word");
+      }
+      h->df_ctl_cap = 64;
+    }
+    CK(hipMemsetAsync(h->d_df_ctl, 0, sizeof(int), h->stream));
+    const uint8_t* mm = allow_diag ? (restrict_corner ? h->d_mm_r1 : h->d_mm_r0) : (restrict_corner ? h->d_mm_r1_nd : h->d_mm_r0_nd);
+    const unsigned gx = (unsigned)((h->RC + PF_FP_THREADS - 1) / PF_FP_THREADS), gy = (unsigned)(K < 65535 ? K : 65535);
+    CK(hipEventRecord(h->ev0, h->stream));
+    hipLaunchKernelGGL(k_dist_field_parent_map_thread_per_cell<>, dim3(gx, gy), dim3(PF_FP_THREADS), 0, h->stream, mm, h->RC, h->C, K, d_fields, d_parents,
+                       h->d_df_ctl);
+    CK(hipGetLastError());
+    CK(hipEventRecord(h->ev1, h->stream));
+    int err = 0;
+    CK(hipMemcpyAsync(&err, h->d_df_ctl, sizeof(int), hipMemcpyDeviceToHost, h->stream));
+    CK(hipStreamSynchronize(h->stream));
+    CK(hipEventElapsedTime(&h->last_ms, h->ev0, h->ev1));
+    h->d2h_small += 1;
+    if (err) return failmsg(h, "pf_dist_field_parents: a finite cell has no parent: the fields are no fixed point of this grid and policy");
+    return 0;
+  };
+  return run() ? -1 : 0;
+}
+
+int pf_dist_field_paths(pf_handle* h, int32_t K, const uint8_t* d_parents, const double* d_fields, int32_t n, const int32_t* d_field_idx,
+                        const int32_t* d_target, int32_t reverse, int32_t path_cap, int32_t* d_cells, int32_t* d_len, int32_t* d_status,
+                        int32_t* d_chosen) {
+  if (!h) return -2;
+  if (K < 1 || n < 0 || path_cap < 1 || !d_parents || !d_target || !d_cells || !d_len || !d_status || (!d_field_idx && !d_fields)) {
+    failmsg(h, "pf_dist_field_paths: bad arguments (K >= 1, n >= 0, path_cap >= 1; parents, targets and outputs must not be null; "
+               "without field indices the fields are needed for the nearest source)");
+    return -1;
+  }
+  if (n == 0) return 0;
+  auto run = [&]() -> int {
+    CK(hipSetDevice(h->device));
+    CK(hipEventRecord(h->ev0, h->stream));
+    hipLaunchKernelGGL(k_dist_field_trace_query_lanes<>, dim3((unsigned)((n + PF_FP_TRACE_THREADS - 1) / PF_FP_TRACE_THREADS)), dim3(PF_FP_TRACE_THREADS), 0,
+                       h->stream, d_parents, d_fields, h->RC, h->C, K, n, d_field_idx, d_target, reverse ? 1 : 0, path_cap, d_cells, d_len, d_status,
+                       d_chosen);
+    CK(hipGetLastError());
+    CK(hipEventRecord(h->ev1, h->stream));
+    CK(hipStreamSynchronize(h->stream));
+    CK(hipEventElapsedTime(&h->last_ms, h->ev0, h->ev1));
+    return 0;
+  };
+  return run() ? -1 : 0;
+}
+
+}  // extern "C"

@@ -156,6 +156,8 @@ SYMBOLS = {
     "pf_pso_scan_batch": (C.c_int, [_vp, _i32, _i32, _i32] + [_vp] * 8),
     "pf_pso_commit_batch": (C.c_int, [_vp, _i32, _i32, _i32, _i32, _i32, _i32] + [_vp] * 21),
     "pf_dist_field_batch": (C.c_int, [_vp, _i32, _i32, _i32, _vp, _vp, _vp]),
+    "pf_dist_field_parents": (C.c_int, [_vp, _i32, _i32, _i32, _vp, _vp]),
+    "pf_dist_field_paths": (C.c_int, [_vp, _i32, _vp, _vp, _i32, _vp, _vp, _i32, _i32, _vp, _vp, _vp, _vp]),
 }
 
 

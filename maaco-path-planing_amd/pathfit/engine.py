@@ -233,7 +233,28 @@ class Engine:
             if info is not None:
                 info.free()
 
+    def dist_field_parents(self, K, d_fields, d_parents, allow_diag=True, restrict_corner=True):
+        """Parent maps of K fields (d_fields [K, R * C] doubles, the policy they were computed under) -> d_parents [K, R * C] uint8:
+        0..7 the move of the tree's last step into the cell, 8 the source, 255 no route (pf_dist_field_parents)."""
+        self._ck(self.L.pf_dist_field_parents(self.h, int(allow_diag), int(restrict_corner), int(K), d_fields.ptr if d_fields else None,
+                                              d_parents.ptr if d_parents else None))
+        self._logk("dist_field_parents")
+
+    def dist_field_paths(self, K, d_parents, d_target, n, path_cap, d_cells, d_len, d_status, d_field_idx=None, d_fields=None,
+                         reverse=False, d_chosen=None):
+        """n queries (d_field_idx[q], d_target[q]) traced through the parent maps into rows laid out as astar_batch's; d_field_idx
+        None: each query takes its nearest source by d_fields; d_chosen int32[n] takes the field used (pf_dist_field_paths)."""
+        self._ck(self.L.pf_dist_field_paths(self.h, int(K), d_parents.ptr if d_parents else None, d_fields.ptr if d_fields else None, int(n),
+                                            d_field_idx.ptr if d_field_idx else None, d_target.ptr if d_target else None, int(bool(reverse)),
+                                            int(path_cap), d_cells.ptr if d_cells else None, d_len.ptr if d_len else None,
+                                            d_status.ptr if d_status else None, d_chosen.ptr if d_chosen else None))
+        self._logk("dist_field_paths")
+
     # ------------------------------------------------------------------ K1
+    def score_batch(self, n, path_cap, d_cells, d_len, d_stats, sp):
+        """Rows of astar_batch's layout in HBM -> d_stats [n, 5] doubles (pf_score_batch)."""
+        self._ck(self.L.pf_score_batch(self.h, C.byref(sp), int(n), int(path_cap), d_cells.ptr, d_len.ptr, d_stats.ptr))
+
     def score_host(self, paths, sp):
         n = len(paths)
         cap = max([len(p) for p in paths] + [1])
