@@ -237,7 +237,8 @@ constexpr unsigned long long make_pairs_eh() { unsigned long long m = 0; for (in
 #define PF_SW_SPILL 16384
 static_assert((double)PF_SW_NBK >= 2.8285 * PF_SW_Q + 1.0, "a push lies at most 2*sqrt(2) above the pop that made it: the circular range must cover that");
 static_assert(4 * (PF_SW_NBK + 1) <= PF_SORT_LDS, "bucket counts and the sort's staging area share the wave's LDS");
-static_assert(((size_t)(PF_SW_NBK + 1) * PF_SW_CAP + PF_SW_SPILL) * 16 <= (size_t)PF_POOL_STRIDE, "bucket pool + spill list fit the slot's HBM scratch");
+#define PF_SW_DUMP 64       /* one entry per lane behind the spill list: where a lane without a pool push stores in a rotated trip (never read) */
+static_assert(((size_t)(PF_SW_NBK + 1) * PF_SW_CAP + PF_SW_SPILL + PF_SW_DUMP) * 16 <= (size_t)PF_POOL_STRIDE, "bucket pool + spill list + dump entries fit the slot's HBM scratch");
 // A pool entry is 16 bytes: (g, packed cell).  Its f is not stored: f = g + h(cell) is the very fp64 operation that
 // produced it when the entry was pushed (astar.py:90 / MPA.py:140), so reading an entry back recomputes it bit for bit
 // -- one 16-byte store per push and one 16-byte load per refilled entry instead of three scattered ones each
@@ -447,9 +448,16 @@ PF_DEV void take_smallest64(const SwPool& P, int bi, int c0, double& wf, double&
 #ifdef PF_STAMPS
 #define SW_T(var) const unsigned long long var = __builtin_amdgcn_s_memtime(); __builtin_amdgcn_sched_barrier(0);
 #define SW_ACC(i, a, b) sw_acc[i] += (b) - (a);
+#define SW_SET(var, t) var = (t);
 #else
 #define SW_T(var)
 #define SW_ACC(i, a, b)
+#define SW_SET(var, t)
+#endif
+// Trip rotation: a trip that neither feeds the window nor is followed by a refill issues the NEXT trip's record load
+// right after its own record stores and appends to the pool in that load's shadow.  0: off, 1: the MPA variant only, 2: every variant.
+#ifndef PF_ROTATE
+#define PF_ROTATE 2
 #endif
 // VARIANT 0, at refill: an entry whose cell is closed or whose g is no longer the record's g was superseded by a
 // decrease-key (astar.py:96-100 rewrites it in place) and can never be a pop of the reference -- g only falls and a
@@ -657,80 +665,92 @@ __device__ __forceinline__ int pop_loop_sw(const Grid& G, Rec* rec, const Open& 
 #ifdef PF_STAMPS
   unsigned long long sw_acc[8] = {0, 0, 0, 0, 0, 0, 0, 0}, sw_cnt[8] = {0, 0, 0, 0, 0, 0, 0, 0};
   unsigned long long sw_er[6] = {0, 0, 0, 0, 0, 0};           // early refills: count, entries, largest run, buckets, clocks waiting for the entries, clocks sorting
+  unsigned long long sw_rot[2] = {0, 0};                      // rotated trips: clocks of the rotated issue site (heads + addresses + load issue), count
+  unsigned long long t3 = 0;                                  // the trip's loads have arrived
 #endif
+  // ---- pop: up to seven heads of the window at once, nine lanes each ----
+  // The window is sorted, so the next pops are known.  Lane group h relaxes head h in registers; the groups replay
+  // each other's effects on the cells they share (below), and head h takes effect (and counts as a pop) iff every
+  // earlier head did, no earlier head pushed a key at or below head h's f, no earlier head improved head h's own
+  // cell, and no earlier head was the target: exactly the pops, in order, that the sequential loop would make.  A
+  // head that does not qualify simply stays in the window.
+  constexpr int NH = 7;
+  static_assert(NH == 7, "the lane <-> (group, sub) and lane <-> (head pair) maps below are written for 7 x 9 lanes");
+  // A trip begins at one of two places: at the top of the loop (after the refills), or -- ROTATED -- in the tail of the trip before
+  // it, right behind that trip's record stores (see there).  Both run the same two pieces (trip_heads, trip_shadow: below), which leave
+  // the trip's state in the locals declared at the top of the outer loop.
+  constexpr bool ROT = PF_ROTATE == 2 || (PF_ROTATE == 1 && SEM == 1);
+#ifdef PF_STAMPS
+  constexpr bool STAMPS = true;
+#else
+  constexpr bool STAMPS = false;
+#endif
+  // The outer loop is the way into a trip from the top; the inner one chains the trips that follow a rotated one (they never
+  // pass the top: the compiler sees that no load of the rotated site is in flight there).
   for (;;) {
-    SW_T(t0)
-    [[maybe_unused]] unsigned scope_anchor = 0;                 // dead on purpose: it and the block of the spill section keep the loop's compiled code
-    if (PF_EARLY_REFILL) sw_early_refill<SEM>(P, W, O, rec, C, lane, PF_EARLY_BELOW);
-    if (W.wp == W.wn) {
-      const int rr_ = sw_refill<SEM, PLAT>(P, W, O, rec, C, lane);
-      if (rr_ == 1) { status = 1; break; }
-      if (rr_ == 3) { status = 3; break; }
-      if (rr_ == 4) continue;
-    }
-    SW_T(t1)
-    // ---- pop: up to seven heads of the window at once, nine lanes each ----
-    // The window is sorted, so the next pops are known.  Lane group h relaxes head h in registers; the groups replay
-    // each other's effects on the cells they share (below), and head h takes effect (and counts as a pop) iff every
-    // earlier head did, no earlier head pushed a key at or below head h's f, no earlier head improved head h's own
-    // cell, and no earlier head was the target: exactly the pops, in order, that the sequential loop would make.  A
-    // head that does not qualify simply stays in the window.
-    constexpr int NH = 7;
-    static_assert(NH == 7, "the lane <-> (group, sub) and lane <-> (head pair) maps below are written for 7 x 9 lanes");
-    const int nh = W.wn - W.wp < NH ? W.wn - W.wp : NH;
-    // The lane-role predicates (grp == h, sub < 8, ...) are recomputed where they are used (one v_cmp each): as
-    // loop invariants they sat in ~25 SGPR pairs, overflowed the scalar register file and came back through two
-    // v_readlane each, >100 instructions per trip.
-    int grp = grp0, sub = sub0, lane_t = lane;
-    asm volatile("" : "+v"(grp), "+v"(sub), "+v"(lane_t));
-    // my group's head cell: ONE crossbar permute from the window lane that holds it (seven v_readlane + six selects -- ~40 wave
-    // instructions with their scalar index arithmetic -- bought the load addresses ~70 clocks of LDS latency at 4x the issue slots)
-    const int hsrc = W.wp + grp < 64 ? W.wp + grp : 63;            // my group's head lives in this window lane
-    const int prc = bperm_i(hsrc, W.wc);                        // (r << 16 | c)
-    const pf_u64 mHave = B(grp < nh);                           // (lane 63 is group 7: never; as a wave mask, see below)
-    const bool have = PL(mHave);
-    const int pr = prc >> 16, pc = prc & 0xFFFF;
-    const int cur = pr * C + pc;
-    // ---- one batch of loads: 8 neighbour records, the cell's own record, its move mask (and g, MPA variant) ----
-    int nidx = cur + doff;
-    nidx = nidx < 0 ? 0 : (nidx >= RC ? RC - 1 : nidx);        // the move mask rejects what the clamp invents
+    int nh = 0, grp = 0, sub = 0, lane_t = 0, hsrc = 0, prc = 0, pr = 0, pc = 0, cur = 0, nidx = 0, rch = 0, nr = 0, nc = 0;
+    pf_u64 mHave = 0ull, nearg = 0ull;
+    bool have = false, rotated = false;
     Rec rn; rn.g = 0.0; rn.tagmm = 0; rn.meta = 0;
-    double cur_g = 0.0;
-    // ONE vector-memory instruction per trip: the head's move mask is the low byte of its own record (every record carries its
-    // cell's static mask: k_slot_init, and every store keeps it), which the self lane loads anyway -- the separate byte load from
-    // the mask table was a second fully divergent access (address processing for 63 lanes, seven more sectors) for nothing.
-    if (have) rn = rec[nidx];                                   // (MPA variant: g_score[current] comes from the self lane's record too)
-#if defined(PF_STAMPS) && defined(PF_WAIT_EARLY)
-    { SW_T(ti_) asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); SW_T(tj_) sw_cnt[0] += tj_ - ti_; }   // diagnostic: the bare load latency
-#endif
-    // -- everything below is in the shadow of the loads --
-    const double pg = bperm_d(hsrc, W.wg);
-    const unsigned long long f_last = dbits(bcast_d(W.wf, W.wp + nh - 1));   // f of the trip's last head (uniform) for the push test below
-    // lanes 0..48 look at the head pair (e, h) = (lane / 7, lane % 7): too close to be independent?
-    const int pe = (lane_t * 37) >> 8, ph = lane_t - 7 * pe;
-    const int rce = bperm_i(W.wp + pe < 64 ? W.wp + pe : 63, W.wc), rch = bperm_i(W.wp + ph < 64 ? W.wp + ph : 63, W.wc);
-    const int nr = pr + ddr, nc = pc + ddc;
-    const int hdr = nr - tr, hdc = nc - tc;                    // |.| < 2^15: the squares fit 32 bits
-    double hn = VARIANT == 2 ? 0.0 : __builtin_sqrt((double)(__mul24(hdr, hdr) + __mul24(hdc, hdc)));   // astar.py:90 / MPA.py:140 / dijkstra.py:89 (24-bit multiplies run at full rate)
-    asm volatile("" : "+v"(hn));                               // computed in the shadow of the loads
-    // Heads within 2 cells of each other touch common records.  Instead of stopping the trip there, every lane
-    // replays, in head order, what the earlier heads of this trip do to ITS cell: for an earlier head e the lane that
-    // handles the same cell is fixed by geometry (cell - head e in [-1,1]^2 picks e's move lane, or e's self lane = the
-    // pop of that cell).  The pair lanes (e, h) = (lane / 7, lane % 7) classify head h - head e once (25 offsets +
-    // "far"); each lane then reads its source lane from a table in LDS, [e][offset][sub] -> bpermute address (bit 0:
-    // head e IS my cell; 63*4: none).  All in the shadow of the loads.
-    const int Dr_ = (rch >> 16) - (rce >> 16), Dc_ = (rch & 0xFFFF) - (rce & 0xFFFF);
-    // (predicates as wave masks from here on: B(compare) / PL(mask), pf_device.h -- every ballot below is a scalar AND)
-    constexpr pf_u64 PAIRS_EH = make_pairs_eh();                // lane < 49 && e < h
-    const pf_u64 nearg = PAIRS_EH & B(ph < nh) & B((unsigned)(Dr_ + 2) <= 4u) & B((unsigned)(Dc_ + 2) <= 4u);   // bit 7e+h
-    const int pcode = PL(nearg) ? (Dr_ + 2) * 5 + (Dc_ + 2) : 25;
-    const unsigned char* geo = (const unsigned char*)O.lf + PF_GEO_OFF;
+    double pg = 0.0, hn = 0.0;
+    unsigned long long f_last = 0ull;
     int fsrc[NH - 1];
-    {
+    // (1) the heads' cells, the addresses and the trip's ONE batch of loads
+    auto trip_heads = [&]() {
+      nh = W.wn - W.wp < NH ? W.wn - W.wp : NH;
+      // The lane-role predicates (grp == h, sub < 8, ...) are recomputed where they are used (one v_cmp each): as
+      // loop invariants they sat in ~25 SGPR pairs, overflowed the scalar register file and came back through two
+      // v_readlane each, >100 instructions per trip.
+      grp = grp0; sub = sub0; lane_t = lane;
+      asm volatile("" : "+v"(grp), "+v"(sub), "+v"(lane_t));
+      // my group's head cell: ONE crossbar permute from the window lane that holds it (seven v_readlane + six selects -- ~40 wave
+      // instructions with their scalar index arithmetic -- bought the load addresses ~70 clocks of LDS latency at 4x the issue slots)
+      hsrc = W.wp + grp < 64 ? W.wp + grp : 63;                   // my group's head lives in this window lane
+      prc = bperm_i(hsrc, W.wc);                                  // (r << 16 | c)
+      mHave = B(grp < nh);                                        // (lane 63 is group 7: never; as a wave mask, see below)
+      have = PL(mHave);
+      pr = prc >> 16; pc = prc & 0xFFFF;
+      cur = pr * C + pc;
+      // ---- one batch of loads: 8 neighbour records, the cell's own record, its move mask (and g, MPA variant) ----
+      nidx = cur + doff;
+      nidx = nidx < 0 ? 0 : (nidx >= RC ? RC - 1 : nidx);        // the move mask rejects what the clamp invents
+      rn.g = 0.0; rn.tagmm = 0; rn.meta = 0;
+      // ONE vector-memory instruction per trip: the head's move mask is the low byte of its own record (every record carries its
+      // cell's static mask: k_slot_init, and every store keeps it), which the self lane loads anyway -- the separate byte load from
+      // the mask table was a second fully divergent access (address processing for 63 lanes, seven more sectors) for nothing.
+      if (have) rn = rec[nidx];                                   // (MPA variant: g_score[current] comes from the self lane's record too)
+#if defined(PF_STAMPS) && defined(PF_WAIT_EARLY)
+      { SW_T(ti_) asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); SW_T(tj_) sw_cnt[0] += tj_ - ti_; }   // diagnostic: the bare load latency
+#endif
+    };
+    // (2) what the relaxation needs besides the records -- in the shadow of the loads
+    auto trip_shadow = [&]() {
+      pg = bperm_d(hsrc, W.wg);
+      f_last = dbits(bcast_d(W.wf, W.wp + nh - 1));               // f of the trip's last head (uniform) for the push test below
+      // lanes 0..48 look at the head pair (e, h) = (lane / 7, lane % 7): too close to be independent?
+      const int pe = (lane_t * 37) >> 8, ph = lane_t - 7 * pe;
+      const int rce = bperm_i(W.wp + pe < 64 ? W.wp + pe : 63, W.wc);
+      rch = bperm_i(W.wp + ph < 64 ? W.wp + ph : 63, W.wc);
+      nr = pr + ddr; nc = pc + ddc;
+      const int hdr = nr - tr, hdc = nc - tc;                    // |.| < 2^15: the squares fit 32 bits
+      hn = VARIANT == 2 ? 0.0 : __builtin_sqrt((double)(__mul24(hdr, hdr) + __mul24(hdc, hdc)));   // astar.py:90 / MPA.py:140 / dijkstra.py:89 (24-bit multiplies run at full rate)
+      asm volatile("" : "+v"(hn));                               // computed in the shadow of the loads
+      // Heads within 2 cells of each other touch common records.  Instead of stopping the trip there, every lane
+      // replays, in head order, what the earlier heads of this trip do to ITS cell: for an earlier head e the lane that
+      // handles the same cell is fixed by geometry (cell - head e in [-1,1]^2 picks e's move lane, or e's self lane = the
+      // pop of that cell).  The pair lanes (e, h) = (lane / 7, lane % 7) classify head h - head e once (25 offsets +
+      // "far"); each lane then reads its source lane from a table in LDS, [e][offset][sub] -> bpermute address (bit 0:
+      // head e IS my cell; 63*4: none).  All in the shadow of the loads.
+      const int Dr_ = (rch >> 16) - (rce >> 16), Dc_ = (rch & 0xFFFF) - (rce & 0xFFFF);
+      // (predicates as wave masks from here on: B(compare) / PL(mask), pf_device.h -- every ballot below is a scalar AND)
+      constexpr pf_u64 PAIRS_EH = make_pairs_eh();                // lane < 49 && e < h
+      nearg = PAIRS_EH & B(ph < nh) & B((unsigned)(Dr_ + 2) <= 4u) & B((unsigned)(Dc_ + 2) <= 4u);   // bit 7e+h
+      const int pcode = PL(nearg) ? (Dr_ + 2) * 5 + (Dc_ + 2) : 25;
+      const unsigned char* geo = (const unsigned char*)O.lf + PF_GEO_OFF;
 #pragma unroll
-      for (int e = 0; e < NH - 1; ++e) fsrc[e] = 63 * 4;        // no counterpart anywhere ...
-      if (nearg) {                                              // ... unless SOME pair of heads is near (one wave-uniform test for the whole block)
-        int pc_[NH - 1];                                        // the six permutes go out together, then the six table reads:
+      for (int e = 0; e < NH - 1; ++e) fsrc[e] = 63 * 4;          // no counterpart anywhere ...
+      if (nearg) {                                                // ... unless SOME pair of heads is near (one wave-uniform test for the whole block)
+        int pc_[NH - 1];                                          // the six permutes go out together, then the six table reads:
 #pragma unroll                                                  // two LDS round trips in all instead of two per row
         for (int e = 0; e < NH - 1; ++e) pc_[e] = bperm_i(7 * e + grp, pcode);   // (groups <= e read a pair lane with pe >= ph: "far")
 #pragma unroll
@@ -738,14 +758,33 @@ __device__ __forceinline__ int pop_loop_sw(const Grid& G, Rec* rec, const Open& 
       }
 #pragma unroll
       for (int e = 0; e < NH - 1; ++e) asm volatile("" : "+v"(fsrc[e]));
+    };
+    {
+      SW_T(t0)
+      [[maybe_unused]] unsigned scope_anchor = 0;               // dead on purpose: it and the block of the spill section keep the loop's compiled code
+      if (PF_EARLY_REFILL) sw_early_refill<SEM>(P, W, O, rec, C, lane, PF_EARLY_BELOW);
+      if (W.wp == W.wn) {
+        const int rr_ = sw_refill<SEM, PLAT>(P, W, O, rec, C, lane);
+        if (rr_ == 1) { status = 1; break; }
+        if (rr_ == 3) { status = 3; break; }
+        if (rr_ == 4) continue;
+      }
+      SW_T(t1)
+      trip_heads();
+      // -- everything below is in the shadow of the loads --
+      trip_shadow();
+      SW_T(t2)
+      // The wait for the records stands HERE, once per way into the trip (the rotated way has its own, below): behind this load
+      // nothing else is in flight, behind the rotated one the pool store is, and a wait that both ways shared would have to
+      // assume the worse of the two.
+      if (ROT || STAMPS) asm volatile("; trip: records" :: "v"(rn.meta));
+      SW_T(t2b)
+      SW_ACC(0, t0, t1) SW_ACC(1, t1, t2) SW_ACC(2, t2, t2b) SW_SET(t3, t2b)
     }
-    SW_T(t2)
+    for (;;) {
     // ---- relax the 8 neighbours of each head in registers ----
-    const uint32_t cur_meta = rn.meta;
-#ifdef PF_STAMPS
-    { unsigned tmp_ = cur_meta; asm volatile("" : "+v"(tmp_)); }   // the loads have arrived
-#endif
-    SW_T(t3)                          // meaningful in the self lanes (sub == 8)
+    const uint32_t cur_meta = rn.meta;                           // meaningful in the self lanes (sub == 8)
+    double cur_g = 0.0;
     // VARIANT 0: an entry superseded by a decrease-key (astar.py:96-100 rewrites it in place) is not a pop of the
     // reference: its head is consumed without effect and without being counted
     constexpr pf_u64 SELF7 = 0x7Full, MOVES = 0x7FFFFFFFFFFFFF80ull;   // lanes 0..6: the self lanes (sub == 8); lanes 7..62: the move lanes (sub < 8)
@@ -858,7 +897,8 @@ __device__ __forceinline__ int pop_loop_sw(const Grid& G, Rec* rec, const Open& 
     const unsigned E = real & ~tgtm;                            // heads whose relaxation takes effect (nothing is relaxed at the target)
     steps += __builtin_popcount(real);
     SW_T(t4)
-    if (consumed == 0) { status = 2; break; }                   // only the step cap can stop head 0
+    SW_ACC(3, t3, t4)
+    if (consumed == 0) { status = 2; goto done; }                   // only the step cap can stop head 0
     W.wp += consumed;
     const pf_u64 mEff = B(((E >> grp) & 1u) != 0u);
     const pf_u64 mBE = mBetter & mEff;
@@ -887,6 +927,71 @@ __device__ __forceinline__ int pop_loop_sw(const Grid& G, Rec* rec, const Open& 
     const pf_u64 mInr = B(pba - W.bcur < NBK);                 // inside the circular bucket range (front bucket: always)
     int pat = 0;
     const unsigned long long pm = mPush, im0 = mTow;
+#ifdef PF_TRIPS
+    auto trips_note = [&]() {
+      n_max += 1;                                               // diagnostic build: trips instead of the open-list high-water mark
+      {                                                         // ... and why each trip stopped where it did
+        const int f0 = __builtin_ctz((((viol | c1) & ~stale7) | ~exist7) | 0x80u);
+        if (f0 >= nh) { if (nh < NH) tr_short += 1; else tr_full += 1; }
+        else if ((viol >> f0) & 1u) tr_viol += 1; else tr_near += 1;      // tr_near: an earlier head improved the head's own cell
+        // how far the trip could go if nearness were resolved by forwarding and only an earlier head improving
+        // head h's own cell stopped it (decisions taken from the loaded state: an estimate)
+        tr_pot += (unsigned)f0;
+      }
+    };
+#endif
+    // ---- the ROTATED trip ----
+    // Nothing of what follows feeds the next trip's heads unless a push enters the window or a refill is due.  So when no push goes
+    // to the window, at least PF_EARLY_BELOW entries are left in it (neither refill runs on that many), and the trip is not the
+    // last one (target, step cap), the NEXT trip begins here: its heads' cells, its addresses and its record load go out right
+    // behind this trip's record stores (one wave, in-order vector memory: the load sees them, as it does from the top of the
+    // loop), and the pool appends, the counters and the next trip's shadow block run while the records travel.  The pool store
+    // is UNCONDITIONAL there -- a lane without a pool push writes its dump entry, which nothing reads -- so the number of vector-
+    // memory instructions behind the load is static and the wait for the records is a counted one (vmcnt(1)): it does not
+    // wait for the store's acknowledgement.  (The spill stores stay under their branch: they only add to that number.)
+    if (ROT) rotated = (mTow == 0ull) & !hit & (W.wn - W.wp >= PF_EARLY_BELOW) & (steps < max_steps);
+    if (ROT && rotated) {
+#ifdef PF_TRIPS
+      trips_note();
+#endif
+      SW_T(r0)
+      trip_heads();
+      SW_T(r1)
+      if (PL(mTop & mInr)) pat = __hip_atomic_fetch_add(&P.cnt[pb], 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+      W.n_pool += __builtin_popcountll(mTop);
+      push_s += (unsigned)__builtin_popcountll(SEM == 0 ? (mPush & ~mInop) : mPush);   // heappush calls of the reference
+      const pf_u64 mFits = mInr & B(pat < CAP);
+      ent_put(P.be + (PL(mTop & mFits) ? pb * CAP + pat : (NBK + 1) * CAP + PF_SW_SPILL + lane), tent, nrc);
+      const unsigned long long sm = mTop & ~mFits;              // bucket full or beyond the circular range: spill list
+      if (sm) {
+        if (PL(sm)) {
+          if (PL(mInr)) __hip_atomic_fetch_add(&P.cnt[pb], -1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);   // a number past the end: give it back
+          const int at = W.n_spill + __builtin_popcountll(sm & ((1ull << lane) - 1ull));
+          if (at < PF_SW_SPILL) ent_put(P.se + at, tent, nrc);
+        }
+        W.n_spill += __builtin_popcountll(sm);
+        st.spills += (unsigned)__builtin_popcountll(sm);
+        if (W.n_spill > PF_SW_SPILL) {                         // never silent
+          asm volatile("; rotated trip: leaves" :: "v"(rn.meta));   // (no load in flight on any way out of the loop: the top's waits stay exact)
+          status = 3; goto done;
+        }
+      }
+      PF_LDS_ORDER();
+#ifndef PF_TRIPS
+      const int n_open = W.n_pool + (W.wn - W.wp);
+      if (n_open > n_max) n_max = n_open;
+#endif
+      SW_T(r2)
+      trip_shadow();
+      SW_T(r3)
+      asm volatile("; rotated trip: records" :: "v"(rn.meta));   // (the counted wait: see the top of the loop)
+      SW_T(r4)
+      SW_ACC(4, t4, r0) SW_ACC(6, r1, r2) SW_ACC(1, r2, r3) SW_ACC(2, r3, r4) SW_SET(t3, r4)
+#ifdef PF_STAMPS
+      sw_acc[7] += 1; sw_rot[0] += r1 - r0; sw_rot[1] += 1;
+#endif
+      continue;
+    }
     if (PL(mTop & mInr)) pat = __hip_atomic_fetch_add(&P.cnt[pb], 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
     W.n_pool += __builtin_popcountll(pm & ~im0);
     push_s += (unsigned)__builtin_popcountll(SEM == 0 ? (mPush & ~mInop) : mPush);   // heappush calls of the reference
@@ -910,7 +1015,7 @@ __device__ __forceinline__ int pop_loop_sw(const Grid& G, Rec* rec, const Open& 
       // (an eviction inside this loop may have lowered the limit below this key: sw_add re-checks)
       if (!sw_add(P, W, bcast_d(fnew, l), bcast_d(tent, l), kc, lane)) { status = 3; break; }
     }
-    if (status == 3) break;
+    if (status == 3) goto done;
     SW_T(t6)
     {                                                           // (a scope of its own on purpose, like scope_anchor: DESIGN.md 4.2)
       const pf_u64 mFits = mInr & B(pat < CAP);
@@ -924,35 +1029,31 @@ __device__ __forceinline__ int pop_loop_sw(const Grid& G, Rec* rec, const Open& 
         }
         W.n_spill += __builtin_popcountll(sm);
         st.spills += (unsigned)__builtin_popcountll(sm);
-        if (W.n_spill > PF_SW_SPILL) { status = 3; break; }     // never silent
+        if (W.n_spill > PF_SW_SPILL) { status = 3; goto done; } // never silent
       }
     }
-    if (hit) { status = 0; break; }
+    if (hit) { status = 0; goto done; }
     PF_LDS_ORDER();
     SW_T(t7)
-    SW_ACC(0, t0, t1) SW_ACC(1, t1, t2) SW_ACC(2, t2, t3) SW_ACC(3, t3, t4) SW_ACC(4, t4, t5) SW_ACC(5, t5, t6) SW_ACC(6, t6, t7)
+    SW_ACC(4, t4, t5) SW_ACC(5, t5, t6) SW_ACC(6, t6, t7)
 #ifdef PF_STAMPS
     sw_acc[7] += 1;
 #endif
 #ifdef PF_TRIPS
-    n_max += 1;                                                 // diagnostic build: trips instead of the open-list high-water mark
-    {                                                           // ... and why each trip stopped where it did
-      const int f0 = __builtin_ctz((((viol | c1) & ~stale7) | ~exist7) | 0x80u);
-      if (f0 >= nh) { if (nh < NH) tr_short += 1; else tr_full += 1; }
-      else if ((viol >> f0) & 1u) tr_viol += 1; else tr_near += 1;      // tr_near: an earlier head improved the head's own cell
-      // how far the trip could go if nearness were resolved by forwarding and only an earlier head improving
-      // head h's own cell stopped it (decisions taken from the loaded state: an estimate)
-      tr_pot += (unsigned)f0;
-    }
+    trips_note();
 #else
     const int n_open = W.n_pool + (W.wn - W.wp);
     if (n_open > n_max) n_max = n_open;
 #endif
+    break;                                                      // the next trip starts at the top
+    }
   }
+done:
 #ifdef PF_STAMPS
   if (lane == 0) {
     for (int i = 0; i < 8; ++i) { atomicAdd(&g_stamps[i], sw_acc[i]); atomicAdd(&g_stamps[8 + i], sw_cnt[i]); }
     for (int i = 0; i < 6; ++i) atomicAdd(&g_stamps[16 + i], sw_er[i]);
+    for (int i = 0; i < 2; ++i) atomicAdd(&g_stamps[22 + i], sw_rot[i]);
   }
 #endif
   if (n_max > st.max_open) st.max_open = n_max;

@@ -4,7 +4,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path[:0] = [os.path.join(ROOT, "maaco-path-planing_amd"), os.path.join(ROOT, "tests")]
 import numpy as np
 from pathfit import _lib
-_lib._SO = os.path.join(ROOT, "maaco-path-planing_amd", "lib", "libpathfit_stamps.so")
+_lib._SO = os.environ.get("PF_STAMPS_LIB") or os.path.join(ROOT, "maaco-path-planing_amd", "lib", "libpathfit_stamps.so")   # (A/B: another stamps build)
 import golden_io as gio
 from pathfit.engine import Engine
 g = gio.upsample(gio.grid("g256")[0], 2)
@@ -27,7 +27,10 @@ for n in ((int(sys.argv[1]),) if len(sys.argv) > 1 else (1,)):
         print(f"us per trip (kernel time / trips of one search) {1e3 * e.last_kernel_ms() / (trips / n):.3f}")
         print(f"n={n} v{v}: {e.last_kernel_ms():.1f} ms pops {pops} trips {trips} pops/trip {pops / trips:.2f} clocks/trip {out[:7].sum() / trips:.0f}: " +
               "; ".join(f"{names[i]} {out[i] / trips:.0f}" for i in range(7)))
-        c = out[8:16].astype(float); er = out[16:].astype(float)
+        if out[23] > 0:     # rotated trips: their load goes out in the tail of the trip before; their pool appends are in the "pool" column
+            print(f"      rotated trips: {int(out[23])} of {trips} ({100.0 * out[23] / trips:.1f} %), rotated issue site (heads + addresses + load issue) "
+                  f"{out[22] / out[23]:.0f} clocks each = {out[22] / trips:.0f} per trip on top of the columns above")
+        c = out[8:16].astype(float); er = out[16:22].astype(float)
         if er[0] > 0:
             print(f"      early refills: {int(er[0])} (every {trips / er[0]:.1f} trips), entries avg {er[1] / er[0]:.1f}, buckets avg {er[3] / er[0]:.1f}, largest bucket avg {er[2] / er[0]:.1f}; "
                   f"clocks per early refill: waiting for the pool entries {er[4] / er[0]:.0f}, sort {er[5] / er[0]:.0f}")
