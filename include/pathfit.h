@@ -417,6 +417,31 @@ int pf_dist_field_paths(pf_handle* h, int32_t K, const uint8_t* d_parents, const
                         const int32_t* d_field_idx, const int32_t* d_target, int32_t reverse, int32_t path_cap, int32_t* d_cells,
                         int32_t* d_len, int32_t* d_status, int32_t* d_chosen);
 
+/* ---- nearest-source fields: one field per source SET, and the source that owns each cell (pathfit.NearestSourceField) ------
+ * B sets in CSR form, both HOST arrays: set b is src[set_off[b] .. set_off[b + 1]), flat cell ids.
+ * pf_dist_field_merged: d_out[b*RC + v] = the length of the shortest path into v from the NEAREST source of set b: the least
+ * fixed point of D[s] = 0 for every free s of the set, D[v] = min fl(D[u] + w) otherwise -- bit for bit the elementwise minimum
+ * of pf_dist_field_batch's rows for the set's sources, in 8 RC bytes whatever the size of the set and in
+ * floor(largest distance to the nearest source) + 1 levels.  A source on an obstacle is skipped, a source listed twice counts
+ * once, a set whose sources all lie on obstacles gives an all-inf row.  d_info as pf_dist_field_batch's (the seeds count as cells
+ * reached and as appends) or NULL.  One workgroup per set, min(B, CUs) of them, on the same list slots.
+ * pf_dist_field_owners: d_owner[b*RC + v] = the index WITHIN set b of the source at the root of v's chain through d_parents,
+ * the parent maps pf_dist_field_parents computed from the merged rows (several cells of code 8 each); the lowest index where a
+ * cell is listed more than once; -1 where the code is 255.  This is the tree a dijkstra.py-shaped search seeded with the whole
+ * set leaves (the smallest (D[u], u) parent at every step), NOT the lowest index among the sources at the same distance;
+ * pf_dist_field_paths with field index b traces the same chain.  d_count (or NULL): int64[set_off[B]], the cells each source
+ * owns (integer atomics: exact).  The roots are found by pointer doubling, one launch per round, ceil(log2(n)) rounds, n the
+ * bound on the cells of a chain: RC, or the largest "levels that held a live cell" of d_info, the [B][4] block the field call
+ * wrote (or NULL).  A code outside 0..8 and 255, a step off the grid, a root that is no source of its set or a chain longer than
+ * the bound fails the call with a message; every word of d_owner is written all the same, nothing is accessed out of range.
+ * Both: B < 1, offsets that do not start at 0 or that decrease, an empty set, an id outside [0, RC) or a null pointer is an
+ * argument error (-1) whose message names the set and the index, found on the host before anything is launched.  Synchronous,
+ * ordered on the handle's stream; pf_last_kernel_ms reports the kernel(s). */
+int pf_dist_field_merged(pf_handle* h, int32_t allow_diag, int32_t restrict_corner, int32_t B, const int32_t* set_off,
+                         const int32_t* src, double* d_out, int64_t* d_info);
+int pf_dist_field_owners(pf_handle* h, int32_t B, const uint8_t* d_parents, const int32_t* set_off, const int32_t* src,
+                         const int64_t* d_info, int32_t* d_owner, int64_t* d_count);
+
 /* Tuning knobs (results never change): "maaco_pack8_min" ants per batch from which eight ants share a wavefront
  * (default 2048); "maaco_load_ahead" the packed walk kernel's load-ahead form (all of a step's loads issued together plus touches of the
  * records two steps ahead): -1 (default) for batches of at most one wavefront per SIMD, 0 never, 1 always;

@@ -4612,11 +4612,8 @@ int pf_pso_commit_batch(pf_handle* h, int32_t n, int32_t K, int32_t N, int32_t W
 // ---------------------------------------------------------------------------
 #include "pf_dist_field.h"
 
-static int dist_field_run(pf_handle* h, const char* who, int allow_diag, int restrict_corner, int K, const int32_t* src, double* d_out, int64_t* d_info) {
-  const std::string me(who);
-  if (K < 1 || !src || !d_out) return failmsg(h, me + ": bad arguments (K >= 1, sources and rows must not be null)");
-  for (int k = 0; k < K; ++k)
-    if (src[k] < 0 || src[k] >= h->RC) return failmsg(h, me + ": source " + std::to_string(k) + " lies outside the grid");
+// the handle's list slots for G workgroups (fewer where memory is short: G falls) and a control block of `words` ints
+static int dist_field_reserve(pf_handle* h, const std::string& me, int& G, size_t words) {
   CK(hipSetDevice(h->device));
   if (h->df_cus < 1) {
     int cus = 0;
@@ -4624,7 +4621,7 @@ static int dist_field_run(pf_handle* h, const char* who, int allow_diag, int res
     h->df_cus = cus;
   }
   const size_t slot_bytes = sizeof(int) * 3 * (size_t)h->RC;
-  int G = K < h->df_cus ? K : h->df_cus;
+  if (G > h->df_cus) G = h->df_cus;
   if (G > h->df_slots) {                                            // grow the slots (a workgroup's lists: 12 RC bytes)
     CK(hipStreamSynchronize(h->stream));
     if (h->d_df_lists) { (void)hipFree(h->d_df_lists); h->d_df_lists = nullptr; h->df_slots = 0; }
@@ -4640,9 +4637,11 @@ static int dist_field_run(pf_handle* h, const char* who, int allow_diag, int res
     }
     h->df_slots = G;
   }
-  if (K + 1 > h->df_ctl_cap) {
+  if (words > (size_t)h->df_ctl_cap) {
+    if (words > 0x7FFFFFFFull) return failmsg(h, me + ": the source table is too large");
+    CK(hipStreamSynchronize(h->stream));
     if (h->d_df_ctl) { (void)hipFree(h->d_df_ctl); h->d_df_ctl = nullptr; h->df_ctl_cap = 0; }
-    const int cap = K + 1 < 64 ? 64 : K + 1;
+    const int cap = words < 64 ? 64 : (int)words;
     if (hipMalloc(&h->d_df_ctl, sizeof(int) * (size_t)cap) != hipSuccess) {
       (void)hipGetLastError();
       h->d_df_ctl = nullptr;
@@ -4650,6 +4649,16 @@ static int dist_field_run(pf_handle* h, const char* who, int allow_diag, int res
     }
     h->df_ctl_cap = cap;
   }
+  return 0;
+}
+
+static int dist_field_run(pf_handle* h, const char* who, int allow_diag, int restrict_corner, int K, const int32_t* src, double* d_out, int64_t* d_info) {
+  const std::string me(who);
+  if (K < 1 || !src || !d_out) return failmsg(h, me + ": bad arguments (K >= 1, sources and rows must not be null)");
+  for (int k = 0; k < K; ++k)
+    if (src[k] < 0 || src[k] >= h->RC) return failmsg(h, me + ": source " + std::to_string(k) + " lies outside the grid");
+  int G = K;
+  if (dist_field_reserve(h, me, G, (size_t)K + 1)) return -2;
   std::vector<int> ctl((size_t)K + 1);
   ctl[0] = 0;
   for (int k = 0; k < K; ++k) ctl[(size_t)k + 1] = src[k];
@@ -4745,6 +4754,136 @@ int pf_dist_field_paths(pf_handle* h, int32_t K, const uint8_t* d_parents, const
     return 0;
   };
   return run() ? -1 : 0;
+}
+
+}  // extern "C"
+
+// ---------------------------------------------------------------------------
+// Nearest-source fields: one field seeded with a whole source set, and the owner of every cell (pf_nearest_field.h, DESIGN.md
+// 4.13).  pf_dist_field_merged runs on the distance fields' list slots; pf_dist_field_owners needs one int32 [B][RC] scratch
+// buffer for the length of the call.  Both keep the sets in the distance-field control block: {error word, off[B + 1], ids}.
+// ---------------------------------------------------------------------------
+#include "pf_nearest_field.h"
+
+// the sets of a call, checked on the host; -> words of the control block
+static int nearest_sets_check(pf_handle* h, const std::string& me, int B, const int32_t* set_off, const int32_t* src, std::vector<int>& ctl) {
+  if (B < 1) return failmsg(h, me + ": bad arguments (B = " + std::to_string(B) + ": at least one source set is needed)");
+  if (!set_off || !src) return failmsg(h, me + ": bad arguments (the set offsets and the sources must not be null)");
+  if (set_off[0] != 0) return failmsg(h, me + ": set_off[0] = " + std::to_string(set_off[0]) + ": the offsets must start at 0");
+  for (int b = 0; b < B; ++b) {
+    if (set_off[b + 1] < set_off[b])
+      return failmsg(h, me + ": set " + std::to_string(b) + ": set_off[" + std::to_string(b + 1) + "] = " + std::to_string(set_off[b + 1]) + " lies below set_off[" +
+                            std::to_string(b) + "] = " + std::to_string(set_off[b]));
+    if (set_off[b + 1] == set_off[b]) return failmsg(h, me + ": set " + std::to_string(b) + " is empty");
+  }
+  for (int b = 0; b < B; ++b)
+    for (int j = set_off[b]; j < set_off[b + 1]; ++j)
+      if (src[j] < 0 || src[j] >= h->RC)
+        return failmsg(h, me + ": set " + std::to_string(b) + ", source " + std::to_string(j - set_off[b]) + " (index " + std::to_string(j) + ") = " +
+                              std::to_string(src[j]) + " lies outside the grid");
+  ctl.assign(1, 0);
+  ctl.insert(ctl.end(), set_off, set_off + B + 1);
+  ctl.insert(ctl.end(), src, src + set_off[B]);
+  return 0;
+}
+
+extern "C" {
+
+int pf_dist_field_merged(pf_handle* h, int32_t allow_diag, int32_t restrict_corner, int32_t B, const int32_t* set_off, const int32_t* src, double* d_out,
+                         int64_t* d_info) {
+  if (!h) return -2;
+  const std::string me("pf_dist_field_merged");
+  auto run = [&]() -> int {
+    std::vector<int> ctl;
+    if (nearest_sets_check(h, me, B, set_off, src, ctl)) return -2;
+    if (!d_out) return failmsg(h, me + ": bad arguments (the rows must not be null)");
+    int G = B;
+    if (dist_field_reserve(h, me, G, ctl.size())) return -2;
+    CK(hipMemcpyAsync(h->d_df_ctl, ctl.data(), sizeof(int) * ctl.size(), hipMemcpyHostToDevice, h->stream));
+    CK(hipStreamSynchronize(h->stream));                            // (ctl is pageable and leaves scope)
+    const uint8_t* mm = allow_diag ? (restrict_corner ? h->d_mm_r1 : h->d_mm_r0) : (restrict_corner ? h->d_mm_r1_nd : h->d_mm_r0_nd);
+    CK(hipEventRecord(h->ev0, h->stream));
+    hipLaunchKernelGGL(k_dist_field_merged_source_sets<>, dim3(G), dim3(PF_DF_THREADS), 0, h->stream, (const uint8_t*)h->d_occ, mm, h->RC, h->C, B,
+                       (const int*)(h->d_df_ctl + 1), (const int*)(h->d_df_ctl + 2 + B), d_out, h->d_df_lists, (long long*)d_info, h->d_df_ctl);
+    CK(hipGetLastError());
+    CK(hipEventRecord(h->ev1, h->stream));
+    int err = 0;
+    CK(hipMemcpyAsync(&err, h->d_df_ctl, sizeof(int), hipMemcpyDeviceToHost, h->stream));
+    CK(hipStreamSynchronize(h->stream));
+    CK(hipEventElapsedTime(&h->last_ms, h->ev0, h->ev1));
+    h->d2h_small += 1;
+    if (err == PF_DF_ERR_LEVELS) return failmsg(h, me + ": internal: level bound");
+    if (err) return failmsg(h, me + ": internal: list bound");
+    return 0;
+  };
+  return run() ? -1 : 0;
+}
+
+int pf_dist_field_owners(pf_handle* h, int32_t B, const uint8_t* d_parents, const int32_t* set_off, const int32_t* src, const int64_t* d_info, int32_t* d_owner,
+                         int64_t* d_count) {
+  if (!h) return -2;
+  const std::string me("pf_dist_field_owners");
+  int* d_scratch = nullptr;
+  auto run = [&]() -> int {
+    std::vector<int> ctl;
+    if (nearest_sets_check(h, me, B, set_off, src, ctl)) return -2;
+    if (!d_parents || !d_owner) return failmsg(h, me + ": bad arguments (the parent maps and the owner rows must not be null)");
+    const int RC = h->RC;
+    int G = 0;                                                      // (no list slots: the control block only)
+    if (dist_field_reserve(h, me, G, ctl.size())) return -2;
+    // the rounds are fixed here, before the first launch: chains of at most n cells resolve in ceil(log2(n)) rounds
+    long long n = RC;
+    if (d_info) {
+      std::vector<long long> info((size_t)B * 4);
+      CK(hipMemcpyAsync(info.data(), d_info, sizeof(long long) * info.size(), hipMemcpyDeviceToHost, h->stream));
+      CK(hipStreamSynchronize(h->stream));
+      const size_t nb = sizeof(long long) * info.size();
+      if (nb <= 128) h->d2h_small += 1; else { h->d2h_bulk += 1; h->d2h_bulk_bytes += (long long)nb; }
+      long long most = 1;                                           // the cells of a chain lie in distinct live levels
+      for (int b = 0; b < B; ++b) most = std::max(most, info[(size_t)b * 4]);
+      n = std::min(n, most);
+    }
+    int rounds = 0;
+    while ((1ll << rounds) < n) rounds += 1;
+    const size_t words = (size_t)B * (size_t)RC;
+    if (hipMalloc(&d_scratch, sizeof(int) * words) != hipSuccess) {
+      (void)hipGetLastError();
+      d_scratch = nullptr;
+      return failmsg(h, me + ": no device memory for the second link buffer (" + std::to_string((sizeof(int) * words) >> 20) + " MiB)");
+    }
+    CK(hipMemcpyAsync(h->d_df_ctl, ctl.data(), sizeof(int) * ctl.size(), hipMemcpyHostToDevice, h->stream));
+    CK(hipStreamSynchronize(h->stream));                            // (ctl is pageable and leaves scope)
+    if (d_count) CK(hipMemsetAsync(d_count, 0, sizeof(int64_t) * (size_t)set_off[B], h->stream));
+    const int* d_off = h->d_df_ctl + 1;
+    const int* d_src = h->d_df_ctl + 2 + B;
+    int most_src = 1;
+    for (int b = 0; b < B; ++b) most_src = std::max(most_src, set_off[b + 1] - set_off[b]);
+    const unsigned gx = (unsigned)((RC + PF_NF_THREADS - 1) / PF_NF_THREADS), gy = (unsigned)(B < 65535 ? B : 65535);
+    const unsigned sx = (unsigned)std::min((most_src + PF_NF_THREADS - 1) / PF_NF_THREADS, 64);
+    int* buf[2] = {(rounds & 1) ? (int*)d_owner : d_scratch, (rounds & 1) ? d_scratch : (int*)d_owner};   // the last round ends in the scratch buffer
+    CK(hipEventRecord(h->ev0, h->stream));
+    hipLaunchKernelGGL(k_nearest_owner_links<>, dim3(gx, gy), dim3(PF_NF_THREADS), 0, h->stream, d_parents, RC, h->C, B, buf[0], h->d_df_ctl);
+    hipLaunchKernelGGL(k_nearest_owner_stamp_ranks<>, dim3(sx, gy), dim3(PF_NF_THREADS), 0, h->stream, RC, B, d_off, d_src, buf[0]);
+    for (int t = 0; t < rounds; ++t)
+      hipLaunchKernelGGL(k_nearest_owner_doubling<>, dim3(gx, gy), dim3(PF_NF_THREADS), 0, h->stream, RC, B, (const int*)buf[t & 1], buf[(t + 1) & 1]);
+    hipLaunchKernelGGL(k_nearest_owner_write_and_count<>, dim3(gx, gy), dim3(PF_NF_THREADS), 0, h->stream, RC, B, d_off, (const int*)d_scratch, (int*)d_owner,
+                       (unsigned long long*)d_count, h->d_df_ctl);
+    CK(hipGetLastError());
+    CK(hipEventRecord(h->ev1, h->stream));
+    int err = 0;
+    CK(hipMemcpyAsync(&err, h->d_df_ctl, sizeof(int), hipMemcpyDeviceToHost, h->stream));
+    CK(hipStreamSynchronize(h->stream));
+    CK(hipEventElapsedTime(&h->last_ms, h->ev0, h->ev1));
+    h->d2h_small += 1;
+    if (err & PF_NF_ERR_CODE) return failmsg(h, me + ": the parent maps hold a code outside 0..8 and 255, or a step off the grid");
+    if (err & PF_NF_ERR_ROOT) return failmsg(h, me + ": a root of the parent maps is no source of its set: the maps belong to other sets");
+    if (err) return failmsg(h, me + ": a chain holds more cells than the bound of " + std::to_string(n) + " (" + std::to_string(rounds) +
+                               " rounds): the parent maps are no forest, or d_info belongs to another field");
+    return 0;
+  };
+  const int rc = run();
+  if (d_scratch) { (void)hipStreamSynchronize(h->stream); (void)hipFree(d_scratch); }
+  return rc ? -1 : 0;
 }
 
 }  // extern "C"

@@ -184,7 +184,11 @@ class DistanceField:
             kidx = np.array([self._k_checked(v) for v in ks], np.int32).reshape(n)
         if path_cap is not None and int(path_cap) < 1:
             raise ValueError(f"{who}: path_cap must be >= 1")
-        # every argument is checked: the device
+        return self._paths_of(ids, kidx, reverse, path_cap)
+
+    def _paths_of(self, ids, kidx, reverse, path_cap):
+        """paths() once every argument is checked: the device."""
+        who, n = type(self).__name__, len(ids)
         self._check_open()
         if n == 0:
             self.chosen = np.zeros(0, np.int32)

@@ -250,6 +250,26 @@ class Engine:
                                             d_status.ptr if d_status else None, d_chosen.ptr if d_chosen else None))
         self._logk("dist_field_paths")
 
+    def dist_field_merged(self, set_off, sources, d_out, allow_diag=True, restrict_corner=True, d_info=None):
+        """One field per source SET (host int32 CSR: set b = sources[set_off[b]:set_off[b + 1]]) -> d_out [B, R * C] doubles, the
+        length from each cell's nearest source of the set; d_info [B, 4] int64 as dist_field_batch's (pf_dist_field_merged)."""
+        off = np.ascontiguousarray(set_off, np.int32).reshape(-1)
+        src = np.ascontiguousarray(sources, np.int32).reshape(-1)
+        self._ck(self.L.pf_dist_field_merged(self.h, int(allow_diag), int(restrict_corner), int(off.size) - 1, off.ctypes.data if off.size else None,
+                                             src.ctypes.data if src.size else None, d_out.ptr if d_out else None, d_info.ptr if d_info else None))
+        self._logk("dist_field_merged")
+
+    def dist_field_owners(self, set_off, sources, d_parents, d_owner, d_info=None, d_count=None):
+        """The parent maps of merged fields (d_parents [B, R * C] uint8) -> d_owner [B, R * C] int32, the index within its set of the
+        source at the root of each cell's chain (-1: no route); d_count [len(sources)] int64 the cells each source owns; d_info: the
+        field call's block, which bounds the rounds of the pointer doubling (pf_dist_field_owners)."""
+        off = np.ascontiguousarray(set_off, np.int32).reshape(-1)
+        src = np.ascontiguousarray(sources, np.int32).reshape(-1)
+        self._ck(self.L.pf_dist_field_owners(self.h, int(off.size) - 1, d_parents.ptr if d_parents else None, off.ctypes.data if off.size else None,
+                                             src.ctypes.data if src.size else None, d_info.ptr if d_info else None, d_owner.ptr if d_owner else None,
+                                             d_count.ptr if d_count else None))
+        self._logk("dist_field_owners")
+
     # ------------------------------------------------------------------ K1
     def score_batch(self, n, path_cap, d_cells, d_len, d_stats, sp):
         """Rows of astar_batch's layout in HBM -> d_stats [n, 5] doubles (pf_score_batch)."""
