@@ -644,6 +644,12 @@ int pf_span_total(pf_handle* h, double* ms_out, int64_t* count_out, int32_t rese
  * engine (-1: the engine has no scratch on this handle)}.  The slots exist from the first search launch on. */
 int pf_selftest_slot_state(pf_handle* h, int32_t slot, int64_t* out3);
 
+/* Branch counters of the A* open list (pf_astar_sw.h, OP_*: 21 of them, in that order), summed over every search of this process
+ * since the last reset; the first n are copied to out, the rest of out[0..n) is zeroed; reset != 0 clears them.  They exist only in
+ * the diagnostic builds compiled with -DPF_OPEN_PATHS (the stress variants of build.py): any other build zeroes out, sets the
+ * handle's error text to "not compiled in" and returns 1.  Synchronises the device. */
+int pf_selftest_open_paths(pf_handle* h, int64_t* out, int32_t n, int32_t reset);
+
 /* Target-cell proposals of MPA._get_levy_target_node / _get_brownian_target_node (MPA.py:250-282) for n keyed streams
  * (seed, DOM_MPA, 0, i) from cells d_cur[i] (and elite cells d_elite[i], < 0 = None): the device arithmetic, with the
  * proposals whose accept test / rounding lies within the libm-disagreement margin recomputed by the host's glibc

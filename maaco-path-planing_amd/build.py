@@ -6,6 +6,12 @@ hipcc cross-compiles gfx950 without a GPU; the .so travels to the GPU box with
 the repo snapshot.  PF_EXTRA_FLAGS adds compiler flags:
 -DPF_TRACE / -DPF_STAMPS / -DPF_WALK_PROBE the diagnostic builds of scripts/.  -ffp-contract=off: the reference's arithmetic is unfused
 IEEE double and bit-exact path parity depends on it.
+
+    python maaco-path-planing_amd/build.py --variants [--force]
+
+also builds the stress variants of the A* open list (VARIANTS below) into lib/stress/libpathfit_<name>.so: the shipped code under
+a bucket geometry that makes its rare branches common, with the branch counters of -DPF_OPEN_PATHS compiled in
+(tests/test_gpu_open_list_stress.py runs tests/open_list_cases.py against each).
 """
 import os
 import subprocess
@@ -19,18 +25,71 @@ OUT = os.path.join(HERE, "lib", "libpathfit.so")
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 FLAGS = ["-O3", "--offload-arch=gfx950", "-ffp-contract=off", "-fPIC", "-shared", "-std=c++17",
          "-Wall", "-Wno-unused-function"]
+# Stress variants of the open list (pf_astar_sw.h): name -> the flags added to FLAGS, and what they make common.  Every variant
+# carries -DPF_OPEN_PATHS; PF_RUN_SORT, PF_EARLY_REFILL and PF_ROTATE keep their shipped values.
+VARIANTS = {
+    "cap8": ["-DPF_SW_CAP=8"],                                                             # full buckets, spill list, respill
+    "wide64": ["-DPF_SW_Q=16.0", "-DPF_SW_NBK=64", "-DPF_SW_CAP=64"],                      # buckets of (nearly) 64, concatenation, wrap
+    "wide256": ["-DPF_SW_Q=16.0", "-DPF_SW_NBK=64", "-DPF_SW_CAP=256", "-DPF_SELECT_MIN=65"],   # buckets > 64, pivot selection, evictions
+    "spill256": ["-DPF_SW_CAP=8", "-DPF_SW_SPILL=256"],                                    # the spill list filling up: status 3
+}
+VARIANT_COMMON = ["-DPF_OPEN_PATHS"]
+MAX_JOBS = 16
+
+
+def _stale(out):
+    return not os.path.exists(out) or any(os.path.getmtime(out) < os.path.getmtime(d) for d in DEPS)
+
+
+def _cmd(out, extra):
+    return [HIPCC] + FLAGS + os.environ.get("PF_EXTRA_FLAGS", "").split() + list(extra) + ["-o", out, SRC]
 
 
 def build(force=False, verbose=False):
     os.makedirs(os.path.dirname(OUT), exist_ok=True)
-    if not force and os.path.exists(OUT) and all(os.path.getmtime(OUT) >= os.path.getmtime(d) for d in DEPS):
+    if not force and not _stale(OUT):
         return OUT
-    cmd = [HIPCC] + FLAGS + os.environ.get("PF_EXTRA_FLAGS", "").split() + ["-o", OUT, SRC]
+    cmd = _cmd(OUT, [])
     if verbose:
         print(" ".join(cmd))
     subprocess.check_call(cmd)
     return OUT
 
 
+def variant_path(name):
+    return os.path.join(HERE, "lib", "stress", "libpathfit_%s.so" % name)
+
+
+def variant_flags(name):
+    return VARIANT_COMMON + VARIANTS[name]
+
+
+def build_variant(name, force=False, verbose=False):
+    """lib/stress/libpathfit_<name>.so: the main library's flags plus the variant's, the same staleness rule."""
+    return build_variants([name], force, verbose)[0]
+
+
+def build_variants(names=None, force=False, verbose=False):
+    """Several variants at once: one hipcc child each, at most MAX_JOBS at a time."""
+    names = list(VARIANTS) if names is None else list(names)
+    outs = [variant_path(n) for n in names]
+    os.makedirs(os.path.dirname(variant_path("x")), exist_ok=True)
+    todo = [(n, o) for n, o in zip(names, outs) if force or _stale(o)]
+    failed = []
+    for i in range(0, len(todo), MAX_JOBS):
+        procs = []
+        for n, o in todo[i:i + MAX_JOBS]:
+            cmd = _cmd(o, variant_flags(n))
+            if verbose:
+                print(" ".join(cmd), flush=True)
+            procs.append((n, subprocess.Popen(cmd)))
+        failed += [n for n, p in procs if p.wait() != 0]
+    if failed:
+        raise subprocess.CalledProcessError(1, "hipcc (stress variants: %s)" % ", ".join(failed))
+    return outs
+
+
 if __name__ == "__main__":
     print(build(force="--force" in sys.argv, verbose=True))
+    if "--variants" in sys.argv:
+        print("\n".join(build_variants(force="--force" in sys.argv, verbose=True)))

@@ -2562,6 +2562,24 @@ int pf_selftest_slot_state(pf_handle* h, int32_t slot, int64_t* out3) {
   out3[0] = st[0]; out3[1] = st[1]; out3[2] = h->d_st_epoch ? (int64_t)ep : -1;
   return 0;
 }
+int pf_selftest_open_paths(pf_handle* h, int64_t* out, int32_t n, int32_t reset) {
+  if (!h || !out || n < 0) return failmsg(h, "pf_selftest_open_paths: bad arguments");
+  for (int i = 0; i < n; ++i) out[i] = 0;
+#ifdef PF_OPEN_PATHS
+  static_assert(pf::PF_OP_N <= 32, "g_open_paths holds the counters");
+  CK(hipSetDevice(h->device));
+  CK(hipDeviceSynchronize());
+  unsigned long long v[32];
+  CK(hipMemcpyFromSymbol(v, HIP_SYMBOL(pf::g_open_paths), sizeof(v)));
+  for (int i = 0; i < n && i < (int)pf::PF_OP_N; ++i) out[i] = (int64_t)v[i];
+  if (reset) { unsigned long long z[32] = {0}; CK(hipMemcpyToSymbol(HIP_SYMBOL(pf::g_open_paths), z, sizeof(z))); }
+  return 0;
+#else
+  (void)reset;
+  h->err = "pf_selftest_open_paths: the branch counters are not compiled in (build with -DPF_OPEN_PATHS)";
+  return 1;
+#endif
+}
 int pf_selftest_rng(pf_handle* h, uint64_t seed, uint64_t dom, uint64_t it, uint64_t agent, uint64_t* d_u64,
                     double* d_f64, int64_t* d_i64) {
   if (!h || !d_u64 || !d_f64 || !d_i64) return failmsg(h, "pf_selftest_rng: bad arguments");

@@ -52,6 +52,10 @@ struct AStat {
 #ifdef PF_STAMPS
 __device__ unsigned long long g_stamps[24];
 #endif
+// diagnostic build only (-DPF_OPEN_PATHS): how often each branch of the open list ran (pf_astar_sw.h: OP_*), summed over all searches
+#ifdef PF_OPEN_PATHS
+__device__ unsigned long long g_open_paths[32];
+#endif
 
 // Mark cells[0..n) of a path as "avoid" for this slot's current eval epoch.
 PF_DEV void mark_avoid(const Slot& s, const int* cells, int n, int lane) {

@@ -51,6 +51,43 @@ PF_DEV unsigned long long dbits(double x) { return (unsigned long long)__double_
 #define PF_SW_CAP 256    /* entries per bucket (a stress build with -DPF_SW_CAP=8 drives everything through the spill list) */
 #endif
 
+// diagnostic build only (-DPF_OPEN_PATHS, the stress variants of build.py): which branches of the open list a search took.  Counted per
+// wave in SwWin::op (uniform values), added once per search to g_open_paths (pf_astar.h); pf_selftest_open_paths reads them.  Without
+// the macro every line below expands to nothing.  The order is the ABI of pf_selftest_open_paths (tests/open_list_cases.py names it).
+enum {
+  OP_FRONT_APPEND,      // pool append to the front bucket
+  OP_SPILL_FULL,        // spill: the bucket is full
+  OP_SPILL_RANGE,       // spill: the key is beyond the circular range
+  OP_SPILL_LIST_FULL,   // the spill list is full too (status 3)
+  OP_WIN_PLAIN,         // win_insert: room above (wn < 64)
+  OP_WIN_SHIFT,         // win_insert: 64 = wn, room below (wp > 0): shift down
+  OP_WIN_EVICT,         // win_insert: 64 live lanes, the largest key returns to the pool
+  OP_FRONT_LE64,        // refill from the front bucket, <= 64 entries
+  OP_FRONT_GT64,        // refill from the front bucket, > 64 entries
+  OP_REFILL_ONE,        // regular refill: one bucket
+  OP_REFILL_MANY,       // regular refill: several buckets concatenated
+  OP_BIG_MERGE,         // regular refill of a bucket > 64: take_smallest64
+  OP_BIG_SELECT,        // regular refill of a bucket > 64: take_smallest_select
+  OP_SPILL_ONLY,        // refill that finds only spilled entries
+  OP_SPILL_ONLY_MOVED,  // ... and moves bcur to the smallest spilled key
+  OP_REFILL_RET4,       // refill returning 4 (call again)
+  OP_RESPILL,           // respill calls
+  OP_RESPILL_STAYED,    // spilled entries still (or again) in the spill list after a respill
+  OP_RESPILL_OFFERED,   // spilled entries a respill placed in the window or a bucket
+  OP_EARLY_REFILL,      // early refills taken
+  OP_ROTATED,           // rotated trips
+  PF_OP_N
+};
+#ifdef PF_OPEN_PATHS
+#define SW_OP(op, i, n) (op)[i] += (unsigned)(n);
+#define SW_OP_PARAM , unsigned* op
+#define SW_OP_PASS(W) , (W).op
+#else
+#define SW_OP(op, i, n)
+#define SW_OP_PARAM
+#define SW_OP_PASS(W)
+#endif
+
 PF_DEV bool key_lt(double f1, double g1, int c1, double f2, double g2, int c2) {   // branch-free (f, g, cell) order
   return (f1 < f2) | ((f1 == f2) & ((g1 < g2) | ((g1 == g2) & (c1 < c2))));
 }
@@ -234,7 +271,9 @@ PF_DEV void geo_to_lds(char* smem, int lane) {
 
 // lanes 0..48 as head pairs (e, h) = (lane / 7, lane % 7): the lanes with e < h
 constexpr unsigned long long make_pairs_eh() { unsigned long long m = 0; for (int l = 0; l < 49; ++l) if (l / 7 < l % 7) m |= 1ull << l; return m; }
-#define PF_SW_SPILL 16384
+#ifndef PF_SW_SPILL
+#define PF_SW_SPILL 16384   /* entries of the spill list (a stress build with -DPF_SW_CAP=8 -DPF_SW_SPILL=256 fills it: status 3) */
+#endif
 static_assert((double)PF_SW_NBK >= 2.8285 * PF_SW_Q + 1.0, "a push lies at most 2*sqrt(2) above the pop that made it: the circular range must cover that");
 static_assert(4 * (PF_SW_NBK + 1) <= PF_SORT_LDS, "bucket counts and the sort's staging area share the wave's LDS");
 #define PF_SW_DUMP 64       /* one entry per lane behind the spill list: where a lane without a pool push stores in a rotated trip (never read) */
@@ -263,17 +302,19 @@ PF_DEV void ent_get(const SwPool& P, const PoolEnt* e, double& f, double& g, int
 // append one entry (uniform values): to the front bucket when it sorts before every regular bucket (f below the
 // boundary of bucket bcur), else to its f bucket, else (bucket full / out of range) to the spill list;
 // false only when the spill list is full too
-PF_DEV bool pool_put1(const SwPool& P, double f, double g, int c, int bcur, int& n_spill, int lane) {
+PF_DEV bool pool_put1(const SwPool& P, double f, double g, int c, int bcur, int& n_spill, int lane SW_OP_PARAM) {
   const int ba = (int)(f * PF_SW_Q);
   const int b = ba < bcur ? PF_SW_NBK : (ba & (PF_SW_NBK - 1));
   PF_LDS_ORDER();
   const int n = P.cnt[b];
   if (n >= PF_SW_CAP || ba - bcur >= PF_SW_NBK) {
-    if (n_spill >= PF_SW_SPILL) return false;
+    SW_OP(op, OP_SPILL_RANGE, ba - bcur >= PF_SW_NBK ? 1 : 0) SW_OP(op, OP_SPILL_FULL, ba - bcur >= PF_SW_NBK ? 0 : 1)
+    if (n_spill >= PF_SW_SPILL) { SW_OP(op, OP_SPILL_LIST_FULL, 1) return false; }
     if (lane == 0) ent_put(P.se + n_spill, g, c);
     n_spill += 1;
     return true;
   }
+  SW_OP(op, OP_FRONT_APPEND, b == PF_SW_NBK ? 1 : 0)
   if (lane == 0) { ent_put(P.be + b * PF_SW_CAP + n, g, c); P.cnt[b] = n + 1; }
   PF_LDS_ORDER();
   return true;
@@ -285,6 +326,9 @@ struct SwWin {
   double lf, lg; int lc;        // keys below this limit belong to the window; every pool entry is at or above it
   int bcur;                     // first regular bucket (absolute index) not yet taken
   int n_pool, n_spill;          // entries outside the window (spilled ones included) / in the spill list
+#ifdef PF_OPEN_PATHS
+  unsigned op[PF_OP_N];         // branch counts of this search (diagnostic build)
+#endif
 };
 // insert a key that is below the limit; a full window returns its largest entry to the pool, which becomes the limit
 PF_DEV bool win_insert(const SwPool& P, SwWin& W, double kf, double kg, int kc, int lane) {
@@ -294,21 +338,24 @@ PF_DEV bool win_insert(const SwPool& P, SwWin& W, double kf, double kg, int kc, 
     if (lane > p && lane <= W.wn) { W.wf = sf; W.wg = sg; W.wc = sc; }
     if (lane == p) { W.wf = kf; W.wg = kg; W.wc = kc; }
     W.wn += 1;
+    SW_OP(W.op, OP_WIN_PLAIN, 1)
   } else if (W.wp > 0) {
     const double sf = wave_down_d(W.wf), sg = wave_down_d(W.wg); const int sc = wave_down_i(W.wc);
     if (lane >= W.wp - 1 && lane < p - 1) { W.wf = sf; W.wg = sg; W.wc = sc; }
     if (lane == p - 1) { W.wf = kf; W.wg = kg; W.wc = kc; }
     W.wp -= 1;
+    SW_OP(W.op, OP_WIN_SHIFT, 1)
   } else {
     // 64 live entries: the largest key (the new one, or lane 63's) returns to the pool and becomes the limit
     double ef = kf, eg = kg; int ec = kc;
+    SW_OP(W.op, OP_WIN_EVICT, 1)
     if (p < 64) {
       ef = bcast_d(W.wf, 63); eg = bcast_d(W.wg, 63); ec = bcast_i(W.wc, 63);
       const double sf = wave_up_d(W.wf), sg = wave_up_d(W.wg); const int sc = wave_up_i(W.wc);
       if (lane > p) { W.wf = sf; W.wg = sg; W.wc = sc; }
       if (lane == p) { W.wf = kf; W.wg = kg; W.wc = kc; }
     }
-    if (!pool_put1(P, ef, eg, ec, W.bcur, W.n_spill, lane)) return false;
+    if (!pool_put1(P, ef, eg, ec, W.bcur, W.n_spill, lane SW_OP_PASS(W))) return false;
     W.n_pool += 1;
     W.lf = ef; W.lg = eg; W.lc = ec;
   }
@@ -317,7 +364,7 @@ PF_DEV bool win_insert(const SwPool& P, SwWin& W, double kf, double kg, int kc, 
 // key below the limit -> window, else -> pool (front bucket / f bucket / spill list)
 PF_DEV bool sw_add(const SwPool& P, SwWin& W, double kf, double kg, int kc, int lane) {
   if (key_lt(kf, kg, kc, W.lf, W.lg, W.lc)) return win_insert(P, W, kf, kg, kc, lane);
-  if (!pool_put1(P, kf, kg, kc, W.bcur, W.n_spill, lane)) return false;
+  if (!pool_put1(P, kf, kg, kc, W.bcur, W.n_spill, lane SW_OP_PASS(W))) return false;
   W.n_pool += 1;
   return true;
 }
@@ -327,6 +374,7 @@ template <bool PLAT>
 PF_DEV bool respill(const SwPool& P, SwWin& W, int lane) {
   const int n = W.n_spill;
   W.n_spill = 0; W.n_pool -= n;
+  SW_OP(W.op, OP_RESPILL, 1)
   for (int base = 0; base < n; base += 64) {
     const int m = n - base < 64 ? n - base : 64;
     double ef = 0.0, eg = 0.0; int ec = 0;
@@ -355,6 +403,8 @@ PF_DEV bool respill(const SwPool& P, SwWin& W, int lane) {
       if (!sw_add(P, W, bcast_d(ef, k), bcast_d(eg, k), bcast_i(ec, k), lane)) return false;
     }
   }
+  // (every offered entry leaves at most one entry in the spill list -- itself, or the key its insert evicted: n_spill <= n)
+  SW_OP(W.op, OP_RESPILL_STAYED, W.n_spill) SW_OP(W.op, OP_RESPILL_OFFERED, n - W.n_spill)
   return true;
 }
 // A bucket larger than the window: leave its 64 smallest entries sorted in the lanes, compact the rest in place.
@@ -523,6 +573,7 @@ PF_DEV void sw_early_refill(const SwPool& P, SwWin& W, const Open& O, const Rec*
         W.wp = 0; W.wn = rem + live; W.n_pool -= total;
         W.bcur = b0 + k;
         W.lf = (double)W.bcur * (1.0 / PF_SW_Q); W.lg = -PF_INF; W.lc = 0;
+        SW_OP(W.op, OP_EARLY_REFILL, 1)
         PF_LDS_ORDER();
       }
     }
@@ -553,9 +604,11 @@ PF_DEV int sw_refill(const SwPool& P, SwWin& W, const Open& O, const Rec* rec, i
 #endif
         W.wp = 0; W.wn = live; W.n_pool -= cF;
         W.lf = (double)W.bcur * (1.0 / PF_SW_Q); W.lg = -PF_INF; W.lc = 0;
+        SW_OP(W.op, OP_FRONT_LE64, 1)
       } else {
         int nt = PLAT && cF >= PF_SELECT_MIN ? take_smallest_select(P, (char*)O.lf, NBK, cF, W.wf, W.wg, W.wc, lane) : 0;
         if (nt == 0) { take_smallest64(P, NBK, cF, W.wf, W.wg, W.wc, lane); nt = 64; }
+        SW_OP(W.op, OP_FRONT_GT64, 1)
         W.wp = 0; W.wn = nt; W.n_pool -= nt;
         W.lf = bcast_d(W.wf, nt - 1); W.lg = bcast_d(W.wg, nt - 1); W.lc = bcast_i(W.wc, nt - 1);   // the rest of the front bucket is above this key
       }
@@ -568,14 +621,16 @@ PF_DEV int sw_refill(const SwPool& P, SwWin& W, const Open& O, const Rec* rec, i
       }
       if (b0 < 0) {                                  // only spilled entries are left (their buckets emptied since)
         if (W.n_spill == 0) return 3;   // (n_pool > 0 with nothing anywhere: never loop silently)
+        SW_OP(W.op, OP_SPILL_ONLY, 1)
         // window, front bucket and every regular bucket are empty: the circular range may start at the smallest
         // spilled key, which brings the entries that were beyond it back in range
         unsigned minb = 0xFFFFFFFFu;
         for (int base = 0; base < W.n_spill; base += 64)
           if (base + lane < W.n_spill) { double f_, g_; int c_; ent_get(P, P.se + base + lane, f_, g_, c_); const unsigned b_ = (unsigned)(int)(f_ * PF_SW_Q); minb = b_ < minb ? b_ : minb; }
         minb = wave_min_u32(minb);
-        if ((int)minb > W.bcur) { W.bcur = (int)minb; W.lf = (double)W.bcur * (1.0 / PF_SW_Q); W.lg = -PF_INF; W.lc = 0; }
+        if ((int)minb > W.bcur) { W.bcur = (int)minb; W.lf = (double)W.bcur * (1.0 / PF_SW_Q); W.lg = -PF_INF; W.lc = 0; SW_OP(W.op, OP_SPILL_ONLY_MOVED, 1) }
         if (!respill<PLAT>(P, W, lane)) return 3;
+        SW_OP(W.op, OP_REFILL_RET4, 1)
         return 4;
       }
       const int cb = P.cnt[(b0 + lane) & (NBK - 1)]; // lane k: size of the k-th bucket from b0 (wraps onto empty ones)
@@ -612,8 +667,12 @@ PF_DEV int sw_refill(const SwPool& P, SwWin& W, const Open& O, const Rec* rec, i
         W.wp = 0; W.wn = live; W.n_pool -= total;
         W.bcur = b0 + k;
         W.lf = (double)W.bcur * (1.0 / PF_SW_Q); W.lg = -PF_INF; W.lc = 0;
+        // (one / several: the non-empty buckets among the k taken)
+        SW_OP(W.op, OP_REFILL_ONE, __builtin_popcountll(__ballot(lane < k && cb > 0)) == 1 ? 1 : 0)
+        SW_OP(W.op, OP_REFILL_MANY, __builtin_popcountll(__ballot(lane < k && cb > 0)) > 1 ? 1 : 0)
       } else {
         int nt = PLAT && c0 >= PF_SELECT_MIN ? take_smallest_select(P, (char*)O.lf, b0 & (NBK - 1), c0, W.wf, W.wg, W.wc, lane) : 0;
+        SW_OP(W.op, OP_BIG_SELECT, nt != 0 ? 1 : 0) SW_OP(W.op, OP_BIG_MERGE, nt == 0 ? 1 : 0)
         if (nt == 0) { take_smallest64(P, b0 & (NBK - 1), c0, W.wf, W.wg, W.wc, lane); nt = 64; }
         W.wp = 0; W.wn = nt; W.n_pool -= nt;
         W.bcur = b0;
@@ -622,7 +681,7 @@ PF_DEV int sw_refill(const SwPool& P, SwWin& W, const Open& O, const Rec* rec, i
     }
     PF_LDS_ORDER();
     if (W.n_spill > 0 && !respill<PLAT>(P, W, lane)) return 3;
-    if (W.wn == 0) return 4;                                    // everything taken was superseded: take the next buckets
+    if (W.wn == 0) { SW_OP(W.op, OP_REFILL_RET4, 1) return 4; }   // everything taken was superseded: take the next buckets
   }
   return 0;
 }
@@ -646,6 +705,9 @@ __device__ __forceinline__ int pop_loop_sw(const Grid& G, Rec* rec, const Open& 
   W.bcur = (int)(h0 * PF_SW_Q) + 1;                           // first bucket (absolute index) not yet taken into the window
   W.lf = (double)W.bcur * (1.0 / PF_SW_Q); W.lg = -PF_INF; W.lc = 0;   // keys below (lf, lg, lc) belong to the window
   W.n_pool = 0; W.n_spill = 0;
+#ifdef PF_OPEN_PATHS
+  for (int i = 0; i < PF_OP_N; ++i) W.op[i] = 0u;
+#endif
   int steps = 0, status = 1;
   unsigned nbr_s = 0, push_s = 0, dk_s = 0;                  // event counts of the wave (uniform)
   int n_max = 1;
@@ -963,7 +1025,9 @@ __device__ __forceinline__ int pop_loop_sw(const Grid& G, Rec* rec, const Open& 
       const pf_u64 mFits = mInr & B(pat < CAP);
       ent_put(P.be + (PL(mTop & mFits) ? pb * CAP + pat : (NBK + 1) * CAP + PF_SW_SPILL + lane), tent, nrc);
       const unsigned long long sm = mTop & ~mFits;              // bucket full or beyond the circular range: spill list
+      SW_OP(W.op, OP_FRONT_APPEND, __builtin_popcountll(mTop & mFits & B(pb == NBK)))
       if (sm) {
+        SW_OP(W.op, OP_SPILL_FULL, __builtin_popcountll(sm & mInr)) SW_OP(W.op, OP_SPILL_RANGE, __builtin_popcountll(sm & ~mInr))
         if (PL(sm)) {
           if (PL(mInr)) __hip_atomic_fetch_add(&P.cnt[pb], -1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);   // a number past the end: give it back
           const int at = W.n_spill + __builtin_popcountll(sm & ((1ull << lane) - 1ull));
@@ -972,6 +1036,7 @@ __device__ __forceinline__ int pop_loop_sw(const Grid& G, Rec* rec, const Open& 
         W.n_spill += __builtin_popcountll(sm);
         st.spills += (unsigned)__builtin_popcountll(sm);
         if (W.n_spill > PF_SW_SPILL) {                         // never silent
+          SW_OP(W.op, OP_SPILL_LIST_FULL, 1)
           asm volatile("; rotated trip: leaves" :: "v"(rn.meta));   // (no load in flight on any way out of the loop: the top's waits stay exact)
           status = 3; goto done;
         }
@@ -990,6 +1055,7 @@ __device__ __forceinline__ int pop_loop_sw(const Grid& G, Rec* rec, const Open& 
 #ifdef PF_STAMPS
       sw_acc[7] += 1; sw_rot[0] += r1 - r0; sw_rot[1] += 1;
 #endif
+      SW_OP(W.op, OP_ROTATED, 1)
       continue;
     }
     if (PL(mTop & mInr)) pat = __hip_atomic_fetch_add(&P.cnt[pb], 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
@@ -1021,7 +1087,9 @@ __device__ __forceinline__ int pop_loop_sw(const Grid& G, Rec* rec, const Open& 
       const pf_u64 mFits = mInr & B(pat < CAP);
       if (PL(mTop & mFits)) ent_put(P.be + pb * CAP + pat, tent, nrc);
       const unsigned long long sm = mTop & ~mFits;              // bucket full or beyond the circular range: spill list
+      SW_OP(W.op, OP_FRONT_APPEND, __builtin_popcountll(mTop & mFits & B(pb == NBK)))
       if (sm) {
+        SW_OP(W.op, OP_SPILL_FULL, __builtin_popcountll(sm & mInr)) SW_OP(W.op, OP_SPILL_RANGE, __builtin_popcountll(sm & ~mInr))
         if (PL(sm)) {
           if (PL(mInr)) __hip_atomic_fetch_add(&P.cnt[pb], -1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);   // a number past the end: give it back
           const int at = W.n_spill + __builtin_popcountll(sm & ((1ull << lane) - 1ull));
@@ -1029,7 +1097,7 @@ __device__ __forceinline__ int pop_loop_sw(const Grid& G, Rec* rec, const Open& 
         }
         W.n_spill += __builtin_popcountll(sm);
         st.spills += (unsigned)__builtin_popcountll(sm);
-        if (W.n_spill > PF_SW_SPILL) { status = 3; goto done; } // never silent
+        if (W.n_spill > PF_SW_SPILL) { SW_OP(W.op, OP_SPILL_LIST_FULL, 1) status = 3; goto done; } // never silent
       }
     }
     if (hit) { status = 0; goto done; }
@@ -1055,6 +1123,10 @@ done:
     for (int i = 0; i < 6; ++i) atomicAdd(&g_stamps[16 + i], sw_er[i]);
     for (int i = 0; i < 2; ++i) atomicAdd(&g_stamps[22 + i], sw_rot[i]);
   }
+#endif
+#ifdef PF_OPEN_PATHS
+  if (lane == 0)
+    for (int i = 0; i < PF_OP_N; ++i) if (W.op[i]) atomicAdd(&g_open_paths[i], (unsigned long long)W.op[i]);
 #endif
   if (n_max > st.max_open) st.max_open = n_max;
   st.pops += (unsigned long long)steps; st.pushes += 1u + push_s;

@@ -155,6 +155,8 @@ class MPA(BestSoFar):
             if st[0] == 3 and self.path_cap < self.rows * self.cols:
                 self.path_cap = min(self.rows * self.cols, self.path_cap * 4)
                 continue
+            if st[0] == 3:                                               # not the row: the open list's scratch ran out
+                raise RuntimeError("pathfit: scratch/path capacity overflow in the initial search (path_cap=%d)" % self.path_cap)
             break
         p = paths[0]
         if len(p) == 0:                                                  # :235-236

@@ -254,6 +254,8 @@ class _ConnectorSolver(BasePathfinder):
                                                allow_diag=self.allow_diagonal_moves, restrict_corner=getattr(self, self._strict))
             if st[0] != 3:
                 break
+        if st[0] == 3:                                                   # a row of R * C cells holds every path: the open list's scratch ran out
+            raise RuntimeError("pathfit: open-list scratch overflow in %s.solve" % type(self).__name__)
         path = CellPath(paths[0], self.cols).tolist()
         res = self._calculate_stats_for_path(path)
         if len(path) > 1:
