@@ -650,6 +650,10 @@ int pf_selftest_slot_state(pf_handle* h, int32_t slot, int64_t* out3);
  * handle's error text to "not compiled in" and returns 1.  Synchronises the device. */
 int pf_selftest_open_paths(pf_handle* h, int64_t* out, int32_t n, int32_t reset);
 
+/* The same for the branches of the parallel closed-set engine (pf_settle.h, ST_*: 21 of them, in that order): the contract of
+ * pf_selftest_open_paths, a device array of its own, and the same -DPF_OPEN_PATHS builds. */
+int pf_selftest_settle_paths(pf_handle* h, int64_t* out, int32_t n, int32_t reset);
+
 /* Target-cell proposals of MPA._get_levy_target_node / _get_brownian_target_node (MPA.py:250-282) for n keyed streams
  * (seed, DOM_MPA, 0, i) from cells d_cur[i] (and elite cells d_elite[i], < 0 = None): the device arithmetic, with the
  * proposals whose accept test / rounding lies within the libm-disagreement margin recomputed by the host's glibc

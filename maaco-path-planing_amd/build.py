@@ -11,7 +11,8 @@ IEEE double and bit-exact path parity depends on it.
 
 also builds the stress variants of the A* open list (VARIANTS below) into lib/stress/libpathfit_<name>.so: the shipped code under
 a bucket geometry that makes its rare branches common, with the branch counters of -DPF_OPEN_PATHS compiled in
-(tests/test_gpu_open_list_stress.py runs tests/open_list_cases.py against each).
+(tests/test_gpu_open_list_stress.py runs tests/open_list_cases.py against each), and the stress variants of the parallel closed-set
+engine (SETTLE_VARIANTS: tests/test_gpu_settle_stress.py runs tests/settle_cases.py against each).
 """
 import os
 import subprocess
@@ -32,6 +33,15 @@ VARIANTS = {
     "wide64": ["-DPF_SW_Q=16.0", "-DPF_SW_NBK=64", "-DPF_SW_CAP=64"],                      # buckets of (nearly) 64, concatenation, wrap
     "wide256": ["-DPF_SW_Q=16.0", "-DPF_SW_NBK=64", "-DPF_SW_CAP=256", "-DPF_SELECT_MIN=65"],   # buckets > 64, pivot selection, evictions
     "spill256": ["-DPF_SW_CAP=8", "-DPF_SW_SPILL=256"],                                    # the spill list filling up: status 3
+}
+# Stress variants of the parallel closed-set engine (pf_settle.h), the same way: its shipped code under a band geometry that makes its
+# rare branches common.  The branch counters of -DPF_OPEN_PATHS cover both engines.
+SETTLE_VARIANTS = {
+    "st_cap4": ["-DPF_SETTLE_CAP=4"],                                                      # full buckets: hand-backs from the main loop
+    "st_q1": ["-DPF_ST_Q=1.0"],                                                            # bands of hundreds of nodes: the partial take, many-band takes
+    "st_q96": ["-DPF_ST_Q=96.0"],                                                          # pushes beyond the circular band range
+    "st_touch": ["-DPF_ST_TOUCH_NUM=1", "-DPF_ST_TOUCH_DEN=4"],                           # the touched list filling up on the far pairs
+    "st_wide2": ["-DPF_ST_WIDE=2", "-DPF_ST_Q=1.0"],                                       # two nodes per lane and trip
 }
 VARIANT_COMMON = ["-DPF_OPEN_PATHS"]
 MAX_JOBS = 16
@@ -61,7 +71,7 @@ def variant_path(name):
 
 
 def variant_flags(name):
-    return VARIANT_COMMON + VARIANTS[name]
+    return VARIANT_COMMON + (VARIANTS[name] if name in VARIANTS else SETTLE_VARIANTS[name])
 
 
 def build_variant(name, force=False, verbose=False):
@@ -71,7 +81,7 @@ def build_variant(name, force=False, verbose=False):
 
 def build_variants(names=None, force=False, verbose=False):
     """Several variants at once: one hipcc child each, at most MAX_JOBS at a time."""
-    names = list(VARIANTS) if names is None else list(names)
+    names = list(VARIANTS) + list(SETTLE_VARIANTS) if names is None else list(names)
     outs = [variant_path(n) for n in names]
     os.makedirs(os.path.dirname(variant_path("x")), exist_ok=True)
     todo = [(n, o) for n, o in zip(names, outs) if force or _stale(o)]

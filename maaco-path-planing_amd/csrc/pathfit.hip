@@ -77,7 +77,7 @@ PF_DEV Slot slot_load(const Common& c, int RC) {
   s.sm.touched = c.st_lab ? c.st_touched + (size_t)blockIdx.x * 2 * RC : nullptr;
   s.sm.par = c.st_lab ? c.st_par + (size_t)blockIdx.x * RC : nullptr;
   s.sm.epoch = c.st_lab ? c.st_epoch + blockIdx.x : nullptr;
-  s.sm.touched_cap = 2 * RC;
+  s.sm.touched_cap = PF_ST_TOUCHED_CAP(RC);
   s.sm.astar_too = c.st_astar;
   return s;
 }
@@ -2577,6 +2577,24 @@ int pf_selftest_open_paths(pf_handle* h, int64_t* out, int32_t n, int32_t reset)
 #else
   (void)reset;
   h->err = "pf_selftest_open_paths: the branch counters are not compiled in (build with -DPF_OPEN_PATHS)";
+  return 1;
+#endif
+}
+int pf_selftest_settle_paths(pf_handle* h, int64_t* out, int32_t n, int32_t reset) {
+  if (!h || !out || n < 0) return failmsg(h, "pf_selftest_settle_paths: bad arguments");
+  for (int i = 0; i < n; ++i) out[i] = 0;
+#ifdef PF_OPEN_PATHS
+  static_assert(pf::PF_ST_OP_N <= 32, "g_settle_paths holds the counters");
+  CK(hipSetDevice(h->device));
+  CK(hipDeviceSynchronize());
+  unsigned long long v[32];
+  CK(hipMemcpyFromSymbol(v, HIP_SYMBOL(pf::g_settle_paths), sizeof(v)));
+  for (int i = 0; i < n && i < (int)pf::PF_ST_OP_N; ++i) out[i] = (int64_t)v[i];
+  if (reset) { unsigned long long z[32] = {0}; CK(hipMemcpyToSymbol(HIP_SYMBOL(pf::g_settle_paths), z, sizeof(z))); }
+  return 0;
+#else
+  (void)reset;
+  h->err = "pf_selftest_settle_paths: the branch counters are not compiled in (build with -DPF_OPEN_PATHS)";
   return 1;
 #endif
 }

@@ -55,6 +55,7 @@ __device__ unsigned long long g_stamps[24];
 // diagnostic build only (-DPF_OPEN_PATHS): how often each branch of the open list ran (pf_astar_sw.h: OP_*), summed over all searches
 #ifdef PF_OPEN_PATHS
 __device__ unsigned long long g_open_paths[32];
+__device__ unsigned long long g_settle_paths[32];   // ... and of the parallel closed-set engine (pf_settle.h: ST_*)
 #endif
 
 // Mark cells[0..n) of a path as "avoid" for this slot's current eval epoch.

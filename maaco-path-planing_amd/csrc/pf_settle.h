@@ -26,12 +26,24 @@
 namespace pf {
 
 #define PF_ST_SEQ 5                 /* internal: not certified -> the caller runs the sequential engine */
+#ifndef PF_SETTLE_CAP
 #define PF_SETTLE_CAP 1024          /* entries per bucket (16 B each) */
+#endif
 // the band structure of this engine is its own (the pop loop's bucket width is tuned separately, pf_astar_sw.h)
 #ifndef PF_ST_Q
 #define PF_ST_Q 64.0
 #endif
 #define PF_ST_NBK 256
+// the touched list holds PF_ST_TOUCH_NUM / PF_ST_TOUCH_DEN x RC cells of the slot's 2 RC (the stride of the allocation, whatever the cap)
+#ifndef PF_ST_TOUCH_NUM
+#define PF_ST_TOUCH_NUM 2
+#endif
+#ifndef PF_ST_TOUCH_DEN
+#define PF_ST_TOUCH_DEN 1
+#endif
+#define PF_ST_TOUCHED_CAP(RC) ((RC) * PF_ST_TOUCH_NUM / PF_ST_TOUCH_DEN)
+static_assert(PF_ST_TOUCH_NUM >= 1 && PF_ST_TOUCH_DEN >= 1 && PF_ST_TOUCH_NUM <= 2 * PF_ST_TOUCH_DEN, "the touched list lies inside the slot's 2 RC cells");
+static_assert(PF_SETTLE_CAP >= 1 && PF_SETTLE_CAP <= 1024 && (size_t)PF_ST_NBK * PF_SETTLE_CAP * 12 <= PF_POOL_STRIDE, "the bucket pool lies inside the slot's open-list scratch");
 #define PF_LAB_KEYMASK ((1ull << 57) - 1ull)
 #ifndef PF_ST_WIDE
 #define PF_ST_WIDE 1                /* nodes per lane and trip (64 x this many nodes per trip) */
@@ -43,6 +55,45 @@ static_assert(PF_ST_MARK_OFF + 256 * PF_ST_WIDE <= PF_ST_WIN_OFF && PF_ST_WIN_OF
 static_assert(PF_ST_MARK_OFF >= 4 * PF_ST_NBK && PF_ST_MARK_OFF + 256 * PF_ST_WIDE <= PF_GEO_OFF, "band marks between the bucket counts and the replay table");
 #define PF_PAR_IRREG 0x7Fu            /* par[x]: x is irregular (no earlier argmin parent) */
 #define PF_PAR_SEEN 0x80u             /* par[x] bit 7: reached by the ancestor walk of this search */
+
+// diagnostic build only (-DPF_OPEN_PATHS, the stress variants of build.py): which branches of the engine a search took.  Counted per
+// wave in uniform values, added once per search to g_settle_paths (pf_astar.h) by lane 0; pf_selftest_settle_paths reads them.  Without
+// the macro every line below expands to nothing.  The order is the ABI of pf_selftest_settle_paths (tests/settle_cases.py names it).
+enum {
+  ST_WIPE,              // setup: the label epoch ran out, the label array was wiped
+  ST_TRIPS,             // trips of the main loop
+  ST_TAKE_ONE,          // trip: one whole band taken
+  ST_TAKE_MANY,         // trip: several whole bands taken together
+  ST_TAKE_PART,         // trip: 64 K entries of a band larger than a trip
+  ST_SUPERSEDED,        // taken entries skipped as superseded (the node holds a lower label by now)
+  ST_STOP_BOUND,        // loop exit: the current band lies above the goal's f
+  ST_STOP_EMPTY,        // loop exit: the open list is exhausted
+  ST_BACK_BUCKET,       // hand-back: a bucket is full
+  ST_BACK_RANGE,        // hand-back: a push beyond the circular band range
+  ST_BACK_TOUCHED,      // hand-back: the touched list is full
+  ST_BACK_WINNERS,      // hand-back: the trip's winner list is full
+  ST_BACK,              // searches handed back from the main loop, for whichever of the four reasons
+  ST_UNREACHED,         // certificate: the goal was never reached (status 1)
+  ST_ALL_REGULAR,       // certificate: the regularity pass found every node regular
+  ST_IRREGULAR,         // certificate: the pass found an irregular node (cone_walk runs)
+  ST_CONE_GOAL,         // cone_walk: the goal itself is irregular (handed back)
+  ST_CONE_ANCESTOR,     // cone_walk: an irregular ancestor met (handed back)
+  ST_CONE_QUEUE,        // cone_walk: the queue is full (handed back)
+  ST_CONE_OK,           // cone_walk: the goal's cone certified
+  ST_ROW_SHORT,         // path write-out: the row is too short (status 3)
+  PF_ST_OP_N
+};
+#ifdef PF_OPEN_PATHS
+#define ST_OP(i, n) op[i] += (unsigned)(n);
+#define ST_DO(...) __VA_ARGS__
+#define ST_OP_PARAM , unsigned* op
+#define ST_OP_PASS , op
+#else
+#define ST_OP(i, n)
+#define ST_DO(...)
+#define ST_OP_PARAM
+#define ST_OP_PASS
+#endif
 
 PF_DEV unsigned long long lab_enc(double g, unsigned code) {
   const unsigned long long b = dbits(g);
@@ -66,15 +117,16 @@ PF_DEV int opposite_move(int m) { return m < 4 ? (m ^ 1) : 11 - m; }   // helper
 // with the engine switched off: register allocation / code layout).
 template <int VARIANT>
 __device__ __attribute__((noinline)) bool cone_walk(const uint8_t* gmm, int C, uint64_t magicC, const unsigned long long* lab, unsigned char* par,
-                                                    int* queue, int qcap, int start, int target, int tr, int tc, unsigned code, double F, int lane) {
+                                                    int* queue, int qcap, int start, int target, int tr, int tc, unsigned code, double F, int lane ST_OP_PARAM) {
   const unsigned long long blocked = (unsigned long long)code << 57;
   __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");
   __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
-  if ((par[target] & 0x7Fu) == PF_PAR_IRREG) return false;               // the goal itself
+  if ((par[target] & 0x7Fu) == PF_PAR_IRREG) { ST_OP(0, 1) return false; }   // the goal itself
   int qh = 0, qt = 1;
   if (lane == 0) { queue[0] = target; par[target] |= PF_PAR_SEEN; }
   __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup"); __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
   bool tainted = false;
+  ST_DO(bool qfull = false;)
   while (qh < qt) {
     const bool in = qh + lane < qt;
     const int x = in ? queue[qh + lane] : start;
@@ -112,11 +164,11 @@ __device__ __attribute__((noinline)) bool cone_walk(const uint8_t* gmm, int C, u
       const unsigned long long fm = __ballot(fresh);
       if (fm) {
         const int at = qt + __builtin_popcountll(fm & ((1ull << lane) - 1ull));
-        if (fresh) { if (at < qcap) queue[at] = p; else tainted = true; }
+        if (fresh) { if (at < qcap) queue[at] = p; else { tainted = true; ST_DO(qfull = true;) } }
         qt += __builtin_popcountll(fm);
       }
     }
-    if (__ballot(tainted)) return false;
+    if (__ballot(tainted)) { ST_OP(1, __ballot(tainted && !qfull) != 0) ST_OP(2, __ballot(qfull) != 0) return false; }
     __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup"); __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
   }
   __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");
@@ -126,7 +178,7 @@ __device__ __attribute__((noinline)) bool cone_walk(const uint8_t* gmm, int C, u
 
 template <int VARIANT>
 __device__ __forceinline__ int settle_impl(const Grid& G, const Open& O, const SettleMem& M, int start, int target, int tr, int tc,
-                                           const int* av_list, int av_n, int* out, int out_cap, int& out_n, AStat& st, int lane) {
+                                           const int* av_list, int av_n, int* out, int out_cap, int& out_n, AStat& st, int lane ST_OP_PARAM) {
   constexpr int NBK = PF_ST_NBK, CAP = PF_SETTLE_CAP;
   const int C = G.C, RC = G.R * G.C;
   int* cnt = (int*)O.lf;                                            // LDS [NBK] entries per bucket
@@ -139,6 +191,7 @@ __device__ __forceinline__ int settle_impl(const Grid& G, const Open& O, const S
     for (int i = lane; i < RC; i += 64) M.lab[i] = ~0ull;
     __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
     ep = 1u;
+    ST_OP(ST_WIPE, 1)
   }
   if (lane == 0) M.epoch[0] = ep;
   const unsigned code = 127u - ep;
@@ -164,6 +217,7 @@ __device__ __forceinline__ int settle_impl(const Grid& G, const Open& O, const S
   int trips = 0;
   for (;;) {
     trips += 1;
+    ST_OP(ST_TRIPS, 1)
     const unsigned long long vt = __hip_atomic_load(&M.lab[target], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);   // (at L2, where the atomics land)
     // ---- next non-empty bucket ----
     PF_LDS_ORDER();
@@ -174,10 +228,10 @@ __device__ __forceinline__ int settle_impl(const Grid& G, const Open& O, const S
         const unsigned long long nz = __ballot(c_ > 0);
         if (nz) { b0 = bcur + base + __builtin_ctzll(nz); break; }
       }
-      if (b0 < 0) break;                                             // open list exhausted
+      if (b0 < 0) { ST_OP(ST_STOP_EMPTY, 1) break; }                 // open list exhausted
       bcur = b0;
     }
-    if (F != PF_INF && (double)bcur > F * PF_ST_Q) break;            // every remaining entry has f above the goal's
+    if (F != PF_INF && (double)bcur > F * PF_ST_Q) { ST_OP(ST_STOP_BOUND, 1) break; }   // every remaining entry has f above the goal's
     // ---- K entries per lane: the whole buckets from bcur on that fit 64 K slots (a fixpoint does not care about the order, and
     // one 1/64-wide band alone rarely holds that many nodes), or 64 K entries of the first one when it is larger.  A trip is
     // three dependent memory round trips whatever its width (r03: ~3/4 of its time on an idle chip), so K nodes per lane cost
@@ -191,6 +245,7 @@ __device__ __forceinline__ int settle_impl(const Grid& G, const Open& O, const S
       const int cb = bcur + lane <= lim ? cnt[(bcur + lane) & (NBK - 1)] : 0;   // lane k: size of the k-th band from bcur
       const int c0 = bcast_i(cb, 0);
       if (c0 > 64 * K) {
+        ST_OP(ST_TAKE_PART, 1)
 #pragma unroll
         for (int u = 0; u < K; ++u) eidx[u] = (bcur & (NBK - 1)) * CAP + c0 - 64 * K + 64 * u + lane;
         PF_LDS_ORDER();
@@ -199,6 +254,8 @@ __device__ __forceinline__ int settle_impl(const Grid& G, const Open& O, const S
         const int incl = wave_incl_sum(cb);
         const int k = __builtin_popcountll(__ballot(incl <= 64 * K));   // (sizes are >= 0: the bands that fit are a prefix; k >= 1)
         const int total = bcast_i(incl, k - 1);
+        ST_OP(ST_TAKE_ONE, __builtin_popcountll(__ballot(lane < k && cb > 0)) == 1 ? 1 : 0)
+        ST_OP(ST_TAKE_MANY, __builtin_popcountll(__ballot(lane < k && cb > 0)) > 1 ? 1 : 0)
         int* mark = (int*)((char*)O.lf + PF_ST_MARK_OFF);               // [64 K]: where, among the taken entries, each band starts
 #pragma unroll
         for (int u = 0; u < K; ++u) mark[64 * u + lane] = 0;
@@ -247,6 +304,7 @@ __device__ __forceinline__ int settle_impl(const Grid& G, const Open& O, const S
       rr[u] = row_of(G, cell[u]); cc[u] = cell[u] - rr[u] * C;
       long hdr = rr[u] - tr, hdc = cc[u] - tc;
       const double f = VARIANT == 2 ? g[u] : g[u] + __builtin_sqrt((double)(hdr * hdr + hdc * hdc));
+      ST_OP(ST_SUPERSEDED, __builtin_popcountll(__ballot(have[u] && own[u] != lab_enc(g[u], code))))
       have[u] = have[u] && cell[u] != target && own[u] == lab_enc(g[u], code) && !(own[u] == blocked && cell[u] != start) && f <= F;   // superseded / goal / outside the region
       if (have[u]) exp_l += 1;
     }
@@ -283,7 +341,8 @@ __device__ __forceinline__ int settle_impl(const Grid& G, const Open& O, const S
       const int total = bcast_i(incl, 63);
       int* ln = (int*)((char*)O.lf + PF_ST_WIN_OFF);
       double* lt = (double*)((char*)O.lf + PF_ST_WIN_OFF + 4 * PF_ST_WIN_CAP);
-      if (total > PF_ST_WIN_CAP) { fail = true; break; }
+      if (total > PF_ST_WIN_CAP) { ST_OP(ST_BACK_WINNERS, 1) ST_OP(ST_BACK, 1) fail = true; break; }
+      ST_DO(unsigned why = 0u;)
       int wi = incl - wcnt;
 #pragma unroll
       for (int u = 0; u < K; ++u)
@@ -306,14 +365,16 @@ __device__ __forceinline__ int settle_impl(const Grid& G, const Open& O, const S
           const int at = __hip_atomic_fetch_add(&cnt[ba & (NBK - 1)], 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
           if (at >= CAP || ba - bcur >= NBK) fail = true;
           else { eg[(size_t)(ba & (NBK - 1)) * CAP + at] = t; ec[(size_t)(ba & (NBK - 1)) * CAP + at] = n; }
+          ST_DO(why |= ba - bcur >= NBK ? 2u : (at >= CAP ? 1u : 0u);)
           const int tt = nt + c0 + lane;
-          if (tt < M.touched_cap) M.touched[tt] = n; else fail = true;
+          if (tt < M.touched_cap) M.touched[tt] = n; else { fail = true; ST_DO(why |= 4u;) }
         }
       }
       nt += total;
       PF_LDS_ORDER();
+      ST_OP(ST_BACK_BUCKET, __ballot(why & 1u) != 0) ST_OP(ST_BACK_RANGE, __ballot(why & 2u) != 0) ST_OP(ST_BACK_TOUCHED, __ballot(why & 4u) != 0)
     }
-    if (__ballot(fail)) { fail = true; break; }
+    if (__ballot(fail)) { ST_OP(ST_BACK, 1) fail = true; break; }
     F = (vt >> 57) == code ? lab_dec(vt) : PF_INF;                   // (h(goal) = 0: f = g) -- the bound the NEXT trip works with
   }
   st.pops += (unsigned long long)wave_sum_i((int)exp_l); st.pushes += 1u + (unsigned)wave_sum_i((int)push_l);
@@ -323,7 +384,7 @@ __device__ __forceinline__ int settle_impl(const Grid& G, const Open& O, const S
   __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");
   __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");                  // the passes below read the labels the atomics left in L2
   const unsigned long long vt = M.lab[target];
-  if ((vt >> 57) != code || vt == blocked) return 1;                 // the goal was never reached: astar.py:101 -> []
+  if ((vt >> 57) != code || vt == blocked) { ST_OP(ST_UNREACHED, 1) return 1; }   // the goal was never reached: astar.py:101 -> []
   F = lab_dec(vt);
   // ---- regularity + parents, one touched node per lane ----
   // par[x] = the move from its smallest-key regular parent (0..7), or PF_PAR_IRREG when x is irregular
@@ -358,15 +419,19 @@ __device__ __forceinline__ int settle_impl(const Grid& G, const Open& O, const S
   }
   if (__ballot(bad)) {
     // Irregular nodes exist: certify the goal's ancestor cone instead of the whole region (cone_walk below).
-    if (!cone_walk<VARIANT>(G.mm, C, G.magicC, M.lab, M.par, M.touched, M.touched_cap, start, target, tr, tc, code, F, lane)) return PF_ST_SEQ;
-  }
+    ST_OP(ST_IRREGULAR, 1)
+    ST_DO(unsigned cw[3] = {0u, 0u, 0u};)
+    const bool clean = cone_walk<VARIANT>(G.mm, C, G.magicC, M.lab, M.par, M.touched, M.touched_cap, start, target, tr, tc, code, F, lane ST_DO(, cw));
+    ST_OP(ST_CONE_GOAL, cw[0]) ST_OP(ST_CONE_ANCESTOR, cw[1]) ST_OP(ST_CONE_QUEUE, cw[2]) ST_OP(ST_CONE_OK, clean ? 1 : 0)
+    if (!clean) return PF_ST_SEQ;
+  } ST_DO(else { op[ST_ALL_REGULAR] += 1u; })
   __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");
   __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
   // ---- the path: parents from the goal (astar.py:65-69), then reverse in place ----
   int n = 0, cell = target;
   const int guard = RC;
   while (cell != start) {
-    if (n >= out_cap - 1 || n > guard) return 3;
+    if (n >= out_cap - 1 || n > guard) { ST_OP(ST_ROW_SHORT, 1) return 3; }
     if (lane == 0) out[n] = cell;
     const int mv = M.par[cell] & 7;
     cell -= move_dr(mv) * C + move_dc(mv);
@@ -398,7 +463,9 @@ __device__ __attribute__((noinline)) long long settle_call(const uint8_t* gmm, i
   SettleMem M; M.lab = lab; M.touched = touched; M.par = par; M.epoch = epoch; M.touched_cap = touched_cap; M.astar_too = true;
   AStat st = {0, 0, 0, 0, 0, 0};
   int out_n = 0;
-  const int rs = settle_impl<VARIANT>(G, O, M, start, target, tr, tc, av_list, av_n, out, out_cap, out_n, st, lane);
+  ST_DO(unsigned op[PF_ST_OP_N]; for (int i = 0; i < PF_ST_OP_N; ++i) op[i] = 0u;)
+  const int rs = settle_impl<VARIANT>(G, O, M, start, target, tr, tc, av_list, av_n, out, out_cap, out_n, st, lane ST_OP_PASS);
+  ST_DO(if (lane == 0) for (int i = 0; i < PF_ST_OP_N; ++i) if (op[i]) atomicAdd(&g_settle_paths[i], (unsigned long long)op[i]);)
   PF_LDS_ORDER();
   if (lane == 0) { unsigned* w = (unsigned*)(pf_dyn_lds + PF_SX_OFF); w[0] = (unsigned)st.pops; w[1] = (unsigned)st.pushes; w[2] = (unsigned)st.nbr; w[3] = (unsigned)st.max_open; }
   PF_LDS_ORDER();

@@ -98,6 +98,7 @@ SYMBOLS = {
     "pf_selftest_rng": (C.c_int, [_vp, _u64, _u64, _u64, _u64, _vp, _vp, _vp]),
     "pf_selftest_slot_state": (C.c_int, [_vp, _i32, _vp]),
     "pf_selftest_open_paths": (C.c_int, [_vp, _vp, _i32, _i32]),
+    "pf_selftest_settle_paths": (C.c_int, [_vp, _vp, _i32, _i32]),
     "pf_ga_select_dev": (C.c_int, [_vp, _u64, _i32, _i32, _i32, _vp, _vp, _vp]),
     "pf_ga_breed_dev": (C.c_int, [_vp, _u64, _i32, _i32, _i32, _dbl, _dbl, _vp, _vp, _i32, _i32, _vp]),
     "pf_ga_assemble_dev": (C.c_int, [_vp, _i32, _i32, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i32, _i32, _vp, _vp, _vp, _vp]),
