@@ -5,6 +5,7 @@ HBM between calls; the ``*_host`` conveniences stage numpy arrays for the
 facades and tests.
 """
 import ctypes as C
+import weakref
 
 import numpy as np
 
@@ -116,6 +117,7 @@ class Engine:
         self.device = int(device)
         self._out13 = (C.c_double * 13)()   # pf_maaco_iterate's answer block, reused
         self.klog = None          # a list: every hot-path launch appends (kernel family, its HIP-event ms, its counters)
+        self._mpa_owner = None    # weak reference to the solo MPA whose pf_mpa_setup the handle holds (see mpa_setup)
 
     def update_grid(self, grid):
         """Dynamic maps: replace the occupancy (same shape); solvers built on the old map must be set up again."""
@@ -474,7 +476,21 @@ class Engine:
 
     # ------------------------------------------------------------------ K7
     def mpa_setup(self, mp, sp):
+        """The handle holds ONE solo MPA set-up (parameters, memoised initial path, pruning bounds) and one set of look-ahead
+        level buffers.  The facade object whose set-up it held (mpa_set_owner) is told first (its _own_views()), while the
+        level rows its candidate views point into are still there: the next merged sweep rewrites them and may free them."""
+        cur = self.mpa_owner()
+        self._mpa_owner = None
+        if cur is not None:
+            cur._own_views()
         self._ck(self.L.pf_mpa_setup(self.h, C.byref(mp), C.byref(sp)))
+
+    def mpa_set_owner(self, owner):
+        """`owner` (an MPA facade) has just called mpa_setup: the set-up is its own until the next mpa_setup."""
+        self._mpa_owner = weakref.ref(owner)
+
+    def mpa_owner(self):
+        return self._mpa_owner() if self._mpa_owner is not None else None
 
     def mpa_phase(self, phase, CF, it, seed, n, path_cap, d_pop_cells, d_pop_len, d_pop_stats, d_gidx, d_slot,
                   elite_cells_ptr, elite_len, elite_stats_ptr, d_out_cells, d_out_len, d_out_stats, d_status):

@@ -139,9 +139,12 @@ class MPA(BestSoFar):
         self._t = self.target_node[0] * self.cols + self.target_node[1]
         self._sp = score_params(1, restrict_diagonal_near_obstacle, turn_penalty_factor, safety_penalty_factor,
                                 min_safe_distance, diagonal_obstacle_penalty)
-        self.engine.mpa_setup(MpaParams(float(P_const), float(levy_beta), levy_sigma(levy_beta), float(FADs_rate),
-                                        int(num_predators), self._s, self._t, int(bool(allow_diagonal_moves)),
-                                        int(bool(restrict_diagonal_near_obstacle))), self._sp)
+        self._mp = MpaParams(float(P_const), float(levy_beta), levy_sigma(levy_beta), float(FADs_rate),
+                             int(num_predators), self._s, self._t, int(bool(allow_diagonal_moves)),
+                             int(bool(restrict_diagonal_near_obstacle)))
+        self.engine.mpa_setup(self._mp, self._sp)
+        if hasattr(self.engine, "mpa_set_owner"):
+            self.engine.mpa_set_owner(self)
         self.path_cap = min(self.rows * self.cols, 8 * (self.rows + self.cols) + 64)
         self._init_population()
 
@@ -224,6 +227,7 @@ class MPA(BestSoFar):
     def step(self, it):
         """One iteration of MPA.py:332-440 (it is 1-based)."""
         e, N, cap = self.engine, self.n_local, self.path_cap
+        self._claim()
         self._sort()                                                     # :333
         e.mpa_pick_elite(cap, self.d_cells, self.d_len, self.d_stats, self.d_order)   # :334 elite = population[0].copy()
         CF, phase = cf_and_phase(it, self.num_iterations)                # :336
@@ -254,11 +258,33 @@ class MPA(BestSoFar):
         if hasattr(self.engine, "mpa_ahead_drop"):
             self.engine.mpa_ahead_drop()
 
+    def _claim(self):
+        """The handle holds one solo MPA set-up (Engine.mpa_setup): if another MPA on this Engine has stepped since, or the map
+        was set up anew, set this one up again.  That drops the levels swept ahead -- the next take finds nothing waiting, the
+        history gets STALE -- and the other instance has copied the candidate rows it was reading out of the level buffers."""
+        e = self.engine
+        if hasattr(e, "mpa_owner") and e.mpa_owner() is not self:
+            e.mpa_setup(self._mp, self._sp)
+            e.mpa_set_owner(self)
+
+    def _own_views(self):
+        """Candidate rows that are views into the handle's level buffers (after a served or leading step) are copied into this
+        instance's own rows, and d_cand_* / d_c2_* / d_status point there again: the level buffers are about to be rewritten,
+        or freed, by another instance's sweep."""
+        cur = (self.d_cand_cells, self.d_cand_len, self.d_cand_stats, self.d_c2_cells, self.d_c2_len, self.d_c2_stats, self.d_status)
+        if cur[0] is self._own_rows[0]:
+            return
+        for own, view in zip(self._own_rows, cur):
+            own.copy_from(0, view, 0, int(np.prod(view.shape)))
+        (self.d_cand_cells, self.d_cand_len, self.d_cand_stats, self.d_c2_cells, self.d_c2_len, self.d_c2_stats,
+         self.d_status) = self._own_rows
+
     def _sweep(self, it, n, d_gidx, d_slot, world=1):
         """The fused device work of iteration `it` for the n predators stored here (MPA.step and ShardedMPA.step).  With the
         look-ahead on (one rank only: another rank's acceptance changes the global list) an iteration that follows a quiet
         one is served from the sweep that already covered it, or sweeps the iterations after it along with its own."""
         e, cap, K = self.engine, self.path_cap, self.num_iterations
+        self._claim()
         own = self._own_rows
         st = e.mpa_ahead_stats() if world == 1 else {"cap": 0, "always": 0}
         el_c, el_s = self._el_cells.ptr, self._el_stats.ptr

@@ -1,6 +1,7 @@
 """How many candidates does an MPA iteration accept?  The CPU probe behind the look-ahead of DESIGN.md 4.9 (oracle only, no GPU).
 
     python scripts/probe_mpa_acceptance.py [--grid 512] [--predators 4096] [--iterations 20] [--seed 0] [--upto K] [--json OUT]
+    python scripts/probe_mpa_acceptance.py --map door --predators 20 --iterations 48      (a small map of tests/lookahead_cases.py)
 
 Runs oracle/pf_loops.MpaOracle (bit-exact with the device by the parity tests) on the mpa512 bench workload by default (G512,
 4 096 predators, K = 20, seed 0, bench.py's MPA_MAIN parameters) and prints, per iteration:
@@ -85,6 +86,8 @@ def quiet_runs(rows):
 def main():
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
     ap.add_argument("--grid", type=int, default=512, choices=[128, 256, 512, 1024])
+    ap.add_argument("--map", default="", choices=["", "door", "open12", "fig7"],
+                    help="a small map of tests/lookahead_cases.py instead of the bench grid (the look-ahead tests' cases)")
     ap.add_argument("--predators", type=int, default=4096)
     ap.add_argument("--iterations", type=int, default=20)
     ap.add_argument("--seed", type=int, default=0)
@@ -94,8 +97,13 @@ def main():
     import pf_loops
     import pf_oracle as po
     from pathfit import env
-    g = env.bench_grid(a.grid)
-    s, t = (int(np.flatnonzero(g.reshape(-1) == m)[0]) for m in (2, 3))
+    if a.map:
+        sys.path.insert(0, os.path.join(ROOT, "tests"))
+        import lookahead_cases
+        g, s, t = lookahead_cases.grid(a.map)
+    else:
+        g = env.bench_grid(a.grid)
+        s, t = (int(np.flatnonzero(g.reshape(-1) == m)[0]) for m in (2, 3))
     ref = pf_loops.MpaOracle(po.Oracle(g), s, t, a.predators, a.iterations, seed=a.seed, **MPA_MAIN)
     print("| it | searching | accepted | distinct fitness values after it |\n|---|---|---|---|", flush=True)
     rows = acceptance_rows(ref, a.upto or None, lambda r: print("| %d | %d | %d | %d |" % r, flush=True))

@@ -257,7 +257,8 @@ def _sharded_mpa_worker(rank, world, port, out_dir):
     fits = [sm.step(it) for it in range(1, 13)]
     m = sm.local
     np.savez(os.path.join(out_dir, f"r{rank}.npz"), fits=np.array(fits), stats=m.d_stats.download(), lens=m.d_len.download(),
-             cells=m.d_cells.download(), gorder=sm.gorder)
+             cells=m.d_cells.download(), gorder=sm.gorder,
+             ahead=np.array([eng.mpa_ahead_stats()[k] for k in ("cap", "merged_sweeps", "levels_ahead", "served", "stale")]))
     dist.barrier(); dist.destroy_process_group()
 
 
@@ -277,6 +278,8 @@ def test_sharded_mpa_two_ranks_equals_single(tmp_path):
     z0, z1 = np.load(tmp_path / "r0.npz"), np.load(tmp_path / "r1.npz")
     assert np.array_equal(z0["fits"], fits) and np.array_equal(z1["fits"], fits)
     assert np.array_equal(z0["gorder"], sm.gorder) and np.array_equal(z1["gorder"], sm.gorder)
+    for z in (z0, z1):                                     # the look-ahead is on (its default cap) and is one-rank only:
+        assert z["ahead"][0] > 0 and list(z["ahead"][1:]) == [0, 0, 0, 0]   # no merged sweep, nothing served, with world = 2
     stats = np.concatenate([z0["stats"], z1["stats"]]); lens = np.concatenate([z0["lens"], z1["lens"]])
     cells = np.concatenate([z0["cells"], z1["cells"]])
     assert np.array_equal(stats, ref_stats) and np.array_equal(lens, ref_len)
