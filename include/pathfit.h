@@ -442,6 +442,30 @@ int pf_dist_field_merged(pf_handle* h, int32_t allow_diag, int32_t restrict_corn
 int pf_dist_field_owners(pf_handle* h, int32_t B, const uint8_t* d_parents, const int32_t* set_off, const int32_t* src,
                          const int64_t* d_info, int32_t* d_owner, int64_t* d_count);
 
+/* ---- any-angle smoothing: line of sight between cell centres, forward string pulling (pathfit.PathSmoother) ------------
+ * The rule is exact integer geometry.  For a = (r0, c0), b = (r1, c1), dr = r1 - r0, dc = c1 - c0,
+ * s = |dr| + |dc| and a cell (r, c) of the bounding box, k = dr (c - c0) - dc (r - r0): the segment between the centres CROSSES
+ * the cell's open square iff |2k| < s and TOUCHES it in a corner point only iff |2k| == s.  a sees b iff no crossed cell is an
+ * obstacle and, with restrict_corner != 0, no touched one either (on a single diagonal step: the corner-cut rule of the move
+ * policies); a == b is visible iff the cell is free.  Both calls read the handle's occupancy at call time.
+ * pf_line_of_sight_batch: n pairs of cell ids -> d_visible[i] = 0 / 1 and, when d_first_block != NULL, the blocking cell of the
+ * major index (columns if |dc| >= |dr|, else rows) nearest d_from[i], the smallest r C + c among that index's blocking cells;
+ * -1 when visible.  An endpoint outside the grid gives visible = 0, first_block = -1.  One wavefront per pair.
+ * pf_smooth_batch: n path rows laid out as pf_astar_batch's (d_cells[i * path_cap ..], d_len[i]) -> the waypoints the forward
+ * rule keeps: out = [0]; a = 0; j = 1; while j + 1 < L: visible(p[a], p[j + 1]) ? j += 1 : (out += [j], a = j, j = a + 1);
+ * out += [L - 1].  Consecutive input cells are never tested; the input need not be a legal path.  d_way_cells [n * way_cap] the
+ * cells, d_way_idx (or NULL) their positions in the input row, d_way_len their number, d_stats (or NULL) [n * 2] = {the sum of
+ * the segments' Euclidean lengths left to right, the interior waypoints whose two segments are not parallel and equally
+ * directed}, both 0 unless the status is 0.  d_status: 0 ok; 1 = an empty row, a length beyond path_cap or a cell outside [0, R C): length 0, the waypoint row
+ * untouched; 3 = more waypoints than way_cap: length 0, the row's contents unspecified.  One wavefront per path.
+ * Both: n < 0, a cap < 1 or a missing required pointer is an argument error (-1) found before any launch; n == 0 returns 0 and
+ * launches nothing.  Synchronous, ordered on the handle's stream; pf_last_kernel_ms reports the kernel. */
+int pf_line_of_sight_batch(pf_handle* h, int32_t restrict_corner, int32_t n, const int32_t* d_from, const int32_t* d_to,
+                           int32_t* d_visible, int32_t* d_first_block);
+int pf_smooth_batch(pf_handle* h, int32_t restrict_corner, int32_t n, int32_t path_cap, const int32_t* d_cells,
+                    const int32_t* d_len, int32_t way_cap, int32_t* d_way_cells, int32_t* d_way_idx, int32_t* d_way_len,
+                    double* d_stats, int32_t* d_status);
+
 /* Tuning knobs (results never change): "maaco_pack8_min" ants per batch from which eight ants share a wavefront
  * (default 2048); "maaco_load_ahead" the packed walk kernel's load-ahead form (all of a step's loads issued together plus touches of the
  * records two steps ahead): -1 (default) for batches of at most one wavefront per SIMD, 0 never, 1 always;

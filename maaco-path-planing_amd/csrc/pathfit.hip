@@ -4923,3 +4923,58 @@ int pf_dist_field_owners(pf_handle* h, int32_t B, const uint8_t* d_parents, cons
 }
 
 }  // extern "C"
+
+// ---------------------------------------------------------------------------
+// Any-angle smoothing: line-of-sight tests and forward string pulling (pf_smooth.h).  Both read the handle's
+// occupancy bytes at call time (pf_update_grid keeps working) and keep nothing on the handle.
+// ---------------------------------------------------------------------------
+#include "pf_smooth.h"
+
+extern "C" {
+
+int pf_line_of_sight_batch(pf_handle* h, int32_t restrict_corner, int32_t n, const int32_t* d_from, const int32_t* d_to, int32_t* d_visible,
+                           int32_t* d_first_block) {
+  if (!h) return -2;
+  if (n < 0 || !d_from || !d_to || !d_visible) {
+    failmsg(h, "pf_line_of_sight_batch: bad arguments (n >= 0; the endpoints and the visibility flags must not be null)");
+    return -1;
+  }
+  if (n == 0) return 0;
+  auto run = [&]() -> int {
+    CK(hipSetDevice(h->device));
+    CK(hipEventRecord(h->ev0, h->stream));
+    hipLaunchKernelGGL(k_line_of_sight_pairs_lanes_on_major<>, dim3((unsigned)n), dim3(64), 0, h->stream, (const uint8_t*)h->d_occ, h->RC, h->C, restrict_corner ? 1 : 0, n,
+                       d_from, d_to, d_visible, d_first_block);
+    CK(hipGetLastError());
+    CK(hipEventRecord(h->ev1, h->stream));
+    CK(hipStreamSynchronize(h->stream));
+    CK(hipEventElapsedTime(&h->last_ms, h->ev0, h->ev1));
+    return 0;
+  };
+  return run() ? -1 : 0;
+}
+
+int pf_smooth_batch(pf_handle* h, int32_t restrict_corner, int32_t n, int32_t path_cap, const int32_t* d_cells, const int32_t* d_len, int32_t way_cap,
+                    int32_t* d_way_cells, int32_t* d_way_idx, int32_t* d_way_len, double* d_stats, int32_t* d_status) {
+  if (!h) return -2;
+  if (n < 0 || path_cap < 1 || way_cap < 1 || !d_cells || !d_len || !d_way_cells || !d_way_len || !d_status) {
+    failmsg(h, "pf_smooth_batch: bad arguments (n >= 0, path_cap >= 1, way_cap >= 1; the rows, the lengths, the waypoint rows, their lengths and "
+               "the statuses must not be null)");
+    return -1;
+  }
+  if (n == 0) return 0;
+  auto run = [&]() -> int {
+    CK(hipSetDevice(h->device));
+    CK(hipEventRecord(h->ev0, h->stream));
+    hipLaunchKernelGGL(k_smooth_paths_one_wave_per_row<>, dim3((unsigned)n), dim3(64), 0, h->stream, (const uint8_t*)h->d_occ, h->RC, h->C, restrict_corner ? 1 : 0, n, path_cap,
+                       d_cells, d_len, way_cap, d_way_cells, d_way_idx, d_way_len, d_stats, d_status);
+    CK(hipGetLastError());
+    CK(hipEventRecord(h->ev1, h->stream));
+    CK(hipStreamSynchronize(h->stream));
+    CK(hipEventElapsedTime(&h->last_ms, h->ev0, h->ev1));
+    return 0;
+  };
+  return run() ? -1 : 0;
+}
+
+}  // extern "C"

@@ -18,3 +18,4 @@ from .ga_batch import GABatch, GaPopulation  # noqa: F401
 from .pso_batch import PSOBatch, PsoSwarm  # noqa: F401
 from .dist_field import DistanceField  # noqa: F401
 from .nearest_field import NearestSourceField  # noqa: F401
+from .smooth import PathSmoother  # noqa: F401

@@ -162,6 +162,8 @@ SYMBOLS = {
     "pf_dist_field_paths": (C.c_int, [_vp, _i32, _vp, _vp, _i32, _vp, _vp, _i32, _i32, _vp, _vp, _vp, _vp]),
     "pf_dist_field_merged": (C.c_int, [_vp, _i32, _i32, _i32, _vp, _vp, _vp, _vp]),
     "pf_dist_field_owners": (C.c_int, [_vp, _i32, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "pf_line_of_sight_batch": (C.c_int, [_vp, _i32, _i32, _vp, _vp, _vp, _vp]),
+    "pf_smooth_batch": (C.c_int, [_vp, _i32, _i32, _i32, _vp, _vp, _i32, _vp, _vp, _vp, _vp, _vp]),
 }
 
 

@@ -272,6 +272,26 @@ class Engine:
                                              d_count.ptr if d_count else None))
         self._logk("dist_field_owners")
 
+    # ------------------------------------------------------------------ any-angle smoothing
+    def line_of_sight_batch(self, d_from, d_to, n, d_visible, d_first_block=None, restrict_corner=True):
+        """n pairs of cell ids in HBM -> d_visible int32[n] (0 / 1: the segment between the centres meets no obstacle; with
+        restrict_corner, touches none in a corner either) and d_first_block int32[n] (the blocking cell nearest d_from, -1 when
+        visible), on the occupancy the handle holds now (pf_line_of_sight_batch)."""
+        self._ck(self.L.pf_line_of_sight_batch(self.h, int(bool(restrict_corner)), int(n), d_from.ptr if d_from else None, d_to.ptr if d_to else None,
+                                               d_visible.ptr if d_visible else None, d_first_block.ptr if d_first_block else None))
+        self._logk("line_of_sight")
+
+    def smooth_batch(self, n, path_cap, d_cells, d_len, way_cap, d_way_cells, d_way_len, d_status, d_way_idx=None, d_stats=None,
+                     restrict_corner=True):
+        """Rows of astar_batch's layout in HBM -> the waypoints forward string pulling keeps: d_way_cells [n, way_cap], d_way_idx (their
+        positions in the input row), d_way_len, d_stats [n, 2] = (length, turns), d_status (0 ok, 1 bad row, 3 more waypoints than
+        way_cap) (pf_smooth_batch)."""
+        self._ck(self.L.pf_smooth_batch(self.h, int(bool(restrict_corner)), int(n), int(path_cap), d_cells.ptr if d_cells else None,
+                                        d_len.ptr if d_len else None, int(way_cap), d_way_cells.ptr if d_way_cells else None,
+                                        d_way_idx.ptr if d_way_idx else None, d_way_len.ptr if d_way_len else None,
+                                        d_stats.ptr if d_stats else None, d_status.ptr if d_status else None))
+        self._logk("smooth")
+
     # ------------------------------------------------------------------ K1
     def score_batch(self, n, path_cap, d_cells, d_len, d_stats, sp):
         """Rows of astar_batch's layout in HBM -> d_stats [n, 5] doubles (pf_score_batch)."""
