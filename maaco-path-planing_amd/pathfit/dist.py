@@ -380,11 +380,20 @@ def _mkbuf(engine, shape, dtype):
     return engine.buf(shape, dtype)
 
 
+def _require_agents(what, n, comm):
+    """Every rank needs at least one agent: the engine calls reject n <= 0, so a rank without agents would raise in its first
+    launch while the others wait for it in a collective.  The same verdict on every rank, before anything is built or exchanged."""
+    if int(n) < comm.world:
+        raise ValueError("%s: N = %d agents cannot be sharded over a world size of %d ranks (every rank needs at least one)"
+                         % (what, int(n), comm.world))
+
+
 # ======================================================================================================================
 class ShardedMAACO:
     """MAACO.solve_path_planning (MAACO.py:334-371) with the ants of every iteration sharded over ranks."""
 
     def __init__(self, comm, make_local, num_ants, strict=True, chunks=8):
+        _require_agents("ShardedMAACO", num_ants, comm)
         self.comm = comm
         self.counts = _counts(num_ants, comm.world)
         self.a0, self.a1 = shard_range(num_ants, comm.rank, comm.world)
@@ -496,6 +505,7 @@ class ShardedMPA:
     an all_gather of the fitness column + the same stable device sort everywhere."""
 
     def __init__(self, comm, make_local, num_predators_total):
+        _require_agents("ShardedMPA", num_predators_total, comm)
         self.comm = comm
         self.N = num_predators_total
         self.counts = _counts(self.N, comm.world)
@@ -606,6 +616,8 @@ def ShardedPSO(comm, grid, **kw):
     """PSOSolver with the swarm sharded over the ranks of `comm` in contiguous blocks of particles; the asynchronous gbest
     (pso.py:222-229) is repaired across ranks (see PSOSolver.sweep).  solve() returns the same tuple on every rank."""
     from .solvers import PSOSolver
+    if "num_particles" in kw:                      # (a missing argument is the constructor's to report)
+        _require_agents("ShardedPSO", kw["num_particles"], comm)
     return PSOSolver(grid, comm=comm, **kw)
 
 
@@ -613,4 +625,6 @@ def ShardedGA(comm, grid, **kw):
     """GASolver with the individuals sharded over the ranks of `comm` by child index; C3 (all_gather of fitness and
     chromosomes) feeds the replicated tournament selection (see GASolver._solve_device)."""
     from .solvers import GASolver
+    if "population_size" in kw:
+        _require_agents("ShardedGA", kw["population_size"], comm)
     return GASolver(grid, comm=comm, **kw)
