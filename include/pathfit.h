@@ -466,7 +466,32 @@ int pf_smooth_batch(pf_handle* h, int32_t restrict_corner, int32_t n, int32_t pa
                     const int32_t* d_len, int32_t way_cap, int32_t* d_way_cells, int32_t* d_way_idx, int32_t* d_way_len,
                     double* d_stats, int32_t* d_status);
 
-/* Tuning knobs (results never change): "maaco_pack8_min" ants per batch from which eight ants share a wavefront
+/* ---- connected components: labels, sizes, reachability queries (pathfit.Components) ----------------------------------------
+ * Cells are r C + c.  A cell is free iff its grid value is not 1; two free cells are adjacent iff the handle's move mask of the
+ * call's policy allows the move (the byte pf_astar_batch and pf_dist_field_batch use; symmetric under all four policies).  The
+ * masks are read at call time: after pf_update_grid the next call labels the new map.
+ * pf_components: d_labels[v] = -1 on an obstacle, else the rank of v's component when the components are ordered by their
+ * smallest cell id (the numbering the searches' own labels use).  d_info (or NULL): {count, free cells, the size of the largest
+ * component, its label}, the lowest label on a tie, -1 for the last field when count == 0.  Union-find rooted at the smallest
+ * cell id, linked with agent-scope atomics, then flattened, ranked by an exclusive scan of the root flags in cell order and
+ * counted with integer atomics: work and launches do not grow with a component's diameter and the result does not depend on the
+ * order the links land in.  The handle keeps about three int32 words per cell of scratch from the first call on.
+ * pf_component_sizes: d_sizes[l] (or NULL) = the cells labelled l and d_first[l] (or NULL) = the smallest of them (strictly
+ * increasing in l for pf_components' labels; -1 for a label no cell carries), for l in [0, count); labels outside [0, count) are
+ * ignored.  pf_components_same: d_same[i] = 1 iff d_a[i] and d_b[i] both lie in [0, RC), both labels are >= 0 and they are equal
+ * (a free cell is connected to itself), else 0; nothing is read out of range.
+ * A null handle (-2), a missing required pointer, n < 0 or count < 0 (-1, with a message) is an argument error found before any
+ * launch; n == 0 or count == 0 returns 0 and launches nothing.  All three are synchronous and ordered on the handle's stream;
+ * pf_last_kernel_ms reports the kernels.  pf_components_phase_ms: the HIP-event spans of the last pf_components call made under
+ * pf_set_option "components_phases" = 1 -- {init + link, flatten, rank, labels, sizes + info} ms; zeros otherwise. */
+int pf_components(pf_handle* h, int32_t allow_diag, int32_t restrict_corner, int32_t* d_labels, int64_t* d_info);
+int pf_component_sizes(pf_handle* h, const int32_t* d_labels, int32_t count, int64_t* d_sizes, int32_t* d_first);
+int pf_components_same(pf_handle* h, const int32_t* d_labels, int32_t n, const int32_t* d_a, const int32_t* d_b,
+                       int32_t* d_same);
+int pf_components_phase_ms(pf_handle* h, float* ms);
+
+/* Tuning knobs (results never change): "components_phases" 0/1 pf_components records a HIP event after each phase
+ * (pf_components_phase_ms; default 0); "maaco_pack8_min" ants per batch from which eight ants share a wavefront
  * (default 2048); "maaco_load_ahead" the packed walk kernel's load-ahead form (all of a step's loads issued together plus touches of the
  * records two steps ahead): -1 (default) for batches of at most one wavefront per SIMD, 0 never, 1 always;
  * "mpa_prune" 0/1 exact bound pruning of MPA rebuilds (default 1); "mpa_bounds_device" 0/1 the bound tables of pf_mpa_setup /

@@ -1829,8 +1829,11 @@ struct pf_handle {
   long long d2h_small = 0, d2h_bulk = 0, d2h_bulk_bytes = 0;   // device-to-host copies the library made (f1/f2 accounting): <= 128 B / larger
   struct MpaAhead* ahead = nullptr;   // pf_mpa_iter_ahead: level buffers and the levels still to be taken (end of this file)
   int* d_df_lists = nullptr; int df_slots = 0; int* d_df_ctl = nullptr; int df_ctl_cap = 0; int df_cus = 0;   // pf_dist_field_batch: [slots][3][RC] rolling lists; {error word, K sources}
+  int* d_cc = nullptr;                                                // pf_components: parent, rank and size words [3][RC], block counts, control block (first use)
+  hipEvent_t cc_ev[6] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr}; float cc_ms[5] = {0, 0, 0, 0, 0};   // ... its phase spans ("components_phases")
 };
 
+static bool g_cc_phases = false;   // pf_components records one HIP event per phase (pf_set_option "components_phases": the probe's spans)
 static long long g_step_cap = 0;   // > 0: lowers the connectors' step cap (pf_set_option "astar_step_cap": tests of the cap path)
 static std::string g_create_err;
 static int fail(pf_handle* h, const char* what, hipError_t e) {
@@ -1992,8 +1995,9 @@ void pf_destroy(pf_handle* h) {
   void* ptrs[] = {h->d_occ, h->d_mm_r1, h->d_mm_r0, h->d_mm_r1_nd, h->d_mm_r0_nd, h->d_d2near, h->d_rec, h->d_slot_state,
                   h->d_work, h->d_cnt, h->d_pen, h->d_tier2, h->d_tau, h->d_taua, h->d_eta, h->d_dep, h->d_tep, h->d_visit, h->d_visit_epoch,
                   h->d_bits, h->d_flag, h->d_mstate, h->d_mctl, h->d_best_row, h->d_d2wide, h->d_penw, h->d_tmp, h->d_elite_stats, h->d_init_cells, h->d_init_stats, h->d_est, h->d_queue, h->d_jobs, h->d_jres, h->d_prop, h->d_doubt, h->d_scan, h->d_scan3, h->d_okey, h->d_opay, h->d_orank, h->d_elite_cells, h->d_elite_len, h->d_ga_pool, h->d_seg_rows, h->d_st_lab, h->d_st_touched, h->d_st_par, h->d_st_epoch,
-                  h->d_comp[0], h->d_comp[1], h->d_comp[2], h->d_comp[3], h->d_ds, h->d_dt, h->d_df_lists, h->d_df_ctl};
+                  h->d_comp[0], h->d_comp[1], h->d_comp[2], h->d_comp[3], h->d_ds, h->d_dt, h->d_df_lists, h->d_df_ctl, h->d_cc};
   for (void* p : ptrs) if (p) (void)hipFree(p);
+  for (hipEvent_t e : h->cc_ev) if (e) (void)hipEventDestroy(e);
   for (hipEvent_t e : h->span_ev) (void)hipEventDestroy(e);
   if (h->ev0) (void)hipEventDestroy(h->ev0);
   if (h->ev1) (void)hipEventDestroy(h->ev1);
@@ -2528,6 +2532,7 @@ int pf_set_option(pf_handle* h, const char* name, int64_t value) {
   if (!strcmp(name, "astar_settle")) { g_settle = value < 0 ? -1 : (value != 0); return 0; }
   if (!strcmp(name, "astar_settle_tail")) { g_settle_tail = value < 0 ? 0 : (value > 1000 ? 1000 : (int)value); return 0; }
   if (!strcmp(name, "astar_settle_top")) { g_settle_top = value < 0 ? 0 : (value > 1000 ? 1000 : (int)value); return 0; }
+  if (!strcmp(name, "components_phases")) { g_cc_phases = value != 0; return 0; }
   if (!strcmp(name, "plateau_kernels")) { g_plateau_mode = (int)value; return 0; }
   if (!strcmp(name, "maaco_tabu_epoch")) { g_tabu_epoch = (int)value; return 0; }
   if (!strcmp(name, "astar_slot_tag")) {
@@ -4968,6 +4973,132 @@ int pf_smooth_batch(pf_handle* h, int32_t restrict_corner, int32_t n, int32_t pa
     CK(hipEventRecord(h->ev0, h->stream));
     hipLaunchKernelGGL(k_smooth_paths_one_wave_per_row<>, dim3((unsigned)n), dim3(64), 0, h->stream, (const uint8_t*)h->d_occ, h->RC, h->C, restrict_corner ? 1 : 0, n, path_cap,
                        d_cells, d_len, way_cap, d_way_cells, d_way_idx, d_way_len, d_stats, d_status);
+    CK(hipGetLastError());
+    CK(hipEventRecord(h->ev1, h->stream));
+    CK(hipStreamSynchronize(h->stream));
+    CK(hipEventElapsedTime(&h->last_ms, h->ev0, h->ev1));
+    return 0;
+  };
+  return run() ? -1 : 0;
+}
+
+}  // extern "C"
+
+// ---------------------------------------------------------------------------
+// Connected components: labels, sizes and reachability queries (pf_components.h).  The masks are read at call
+// time (pf_update_grid keeps working); the handle keeps only the scratch words, allocated on first use.  Nothing here touches the
+// searches' own labels (ensure_comp / d_comp).
+// ---------------------------------------------------------------------------
+#include "pf_components.h"
+
+extern "C" {
+
+int pf_components(pf_handle* h, int32_t allow_diag, int32_t restrict_corner, int32_t* d_labels, int64_t* d_info) {
+  if (!h) return -2;
+  if (!d_labels) { failmsg(h, "pf_components: bad arguments (the labels must not be null)"); return -1; }
+  auto run = [&]() -> int {
+    CK(hipSetDevice(h->device));
+    const int RC = h->RC, C = h->C;
+    const unsigned nb = (unsigned)((RC + PF_CC_THREADS - 1) / PF_CC_THREADS);
+    if (!h->d_cc) {
+      const size_t bytes = sizeof(unsigned long long) * PF_CC_CTL_WORDS + sizeof(int) * (3 * (size_t)RC + (size_t)nb);
+      if (hipMalloc(&h->d_cc, bytes) != hipSuccess) {
+        (void)hipGetLastError();
+        h->d_cc = nullptr;
+        return failmsg(h, "pf_components: no device memory for the scratch words (" + std::to_string(bytes >> 20) + " MiB)");
+      }
+    }
+    if (g_cc_phases) for (hipEvent_t& e : h->cc_ev) if (!e) CK(hipEventCreate(&e));
+    unsigned long long* const ctl = (unsigned long long*)h->d_cc;    // (in front: 8-byte aligned whatever RC is)
+    int* const parent = h->d_cc + 2 * PF_CC_CTL_WORDS;
+    int* const rank = parent + RC;
+    int* const size = rank + RC;
+    int* const blocks = size + RC;
+    const uint8_t* mm = allow_diag ? (restrict_corner ? h->d_mm_r1 : h->d_mm_r0) : (restrict_corner ? h->d_mm_r1_nd : h->d_mm_r0_nd);
+    const uint8_t* occ = h->d_occ;
+    const dim3 grid(nb), block(PF_CC_THREADS);
+    const unsigned hb = (unsigned)((RC + PF_CC_THREADS * PF_CC_HIST_PER - 1) / (PF_CC_THREADS * PF_CC_HIST_PER));
+    int phase = 0;
+    auto mark = [&]() -> hipError_t { return g_cc_phases ? hipEventRecord(h->cc_ev[phase++], h->stream) : hipSuccess; };
+    CK(hipEventRecord(h->ev0, h->stream));
+    CK(mark());
+    CK(hipMemsetAsync(ctl, 0, sizeof(unsigned long long) * PF_CC_CTL_WORDS, h->stream));
+#if PF_CC_TILED
+    hipLaunchKernelGGL(k_cc_label_tiles_in_lds<>, dim3((unsigned)((C + PF_CC_TW - 1) / PF_CC_TW), (unsigned)((h->R + PF_CC_TH - 1) / PF_CC_TH)), block, 0, h->stream, occ, mm,
+                       h->R, C, parent);
+    hipLaunchKernelGGL(k_cc_link_tile_borders<>, grid, block, 0, h->stream, occ, mm, RC, C, parent);
+#else
+    hipLaunchKernelGGL(k_cc_init_parent_lowest_back_neighbour<>, grid, block, 0, h->stream, occ, mm, RC, C, parent);
+    hipLaunchKernelGGL(k_cc_link_forward_edges<>, grid, block, 0, h->stream, occ, mm, RC, C, parent);
+#endif
+    CK(mark());                                                     // [0] link
+    hipLaunchKernelGGL(k_cc_flatten_and_count_roots<>, grid, block, 0, h->stream, RC, (const int*)parent, (int*)d_labels, blocks);
+    CK(mark());                                                     // [1] flatten
+    hipLaunchKernelGGL(k_cc_scan_block_counts<>, dim3(1), dim3(PF_CC_SCAN_THREADS), 0, h->stream, (int)nb, blocks, ctl);
+    hipLaunchKernelGGL(k_cc_rank_roots<>, grid, block, 0, h->stream, RC, (const int*)parent, (const int*)blocks, rank, size);
+    CK(mark());                                                     // [2] rank
+    hipLaunchKernelGGL(k_cc_write_labels<>, grid, block, 0, h->stream, RC, (const int*)rank, (int*)d_labels);
+    CK(mark());                                                     // [3] labels
+    if (d_info) {
+      hipLaunchKernelGGL((k_cc_histogram<int>), dim3(hb), block, 0, h->stream, RC, (const int*)d_labels, (const unsigned long long*)ctl, 0, size, (unsigned*)nullptr, ctl + 1);
+      hipLaunchKernelGGL(k_cc_largest<>, dim3(nb < 1024u ? nb : 1024u), block, 0, h->stream, (const int*)size, ctl);
+      hipLaunchKernelGGL(k_cc_write_info_block<>, dim3(1), dim3(64), 0, h->stream, (const unsigned long long*)ctl, (long long*)d_info);
+    }
+    CK(mark());                                                     // [4] sizes and info
+    CK(hipGetLastError());
+    CK(hipEventRecord(h->ev1, h->stream));
+    CK(hipStreamSynchronize(h->stream));
+    CK(hipEventElapsedTime(&h->last_ms, h->ev0, h->ev1));
+    for (int i = 0; i < 5; ++i) {
+      h->cc_ms[i] = 0.f;
+      if (g_cc_phases) CK(hipEventElapsedTime(&h->cc_ms[i], h->cc_ev[i], h->cc_ev[i + 1]));
+    }
+    return 0;
+  };
+  return run() ? -1 : 0;
+}
+
+int pf_components_phase_ms(pf_handle* h, float* ms) {
+  if (!h) return -2;
+  if (!ms) { failmsg(h, "pf_components_phase_ms: bad arguments"); return -1; }
+  for (int i = 0; i < 5; ++i) ms[i] = h->cc_ms[i];
+  return 0;
+}
+
+int pf_component_sizes(pf_handle* h, const int32_t* d_labels, int32_t count, int64_t* d_sizes, int32_t* d_first) {
+  if (!h) return -2;
+  if (!d_labels || count < 0) { failmsg(h, "pf_component_sizes: bad arguments (count >= 0; the labels must not be null)"); return -1; }
+  if (count == 0 || (!d_sizes && !d_first)) return 0;
+  auto run = [&]() -> int {
+    CK(hipSetDevice(h->device));
+    const int RC = h->RC;
+    const unsigned nb = (unsigned)((RC + PF_CC_THREADS - 1) / PF_CC_THREADS), cb = (unsigned)((count + PF_CC_THREADS - 1) / PF_CC_THREADS);
+    CK(hipEventRecord(h->ev0, h->stream));
+    if (d_sizes) CK(hipMemsetAsync(d_sizes, 0, sizeof(int64_t) * (size_t)count, h->stream));
+    if (d_first) hipLaunchKernelGGL((k_cc_fill_words_with_a_value<unsigned>), dim3(cb), dim3(PF_CC_THREADS), 0, h->stream, (unsigned*)d_first, (int)count, 0xFFFFFFFFu);
+    hipLaunchKernelGGL((k_cc_histogram<unsigned long long>), dim3((nb + PF_CC_HIST_PER - 1) / PF_CC_HIST_PER), dim3(PF_CC_THREADS), 0, h->stream, RC, (const int*)d_labels, (const unsigned long long*)nullptr,
+                       (int)count, (unsigned long long*)d_sizes, (unsigned*)d_first, (unsigned long long*)nullptr);
+    CK(hipGetLastError());
+    CK(hipEventRecord(h->ev1, h->stream));
+    CK(hipStreamSynchronize(h->stream));
+    CK(hipEventElapsedTime(&h->last_ms, h->ev0, h->ev1));
+    return 0;
+  };
+  return run() ? -1 : 0;
+}
+
+int pf_components_same(pf_handle* h, const int32_t* d_labels, int32_t n, const int32_t* d_a, const int32_t* d_b, int32_t* d_same) {
+  if (!h) return -2;
+  if (n < 0 || !d_labels || !d_a || !d_b || !d_same) {
+    failmsg(h, "pf_components_same: bad arguments (n >= 0; the labels, the two id rows and the answers must not be null)");
+    return -1;
+  }
+  if (n == 0) return 0;
+  auto run = [&]() -> int {
+    CK(hipSetDevice(h->device));
+    CK(hipEventRecord(h->ev0, h->stream));
+    hipLaunchKernelGGL(k_cc_same_pairs<>, dim3((unsigned)((n + PF_CC_THREADS - 1) / PF_CC_THREADS)), dim3(PF_CC_THREADS), 0, h->stream, h->RC, (const int*)d_labels, (int)n,
+                       (const int*)d_a, (const int*)d_b, (int*)d_same);
     CK(hipGetLastError());
     CK(hipEventRecord(h->ev1, h->stream));
     CK(hipStreamSynchronize(h->stream));

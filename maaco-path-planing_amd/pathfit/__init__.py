@@ -19,3 +19,4 @@ from .pso_batch import PSOBatch, PsoSwarm  # noqa: F401
 from .dist_field import DistanceField  # noqa: F401
 from .nearest_field import NearestSourceField  # noqa: F401
 from .smooth import PathSmoother  # noqa: F401
+from .components import Components  # noqa: F401

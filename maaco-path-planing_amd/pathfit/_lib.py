@@ -164,6 +164,10 @@ SYMBOLS = {
     "pf_dist_field_owners": (C.c_int, [_vp, _i32, _vp, _vp, _vp, _vp, _vp, _vp]),
     "pf_line_of_sight_batch": (C.c_int, [_vp, _i32, _i32, _vp, _vp, _vp, _vp]),
     "pf_smooth_batch": (C.c_int, [_vp, _i32, _i32, _i32, _vp, _vp, _i32, _vp, _vp, _vp, _vp, _vp]),
+    "pf_components": (C.c_int, [_vp, _i32, _i32, _vp, _vp]),
+    "pf_component_sizes": (C.c_int, [_vp, _vp, _i32, _vp, _vp]),
+    "pf_components_same": (C.c_int, [_vp, _vp, _i32, _vp, _vp, _vp]),
+    "pf_components_phase_ms": (C.c_int, [_vp, _vp]),
 }
 
 

@@ -292,6 +292,36 @@ class Engine:
                                         d_stats.ptr if d_stats else None, d_status.ptr if d_status else None))
         self._logk("smooth")
 
+    # ------------------------------------------------------------------ connected components
+    def components(self, d_labels, allow_diag=True, restrict_corner=True, d_info=None):
+        """The components of the free cells under the move policy, on the map the handle holds now -> d_labels int32 [R * C] in HBM
+        (-1 on an obstacle, else the rank of the cell's component by its smallest cell id); d_info int64 [4] = (count, free cells,
+        the largest component's size, its label) (pf_components)."""
+        self._ck(self.L.pf_components(self.h, int(bool(allow_diag)), int(bool(restrict_corner)), d_labels.ptr if d_labels else None,
+                                      d_info.ptr if d_info else None))
+        self._logk("components")
+
+    def component_sizes(self, d_labels, count, d_sizes=None, d_first=None):
+        """Labels in HBM -> d_sizes int64 [count] (the cells per label) and d_first int32 [count] (the smallest cell id per label);
+        labels outside [0, count) are ignored (pf_component_sizes)."""
+        self._ck(self.L.pf_component_sizes(self.h, d_labels.ptr if d_labels else None, int(count), d_sizes.ptr if d_sizes else None,
+                                           d_first.ptr if d_first else None))
+        self._logk("component_sizes")
+
+    def components_same(self, d_labels, d_a, d_b, n, d_same):
+        """n pairs of cell ids in HBM -> d_same int32 [n]: 1 where both ids lie inside the grid on free cells of one component, else 0
+        (pf_components_same)."""
+        self._ck(self.L.pf_components_same(self.h, d_labels.ptr if d_labels else None, int(n), d_a.ptr if d_a else None, d_b.ptr if d_b else None,
+                                           d_same.ptr if d_same else None))
+        self._logk("components_same")
+
+    def components_phase_ms(self):
+        """The spans of the last `components` call made under set_option("components_phases", 1): (init + link, flatten, rank,
+        labels, sizes + info) ms."""
+        out = (C.c_float * 5)()
+        self._ck(self.L.pf_components_phase_ms(self.h, out))
+        return tuple(float(v) for v in out)
+
     # ------------------------------------------------------------------ K1
     def score_batch(self, n, path_cap, d_cells, d_len, d_stats, sp):
         """Rows of astar_batch's layout in HBM -> d_stats [n, 5] doubles (pf_score_batch)."""
