@@ -490,6 +490,38 @@ int pf_components_same(pf_handle* h, const int32_t* d_labels, int32_t n, const i
                        int32_t* d_same);
 int pf_components_phase_ms(pf_handle* h, float* ms);
 
+/* ---- clearance fields: exact obstacle distances, the margins of path rows and segments (pathfit.Clearance) -----------------
+ * Cells are r C + c; an obstacle is a cell of grid value 1.  Everything is integer and exact.  The occupancy is
+ * read at call time: after pf_update_grid the next pf_clearance_field sees the new map.
+ * pf_clearance_field: d_d2[v] = the squared Euclidean distance between cell centres from v to the nearest obstacle cell, 0 on an
+ * obstacle.  border != 0: the cells just outside the grid count as obstacles too, so min(r + 1, R - r, c + 1, C - c)^2 takes part
+ * in the minimum; border == 0 (the reference's rule, helper.py:67-80) on a map without an obstacle: every word is PF_CLEAR_NONE.
+ * d_near (or NULL): the nearest obstacle cell INSIDE the grid, the smallest r C + c among the nearest ones, an obstacle's own id
+ * on an obstacle, -1 everywhere on a map without an obstacle.  d_near ignores `border`: the border changes d_d2 only.
+ * d_info (or NULL): {obstacle cells, free cells, the largest d2 over the free cells, the smallest cell id that attains it}, the
+ * last two -1 when no cell is free.  A separable transform: a row pass over wave-wide obstacle masks, then a column pass that
+ * scans outwards while the row distance can still win and hands the columns it could not close within about 2^18 / C rows to
+ * an exact integer lower-envelope pass, so the work does not grow with the clearance.  The handle keeps about three int32 words per cell
+ * of scratch from the first call on (freed by pf_destroy).  R^2 + C^2 >= 2^31 - 1 is an argument error.
+ * pf_clearance_paths: n path rows laid out as pf_astar_batch's against a field in HBM -> d_out[i * 4 ..] = {the smallest d2 over
+ * the row's cells, the position of the first cell that attains it, the number of cells with d2 < margin_d2, the position of the
+ * first such cell or -1}; d_profile (or NULL) [n * path_cap]: d2 per cell, words beyond d_len[i] untouched.  d_status: 0 ok;
+ * 1 = an empty row, a length beyond path_cap or a cell outside [0, R C): d_out = {PF_CLEAR_NONE, -1, 0, -1}, the profile row
+ * untouched, nothing read out of range.  One wavefront per row.
+ * pf_clearance_segments: n pairs of cell ids -> d_min[i] = the smallest d2 over the cells the straight segment between the two
+ * centres crosses (the rule of the smoothing section: |2k| < s), with touched != 0 also over the cells it only touches in a
+ * corner (|2k| == s); d_at (or NULL): the cell of smallest id that attains it.  An endpoint outside the grid gives
+ * PF_CLEAR_NONE and -1; a == b gives that cell's own d2.  One wavefront per pair.
+ * A null handle (-2); a missing required pointer, n < 0, path_cap < 1 or margin_d2 < 0 (-1, with a message) is an argument error
+ * found before any launch; n == 0 returns 0 and launches nothing.  All three are synchronous and ordered on the handle's stream;
+ * pf_last_kernel_ms reports the kernels. */
+#define PF_CLEAR_NONE 0x7FFFFFFF
+int pf_clearance_field(pf_handle* h, int32_t border, int32_t* d_d2, int32_t* d_near, int64_t* d_info);
+int pf_clearance_paths(pf_handle* h, const int32_t* d_d2, int32_t n, int32_t path_cap, const int32_t* d_cells,
+                       const int32_t* d_len, int32_t margin_d2, int32_t* d_out, int32_t* d_profile, int32_t* d_status);
+int pf_clearance_segments(pf_handle* h, const int32_t* d_d2, int32_t touched, int32_t n, const int32_t* d_from,
+                          const int32_t* d_to, int32_t* d_min, int32_t* d_at);
+
 /* Tuning knobs (results never change): "components_phases" 0/1 pf_components records a HIP event after each phase
  * (pf_components_phase_ms; default 0); "maaco_pack8_min" ants per batch from which eight ants share a wavefront
  * (default 2048); "maaco_load_ahead" the packed walk kernel's load-ahead form (all of a step's loads issued together plus touches of the

@@ -1831,6 +1831,7 @@ struct pf_handle {
   int* d_df_lists = nullptr; int df_slots = 0; int* d_df_ctl = nullptr; int df_ctl_cap = 0; int df_cus = 0;   // pf_dist_field_batch: [slots][3][RC] rolling lists; {error word, K sources}
   int* d_cc = nullptr;                                                // pf_components: parent, rank and size words [3][RC], block counts, control block (first use)
   hipEvent_t cc_ev[6] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr}; float cc_ms[5] = {0, 0, 0, 0, 0};   // ... its phase spans ("components_phases")
+  int* d_clear = nullptr;                                             // pf_clearance_field: control block, envelope stacks [RC] int2, row offsets [RC], column flags [C] (first use)
 };
 
 static bool g_cc_phases = false;   // pf_components records one HIP event per phase (pf_set_option "components_phases": the probe's spans)
@@ -1995,7 +1996,7 @@ void pf_destroy(pf_handle* h) {
   void* ptrs[] = {h->d_occ, h->d_mm_r1, h->d_mm_r0, h->d_mm_r1_nd, h->d_mm_r0_nd, h->d_d2near, h->d_rec, h->d_slot_state,
                   h->d_work, h->d_cnt, h->d_pen, h->d_tier2, h->d_tau, h->d_taua, h->d_eta, h->d_dep, h->d_tep, h->d_visit, h->d_visit_epoch,
                   h->d_bits, h->d_flag, h->d_mstate, h->d_mctl, h->d_best_row, h->d_d2wide, h->d_penw, h->d_tmp, h->d_elite_stats, h->d_init_cells, h->d_init_stats, h->d_est, h->d_queue, h->d_jobs, h->d_jres, h->d_prop, h->d_doubt, h->d_scan, h->d_scan3, h->d_okey, h->d_opay, h->d_orank, h->d_elite_cells, h->d_elite_len, h->d_ga_pool, h->d_seg_rows, h->d_st_lab, h->d_st_touched, h->d_st_par, h->d_st_epoch,
-                  h->d_comp[0], h->d_comp[1], h->d_comp[2], h->d_comp[3], h->d_ds, h->d_dt, h->d_df_lists, h->d_df_ctl, h->d_cc};
+                  h->d_comp[0], h->d_comp[1], h->d_comp[2], h->d_comp[3], h->d_ds, h->d_dt, h->d_df_lists, h->d_df_ctl, h->d_cc, h->d_clear};
   for (void* p : ptrs) if (p) (void)hipFree(p);
   for (hipEvent_t e : h->cc_ev) if (e) (void)hipEventDestroy(e);
   for (hipEvent_t e : h->span_ev) (void)hipEventDestroy(e);
@@ -5099,6 +5100,108 @@ int pf_components_same(pf_handle* h, const int32_t* d_labels, int32_t n, const i
     CK(hipEventRecord(h->ev0, h->stream));
     hipLaunchKernelGGL(k_cc_same_pairs<>, dim3((unsigned)((n + PF_CC_THREADS - 1) / PF_CC_THREADS)), dim3(PF_CC_THREADS), 0, h->stream, h->RC, (const int*)d_labels, (int)n,
                        (const int*)d_a, (const int*)d_b, (int*)d_same);
+    CK(hipGetLastError());
+    CK(hipEventRecord(h->ev1, h->stream));
+    CK(hipStreamSynchronize(h->stream));
+    CK(hipEventElapsedTime(&h->last_ms, h->ev0, h->ev1));
+    return 0;
+  };
+  return run() ? -1 : 0;
+}
+
+}  // extern "C"
+
+// ---------------------------------------------------------------------------
+// Clearance fields: exact squared distances to the nearest obstacle, the margins of path rows and segments (pf_clearance.h,
+// DESIGN.md 4.16).  The occupancy is read at call time (pf_update_grid keeps working); the handle keeps only the scratch words,
+// allocated on first use.  Nothing here touches the scorer's own tables (ensure_pen / d_d2near / d_d2wide).
+// ---------------------------------------------------------------------------
+#include "pf_clearance.h"
+
+extern "C" {
+
+int pf_clearance_field(pf_handle* h, int32_t border, int32_t* d_d2, int32_t* d_near, int64_t* d_info) {
+  if (!h) return -2;
+  if (!d_d2) { failmsg(h, "pf_clearance_field: bad arguments (the squared distances must not be null)"); return -1; }
+  if ((long long)h->R * h->R + (long long)h->C * h->C >= 0x7FFFFFFFll) {
+    failmsg(h, "pf_clearance_field: bad arguments (R^2 + C^2 must stay below 2^31 - 1)");
+    return -1;
+  }
+  auto run = [&]() -> int {
+    CK(hipSetDevice(h->device));
+    const int R = h->R, C = h->C, RC = h->RC;
+    if (!h->d_clear) {
+      const size_t bytes = sizeof(unsigned long long) * PF_CL_CTL_WORDS + sizeof(int2) * (size_t)RC + sizeof(int) * ((size_t)RC + (size_t)C);
+      if (hipMalloc(&h->d_clear, bytes) != hipSuccess) {
+        (void)hipGetLastError();
+        h->d_clear = nullptr;
+        return failmsg(h, "pf_clearance_field: no device memory for the scratch words (" + std::to_string(bytes >> 20) + " MiB)");
+      }
+    }
+    unsigned long long* const ctl = (unsigned long long*)h->d_clear;  // (in front: 8-byte aligned whatever RC is)
+    int2* const stack = (int2*)(ctl + PF_CL_CTL_WORDS);
+    int* const dcol = (int*)(stack + RC);
+    int* const colflag = dcol + RC;
+    const uint8_t* occ = h->d_occ;
+    const unsigned rows_per = PF_CL_THREADS / 64;
+    CK(hipEventRecord(h->ev0, h->stream));
+    CK(hipMemsetAsync(ctl, 0, sizeof(unsigned long long) * PF_CL_CTL_WORDS, h->stream));
+    CK(hipMemsetAsync(colflag, 0, sizeof(int) * (size_t)C, h->stream));
+    hipLaunchKernelGGL(k_clear_rows_nearest_in_row<>, dim3(((unsigned)R + rows_per - 1) / rows_per), dim3(PF_CL_THREADS), 0, h->stream, occ, R, C, dcol);
+    hipLaunchKernelGGL(k_clear_cols_outward_scan<>, dim3(((unsigned)C + 63u) / 64u, ((unsigned)R + rows_per - 1) / rows_per), dim3(PF_CL_THREADS), 0, h->stream,
+                       (const int*)dcol, R, C, border ? 1 : 0, clear_scan_rows(C), (int*)d_d2, (int*)d_near, colflag);
+    hipLaunchKernelGGL(k_clear_cols_lower_envelope<>, dim3(((unsigned)C + 63u) / 64u), dim3(64), 0, h->stream, (const int*)dcol, R, C, border ? 1 : 0,
+                       (const int*)colflag, stack, (int*)d_d2, (int*)d_near);
+    if (d_info) {
+      const unsigned nb = (unsigned)((RC + PF_CL_THREADS - 1) / PF_CL_THREADS);
+      hipLaunchKernelGGL(k_clear_info_reduce<>, dim3(nb < 2048u ? nb : 2048u), dim3(PF_CL_THREADS), 0, h->stream, occ, (const int*)d_d2, RC, ctl);
+      hipLaunchKernelGGL(k_clear_write_info_block<>, dim3(1), dim3(64), 0, h->stream, (const unsigned long long*)ctl, RC, (long long*)d_info);
+    }
+    CK(hipGetLastError());
+    CK(hipEventRecord(h->ev1, h->stream));
+    CK(hipStreamSynchronize(h->stream));
+    CK(hipEventElapsedTime(&h->last_ms, h->ev0, h->ev1));
+    return 0;
+  };
+  return run() ? -1 : 0;
+}
+
+int pf_clearance_paths(pf_handle* h, const int32_t* d_d2, int32_t n, int32_t path_cap, const int32_t* d_cells, const int32_t* d_len, int32_t margin_d2,
+                       int32_t* d_out, int32_t* d_profile, int32_t* d_status) {
+  if (!h) return -2;
+  if (n < 0 || path_cap < 1 || margin_d2 < 0 || !d_d2 || !d_cells || !d_len || !d_out || !d_status) {
+    failmsg(h, "pf_clearance_paths: bad arguments (n >= 0, path_cap >= 1, margin_d2 >= 0; the field, the rows, the lengths, the results and the "
+               "statuses must not be null)");
+    return -1;
+  }
+  if (n == 0) return 0;
+  auto run = [&]() -> int {
+    CK(hipSetDevice(h->device));
+    CK(hipEventRecord(h->ev0, h->stream));
+    hipLaunchKernelGGL(k_clear_paths_one_wave_per_row<>, dim3((unsigned)n), dim3(64), 0, h->stream, (const int*)d_d2, h->RC, (int)n, (int)path_cap, (const int*)d_cells,
+                       (const int*)d_len, (int)margin_d2, (int*)d_out, (int*)d_profile, (int*)d_status);
+    CK(hipGetLastError());
+    CK(hipEventRecord(h->ev1, h->stream));
+    CK(hipStreamSynchronize(h->stream));
+    CK(hipEventElapsedTime(&h->last_ms, h->ev0, h->ev1));
+    return 0;
+  };
+  return run() ? -1 : 0;
+}
+
+int pf_clearance_segments(pf_handle* h, const int32_t* d_d2, int32_t touched, int32_t n, const int32_t* d_from, const int32_t* d_to, int32_t* d_min,
+                          int32_t* d_at) {
+  if (!h) return -2;
+  if (n < 0 || !d_d2 || !d_from || !d_to || !d_min) {
+    failmsg(h, "pf_clearance_segments: bad arguments (n >= 0; the field, the endpoints and the minima must not be null)");
+    return -1;
+  }
+  if (n == 0) return 0;
+  auto run = [&]() -> int {
+    CK(hipSetDevice(h->device));
+    CK(hipEventRecord(h->ev0, h->stream));
+    hipLaunchKernelGGL(k_clear_segments_lanes_on_major<>, dim3((unsigned)n), dim3(64), 0, h->stream, (const int*)d_d2, h->RC, h->C, touched ? 1 : 0, (int)n,
+                       (const int*)d_from, (const int*)d_to, (int*)d_min, (int*)d_at);
     CK(hipGetLastError());
     CK(hipEventRecord(h->ev1, h->stream));
     CK(hipStreamSynchronize(h->stream));

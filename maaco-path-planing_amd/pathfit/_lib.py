@@ -168,6 +168,9 @@ SYMBOLS = {
     "pf_component_sizes": (C.c_int, [_vp, _vp, _i32, _vp, _vp]),
     "pf_components_same": (C.c_int, [_vp, _vp, _i32, _vp, _vp, _vp]),
     "pf_components_phase_ms": (C.c_int, [_vp, _vp]),
+    "pf_clearance_field": (C.c_int, [_vp, _i32, _vp, _vp, _vp]),
+    "pf_clearance_paths": (C.c_int, [_vp, _vp, _i32, _i32, _vp, _vp, _i32, _vp, _vp, _vp]),
+    "pf_clearance_segments": (C.c_int, [_vp, _vp, _i32, _i32, _vp, _vp, _vp, _vp]),
 }
 
 

@@ -1,0 +1,253 @@
+"""Clearance: the exact distance from every cell of a grid to the nearest obstacle (pf_clearance_field), obstacles inflated by a
+robot's radius, and how close path rows (pf_clearance_paths) and straight segments (pf_clearance_segments) pass.  The field stays
+in HBM (`d2_device`); `d2` downloads it once.  `refresh` computes it again after `engine.update_grid`.  Everything is integer:
+squared distances between cell centres, no tolerance anywhere."""
+import math
+
+import numpy as np
+
+from ._lib import PathfitError
+from .engine import Engine
+from .paths import CellPath
+
+PF_CLEAR_NONE = 2 ** 31 - 1                                           # d2 on a map without an obstacle (include/pathfit.h)
+
+
+def margin_to_sq(margin):
+    """The smallest integer n with math.sqrt(n) >= margin: d2 < n exactly where sqrt(d2) < margin, which is helper.py:76-78's test
+    for a safety penalty at min_safe_distance = margin."""
+    try:
+        m = float(margin)
+    except (TypeError, ValueError):
+        m = math.nan
+    if isinstance(margin, bool) or not (0.0 < m < 46340.0):
+        raise ValueError(f"Clearance: margin must be a number in (0, 46340), got {margin!r}")
+    n = int(math.ceil(m * m))
+    while n > 0 and math.sqrt(n - 1) >= m:
+        n -= 1
+    while math.sqrt(n) < m:
+        n += 1
+    return n
+
+
+class Clearance:
+    """d2[r, c] = the squared Euclidean distance between cell centres to the nearest obstacle cell (grid value 1), 0 on an obstacle,
+    PF_CLEAR_NONE on a map without one.  border=True: the cells just outside the grid count as obstacles too (the reference's
+    safety term does not: helper.py:67-80).  nearest=True also keeps the nearest obstacle cell per cell (the smallest id on a tie);
+    it never names the border."""
+
+    def __init__(self, grid, border=False, nearest=False, engine=None):
+        who = type(self).__name__
+        self.grid = np.array(grid, dtype=int)
+        if self.grid.ndim != 2:
+            raise ValueError(f"{who}: grid must be 2-D")
+        self.rows, self.cols = self.grid.shape
+        self.border, self.want_nearest = bool(border), bool(nearest)
+        if engine is not None and (engine.R, engine.C) != self.grid.shape:
+            raise ValueError(f"{who}: the engine's grid has another shape")
+        # every argument is checked: the device
+        self._own_engine = engine is None
+        self.engine = engine if engine is not None else Engine(self.grid)
+        self.d2_device = self.near_device = self.ibuf = None
+        self.d2_device = self.engine.buf(self.rows * self.cols, np.int32)
+        if self.want_nearest:
+            self.near_device = self.engine.buf(self.rows * self.cols, np.int32)
+        self.ibuf = self.engine.buf(4, np.int64)
+        self.refresh()
+
+    def refresh(self):
+        """Compute the field of the map the engine holds now (after engine.update_grid); everything downloaded before is dropped."""
+        self._check_open()
+        self._d2 = self._near = None
+        held = getattr(self.engine, "grid_u8", None)
+        if held is not None:
+            self.grid = np.array(held, dtype=int)
+        self.engine.clearance_field(self.d2_device, self.border, self.near_device, self.ibuf)
+        self.kernel_ms = self.engine.last_kernel_ms()
+        self.info = self.ibuf.download()
+        self.obstacle_cells, self.free_cells = int(self.info[0]), int(self.info[1])
+        v = int(self.info[3])
+        self.most_open = ((v // self.cols, v % self.cols), int(self.info[2])) if v >= 0 else (None, -1)   # ((r, c), d2) of the free cell furthest from any obstacle
+        return self
+
+    def _check_open(self):
+        if self.d2_device is None or not getattr(self.engine, "h", None):
+            raise PathfitError(f"{type(self).__name__}: the field is closed")
+
+    @property
+    def d2(self):
+        """int32 [R, C], downloaded on first use."""
+        if self._d2 is None:
+            self._check_open()
+            self._d2 = self.d2_device.download().reshape(self.rows, self.cols)
+        return self._d2
+
+    @property
+    def distance(self):
+        """float64 [R, C]: the square root of d2, inf where d2 is PF_CLEAR_NONE."""
+        d2 = self.d2
+        out = np.sqrt(d2.astype(np.float64))
+        out[d2 == PF_CLEAR_NONE] = np.inf
+        return out
+
+    @property
+    def nearest(self):
+        """int32 [R, C]: the id of the nearest obstacle cell inside the grid (-1 without any); needs nearest=True."""
+        if not self.want_nearest:
+            raise PathfitError(f"{type(self).__name__}: the nearest obstacles were not asked for (construct with nearest=True)")
+        if self._near is None:
+            self._check_open()
+            self._near = self.near_device.download().reshape(self.rows, self.cols)
+        return self._near
+
+    # ------------------------------------------------------------------ margins
+    @staticmethod
+    def _margin_sq(margin, margin_sq, least):
+        if (margin is None) == (margin_sq is None):
+            raise ValueError("Clearance: give exactly one of margin and margin_sq")
+        if margin is not None:
+            return max(margin_to_sq(margin), least)
+        try:
+            ok = not isinstance(margin_sq, bool) and int(margin_sq) == margin_sq and least <= int(margin_sq) <= PF_CLEAR_NONE
+        except (TypeError, ValueError, OverflowError):
+            ok = False
+        if not ok:
+            raise ValueError(f"Clearance: margin_sq must be an integer in [{least}, 2^31 - 1], got {margin_sq!r}")
+        return int(margin_sq)
+
+    def inflated(self, margin=None, margin_sq=None):
+        """The grid with 1 wherever d2 < margin_sq (a marker 2 / 3 on such a cell becomes 1) and the original value elsewhere: the
+        map a robot of that radius plans on, for Engine(...) or update_grid.  margin (a distance) means margin_sq = the smallest n
+        with sqrt(n) >= margin; margin_sq = 1 returns the original obstacle set.  Runs in numpy on the downloaded field."""
+        msq = self._margin_sq(margin, margin_sq, 1)
+        out = self.grid.copy()
+        out[self.d2 < msq] = 1
+        return out
+
+    # ------------------------------------------------------------------ path rows
+    def _rows(self, paths):
+        try:
+            paths = list(paths)
+        except TypeError:
+            raise ValueError(f"Clearance: paths must be a sequence of paths, got {paths!r}") from None
+        RC, out = self.rows * self.cols, []
+        for i, p in enumerate(paths):
+            if isinstance(p, CellPath):
+                if p.C != self.cols:
+                    raise ValueError(f"Clearance: paths[{i}] belongs to a grid of {p.C} columns, not {self.cols}")
+                a = np.asarray(p.cells, np.int64)
+            elif isinstance(p, np.ndarray) and p.ndim == 1 and p.dtype.kind in "iu":
+                a = p.astype(np.int64)
+            else:
+                try:
+                    a = np.array([self._cell(f"paths[{i}][{j}]", q, True) for j, q in enumerate(p)], np.int64)
+                except TypeError:
+                    raise ValueError(f"Clearance: paths[{i}] must be a CellPath, a list of (r, c) pairs or an int32 cell array, got {p!r}") from None
+            bad = np.flatnonzero((a < 0) | (a >= RC))
+            if len(bad):
+                raise ValueError(f"Clearance: paths[{i}][{int(bad[0])}] = cell {int(a[bad[0]])} is outside the {self.rows}x{self.cols} grid")
+            out.append(a.astype(np.int32))
+        return out
+
+    def _cell(self, what, p, inside):
+        try:
+            r, c = (int(v) for v in p)
+        except (TypeError, ValueError):
+            raise ValueError(f"Clearance: {what} must be an (r, c) pair, got {p!r}") from None
+        if not (0 <= r < self.rows and 0 <= c < self.cols):
+            if not inside:
+                return -1
+            raise ValueError(f"Clearance: {what} = {(r, c)} is outside the {self.rows}x{self.cols} grid")
+        return r * self.cols + c
+
+    def path_clearance(self, paths, margin=None, margin_sq=None):
+        """paths: a sequence of CellPath, lists of (r, c) or int32 cell arrays -> (int32 [n, 4], status int32 [n]).  Per path: the
+        smallest d2 over its cells, the position of the first cell that attains it, the number of cells with d2 < margin_sq and the
+        position of the first such cell (-1: none).  An empty path gives (PF_CLEAR_NONE, -1, 0, -1) and status 1."""
+        msq = self._margin_sq(margin, margin_sq, 0)
+        rows = self._rows(paths)
+        n = len(rows)
+        if n == 0:
+            return np.zeros((0, 4), np.int32), np.zeros(0, np.int32)
+        cap = max(max(len(r) for r in rows), 1)
+        cells, lens = np.zeros((n, cap), np.int32), np.zeros(n, np.int32)
+        for i, r in enumerate(rows):
+            cells[i, :len(r)] = r
+            lens[i] = len(r)
+        self._check_open()
+        e = self.engine
+        dc, dl = e.put(cells), e.put(lens)
+        try:
+            return self._paths(dc, dl, n, cap, msq)
+        finally:
+            dc.free()
+            dl.free()
+
+    def path_clearance_device(self, d_cells, d_len, n, path_cap, margin=None, margin_sq=None):
+        """path_clearance on rows already in HBM (d_cells int32 [n, path_cap], d_len int32 [n]: a solver's population rows, a trace's
+        output); the rows are not downloaded.  A row with a length outside [1, path_cap] or a cell outside the grid has status 1."""
+        msq = self._margin_sq(margin, margin_sq, 0)
+        n, path_cap = int(n), int(path_cap)
+        if n < 1 or path_cap < 1:
+            raise ValueError(f"Clearance: path_clearance_device needs n >= 1 and path_cap >= 1 (got {n}, {path_cap})")
+        self._check_open()
+        return self._paths(d_cells, d_len, n, path_cap, msq)
+
+    def _paths(self, d_cells, d_len, n, path_cap, msq):
+        e = self.engine
+        do, ds = e.buf((n, 4), np.int32), e.buf(n, np.int32)
+        try:
+            e.clearance_paths(self.d2_device, n, path_cap, d_cells, d_len, msq, do, ds)
+            self.paths_kernel_ms = e.last_kernel_ms()
+            return do.download(), ds.download()
+        finally:
+            do.free()
+            ds.free()
+
+    # ------------------------------------------------------------------ segments
+    def segment_clearance(self, pairs, touched=False):
+        """pairs ((r, c), (r, c)) -> (int32 [n], list): the smallest d2 over the cells the straight segment between the two centres
+        crosses (touched=True: and the cells it only touches in a corner), and the cell of smallest id that attains it as (r, c).
+        An endpoint outside the grid gives PF_CLEAR_NONE and None."""
+        try:
+            pairs = list(pairs)
+        except TypeError:
+            raise ValueError(f"Clearance: pairs must be a list of ((r, c), (r, c)), got {pairs!r}") from None
+        n = len(pairs)
+        ids = np.empty((2, max(n, 1)), np.int32)
+        for i, pr in enumerate(pairs):
+            try:
+                ok = not isinstance(pr, (str, bytes)) and len(pr) == 2
+            except TypeError:
+                ok = False
+            if not ok:
+                raise ValueError(f"Clearance: pairs[{i}] must be two (r, c) pairs, got {pr!r}")
+            ids[0, i], ids[1, i] = self._cell(f"pairs[{i}][0]", pr[0], False), self._cell(f"pairs[{i}][1]", pr[1], False)
+        if n == 0:
+            return np.zeros(0, np.int32), []
+        self._check_open()
+        e = self.engine
+        bufs = [e.put(ids[0, :n]), e.put(ids[1, :n]), e.buf(n, np.int32), e.buf(n, np.int32)]
+        try:
+            e.clearance_segments(self.d2_device, bufs[0], bufs[1], n, bufs[2], bufs[3], touched)
+            self.segments_kernel_ms = e.last_kernel_ms()
+            dmin, at = bufs[2].download(), bufs[3].download()
+        finally:
+            for b in bufs:
+                b.free()
+        return dmin, [None if x < 0 else (int(x) // self.cols, int(x) % self.cols) for x in at]
+
+    def close(self):
+        for name in ("d2_device", "near_device", "ibuf"):
+            buf = getattr(self, name, None)
+            setattr(self, name, None)
+            if buf is not None:
+                buf.free()
+        if getattr(self, "_own_engine", False) and getattr(self, "engine", None) is not None:
+            self.engine.close()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass

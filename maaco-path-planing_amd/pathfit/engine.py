@@ -322,6 +322,34 @@ class Engine:
         self._ck(self.L.pf_components_phase_ms(self.h, out))
         return tuple(float(v) for v in out)
 
+    # ------------------------------------------------------------------ clearance fields
+    def clearance_field(self, d_d2, border=False, d_near=None, d_info=None):
+        """The exact squared distance from every cell to the nearest obstacle, on the map the handle holds now -> d_d2 int32 [R * C]
+        in HBM (0 on an obstacle, PF_CLEAR_NONE without any; border: the cells just outside the grid count too); d_near int32
+        [R * C] the nearest obstacle cell inside the grid (the smallest id on a tie, -1 without any; never the border); d_info int64
+        [4] = (obstacle cells, free cells, the largest d2 over the free cells, the smallest cell that attains it)
+        (pf_clearance_field)."""
+        self._ck(self.L.pf_clearance_field(self.h, int(bool(border)), d_d2.ptr if d_d2 else None, d_near.ptr if d_near else None,
+                                           d_info.ptr if d_info else None))
+        self._logk("clearance_field")
+
+    def clearance_paths(self, d_d2, n, path_cap, d_cells, d_len, margin_d2, d_out, d_status, d_profile=None):
+        """Rows of astar_batch's layout in HBM against a field in HBM -> d_out int32 [n, 4] = (the smallest d2, the first position
+        that attains it, the cells with d2 < margin_d2, the first such position or -1), d_profile int32 [n, path_cap] d2 per cell,
+        d_status (0 ok, 1 bad row) (pf_clearance_paths)."""
+        self._ck(self.L.pf_clearance_paths(self.h, d_d2.ptr if d_d2 else None, int(n), int(path_cap), d_cells.ptr if d_cells else None,
+                                           d_len.ptr if d_len else None, int(margin_d2), d_out.ptr if d_out else None,
+                                           d_profile.ptr if d_profile else None, d_status.ptr if d_status else None))
+        self._logk("clearance_paths")
+
+    def clearance_segments(self, d_d2, d_from, d_to, n, d_min, d_at=None, touched=False):
+        """n pairs of cell ids in HBM -> d_min int32 [n], the smallest d2 over the cells the segment between the centres crosses
+        (touched: and those it only touches in a corner), and d_at int32 [n], the smallest cell id that attains it; PF_CLEAR_NONE
+        and -1 for an endpoint outside the grid (pf_clearance_segments)."""
+        self._ck(self.L.pf_clearance_segments(self.h, d_d2.ptr if d_d2 else None, int(bool(touched)), int(n), d_from.ptr if d_from else None,
+                                              d_to.ptr if d_to else None, d_min.ptr if d_min else None, d_at.ptr if d_at else None))
+        self._logk("clearance_segments")
+
     # ------------------------------------------------------------------ K1
     def score_batch(self, n, path_cap, d_cells, d_len, d_stats, sp):
         """Rows of astar_batch's layout in HBM -> d_stats [n, 5] doubles (pf_score_batch)."""
