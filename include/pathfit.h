@@ -522,6 +522,31 @@ int pf_clearance_paths(pf_handle* h, const int32_t* d_d2, int32_t n, int32_t pat
 int pf_clearance_segments(pf_handle* h, const int32_t* d_d2, int32_t touched, int32_t n, const int32_t* d_from,
                           const int32_t* d_to, int32_t* d_min, int32_t* d_at);
 
+/* ---- widest-path fields over a clearance field: the largest robot that fits, and where (pathfit.Clearance.widest) ------------
+ * d_d2: an int32 [R C] field in HBM, what pf_clearance_field left there (either `border`); any non-negative array is defined,
+ * the caller vouches that it belongs to the map.  The call reads d_d2 only, never the handle's occupancy.  The B source sets
+ * are pf_dist_field_merged's host CSR arrays: set b = src[set_off[b] .. set_off[b + 1]).
+ * The capacity of a move u -> v is min(d2[u], d2[v]); a diagonal under restrict_corner != 0 also takes the two side cells' d2
+ * into the minimum, and does not exist with allow_diag == 0.  d_out[b * R C + v] = w[b][v] = the largest, over all walks from
+ * a source of set b to v, of the smallest capacity on the walk; d2[s] on a source s with d2[s] >= 1; 0 where no source reaches
+ * with capacity >= 1 (every cell with d2 == 0).  Equivalently, for every t >= 1: w[b][v] >= t iff v and a source of set b lie
+ * in one component, under the same policy, of the map whose obstacles are the cells with d2 < t.  A source with d2 == 0 is
+ * skipped, one listed twice counts once, a set without a usable source gives an all-zero row.
+ * d_info (or NULL) int64 [B][4]: {the sources that counted, the cells with w >= 1, the smallest w >= 1, the smallest cell id
+ * that attains it}, the last two -1 when nothing is reached.
+ * Tiles of 64 x 16 cells are relaxed to their own fixed point in LDS, one launch per round over the queued tiles of all B sets;
+ * the rounds grow with the tiles a widest route crosses (at most 1 + its tile-border crossings), not with its cells, and the
+ * host reads one 4-byte queue length per round.  The result is the least fixed point, identical run to run.
+ * The handle keeps four int32 words per (set, tile) plus the sets as scratch from the first call on (grown on demand, freed by
+ * pf_destroy).  A null handle (-2); B < 1, offsets that do not start at 0 or fall, an empty set, an id outside the grid or a
+ * null pointer (-1, with a message that names the set and the index) is an argument error found before any launch.
+ * Synchronous and ordered on the handle's stream; pf_last_kernel_ms reports the span of the kernels.
+ * pf_clearance_widest_work (host side): out4 = {launches of the tile kernel, tile visits, words raised, 0} of the last call.
+ * These depend on the schedule (which halo words a tile happened to see): figures for a probe, never part of the result. */
+int pf_clearance_widest(pf_handle* h, int32_t allow_diag, int32_t restrict_corner, const int32_t* d_d2, int32_t B,
+                        const int32_t* set_off, const int32_t* src, int32_t* d_out, int64_t* d_info);
+int pf_clearance_widest_work(pf_handle* h, int64_t* out4);
+
 /* Tuning knobs (results never change): "components_phases" 0/1 pf_components records a HIP event after each phase
  * (pf_components_phase_ms; default 0); "maaco_pack8_min" ants per batch from which eight ants share a wavefront
  * (default 2048); "maaco_load_ahead" the packed walk kernel's load-ahead form (all of a step's loads issued together plus touches of the

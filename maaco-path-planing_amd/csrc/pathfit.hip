@@ -1832,6 +1832,7 @@ struct pf_handle {
   int* d_cc = nullptr;                                                // pf_components: parent, rank and size words [3][RC], block counts, control block (first use)
   hipEvent_t cc_ev[6] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr}; float cc_ms[5] = {0, 0, 0, 0, 0};   // ... its phase spans ("components_phases")
   int* d_clear = nullptr;                                             // pf_clearance_field: control block, envelope stacks [RC] int2, row offsets [RC], column flags [C] (first use)
+  char* d_widest = nullptr; size_t widest_bytes = 0; long long widest_work[4] = {0, 0, 0, 0};   // pf_clearance_widest: counters, info words, the sets, tile queues and flags (first use, grown on demand); the last call's work
 };
 
 static bool g_cc_phases = false;   // pf_components records one HIP event per phase (pf_set_option "components_phases": the probe's spans)
@@ -1996,7 +1997,7 @@ void pf_destroy(pf_handle* h) {
   void* ptrs[] = {h->d_occ, h->d_mm_r1, h->d_mm_r0, h->d_mm_r1_nd, h->d_mm_r0_nd, h->d_d2near, h->d_rec, h->d_slot_state,
                   h->d_work, h->d_cnt, h->d_pen, h->d_tier2, h->d_tau, h->d_taua, h->d_eta, h->d_dep, h->d_tep, h->d_visit, h->d_visit_epoch,
                   h->d_bits, h->d_flag, h->d_mstate, h->d_mctl, h->d_best_row, h->d_d2wide, h->d_penw, h->d_tmp, h->d_elite_stats, h->d_init_cells, h->d_init_stats, h->d_est, h->d_queue, h->d_jobs, h->d_jres, h->d_prop, h->d_doubt, h->d_scan, h->d_scan3, h->d_okey, h->d_opay, h->d_orank, h->d_elite_cells, h->d_elite_len, h->d_ga_pool, h->d_seg_rows, h->d_st_lab, h->d_st_touched, h->d_st_par, h->d_st_epoch,
-                  h->d_comp[0], h->d_comp[1], h->d_comp[2], h->d_comp[3], h->d_ds, h->d_dt, h->d_df_lists, h->d_df_ctl, h->d_cc, h->d_clear};
+                  h->d_comp[0], h->d_comp[1], h->d_comp[2], h->d_comp[3], h->d_ds, h->d_dt, h->d_df_lists, h->d_df_ctl, h->d_cc, h->d_clear, h->d_widest};
   for (void* p : ptrs) if (p) (void)hipFree(p);
   for (hipEvent_t e : h->cc_ev) if (e) (void)hipEventDestroy(e);
   for (hipEvent_t e : h->span_ev) (void)hipEventDestroy(e);
@@ -5209,6 +5210,108 @@ int pf_clearance_segments(pf_handle* h, const int32_t* d_d2, int32_t touched, in
     return 0;
   };
   return run() ? -1 : 0;
+}
+
+}  // extern "C"
+
+// ---------------------------------------------------------------------------
+// Widest-path fields over a clearance field (pf_widest.h).  Reads the caller's d2 only, never the handle's
+// occupancy or masks; the handle keeps the scratch block (grown when a call needs more) and the last call's work counters.
+// ---------------------------------------------------------------------------
+#include "pf_widest.h"
+
+extern "C" {
+
+int pf_clearance_widest(pf_handle* h, int32_t allow_diag, int32_t restrict_corner, const int32_t* d_d2, int32_t B, const int32_t* set_off, const int32_t* src,
+                        int32_t* d_out, int64_t* d_info) {
+  if (!h) return -2;
+  const std::string me("pf_clearance_widest");
+  auto run = [&]() -> int {
+    std::vector<int> sets;
+    if (nearest_sets_check(h, me, B, set_off, src, sets)) return -2;
+    if (!d_d2 || !d_out) return failmsg(h, me + ": bad arguments (the field and the rows must not be null)");
+    CK(hipSetDevice(h->device));
+    const int R = h->R, C = h->C, RC = h->RC;
+    const int tiles_x = (C + PF_WD_TW - 1) / PF_WD_TW, tiles_y = (R + PF_WD_TH - 1) / PF_WD_TH, ntiles = tiles_x * tiles_y;
+    if ((long long)B * ntiles >= 0x7FFFFFFFll) return failmsg(h, me + ": bad arguments (B times the number of tiles must stay below 2^31 - 1)");
+    const size_t T = (size_t)B * (size_t)ntiles, nsets = sets.size() - 1;   // (sets[0] is the nearest fields' error word: not uploaded)
+    // the block: {words raised, spare} | keys [B] | cells [B] | sources [B] | queue lengths [2] + 2 spare | off [B + 1], ids | queues [2][T] | flags [2][T]
+    const size_t n64 = 2 + 3 * (size_t)B;
+    const size_t bytes = sizeof(unsigned long long) * n64 + sizeof(int) * (4 + nsets + 4 * T);
+    if (bytes > h->widest_bytes) {
+      if (h->d_widest) { CK(hipStreamSynchronize(h->stream)); (void)hipFree(h->d_widest); }
+      h->d_widest = nullptr; h->widest_bytes = 0;
+      if (hipMalloc(&h->d_widest, bytes) != hipSuccess) {
+        (void)hipGetLastError();
+        h->d_widest = nullptr;
+        return failmsg(h, me + ": no device memory for the scratch words (" + std::to_string(bytes >> 20) + " MiB)");
+      }
+      h->widest_bytes = bytes;
+    }
+    unsigned long long* const raised = (unsigned long long*)h->d_widest;
+    unsigned long long* const keys = raised + 2;
+    unsigned long long* const cells = keys + B;
+    unsigned long long* const nsrc = cells + B;
+    int* const count = (int*)(nsrc + B);
+    int* const d_off = count + 4;
+    int* const d_src = d_off + B + 1;
+    int* const queue = d_off + nsets;
+    int* const flag = queue + 2 * T;
+    h->widest_work[0] = h->widest_work[1] = h->widest_work[2] = h->widest_work[3] = 0;
+    CK(hipEventRecord(h->ev0, h->stream));
+    CK(hipMemsetAsync(raised, 0, sizeof(unsigned long long) * 2, h->stream));
+    CK(hipMemsetAsync(keys, 0xFF, sizeof(unsigned long long) * (size_t)B, h->stream));
+    CK(hipMemsetAsync(cells, 0, sizeof(unsigned long long) * 2 * (size_t)B + sizeof(int) * 4, h->stream));   // cells, sources, queue lengths
+    CK(hipMemsetAsync(flag, 0, sizeof(int) * 2 * T, h->stream));
+    CK(hipMemsetAsync(d_out, 0, sizeof(int) * (size_t)B * (size_t)RC, h->stream));
+    CK(hipMemcpyAsync(d_off, sets.data() + 1, sizeof(int) * nsets, hipMemcpyHostToDevice, h->stream));
+    CK(hipStreamSynchronize(h->stream));                            // (sets is pageable and leaves scope)
+    int most_src = 1;
+    for (int b = 0; b < B; ++b) most_src = std::max(most_src, set_off[b + 1] - set_off[b]);
+    const unsigned gy = (unsigned)(B < 65535 ? B : 65535);
+    hipLaunchKernelGGL(k_widest_seed_sets<>, dim3((unsigned)std::min((most_src + PF_WD_THREADS - 1) / PF_WD_THREADS, 64), gy), dim3(PF_WD_THREADS), 0, h->stream,
+                       (const int*)d_d2, RC, C, tiles_x, ntiles, (int)B, (const int*)d_off, (const int*)d_src, (int*)d_out, flag, queue, count, nsrc);
+    CK(hipGetLastError());
+    int n = 0;
+    CK(hipMemcpyAsync(&n, count, sizeof(int), hipMemcpyDeviceToHost, h->stream));
+    CK(hipStreamSynchronize(h->stream));
+    long long launches = 0, visits = 0;
+    for (long long round = 0; n > 0; ++round) {
+      if (round > (long long)RC) return failmsg(h, me + ": internal: round bound");
+      if (n < 0 || (size_t)n > T) return failmsg(h, me + ": internal: queue bound");
+      const int p = (int)(round & 1);
+      hipLaunchKernelGGL(k_widest_relax_tiles_in_lds<>, dim3((unsigned)n), dim3(PF_WD_THREADS), 0, h->stream, (const int*)d_d2, R, C, allow_diag ? 1 : 0,
+                         restrict_corner ? 1 : 0, tiles_x, tiles_y, (int*)d_out, (const int*)(queue + (size_t)p * T), n, round == 0 ? 1 : 0, flag + (size_t)p * T, count + p,
+                         flag + (size_t)(p ^ 1) * T, queue + (size_t)(p ^ 1) * T, count + (p ^ 1), raised);
+      CK(hipGetLastError());
+      launches += 1; visits += n;
+      CK(hipMemcpyAsync(&n, count + (p ^ 1), sizeof(int), hipMemcpyDeviceToHost, h->stream));
+      CK(hipStreamSynchronize(h->stream));
+    }
+    if (d_info) {
+      const unsigned nb = (unsigned)((RC + PF_WD_THREADS - 1) / PF_WD_THREADS);
+      hipLaunchKernelGGL(k_widest_info_sum<>, dim3(nb < 1024u ? nb : 1024u, gy), dim3(PF_WD_THREADS), 0, h->stream, (const int*)d_out, RC, (int)B, keys, cells);
+      hipLaunchKernelGGL(k_widest_write_info<>, dim3(((unsigned)B + PF_WD_THREADS - 1) / PF_WD_THREADS), dim3(PF_WD_THREADS), 0, h->stream, (int)B,
+                         (const unsigned long long*)keys, (const unsigned long long*)cells, (const unsigned long long*)nsrc, (long long*)d_info);
+      CK(hipGetLastError());
+    }
+    CK(hipEventRecord(h->ev1, h->stream));
+    unsigned long long words = 0;
+    CK(hipMemcpyAsync(&words, raised, sizeof(words), hipMemcpyDeviceToHost, h->stream));
+    CK(hipStreamSynchronize(h->stream));
+    CK(hipEventElapsedTime(&h->last_ms, h->ev0, h->ev1));
+    h->d2h_small += launches + 2;
+    h->widest_work[0] = launches; h->widest_work[1] = visits; h->widest_work[2] = (long long)words;
+    return 0;
+  };
+  return run() ? -1 : 0;
+}
+
+int pf_clearance_widest_work(pf_handle* h, int64_t* out4) {
+  if (!h) return -2;
+  if (!out4) { failmsg(h, "pf_clearance_widest_work: bad arguments (the four words must not be null)"); return -1; }
+  for (int i = 0; i < 4; ++i) out4[i] = h->widest_work[i];
+  return 0;
 }
 
 }  // extern "C"

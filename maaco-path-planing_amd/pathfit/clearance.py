@@ -1,12 +1,15 @@
 """Clearance: the exact distance from every cell of a grid to the nearest obstacle (pf_clearance_field), obstacles inflated by a
 robot's radius, and how close path rows (pf_clearance_paths) and straight segments (pf_clearance_segments) pass.  The field stays
 in HBM (`d2_device`); `d2` downloads it once.  `refresh` computes it again after `engine.update_grid`.  Everything is integer:
-squared distances between cell centres, no tolerance anywhere."""
+squared distances between cell centres, no tolerance anywhere.  `widest` turns the field into widest-path fields
+(pf_clearance_widest): how large a robot gets from a source to every cell, which cells a robot of a given radius reaches, and
+(`widest_path`) the shortest route among those that keep furthest from the walls."""
 import math
 
 import numpy as np
 
 from ._lib import PathfitError
+from .dist_field import DistanceField
 from .engine import Engine
 from .paths import CellPath
 
@@ -28,6 +31,58 @@ def margin_to_sq(margin):
     while math.sqrt(n) < m:
         n += 1
     return n
+
+
+class WidestField:
+    """What Clearance.widest returns: w[b, r, c] = the largest margin_sq with which a robot gets from a source of set b to (r, c)
+    (0: not at all), kept in HBM (`w_device`, int32 [B, R * C]); `info` int64 [B, 4] = (sources that counted, cells reached, the
+    smallest w >= 1, the smallest cell id that attains it; -1, -1 when nothing is reached)."""
+
+    def __init__(self, clearance, w_device, info, kernel_ms):
+        self.clearance, self.w_device, self.info, self.kernel_ms = clearance, w_device, info, kernel_ms
+        self.B, self.rows, self.cols = int(info.shape[0]), clearance.rows, clearance.cols
+        self._w = None
+
+    @property
+    def w(self):
+        """int32 [B, R, C], downloaded on first use."""
+        if self._w is None:
+            if self.w_device is None:
+                raise PathfitError("Clearance: the widest-path field is closed")
+            self._w = self.w_device.download().reshape(self.B, self.rows, self.cols)
+        return self._w
+
+    @property
+    def radius(self):
+        """float64 [B, R, C]: the square root of w, inf where w is PF_CLEAR_NONE (a map without an obstacle)."""
+        w = self.w
+        out = np.sqrt(w.astype(np.float64))
+        out[w == PF_CLEAR_NONE] = np.inf
+        return out
+
+    def at(self, b, cell):
+        """w[b] at one cell id, read from HBM alone when nothing was downloaded yet."""
+        if self._w is not None:
+            return int(self._w.reshape(self.B, -1)[int(b), int(cell)])
+        if self.w_device is None:
+            raise PathfitError("Clearance: the widest-path field is closed")
+        return int(self.w_device.read(int(b) * self.rows * self.cols + int(cell), 1)[0])
+
+    def reachable(self, margin=None, margin_sq=None):
+        """bool [B, R, C]: the cells a robot of that margin reaches from a source of the set, w >= margin_sq (margin as in
+        Clearance.inflated)."""
+        return self.w >= Clearance._margin_sq(margin, margin_sq, 1)
+
+    def close(self):
+        buf, self.w_device = getattr(self, "w_device", None), None
+        if buf is not None:
+            buf.free()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
 
 
 class Clearance:
@@ -236,6 +291,134 @@ class Clearance:
             for b in bufs:
                 b.free()
         return dmin, [None if x < 0 else (int(x) // self.cols, int(x) % self.cols) for x in at]
+
+    # ------------------------------------------------------------------ widest paths
+    def _source_sets(self, sources):
+        """One (r, c), a list of cells (one set) or a list of lists (B sets) -> a list of int32 id arrays."""
+        def is_seq(x):
+            return not isinstance(x, (str, bytes)) and hasattr(x, "__len__") and hasattr(x, "__getitem__")
+
+        def is_num(x):
+            return isinstance(x, (int, np.integer)) and not isinstance(x, bool)
+        bad = ValueError(f"Clearance: sources must be an (r, c) pair, a list of such pairs or a list of such lists, got {sources!r}")
+        if not is_seq(sources):
+            raise bad
+        if len(sources) == 0:
+            raise ValueError("Clearance: sources is empty")
+        first = sources[0]
+        if is_num(first):
+            return [np.array([self._pair("sources", sources)], np.int32)]
+        if not is_seq(first):
+            raise bad
+        if len(first) == 0 or is_seq(first[0]):
+            sets, names = list(sources), [f"sources[{b}]" for b in range(len(sources))]
+        elif is_num(first[0]):
+            sets, names = [sources], ["sources"]
+        else:
+            raise bad
+        out = []
+        for name, cells in zip(names, sets):
+            if not is_seq(cells):
+                raise ValueError(f"Clearance: {name} must be a list of (r, c) pairs, got {cells!r}")
+            if len(cells) == 0:
+                raise ValueError(f"Clearance: {name} is empty")
+            out.append(np.array([self._pair(f"{name}[{j}]", p) for j, p in enumerate(cells)], np.int32))
+        return out
+
+    def _pair(self, what, p):
+        try:
+            ok = not isinstance(p, (str, bytes)) and len(p) == 2
+        except TypeError:
+            ok = False
+        if not ok:
+            raise ValueError(f"Clearance: {what} must be an (r, c) pair, got {p!r}")
+        return self._cell(what, p, True)
+
+    def widest(self, sources, allow_diagonal_moves=True, restrict_diagonal_near_obstacle=True):
+        """sources: one (r, c), a list of cells (one set) or a list of lists (B sets) -> a WidestField: w[b, r, c] = the largest
+        margin_sq with which a robot gets from a source of set b to (r, c) under the move policy, 0 where none does.  A move's
+        capacity is the smaller d2 of its two cells (and of the two side cells, for a diagonal near an obstacle under the restricted
+        policy); a walk's is its smallest move's.  w >= t exactly where Components(inflated(margin_sq=t)) joins the cell to a source."""
+        sets = self._source_sets(sources)
+        off = np.zeros(len(sets) + 1, np.int32)
+        off[1:] = np.cumsum([len(s) for s in sets])
+        # every argument is checked: the device
+        self._check_open()
+        e, B = self.engine, len(sets)
+        wbuf = e.buf(B * self.rows * self.cols, np.int32)
+        ibuf = e.buf(B * 4, np.int64)
+        try:
+            e.clearance_widest(self.d2_device, off, np.concatenate(sets), wbuf, allow_diagonal_moves, restrict_diagonal_near_obstacle, ibuf)
+            return WidestField(self, wbuf, ibuf.download().reshape(B, 4), e.last_kernel_ms())
+        except Exception:
+            wbuf.free()
+            raise
+        finally:
+            ibuf.free()
+
+    def max_margin(self, source, target, allow_diagonal_moves=True, restrict_diagonal_near_obstacle=True):
+        """-> (w, sqrt(w)): the largest margin_sq with which a robot gets from source to target (0: not at all; PF_CLEAR_NONE and
+        inf on a map without an obstacle).  A robot fits iff its margin_sq <= w."""
+        s, t = self._pair("source", source), self._pair("target", target)
+        f = self.widest([(s // self.cols, s % self.cols)], allow_diagonal_moves, restrict_diagonal_near_obstacle)
+        try:
+            w = f.at(0, t)
+        finally:
+            f.close()
+        return w, (math.inf if w == PF_CLEAR_NONE else math.sqrt(w))
+
+    def _routes(self, msq, source, targets, ad, rs):
+        """DijkstraSolver.solve()'s paths from cell id `source` to the cell ids `targets` on inflated(margin_sq=msq) with the START
+        marker on the source (the TARGET marker too, for one target): a temporary engine, one DistanceField, one trace."""
+        g = self.inflated(margin_sq=msq)
+        g[g > 1] = 0
+        g.reshape(-1)[source] = 2
+        if len(targets) == 1 and targets[0] != source:
+            g.reshape(-1)[targets[0]] = 3
+        e = Engine(g)
+        try:
+            df = DistanceField(g, [(source // self.cols, source % self.cols)], ad, rs, engine=e)
+            try:
+                return df.paths([(int(t) // self.cols, int(t) % self.cols) for t in targets], k=0)
+            finally:
+                df.close()
+        finally:
+            e.close()
+
+    def widest_paths(self, source, targets, allow_diagonal_moves=True, restrict_diagonal_near_obstacle=True):
+        """-> (a list of CellPath, int32 [n]): for each target the shortest route among the widest ones from source -- the path
+        DijkstraSolver(...).solve() returns on inflated(margin_sq=w[target]), cell for cell -- and its w; an empty path and 0 where no
+        robot gets through.  One widest-path field serves every target; targets that share a threshold w share one distance field
+        on one inflated map, so the cost grows with the number of DISTINCT thresholds among the targets (a temporary engine, a
+        field and a trace each)."""
+        s = self._pair("source", source)
+        try:
+            targets = list(targets)
+        except TypeError:
+            raise ValueError(f"Clearance: targets must be a list of (r, c) pairs, got {targets!r}") from None
+        ids = [self._pair(f"targets[{i}]", p) for i, p in enumerate(targets)]
+        ad, rs = bool(allow_diagonal_moves), bool(restrict_diagonal_near_obstacle)
+        if not ids:
+            return [], np.zeros(0, np.int32)
+        f = self.widest([(s // self.cols, s % self.cols)], ad, rs)
+        try:
+            ws = np.array([f.at(0, t) for t in ids], np.int32) if len(ids) <= 4 else f.w.reshape(-1)[ids].astype(np.int32)
+        finally:
+            f.close()
+        paths = [CellPath(np.zeros(0, np.int32), self.cols) for _ in ids]
+        for msq in sorted(set(int(x) for x in ws if x > 0)):
+            group = [i for i, x in enumerate(ws) if x == msq]
+            for i, p in zip(group, self._routes(msq, s, [ids[i] for i in group], ad, rs)):
+                paths[i] = p
+        return paths, ws
+
+    def widest_path(self, source, target, allow_diagonal_moves=True, restrict_diagonal_near_obstacle=True):
+        """-> (CellPath, w): widest_paths for one target; ([], 0) when no robot gets through, the one-cell path when source ==
+        target (on a free cell)."""
+        self._pair("source", source)
+        self._pair("target", target)
+        paths, ws = self.widest_paths(source, [target], allow_diagonal_moves, restrict_diagonal_near_obstacle)
+        return (paths[0], int(ws[0])) if ws[0] > 0 else ([], 0)
 
     def close(self):
         for name in ("d2_device", "near_device", "ibuf"):

@@ -350,6 +350,24 @@ class Engine:
                                               d_to.ptr if d_to else None, d_min.ptr if d_min else None, d_at.ptr if d_at else None))
         self._logk("clearance_segments")
 
+    def clearance_widest(self, d_d2, set_off, sources, d_out, allow_diag=True, restrict_corner=True, d_info=None):
+        """A clearance field in HBM and source SETS (host int32 CSR, as dist_field_merged's) -> d_out int32 [B, R * C]: the largest,
+        over the walks from a source of the set to the cell, of the smallest move capacity (min of the two cells' d2, and of the two
+        side cells' for a diagonal under restrict_corner), 0 where nothing of capacity >= 1 arrives; d_info int64 [B, 4] = (sources
+        that counted, cells with w >= 1, the smallest w >= 1, the smallest cell that attains it) (pf_clearance_widest)."""
+        off = np.ascontiguousarray(set_off, np.int32).reshape(-1)
+        src = np.ascontiguousarray(sources, np.int32).reshape(-1)
+        self._ck(self.L.pf_clearance_widest(self.h, int(bool(allow_diag)), int(bool(restrict_corner)), d_d2.ptr if d_d2 else None, int(off.size) - 1,
+                                            off.ctypes.data if off.size else None, src.ctypes.data if src.size else None, d_out.ptr if d_out else None,
+                                            d_info.ptr if d_info else None))
+        self._logk("clearance_widest")
+
+    def clearance_widest_work(self):
+        """(launches, tile visits, words raised, 0) of the last clearance_widest call: they depend on the schedule (the probe's figures)."""
+        out = (C.c_int64 * 4)()
+        self._ck(self.L.pf_clearance_widest_work(self.h, out))
+        return tuple(int(v) for v in out)
+
     # ------------------------------------------------------------------ K1
     def score_batch(self, n, path_cap, d_cells, d_len, d_stats, sp):
         """Rows of astar_batch's layout in HBM -> d_stats [n, 5] doubles (pf_score_batch)."""
