@@ -7,6 +7,7 @@ import numpy as np
 import pytest
 
 import golden_io as gio
+from batch_edge_cases import free_pairs, moved, bits               # noqa: F401  (shared by the batch test files)
 
 pytestmark = pytest.mark.gpu
 
@@ -16,30 +17,6 @@ GA_KW = dict(num_generations=6, population_size=24, num_waypoints_per_chromosome
              diagonal_obstacle_penalty_value=100.0)
 PAIRS6 = [((19, 3), (12, 18)), ((18, 5), (12, 1)), ((4, 10), (17, 0)), ((6, 3), (5, 14)), ((0, 1), (18, 10)), ((16, 15), (2, 4))]
 INF = float("inf")
-
-
-def free_pairs(g, k, seed):
-    """k (start, target) pairs of distinct free cells."""
-    rnd = np.random.default_rng(seed)
-    free = np.argwhere(g != 1)
-    out = []
-    while len(out) < k:
-        i, j = rnd.choice(len(free), 2, replace=False)
-        out.append((tuple(int(v) for v in free[i]), tuple(int(v) for v in free[j])))
-    return out
-
-
-def moved(g, s, t):
-    """the grid with its START / TARGET markers at s / t"""
-    h = np.array(g, dtype=int)
-    h[(h == 2) | (h == 3)] = 0
-    h[s] = 2
-    h[t] = 3
-    return h
-
-
-def bits(a):
-    return np.ascontiguousarray(a, np.float64).view(np.int64)
 
 
 def components(g):

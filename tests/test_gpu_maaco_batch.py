@@ -7,30 +7,11 @@ import numpy as np
 import pytest
 
 import golden_io as gio
+from batch_edge_cases import free_pairs, moved               # noqa: F401  (shared by the batch test files)
 
 pytestmark = pytest.mark.gpu
 
 KW = dict(alpha=1.0, beta=7.0, rho=0.1, Q=2.5, a_turn_coef=1.0, wh_max=0.9, wh_min=0.2, k_h_adaptive=0.9, q0_initial=0.5)
-
-
-def free_pairs(g, k, seed):
-    """k (start, target) pairs of distinct free cells."""
-    rnd = np.random.default_rng(seed)
-    free = np.argwhere(g != 1)
-    out = []
-    while len(out) < k:
-        i, j = rnd.choice(len(free), 2, replace=False)
-        out.append((tuple(int(v) for v in free[i]), tuple(int(v) for v in free[j])))
-    return out
-
-
-def moved(g, s, t):
-    """the grid with its START / TARGET markers at s / t"""
-    h = np.array(g, dtype=int)
-    h[(h == 2) | (h == 3)] = 0
-    h[s] = 2
-    h[t] = 3
-    return h
 
 
 def check_vs_oracle(col, ref, C_):

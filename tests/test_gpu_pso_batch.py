@@ -7,6 +7,7 @@ import numpy as np
 import pytest
 
 import golden_io as gio
+from batch_edge_cases import moved, bits               # noqa: F401  (shared by the batch test files)
 
 pytestmark = pytest.mark.gpu
 
@@ -24,15 +25,6 @@ SEEDS6 = [6, 14, 25, 13, 12, 11]
 SOLO_ROUNDS6 = [[1, 2, 1, 2, 1, 1, 3, 1], [1, 1, 2, 4, 1, 2, 1, 1], [1, 1, 1, 3, 1, 2, 1, 1], [3, 2, 2, 2, 3, 1, 2, 1], [1, 1, 1, 1, 1, 1, 1, 1],
                 [2, 2, 3, 1, 1, 1, 1, 3]]
 INF = float("inf")
-
-
-def moved(g, s, t):
-    """the grid with its START / TARGET markers at s / t"""
-    h = np.array(g, dtype=int)
-    h[(h == 2) | (h == 3)] = 0
-    h[s] = 2
-    h[t] = 3
-    return h
 
 
 def components(g):
@@ -55,10 +47,6 @@ def components(g):
                         todo.append((rr, cc))
         n += 1
     return lab, n
-
-
-def bits(a):
-    return np.ascontiguousarray(a, np.float64).view(np.int64)
 
 
 def cellpath(p, cols):
