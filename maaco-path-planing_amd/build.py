@@ -19,8 +19,9 @@ import subprocess
 import sys
 
 HERE = os.path.dirname(os.path.abspath(__file__))
-SRC = os.path.join(HERE, "csrc", "pathfit.hip")
-DEPS = [SRC] + [os.path.join(HERE, "csrc", f) for f in sorted(os.listdir(os.path.join(HERE, "csrc"))) if f.endswith(".h")] + \
+# the translation units of the one library: the solvers, and the field family in a device code object of its own
+SRCS = [os.path.join(HERE, "csrc", f) for f in ("pathfit.hip", "pathfit_fields.hip")]
+DEPS = SRCS + [os.path.join(HERE, "csrc", f) for f in sorted(os.listdir(os.path.join(HERE, "csrc"))) if f.endswith(".h")] + \
        [os.path.join(os.path.dirname(HERE), "include", "pathfit.h")]
 OUT = os.path.join(HERE, "lib", "libpathfit.so")
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
@@ -52,7 +53,7 @@ def _stale(out):
 
 
 def _cmd(out, extra):
-    return [HIPCC] + FLAGS + os.environ.get("PF_EXTRA_FLAGS", "").split() + list(extra) + ["-o", out, SRC]
+    return [HIPCC] + FLAGS + os.environ.get("PF_EXTRA_FLAGS", "").split() + list(extra) + ["-o", out] + SRCS
 
 
 def build(force=False, verbose=False):

@@ -1,5 +1,6 @@
 // pathfit.hip -- kernels K0..K7 and the C-ABI of libpathfit.so (gfx950 / MI355X).
-// See include/pathfit.h for the boundary and DESIGN.md for the data layout.
+// See include/pathfit.h for the boundary and DESIGN.md for the data layout.  The solvers live here; the field family (distance
+// fields .. widest paths) is pathfit_fields.hip, a code object of its own, and pf_host.h is what the two units share.
 #include <hip/hip_runtime.h>
 #include <dlfcn.h>
 #include <rccl/rccl.h>
@@ -14,6 +15,7 @@
 #include <vector>
 
 #include "../../include/pathfit.h"
+#include "pf_host.h"
 #include "pf_astar.h"
 #include "pf_device.h"
 #include "pf_score.h"
@@ -1765,86 +1767,14 @@ struct pf_mpa_batch {
   double create_ms[3] = {0, 0, 0};                           // what create spent: initial paths + scores, bound tables, total
 };
 
-struct pf_handle {
-  int device = 0;
-  hipStream_t stream = nullptr;
-  int R = 0, C = 0, RC = 0;
-  uint8_t *d_occ = nullptr, *d_mm_r1 = nullptr, *d_mm_r0 = nullptr, *d_mm_r1_nd = nullptr, *d_mm_r0_nd = nullptr,
-          *d_d2near = nullptr;
-  std::vector<uint8_t> h_occ;
-  int* d_comp[4] = {nullptr, nullptr, nullptr, nullptr};   // component labels per move-mask policy (lazy)
-  int nslots = 0;
-  int rec_policy = -1;   // which move-mask variant the search records currently carry
-  Rec* d_rec = nullptr;
-  char* d_tier2 = nullptr;
-  uint32_t* d_slot_state = nullptr;
-  int* d_work = nullptr;
-  DevCounters* d_cnt = nullptr;
-  pf_counters last = {};
-  double* d_pen = nullptr;
-  double pen_min_safe = -1.0;
-  int* d_d2wide = nullptr; int wide_W = 0; double* d_penw = nullptr; int penw_n = 0; double penw_min_safe = -1.0;   // min_safe_distance > 15.9
-  int edt_radius = 7;      // radius of the obstacle-distance window d2near was built with
-  double obst_frac = -1.0; // share of obstacle cells (lazy; picks the plateau kernels on open maps)
-  hipEvent_t ev0 = nullptr, ev1 = nullptr, ev2 = nullptr;
-  float last_ms = 0.f;
-  std::string err;
-  // MAACO
-  bool maaco_ready = false;
-  pf_maaco_params mp = {};
-  double *d_tau = nullptr, *d_taua = nullptr, *d_eta = nullptr, *d_dep = nullptr, *d_tep = nullptr;
-  bool bits_clean = false;            // the visit-bit matrix is all zero (k_tau_deposit leaves it so)
-  int marks_n = 0; const int* marks_cells = nullptr;   // the last walk batch marked its own deposits (for these n ants / this path buffer)
-  double* d_mstate = nullptr;         // pf_maaco_iterate's 13 doubles
-  double* h_mstate = nullptr; double* h_mstate_dev = nullptr;   // ... mirrored by the device into pinned host memory (no copy is enqueued)
-  int* d_best_row = nullptr; int best_row_cap = 0;   // the overall best ant's path row, [0] = length (pf_maaco_iterate / pf_maaco_best_path)
-  char* d_mctl = nullptr;             // pf_maaco_iterate's own {work counter @0, DevCounters @16}: zeroed by k_maaco_best_take for the next walk
-  bool mctl_clean = false;
-  unsigned* d_visit = nullptr; unsigned* d_visit_epoch = nullptr; int maaco_slots = 0; int maaco_cus = 256;
-  unsigned long long* d_bits = nullptr; size_t bits_words = 0; int dep_cap = 0;
-  uint8_t* d_flag = nullptr;          // chunk flags of d_bits: [(RC + 63) / 64][bits_words] bytes (MaacoArgs::flag)
-  std::vector<pf_maaco_batch*> maaco_batches;   // pf_maaco_batch_create's objects (freed by pf_destroy, invalidated by pf_update_grid)
-  std::vector<pf_mpa_batch*> mpa_batches;       // pf_mpa_batch_create's, likewise
-  // MPA
-  bool mpa_ready = false;
-  pf_mpa_params mpp = {};
-  pf_score_params mps = {};
-  int* d_tmp = nullptr; int tmp_cap = 0;
-  double* d_elite_stats = nullptr;
-  int* d_init_cells = nullptr; int init_len = 0; int init_cap = 0; double* d_init_stats = nullptr;
-  double* d_ds = nullptr; double* d_dt = nullptr;   // static shortest distances from the start / to the target (pruning bounds)
-  float* d_est = nullptr; int* d_queue = nullptr; int est_cap = 0;   // work estimates and the longest-first queue of a batch
-  void* d_jobs = nullptr; void* d_jres = nullptr; int job_cap = 0;   // the sweep's search jobs / results (k_mpa_plan -> k_mpa_search -> k_mpa_finish)
-  int2* d_prop = nullptr; int* d_doubt = nullptr; int prop_cap = 0;   // MPA proposals {idx, target cell}; doubt list [0] = count, [1..] = predators
-  long long doubts_resolved = 0;
-  void* d_scan = nullptr; void* d_scan3 = nullptr;   // results of the small device scans
-  unsigned long long* d_okey = nullptr; int* d_opay = nullptr; unsigned* d_orank = nullptr; int okey_cap = 0;   // rank_sort scratch: key images, payloads, ranks
-  int* d_elite_cells = nullptr; int* d_elite_len = nullptr;   // the elite of the iteration (MPA.py:334), device resident
-  int* d_ga_pool = nullptr; int ga_pool_cap = 0;              // random.sample's pool copy (small populations; K of them for a batch)
-  double* d_seg_rows = nullptr; int seg_rows_cap = 0;         // pf_best_rows_seg: [K][6]
-  unsigned long long* d_st_lab = nullptr; int* d_st_touched = nullptr; unsigned char* d_st_par = nullptr; unsigned* d_st_epoch = nullptr;   // pf_settle.h scratch
-  int dep_words = 0; long long dep_done = 0;   // MAACO deposit in progress: words of the bit matrix, cells already folded
-  ncclComm_t comm = nullptr; int comm_rank = 0, comm_world = 1;   // RCCL communicator over xGMI (pf_comm_init); collectives run on `stream`
-  std::vector<hipEvent_t> span_ev; int span_n = 0; bool span_open = false; double span_ms = 0.0; long long span_cnt = 0;   // pf_span_*: HIP-event timed spans on `stream`
-  long long d2h_small = 0, d2h_bulk = 0, d2h_bulk_bytes = 0;   // device-to-host copies the library made (f1/f2 accounting): <= 128 B / larger
-  struct MpaAhead* ahead = nullptr;   // pf_mpa_iter_ahead: level buffers and the levels still to be taken (end of this file)
-  int* d_df_lists = nullptr; int df_slots = 0; int* d_df_ctl = nullptr; int df_ctl_cap = 0; int df_cus = 0;   // pf_dist_field_batch: [slots][3][RC] rolling lists; {error word, K sources}
-  int* d_cc = nullptr;                                                // pf_components: parent, rank and size words [3][RC], block counts, control block (first use)
-  hipEvent_t cc_ev[6] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr}; float cc_ms[5] = {0, 0, 0, 0, 0};   // ... its phase spans ("components_phases")
-  int* d_clear = nullptr;                                             // pf_clearance_field: control block, envelope stacks [RC] int2, row offsets [RC], column flags [C] (first use)
-  char* d_widest = nullptr; size_t widest_bytes = 0; long long widest_work[4] = {0, 0, 0, 0};   // pf_clearance_widest: counters, info words, the sets, tile queues and flags (first use, grown on demand); the last call's work
-};
-
-static bool g_cc_phases = false;   // pf_components records one HIP event per phase (pf_set_option "components_phases": the probe's spans)
 static long long g_step_cap = 0;   // > 0: lowers the connectors' step cap (pf_set_option "astar_step_cap": tests of the cap path)
 static std::string g_create_err;
-static int fail(pf_handle* h, const char* what, hipError_t e) {
+int fail(pf_handle* h, const char* what, hipError_t e) {
   std::string m = std::string(what) + ": " + hipGetErrorString(e);
   if (h) h->err = m; else g_create_err = m;
   return -1;
 }
-static int failmsg(pf_handle* h, const std::string& m) { if (h) h->err = m; else g_create_err = m; return -2; }
-#define CK(call) do { hipError_t e_ = (call); if (e_ != hipSuccess) return fail(h, #call, e_); } while (0)
+int failmsg(pf_handle* h, const std::string& m) { if (h) h->err = m; else g_create_err = m; return -2; }
 // pf_*_batch_create: a failed step (a HIP call, or a library call that has set its own message) runs the function's undo()
 static bool failed(pf_handle* h, const char* what, hipError_t e) { if (e != hipSuccess) fail(h, what, e); return e != hipSuccess; }
 static bool failed(pf_handle*, const char*, int rc) { return rc != 0; }
@@ -1927,7 +1857,7 @@ static const int* ensure_comp(pf_handle* h, int policy, const uint8_t* d_mm) {
 static Grid make_grid(pf_handle* h, int allow_diag, int restrict_corner) {
   Grid G;
   G.occ = h->d_occ;
-  G.mm = allow_diag ? (restrict_corner ? h->d_mm_r1 : h->d_mm_r0) : (restrict_corner ? h->d_mm_r1_nd : h->d_mm_r0_nd);
+  G.mm = move_mask(h, allow_diag, restrict_corner);
   G.comp = ensure_comp(h, (allow_diag ? 2 : 0) | (restrict_corner ? 1 : 0), G.mm);
   G.d2near = h->d_d2near; G.R = h->R; G.C = h->C;
   G.magicC = ((1ull << 40) / (uint64_t)h->C) + 1;
@@ -3337,8 +3267,7 @@ static int mpa_bound_table(pf_handle* h, const std::vector<uint8_t>& mm, int cel
   CK(hipMemcpy(d_out, dist.data(), sizeof(double) * (size_t)h->RC, hipMemcpyHostToDevice));
   return 0;
 }
-// the same tables built on the device (end of this file): rows d_out[k][RC] for the K host cells src[k]
-static int dist_field_run(pf_handle* h, const char* who, int allow_diag, int restrict_corner, int K, const int32_t* src, double* d_out, int64_t* d_info);
+// the same tables built on the device: dist_field_run (pathfit_fields.hip)
 static int mpa_bounds(pf_handle* h) {
   if (h->d_ds) { (void)hipFree(h->d_ds); h->d_ds = nullptr; }
   if (h->d_dt) { (void)hipFree(h->d_dt); h->d_dt = nullptr; }
@@ -4642,675 +4571,6 @@ int pf_pso_commit_batch(pf_handle* h, int32_t n, int32_t K, int32_t N, int32_t W
                      d_s_pos, d_s_vel, d_s_stats, d_s_len, d_s_cells, d_pos, d_vel, d_stats, d_len, d_cells, d_pbest, d_pbest_fit, d_pb_cells,
                      d_pb_len, d_gbest, d_gbest_stats, d_gbest_path, d_gfit);
   CK(hipGetLastError());
-  return 0;
-}
-
-}  // extern "C"
-
-// ---------------------------------------------------------------------------
-// Distance fields: exact one-to-all path lengths from K sources (pf_dist_field.h).  One workgroup per source,
-// min(K, CUs) of them looping over the sources; each owns one slot of three rolling cell lists in HBM.  The slots are the
-// handle's (allocated on first use, grown when a call needs more, freed by pf_destroy); nothing in them outlives a call, so
-// pf_update_grid has nothing to invalidate.
-// ---------------------------------------------------------------------------
-#include "pf_dist_field.h"
-
-// the handle's list slots for G workgroups (fewer where memory is short: G falls) and a control block of `words` ints
-static int dist_field_reserve(pf_handle* h, const std::string& me, int& G, size_t words) {
-  CK(hipSetDevice(h->device));
-  if (h->df_cus < 1) {
-    int cus = 0;
-    if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, h->device) != hipSuccess || cus < 1) cus = 256;
-    h->df_cus = cus;
-  }
-  const size_t slot_bytes = sizeof(int) * 3 * (size_t)h->RC;
-  if (G > h->df_cus) G = h->df_cus;
-  if (G > h->df_slots) {                                            // grow the slots (a workgroup's lists: 12 RC bytes)
-    CK(hipStreamSynchronize(h->stream));
-    if (h->d_df_lists) { (void)hipFree(h->d_df_lists); h->d_df_lists = nullptr; h->df_slots = 0; }
-    size_t free_b = 0, total_b = 0;
-    CK(hipMemGetInfo(&free_b, &total_b));
-    const size_t fit = free_b / 2 / slot_bytes;                     // on a large map fewer workgroups loop over more sources each
-    if (fit < (size_t)G) G = (int)fit;
-    if (G < 1 || hipMalloc(&h->d_df_lists, slot_bytes * (size_t)G) != hipSuccess) {
-      (void)hipGetLastError();
-      h->d_df_lists = nullptr;
-      return failmsg(h, me + ": no device memory for the level lists (" + std::to_string(slot_bytes >> 20) + " MiB per workgroup, " +
-                            std::to_string(free_b >> 20) + " MiB are free)");
-    }
-    h->df_slots = G;
-  }
-  if (words > (size_t)h->df_ctl_cap) {
-    if (words > 0x7FFFFFFFull) return failmsg(h, me + ": the source table is too large");
-    CK(hipStreamSynchronize(h->stream));
-    if (h->d_df_ctl) { (void)hipFree(h->d_df_ctl); h->d_df_ctl = nullptr; h->df_ctl_cap = 0; }
-    const int cap = words < 64 ? 64 : (int)words;
-    if (hipMalloc(&h->d_df_ctl, sizeof(int) * (size_t)cap) != hipSuccess) {
-      (void)hipGetLastError();
-      h->d_df_ctl = nullptr;
-      return failmsg(h, me + ": no device memory for the source table");
-    }
-    h->df_ctl_cap = cap;
-  }
-  return 0;
-}
-
-static int dist_field_run(pf_handle* h, const char* who, int allow_diag, int restrict_corner, int K, const int32_t* src, double* d_out, int64_t* d_info) {
-  const std::string me(who);
-  if (K < 1 || !src || !d_out) return failmsg(h, me + ": bad arguments (K >= 1, sources and rows must not be null)");
-  for (int k = 0; k < K; ++k)
-    if (src[k] < 0 || src[k] >= h->RC) return failmsg(h, me + ": source " + std::to_string(k) + " lies outside the grid");
-  int G = K;
-  if (dist_field_reserve(h, me, G, (size_t)K + 1)) return -2;
-  std::vector<int> ctl((size_t)K + 1);
-  ctl[0] = 0;
-  for (int k = 0; k < K; ++k) ctl[(size_t)k + 1] = src[k];
-  CK(hipMemcpyAsync(h->d_df_ctl, ctl.data(), sizeof(int) * ctl.size(), hipMemcpyHostToDevice, h->stream));
-  CK(hipStreamSynchronize(h->stream));                              // (ctl is pageable and leaves scope)
-  const uint8_t* mm = allow_diag ? (restrict_corner ? h->d_mm_r1 : h->d_mm_r0) : (restrict_corner ? h->d_mm_r1_nd : h->d_mm_r0_nd);
-  CK(hipEventRecord(h->ev0, h->stream));
-  hipLaunchKernelGGL(k_dist_field_level_synchronous<>, dim3(G), dim3(PF_DF_THREADS), 0, h->stream, (const uint8_t*)h->d_occ, mm, h->RC, h->C, K,
-                     (const int*)(h->d_df_ctl + 1), d_out, h->d_df_lists, (long long*)d_info, h->d_df_ctl);
-  CK(hipGetLastError());
-  CK(hipEventRecord(h->ev1, h->stream));
-  int err = 0;
-  CK(hipMemcpyAsync(&err, h->d_df_ctl, sizeof(int), hipMemcpyDeviceToHost, h->stream));
-  CK(hipStreamSynchronize(h->stream));
-  CK(hipEventElapsedTime(&h->last_ms, h->ev0, h->ev1));
-  h->d2h_small += 1;
-  if (err == PF_DF_ERR_LEVELS) return failmsg(h, me + ": internal: level bound");
-  if (err) return failmsg(h, me + ": internal: list bound");
-  return 0;
-}
-
-extern "C" {
-
-int pf_dist_field_batch(pf_handle* h, int32_t allow_diag, int32_t restrict_corner, int32_t K, const int32_t* src, double* d_out, int64_t* d_info) {
-  if (!h) return -2;
-  return dist_field_run(h, "pf_dist_field_batch", allow_diag, restrict_corner, K, src, d_out, d_info) ? -1 : 0;
-}
-
-}  // extern "C"
-
-// ---------------------------------------------------------------------------
-// Routing trees: DijkstraSolver's paths from a distance field (pf_field_paths.h).  pf_dist_field_parents turns K
-// fields into K parent maps (one byte per cell) by the field-only rule; pf_dist_field_paths chases n (field, target) queries
-// through them into path rows laid out as pf_astar_batch's.  Both keep nothing on the handle but the error word of the
-// distance-field control block.
-// ---------------------------------------------------------------------------
-#include "pf_field_paths.h"
-
-extern "C" {
-
-int pf_dist_field_parents(pf_handle* h, int32_t allow_diag, int32_t restrict_corner, int32_t K, const double* d_fields, uint8_t* d_parents) {
-  if (!h) return -2;
-  if (K < 1 || !d_fields || !d_parents) { failmsg(h, "pf_dist_field_parents: bad arguments (K >= 1, fields and parents must not be null)"); return -1; }
-  auto run = [&]() -> int {
-    CK(hipSetDevice(h->device));
-    if (!h->d_df_ctl) {                                             // (fields computed elsewhere: no control block yet)
-      if (hipMalloc(&h->d_df_ctl, sizeof(int) * 64) != hipSuccess) {
-        (void)hipGetLastError();
-        h->d_df_ctl = nullptr;
-        return failmsg(h, "pf_dist_field_parents: no device memory for the error word");
-      }
-      h->df_ctl_cap = 64;
-    }
-    CK(hipMemsetAsync(h->d_df_ctl, 0, sizeof(int), h->stream));
-    const uint8_t* mm = allow_diag ? (restrict_corner ? h->d_mm_r1 : h->d_mm_r0) : (restrict_corner ? h->d_mm_r1_nd : h->d_mm_r0_nd);
-    const unsigned gx = (unsigned)((h->RC + PF_FP_THREADS - 1) / PF_FP_THREADS), gy = (unsigned)(K < 65535 ? K : 65535);
-    CK(hipEventRecord(h->ev0, h->stream));
-    hipLaunchKernelGGL(k_dist_field_parent_map_thread_per_cell<>, dim3(gx, gy), dim3(PF_FP_THREADS), 0, h->stream, mm, h->RC, h->C, K, d_fields, d_parents,
-                       h->d_df_ctl);
-    CK(hipGetLastError());
-    CK(hipEventRecord(h->ev1, h->stream));
-    int err = 0;
-    CK(hipMemcpyAsync(&err, h->d_df_ctl, sizeof(int), hipMemcpyDeviceToHost, h->stream));
-    CK(hipStreamSynchronize(h->stream));
-    CK(hipEventElapsedTime(&h->last_ms, h->ev0, h->ev1));
-    h->d2h_small += 1;
-    if (err) return failmsg(h, "pf_dist_field_parents: a finite cell has no parent: the fields are no fixed point of this grid and policy");
-    return 0;
-  };
-  return run() ? -1 : 0;
-}
-
-int pf_dist_field_paths(pf_handle* h, int32_t K, const uint8_t* d_parents, const double* d_fields, int32_t n, const int32_t* d_field_idx,
-                        const int32_t* d_target, int32_t reverse, int32_t path_cap, int32_t* d_cells, int32_t* d_len, int32_t* d_status,
-                        int32_t* d_chosen) {
-  if (!h) return -2;
-  if (K < 1 || n < 0 || path_cap < 1 || !d_parents || !d_target || !d_cells || !d_len || !d_status || (!d_field_idx && !d_fields)) {
-    failmsg(h, "pf_dist_field_paths: bad arguments (K >= 1, n >= 0, path_cap >= 1; parents, targets and outputs must not be null; "
-               "without field indices the fields are needed for the nearest source)");
-    return -1;
-  }
-  if (n == 0) return 0;
-  auto run = [&]() -> int {
-    CK(hipSetDevice(h->device));
-    CK(hipEventRecord(h->ev0, h->stream));
-    hipLaunchKernelGGL(k_dist_field_trace_query_lanes<>, dim3((unsigned)((n + PF_FP_TRACE_THREADS - 1) / PF_FP_TRACE_THREADS)), dim3(PF_FP_TRACE_THREADS), 0,
-                       h->stream, d_parents, d_fields, h->RC, h->C, K, n, d_field_idx, d_target, reverse ? 1 : 0, path_cap, d_cells, d_len, d_status,
-                       d_chosen);
-    CK(hipGetLastError());
-    CK(hipEventRecord(h->ev1, h->stream));
-    CK(hipStreamSynchronize(h->stream));
-    CK(hipEventElapsedTime(&h->last_ms, h->ev0, h->ev1));
-    return 0;
-  };
-  return run() ? -1 : 0;
-}
-
-}  // extern "C"
-
-// ---------------------------------------------------------------------------
-// Nearest-source fields: one field seeded with a whole source set, and the owner of every cell (pf_nearest_field.h, DESIGN.md
-// 4.13).  pf_dist_field_merged runs on the distance fields' list slots; pf_dist_field_owners needs one int32 [B][RC] scratch
-// buffer for the length of the call.  Both keep the sets in the distance-field control block: {error word, off[B + 1], ids}.
-// ---------------------------------------------------------------------------
-#include "pf_nearest_field.h"
-
-// the sets of a call, checked on the host; -> words of the control block
-static int nearest_sets_check(pf_handle* h, const std::string& me, int B, const int32_t* set_off, const int32_t* src, std::vector<int>& ctl) {
-  if (B < 1) return failmsg(h, me + ": bad arguments (B = " + std::to_string(B) + ": at least one source set is needed)");
-  if (!set_off || !src) return failmsg(h, me + ": bad arguments (the set offsets and the sources must not be null)");
-  if (set_off[0] != 0) return failmsg(h, me + ": set_off[0] = " + std::to_string(set_off[0]) + ": the offsets must start at 0");
-  for (int b = 0; b < B; ++b) {
-    if (set_off[b + 1] < set_off[b])
-      return failmsg(h, me + ": set " + std::to_string(b) + ": set_off[" + std::to_string(b + 1) + "] = " + std::to_string(set_off[b + 1]) + " lies below set_off[" +
-                            std::to_string(b) + "] = " + std::to_string(set_off[b]));
-    if (set_off[b + 1] == set_off[b]) return failmsg(h, me + ": set " + std::to_string(b) + " is empty");
-  }
-  for (int b = 0; b < B; ++b)
-    for (int j = set_off[b]; j < set_off[b + 1]; ++j)
-      if (src[j] < 0 || src[j] >= h->RC)
-        return failmsg(h, me + ": set " + std::to_string(b) + ", source " + std::to_string(j - set_off[b]) + " (index " + std::to_string(j) + ") = " +
-                              std::to_string(src[j]) + " lies outside the grid");
-  ctl.assign(1, 0);
-  ctl.insert(ctl.end(), set_off, set_off + B + 1);
-  ctl.insert(ctl.end(), src, src + set_off[B]);
-  return 0;
-}
-
-extern "C" {
-
-int pf_dist_field_merged(pf_handle* h, int32_t allow_diag, int32_t restrict_corner, int32_t B, const int32_t* set_off, const int32_t* src, double* d_out,
-                         int64_t* d_info) {
-  if (!h) return -2;
-  const std::string me("pf_dist_field_merged");
-  auto run = [&]() -> int {
-    std::vector<int> ctl;
-    if (nearest_sets_check(h, me, B, set_off, src, ctl)) return -2;
-    if (!d_out) return failmsg(h, me + ": bad arguments (the rows must not be null)");
-    int G = B;
-    if (dist_field_reserve(h, me, G, ctl.size())) return -2;
-    CK(hipMemcpyAsync(h->d_df_ctl, ctl.data(), sizeof(int) * ctl.size(), hipMemcpyHostToDevice, h->stream));
-    CK(hipStreamSynchronize(h->stream));                            // (ctl is pageable and leaves scope)
-    const uint8_t* mm = allow_diag ? (restrict_corner ? h->d_mm_r1 : h->d_mm_r0) : (restrict_corner ? h->d_mm_r1_nd : h->d_mm_r0_nd);
-    CK(hipEventRecord(h->ev0, h->stream));
-    hipLaunchKernelGGL(k_dist_field_merged_source_sets<>, dim3(G), dim3(PF_DF_THREADS), 0, h->stream, (const uint8_t*)h->d_occ, mm, h->RC, h->C, B,
-                       (const int*)(h->d_df_ctl + 1), (const int*)(h->d_df_ctl + 2 + B), d_out, h->d_df_lists, (long long*)d_info, h->d_df_ctl);
-    CK(hipGetLastError());
-    CK(hipEventRecord(h->ev1, h->stream));
-    int err = 0;
-    CK(hipMemcpyAsync(&err, h->d_df_ctl, sizeof(int), hipMemcpyDeviceToHost, h->stream));
-    CK(hipStreamSynchronize(h->stream));
-    CK(hipEventElapsedTime(&h->last_ms, h->ev0, h->ev1));
-    h->d2h_small += 1;
-    if (err == PF_DF_ERR_LEVELS) return failmsg(h, me + ": internal: level bound");
-    if (err) return failmsg(h, me + ": internal: list bound");
-    return 0;
-  };
-  return run() ? -1 : 0;
-}
-
-int pf_dist_field_owners(pf_handle* h, int32_t B, const uint8_t* d_parents, const int32_t* set_off, const int32_t* src, const int64_t* d_info, int32_t* d_owner,
-                         int64_t* d_count) {
-  if (!h) return -2;
-  const std::string me("pf_dist_field_owners");
-  int* d_scratch = nullptr;
-  auto run = [&]() -> int {
-    std::vector<int> ctl;
-    if (nearest_sets_check(h, me, B, set_off, src, ctl)) return -2;
-    if (!d_parents || !d_owner) return failmsg(h, me + ": bad arguments (the parent maps and the owner rows must not be null)");
-    const int RC = h->RC;
-    int G = 0;                                                      // (no list slots: the control block only)
-    if (dist_field_reserve(h, me, G, ctl.size())) return -2;
-    // the rounds are fixed here, before the first launch: chains of at most n cells resolve in ceil(log2(n)) rounds
-    long long n = RC;
-    if (d_info) {
-      std::vector<long long> info((size_t)B * 4);
-      CK(hipMemcpyAsync(info.data(), d_info, sizeof(long long) * info.size(), hipMemcpyDeviceToHost, h->stream));
-      CK(hipStreamSynchronize(h->stream));
-      const size_t nb = sizeof(long long) * info.size();
-      if (nb <= 128) h->d2h_small += 1; else { h->d2h_bulk += 1; h->d2h_bulk_bytes += (long long)nb; }
-      long long most = 1;                                           // the cells of a chain lie in distinct live levels
-      for (int b = 0; b < B; ++b) most = std::max(most, info[(size_t)b * 4]);
-      n = std::min(n, most);
-    }
-    int rounds = 0;
-    while ((1ll << rounds) < n) rounds += 1;
-    const size_t words = (size_t)B * (size_t)RC;
-    if (hipMalloc(&d_scratch, sizeof(int) * words) != hipSuccess) {
-      (void)hipGetLastError();
-      d_scratch = nullptr;
-      return failmsg(h, me + ": no device memory for the second link buffer (" + std::to_string((sizeof(int) * words) >> 20) + " MiB)");
-    }
-    CK(hipMemcpyAsync(h->d_df_ctl, ctl.data(), sizeof(int) * ctl.size(), hipMemcpyHostToDevice, h->stream));
-    CK(hipStreamSynchronize(h->stream));                            // (ctl is pageable and leaves scope)
-    if (d_count) CK(hipMemsetAsync(d_count, 0, sizeof(int64_t) * (size_t)set_off[B], h->stream));
-    const int* d_off = h->d_df_ctl + 1;
-    const int* d_src = h->d_df_ctl + 2 + B;
-    int most_src = 1;
-    for (int b = 0; b < B; ++b) most_src = std::max(most_src, set_off[b + 1] - set_off[b]);
-    const unsigned gx = (unsigned)((RC + PF_NF_THREADS - 1) / PF_NF_THREADS), gy = (unsigned)(B < 65535 ? B : 65535);
-    const unsigned sx = (unsigned)std::min((most_src + PF_NF_THREADS - 1) / PF_NF_THREADS, 64);
-    int* buf[2] = {(rounds & 1) ? (int*)d_owner : d_scratch, (rounds & 1) ? d_scratch : (int*)d_owner};   // the last round ends in the scratch buffer
-    CK(hipEventRecord(h->ev0, h->stream));
-    hipLaunchKernelGGL(k_nearest_owner_links<>, dim3(gx, gy), dim3(PF_NF_THREADS), 0, h->stream, d_parents, RC, h->C, B, buf[0], h->d_df_ctl);
-    hipLaunchKernelGGL(k_nearest_owner_stamp_ranks<>, dim3(sx, gy), dim3(PF_NF_THREADS), 0, h->stream, RC, B, d_off, d_src, buf[0]);
-    for (int t = 0; t < rounds; ++t)
-      hipLaunchKernelGGL(k_nearest_owner_doubling<>, dim3(gx, gy), dim3(PF_NF_THREADS), 0, h->stream, RC, B, (const int*)buf[t & 1], buf[(t + 1) & 1]);
-    hipLaunchKernelGGL(k_nearest_owner_write_and_count<>, dim3(gx, gy), dim3(PF_NF_THREADS), 0, h->stream, RC, B, d_off, (const int*)d_scratch, (int*)d_owner,
-                       (unsigned long long*)d_count, h->d_df_ctl);
-    CK(hipGetLastError());
-    CK(hipEventRecord(h->ev1, h->stream));
-    int err = 0;
-    CK(hipMemcpyAsync(&err, h->d_df_ctl, sizeof(int), hipMemcpyDeviceToHost, h->stream));
-    CK(hipStreamSynchronize(h->stream));
-    CK(hipEventElapsedTime(&h->last_ms, h->ev0, h->ev1));
-    h->d2h_small += 1;
-    if (err & PF_NF_ERR_CODE) return failmsg(h, me + ": the parent maps hold a code outside 0..8 and 255, or a step off the grid");
-    if (err & PF_NF_ERR_ROOT) return failmsg(h, me + ": a root of the parent maps is no source of its set: the maps belong to other sets");
-    if (err) return failmsg(h, me + ": a chain holds more cells than the bound of " + std::to_string(n) + " (" + std::to_string(rounds) +
-                               " rounds): the parent maps are no forest, or d_info belongs to another field");
-    return 0;
-  };
-  const int rc = run();
-  if (d_scratch) { (void)hipStreamSynchronize(h->stream); (void)hipFree(d_scratch); }
-  return rc ? -1 : 0;
-}
-
-}  // extern "C"
-
-// ---------------------------------------------------------------------------
-// Any-angle smoothing: line-of-sight tests and forward string pulling (pf_smooth.h).  Both read the handle's
-// occupancy bytes at call time (pf_update_grid keeps working) and keep nothing on the handle.
-// ---------------------------------------------------------------------------
-#include "pf_smooth.h"
-
-extern "C" {
-
-int pf_line_of_sight_batch(pf_handle* h, int32_t restrict_corner, int32_t n, const int32_t* d_from, const int32_t* d_to, int32_t* d_visible,
-                           int32_t* d_first_block) {
-  if (!h) return -2;
-  if (n < 0 || !d_from || !d_to || !d_visible) {
-    failmsg(h, "pf_line_of_sight_batch: bad arguments (n >= 0; the endpoints and the visibility flags must not be null)");
-    return -1;
-  }
-  if (n == 0) return 0;
-  auto run = [&]() -> int {
-    CK(hipSetDevice(h->device));
-    CK(hipEventRecord(h->ev0, h->stream));
-    hipLaunchKernelGGL(k_line_of_sight_pairs_lanes_on_major<>, dim3((unsigned)n), dim3(64), 0, h->stream, (const uint8_t*)h->d_occ, h->RC, h->C, restrict_corner ? 1 : 0, n,
-                       d_from, d_to, d_visible, d_first_block);
-    CK(hipGetLastError());
-    CK(hipEventRecord(h->ev1, h->stream));
-    CK(hipStreamSynchronize(h->stream));
-    CK(hipEventElapsedTime(&h->last_ms, h->ev0, h->ev1));
-    return 0;
-  };
-  return run() ? -1 : 0;
-}
-
-int pf_smooth_batch(pf_handle* h, int32_t restrict_corner, int32_t n, int32_t path_cap, const int32_t* d_cells, const int32_t* d_len, int32_t way_cap,
-                    int32_t* d_way_cells, int32_t* d_way_idx, int32_t* d_way_len, double* d_stats, int32_t* d_status) {
-  if (!h) return -2;
-  if (n < 0 || path_cap < 1 || way_cap < 1 || !d_cells || !d_len || !d_way_cells || !d_way_len || !d_status) {
-    failmsg(h, "pf_smooth_batch: bad arguments (n >= 0, path_cap >= 1, way_cap >= 1; the rows, the lengths, the waypoint rows, their lengths and "
-               "the statuses must not be null)");
-    return -1;
-  }
-  if (n == 0) return 0;
-  auto run = [&]() -> int {
-    CK(hipSetDevice(h->device));
-    CK(hipEventRecord(h->ev0, h->stream));
-    hipLaunchKernelGGL(k_smooth_paths_one_wave_per_row<>, dim3((unsigned)n), dim3(64), 0, h->stream, (const uint8_t*)h->d_occ, h->RC, h->C, restrict_corner ? 1 : 0, n, path_cap,
-                       d_cells, d_len, way_cap, d_way_cells, d_way_idx, d_way_len, d_stats, d_status);
-    CK(hipGetLastError());
-    CK(hipEventRecord(h->ev1, h->stream));
-    CK(hipStreamSynchronize(h->stream));
-    CK(hipEventElapsedTime(&h->last_ms, h->ev0, h->ev1));
-    return 0;
-  };
-  return run() ? -1 : 0;
-}
-
-}  // extern "C"
-
-// ---------------------------------------------------------------------------
-// Connected components: labels, sizes and reachability queries (pf_components.h).  The masks are read at call
-// time (pf_update_grid keeps working); the handle keeps only the scratch words, allocated on first use.  Nothing here touches the
-// searches' own labels (ensure_comp / d_comp).
-// ---------------------------------------------------------------------------
-#include "pf_components.h"
-
-extern "C" {
-
-int pf_components(pf_handle* h, int32_t allow_diag, int32_t restrict_corner, int32_t* d_labels, int64_t* d_info) {
-  if (!h) return -2;
-  if (!d_labels) { failmsg(h, "pf_components: bad arguments (the labels must not be null)"); return -1; }
-  auto run = [&]() -> int {
-    CK(hipSetDevice(h->device));
-    const int RC = h->RC, C = h->C;
-    const unsigned nb = (unsigned)((RC + PF_CC_THREADS - 1) / PF_CC_THREADS);
-    if (!h->d_cc) {
-      const size_t bytes = sizeof(unsigned long long) * PF_CC_CTL_WORDS + sizeof(int) * (3 * (size_t)RC + (size_t)nb);
-      if (hipMalloc(&h->d_cc, bytes) != hipSuccess) {
-        (void)hipGetLastError();
-        h->d_cc = nullptr;
-        return failmsg(h, "pf_components: no device memory for the scratch words (" + std::to_string(bytes >> 20) + " MiB)");
-      }
-    }
-    if (g_cc_phases) for (hipEvent_t& e : h->cc_ev) if (!e) CK(hipEventCreate(&e));
-    unsigned long long* const ctl = (unsigned long long*)h->d_cc;    // (in front: 8-byte aligned whatever RC is)
-    int* const parent = h->d_cc + 2 * PF_CC_CTL_WORDS;
-    int* const rank = parent + RC;
-    int* const size = rank + RC;
-    int* const blocks = size + RC;
-    const uint8_t* mm = allow_diag ? (restrict_corner ? h->d_mm_r1 : h->d_mm_r0) : (restrict_corner ? h->d_mm_r1_nd : h->d_mm_r0_nd);
-    const uint8_t* occ = h->d_occ;
-    const dim3 grid(nb), block(PF_CC_THREADS);
-    const unsigned hb = (unsigned)((RC + PF_CC_THREADS * PF_CC_HIST_PER - 1) / (PF_CC_THREADS * PF_CC_HIST_PER));
-    int phase = 0;
-    auto mark = [&]() -> hipError_t { return g_cc_phases ? hipEventRecord(h->cc_ev[phase++], h->stream) : hipSuccess; };
-    CK(hipEventRecord(h->ev0, h->stream));
-    CK(mark());
-    CK(hipMemsetAsync(ctl, 0, sizeof(unsigned long long) * PF_CC_CTL_WORDS, h->stream));
-#if PF_CC_TILED
-    hipLaunchKernelGGL(k_cc_label_tiles_in_lds<>, dim3((unsigned)((C + PF_CC_TW - 1) / PF_CC_TW), (unsigned)((h->R + PF_CC_TH - 1) / PF_CC_TH)), block, 0, h->stream, occ, mm,
-                       h->R, C, parent);
-    hipLaunchKernelGGL(k_cc_link_tile_borders<>, grid, block, 0, h->stream, occ, mm, RC, C, parent);
-#else
-    hipLaunchKernelGGL(k_cc_init_parent_lowest_back_neighbour<>, grid, block, 0, h->stream, occ, mm, RC, C, parent);
-    hipLaunchKernelGGL(k_cc_link_forward_edges<>, grid, block, 0, h->stream, occ, mm, RC, C, parent);
-#endif
-    CK(mark());                                                     // [0] link
-    hipLaunchKernelGGL(k_cc_flatten_and_count_roots<>, grid, block, 0, h->stream, RC, (const int*)parent, (int*)d_labels, blocks);
-    CK(mark());                                                     // [1] flatten
-    hipLaunchKernelGGL(k_cc_scan_block_counts<>, dim3(1), dim3(PF_CC_SCAN_THREADS), 0, h->stream, (int)nb, blocks, ctl);
-    hipLaunchKernelGGL(k_cc_rank_roots<>, grid, block, 0, h->stream, RC, (const int*)parent, (const int*)blocks, rank, size);
-    CK(mark());                                                     // [2] rank
-    hipLaunchKernelGGL(k_cc_write_labels<>, grid, block, 0, h->stream, RC, (const int*)rank, (int*)d_labels);
-    CK(mark());                                                     // [3] labels
-    if (d_info) {
-      hipLaunchKernelGGL((k_cc_histogram<int>), dim3(hb), block, 0, h->stream, RC, (const int*)d_labels, (const unsigned long long*)ctl, 0, size, (unsigned*)nullptr, ctl + 1);
-      hipLaunchKernelGGL(k_cc_largest<>, dim3(nb < 1024u ? nb : 1024u), block, 0, h->stream, (const int*)size, ctl);
-      hipLaunchKernelGGL(k_cc_write_info_block<>, dim3(1), dim3(64), 0, h->stream, (const unsigned long long*)ctl, (long long*)d_info);
-    }
-    CK(mark());                                                     // [4] sizes and info
-    CK(hipGetLastError());
-    CK(hipEventRecord(h->ev1, h->stream));
-    CK(hipStreamSynchronize(h->stream));
-    CK(hipEventElapsedTime(&h->last_ms, h->ev0, h->ev1));
-    for (int i = 0; i < 5; ++i) {
-      h->cc_ms[i] = 0.f;
-      if (g_cc_phases) CK(hipEventElapsedTime(&h->cc_ms[i], h->cc_ev[i], h->cc_ev[i + 1]));
-    }
-    return 0;
-  };
-  return run() ? -1 : 0;
-}
-
-int pf_components_phase_ms(pf_handle* h, float* ms) {
-  if (!h) return -2;
-  if (!ms) { failmsg(h, "pf_components_phase_ms: bad arguments"); return -1; }
-  for (int i = 0; i < 5; ++i) ms[i] = h->cc_ms[i];
-  return 0;
-}
-
-int pf_component_sizes(pf_handle* h, const int32_t* d_labels, int32_t count, int64_t* d_sizes, int32_t* d_first) {
-  if (!h) return -2;
-  if (!d_labels || count < 0) { failmsg(h, "pf_component_sizes: bad arguments (count >= 0; the labels must not be null)"); return -1; }
-  if (count == 0 || (!d_sizes && !d_first)) return 0;
-  auto run = [&]() -> int {
-    CK(hipSetDevice(h->device));
-    const int RC = h->RC;
-    const unsigned nb = (unsigned)((RC + PF_CC_THREADS - 1) / PF_CC_THREADS), cb = (unsigned)((count + PF_CC_THREADS - 1) / PF_CC_THREADS);
-    CK(hipEventRecord(h->ev0, h->stream));
-    if (d_sizes) CK(hipMemsetAsync(d_sizes, 0, sizeof(int64_t) * (size_t)count, h->stream));
-    if (d_first) hipLaunchKernelGGL((k_cc_fill_words_with_a_value<unsigned>), dim3(cb), dim3(PF_CC_THREADS), 0, h->stream, (unsigned*)d_first, (int)count, 0xFFFFFFFFu);
-    hipLaunchKernelGGL((k_cc_histogram<unsigned long long>), dim3((nb + PF_CC_HIST_PER - 1) / PF_CC_HIST_PER), dim3(PF_CC_THREADS), 0, h->stream, RC, (const int*)d_labels, (const unsigned long long*)nullptr,
-                       (int)count, (unsigned long long*)d_sizes, (unsigned*)d_first, (unsigned long long*)nullptr);
-    CK(hipGetLastError());
-    CK(hipEventRecord(h->ev1, h->stream));
-    CK(hipStreamSynchronize(h->stream));
-    CK(hipEventElapsedTime(&h->last_ms, h->ev0, h->ev1));
-    return 0;
-  };
-  return run() ? -1 : 0;
-}
-
-int pf_components_same(pf_handle* h, const int32_t* d_labels, int32_t n, const int32_t* d_a, const int32_t* d_b, int32_t* d_same) {
-  if (!h) return -2;
-  if (n < 0 || !d_labels || !d_a || !d_b || !d_same) {
-    failmsg(h, "pf_components_same: bad arguments (n >= 0; the labels, the two id rows and the answers must not be null)");
-    return -1;
-  }
-  if (n == 0) return 0;
-  auto run = [&]() -> int {
-    CK(hipSetDevice(h->device));
-    CK(hipEventRecord(h->ev0, h->stream));
-    hipLaunchKernelGGL(k_cc_same_pairs<>, dim3((unsigned)((n + PF_CC_THREADS - 1) / PF_CC_THREADS)), dim3(PF_CC_THREADS), 0, h->stream, h->RC, (const int*)d_labels, (int)n,
-                       (const int*)d_a, (const int*)d_b, (int*)d_same);
-    CK(hipGetLastError());
-    CK(hipEventRecord(h->ev1, h->stream));
-    CK(hipStreamSynchronize(h->stream));
-    CK(hipEventElapsedTime(&h->last_ms, h->ev0, h->ev1));
-    return 0;
-  };
-  return run() ? -1 : 0;
-}
-
-}  // extern "C"
-
-// ---------------------------------------------------------------------------
-// Clearance fields: exact squared distances to the nearest obstacle, the margins of path rows and segments (pf_clearance.h,
-// DESIGN.md 4.16).  The occupancy is read at call time (pf_update_grid keeps working); the handle keeps only the scratch words,
-// allocated on first use.  Nothing here touches the scorer's own tables (ensure_pen / d_d2near / d_d2wide).
-// ---------------------------------------------------------------------------
-#include "pf_clearance.h"
-
-extern "C" {
-
-int pf_clearance_field(pf_handle* h, int32_t border, int32_t* d_d2, int32_t* d_near, int64_t* d_info) {
-  if (!h) return -2;
-  if (!d_d2) { failmsg(h, "pf_clearance_field: bad arguments (the squared distances must not be null)"); return -1; }
-  if ((long long)h->R * h->R + (long long)h->C * h->C >= 0x7FFFFFFFll) {
-    failmsg(h, "pf_clearance_field: bad arguments (R^2 + C^2 must stay below 2^31 - 1)");
-    return -1;
-  }
-  auto run = [&]() -> int {
-    CK(hipSetDevice(h->device));
-    const int R = h->R, C = h->C, RC = h->RC;
-    if (!h->d_clear) {
-      const size_t bytes = sizeof(unsigned long long) * PF_CL_CTL_WORDS + sizeof(int2) * (size_t)RC + sizeof(int) * ((size_t)RC + (size_t)C);
-      if (hipMalloc(&h->d_clear, bytes) != hipSuccess) {
-        (void)hipGetLastError();
-        h->d_clear = nullptr;
-        return failmsg(h, "pf_clearance_field: no device memory for the scratch words (" + std::to_string(bytes >> 20) + " MiB)");
-      }
-    }
-    unsigned long long* const ctl = (unsigned long long*)h->d_clear;  // (in front: 8-byte aligned whatever RC is)
-    int2* const stack = (int2*)(ctl + PF_CL_CTL_WORDS);
-    int* const dcol = (int*)(stack + RC);
-    int* const colflag = dcol + RC;
-    const uint8_t* occ = h->d_occ;
-    const unsigned rows_per = PF_CL_THREADS / 64;
-    CK(hipEventRecord(h->ev0, h->stream));
-    CK(hipMemsetAsync(ctl, 0, sizeof(unsigned long long) * PF_CL_CTL_WORDS, h->stream));
-    CK(hipMemsetAsync(colflag, 0, sizeof(int) * (size_t)C, h->stream));
-    hipLaunchKernelGGL(k_clear_rows_nearest_in_row<>, dim3(((unsigned)R + rows_per - 1) / rows_per), dim3(PF_CL_THREADS), 0, h->stream, occ, R, C, dcol);
-    hipLaunchKernelGGL(k_clear_cols_outward_scan<>, dim3(((unsigned)C + 63u) / 64u, ((unsigned)R + rows_per - 1) / rows_per), dim3(PF_CL_THREADS), 0, h->stream,
-                       (const int*)dcol, R, C, border ? 1 : 0, clear_scan_rows(C), (int*)d_d2, (int*)d_near, colflag);
-    hipLaunchKernelGGL(k_clear_cols_lower_envelope<>, dim3(((unsigned)C + 63u) / 64u), dim3(64), 0, h->stream, (const int*)dcol, R, C, border ? 1 : 0,
-                       (const int*)colflag, stack, (int*)d_d2, (int*)d_near);
-    if (d_info) {
-      const unsigned nb = (unsigned)((RC + PF_CL_THREADS - 1) / PF_CL_THREADS);
-      hipLaunchKernelGGL(k_clear_info_reduce<>, dim3(nb < 2048u ? nb : 2048u), dim3(PF_CL_THREADS), 0, h->stream, occ, (const int*)d_d2, RC, ctl);
-      hipLaunchKernelGGL(k_clear_write_info_block<>, dim3(1), dim3(64), 0, h->stream, (const unsigned long long*)ctl, RC, (long long*)d_info);
-    }
-    CK(hipGetLastError());
-    CK(hipEventRecord(h->ev1, h->stream));
-    CK(hipStreamSynchronize(h->stream));
-    CK(hipEventElapsedTime(&h->last_ms, h->ev0, h->ev1));
-    return 0;
-  };
-  return run() ? -1 : 0;
-}
-
-int pf_clearance_paths(pf_handle* h, const int32_t* d_d2, int32_t n, int32_t path_cap, const int32_t* d_cells, const int32_t* d_len, int32_t margin_d2,
-                       int32_t* d_out, int32_t* d_profile, int32_t* d_status) {
-  if (!h) return -2;
-  if (n < 0 || path_cap < 1 || margin_d2 < 0 || !d_d2 || !d_cells || !d_len || !d_out || !d_status) {
-    failmsg(h, "pf_clearance_paths: bad arguments (n >= 0, path_cap >= 1, margin_d2 >= 0; the field, the rows, the lengths, the results and the "
-               "statuses must not be null)");
-    return -1;
-  }
-  if (n == 0) return 0;
-  auto run = [&]() -> int {
-    CK(hipSetDevice(h->device));
-    CK(hipEventRecord(h->ev0, h->stream));
-    hipLaunchKernelGGL(k_clear_paths_one_wave_per_row<>, dim3((unsigned)n), dim3(64), 0, h->stream, (const int*)d_d2, h->RC, (int)n, (int)path_cap, (const int*)d_cells,
-                       (const int*)d_len, (int)margin_d2, (int*)d_out, (int*)d_profile, (int*)d_status);
-    CK(hipGetLastError());
-    CK(hipEventRecord(h->ev1, h->stream));
-    CK(hipStreamSynchronize(h->stream));
-    CK(hipEventElapsedTime(&h->last_ms, h->ev0, h->ev1));
-    return 0;
-  };
-  return run() ? -1 : 0;
-}
-
-int pf_clearance_segments(pf_handle* h, const int32_t* d_d2, int32_t touched, int32_t n, const int32_t* d_from, const int32_t* d_to, int32_t* d_min,
-                          int32_t* d_at) {
-  if (!h) return -2;
-  if (n < 0 || !d_d2 || !d_from || !d_to || !d_min) {
-    failmsg(h, "pf_clearance_segments: bad arguments (n >= 0; the field, the endpoints and the minima must not be null)");
-    return -1;
-  }
-  if (n == 0) return 0;
-  auto run = [&]() -> int {
-    CK(hipSetDevice(h->device));
-    CK(hipEventRecord(h->ev0, h->stream));
-    hipLaunchKernelGGL(k_clear_segments_lanes_on_major<>, dim3((unsigned)n), dim3(64), 0, h->stream, (const int*)d_d2, h->RC, h->C, touched ? 1 : 0, (int)n,
-                       (const int*)d_from, (const int*)d_to, (int*)d_min, (int*)d_at);
-    CK(hipGetLastError());
-    CK(hipEventRecord(h->ev1, h->stream));
-    CK(hipStreamSynchronize(h->stream));
-    CK(hipEventElapsedTime(&h->last_ms, h->ev0, h->ev1));
-    return 0;
-  };
-  return run() ? -1 : 0;
-}
-
-}  // extern "C"
-
-// ---------------------------------------------------------------------------
-// Widest-path fields over a clearance field (pf_widest.h).  Reads the caller's d2 only, never the handle's
-// occupancy or masks; the handle keeps the scratch block (grown when a call needs more) and the last call's work counters.
-// ---------------------------------------------------------------------------
-#include "pf_widest.h"
-
-extern "C" {
-
-int pf_clearance_widest(pf_handle* h, int32_t allow_diag, int32_t restrict_corner, const int32_t* d_d2, int32_t B, const int32_t* set_off, const int32_t* src,
-                        int32_t* d_out, int64_t* d_info) {
-  if (!h) return -2;
-  const std::string me("pf_clearance_widest");
-  auto run = [&]() -> int {
-    std::vector<int> sets;
-    if (nearest_sets_check(h, me, B, set_off, src, sets)) return -2;
-    if (!d_d2 || !d_out) return failmsg(h, me + ": bad arguments (the field and the rows must not be null)");
-    CK(hipSetDevice(h->device));
-    const int R = h->R, C = h->C, RC = h->RC;
-    const int tiles_x = (C + PF_WD_TW - 1) / PF_WD_TW, tiles_y = (R + PF_WD_TH - 1) / PF_WD_TH, ntiles = tiles_x * tiles_y;
-    if ((long long)B * ntiles >= 0x7FFFFFFFll) return failmsg(h, me + ": bad arguments (B times the number of tiles must stay below 2^31 - 1)");
-    const size_t T = (size_t)B * (size_t)ntiles, nsets = sets.size() - 1;   // (sets[0] is the nearest fields' error word: not uploaded)
-    // the block: {words raised, spare} | keys [B] | cells [B] | sources [B] | queue lengths [2] + 2 spare | off [B + 1], ids | queues [2][T] | flags [2][T]
-    const size_t n64 = 2 + 3 * (size_t)B;
-    const size_t bytes = sizeof(unsigned long long) * n64 + sizeof(int) * (4 + nsets + 4 * T);
-    if (bytes > h->widest_bytes) {
-      if (h->d_widest) { CK(hipStreamSynchronize(h->stream)); (void)hipFree(h->d_widest); }
-      h->d_widest = nullptr; h->widest_bytes = 0;
-      if (hipMalloc(&h->d_widest, bytes) != hipSuccess) {
-        (void)hipGetLastError();
-        h->d_widest = nullptr;
-        return failmsg(h, me + ": no device memory for the scratch words (" + std::to_string(bytes >> 20) + " MiB)");
-      }
-      h->widest_bytes = bytes;
-    }
-    unsigned long long* const raised = (unsigned long long*)h->d_widest;
-    unsigned long long* const keys = raised + 2;
-    unsigned long long* const cells = keys + B;
-    unsigned long long* const nsrc = cells + B;
-    int* const count = (int*)(nsrc + B);
-    int* const d_off = count + 4;
-    int* const d_src = d_off + B + 1;
-    int* const queue = d_off + nsets;
-    int* const flag = queue + 2 * T;
-    h->widest_work[0] = h->widest_work[1] = h->widest_work[2] = h->widest_work[3] = 0;
-    CK(hipEventRecord(h->ev0, h->stream));
-    CK(hipMemsetAsync(raised, 0, sizeof(unsigned long long) * 2, h->stream));
-    CK(hipMemsetAsync(keys, 0xFF, sizeof(unsigned long long) * (size_t)B, h->stream));
-    CK(hipMemsetAsync(cells, 0, sizeof(unsigned long long) * 2 * (size_t)B + sizeof(int) * 4, h->stream));   // cells, sources, queue lengths
-    CK(hipMemsetAsync(flag, 0, sizeof(int) * 2 * T, h->stream));
-    CK(hipMemsetAsync(d_out, 0, sizeof(int) * (size_t)B * (size_t)RC, h->stream));
-    CK(hipMemcpyAsync(d_off, sets.data() + 1, sizeof(int) * nsets, hipMemcpyHostToDevice, h->stream));
-    CK(hipStreamSynchronize(h->stream));                            // (sets is pageable and leaves scope)
-    int most_src = 1;
-    for (int b = 0; b < B; ++b) most_src = std::max(most_src, set_off[b + 1] - set_off[b]);
-    const unsigned gy = (unsigned)(B < 65535 ? B : 65535);
-    hipLaunchKernelGGL(k_widest_seed_sets<>, dim3((unsigned)std::min((most_src + PF_WD_THREADS - 1) / PF_WD_THREADS, 64), gy), dim3(PF_WD_THREADS), 0, h->stream,
-                       (const int*)d_d2, RC, C, tiles_x, ntiles, (int)B, (const int*)d_off, (const int*)d_src, (int*)d_out, flag, queue, count, nsrc);
-    CK(hipGetLastError());
-    int n = 0;
-    CK(hipMemcpyAsync(&n, count, sizeof(int), hipMemcpyDeviceToHost, h->stream));
-    CK(hipStreamSynchronize(h->stream));
-    long long launches = 0, visits = 0;
-    for (long long round = 0; n > 0; ++round) {
-      if (round > (long long)RC) return failmsg(h, me + ": internal: round bound");
-      if (n < 0 || (size_t)n > T) return failmsg(h, me + ": internal: queue bound");
-      const int p = (int)(round & 1);
-      hipLaunchKernelGGL(k_widest_relax_tiles_in_lds<>, dim3((unsigned)n), dim3(PF_WD_THREADS), 0, h->stream, (const int*)d_d2, R, C, allow_diag ? 1 : 0,
-                         restrict_corner ? 1 : 0, tiles_x, tiles_y, (int*)d_out, (const int*)(queue + (size_t)p * T), n, round == 0 ? 1 : 0, flag + (size_t)p * T, count + p,
-                         flag + (size_t)(p ^ 1) * T, queue + (size_t)(p ^ 1) * T, count + (p ^ 1), raised);
-      CK(hipGetLastError());
-      launches += 1; visits += n;
-      CK(hipMemcpyAsync(&n, count + (p ^ 1), sizeof(int), hipMemcpyDeviceToHost, h->stream));
-      CK(hipStreamSynchronize(h->stream));
-    }
-    if (d_info) {
-      const unsigned nb = (unsigned)((RC + PF_WD_THREADS - 1) / PF_WD_THREADS);
-      hipLaunchKernelGGL(k_widest_info_sum<>, dim3(nb < 1024u ? nb : 1024u, gy), dim3(PF_WD_THREADS), 0, h->stream, (const int*)d_out, RC, (int)B, keys, cells);
-      hipLaunchKernelGGL(k_widest_write_info<>, dim3(((unsigned)B + PF_WD_THREADS - 1) / PF_WD_THREADS), dim3(PF_WD_THREADS), 0, h->stream, (int)B,
-                         (const unsigned long long*)keys, (const unsigned long long*)cells, (const unsigned long long*)nsrc, (long long*)d_info);
-      CK(hipGetLastError());
-    }
-    CK(hipEventRecord(h->ev1, h->stream));
-    unsigned long long words = 0;
-    CK(hipMemcpyAsync(&words, raised, sizeof(words), hipMemcpyDeviceToHost, h->stream));
-    CK(hipStreamSynchronize(h->stream));
-    CK(hipEventElapsedTime(&h->last_ms, h->ev0, h->ev1));
-    h->d2h_small += launches + 2;
-    h->widest_work[0] = launches; h->widest_work[1] = visits; h->widest_work[2] = (long long)words;
-    return 0;
-  };
-  return run() ? -1 : 0;
-}
-
-int pf_clearance_widest_work(pf_handle* h, int64_t* out4) {
-  if (!h) return -2;
-  if (!out4) { failmsg(h, "pf_clearance_widest_work: bad arguments (the four words must not be null)"); return -1; }
-  for (int i = 0; i < 4; ++i) out4[i] = h->widest_work[i];
   return 0;
 }
 

@@ -75,10 +75,6 @@ PF_DEV void slot_wipe(Slot& s, int RC, int lane) {
   s.avoid_ep = 1; s.tag = 1;
 }
 
-// helper-order move deltas from the move index without a table lookup
-PF_DEV int move_dr(int d) { return (int)((0x0A25u >> (2 * d)) & 3u) - 1; }   // {0,0,1,-1,1,1,-1,-1} + 1 packed
-PF_DEV int move_dc(int d) { return (int)((0x2252u >> (2 * d)) & 3u) - 1; }   // {1,-1,0,0,1,-1,1,-1} + 1 packed
-
 }  // namespace pf
 #include "pf_astar_sw.h"
 #include "pf_settle.h"

@@ -68,7 +68,6 @@ __device__ __forceinline__ int clear_with_border(int d2, int r, int c, int R, in
   return m * m < d2 ? m * m : d2;
 }
 
-template <int PF_LATE = 0>
 __global__ __launch_bounds__(PF_CL_THREADS) void k_clear_rows_nearest_in_row(const uint8_t* __restrict__ occ, int R, int C, int* dcol) {
   const int lane = (int)(threadIdx.x & 63u);
   const int r = (int)(blockIdx.x * (PF_CL_THREADS / 64) + (threadIdx.x >> 6));
@@ -100,7 +99,6 @@ __global__ __launch_bounds__(PF_CL_THREADS) void k_clear_rows_nearest_in_row(con
   }
 }
 
-template <int PF_LATE = 0>
 __global__ __launch_bounds__(PF_CL_THREADS) void k_clear_cols_outward_scan(const int* __restrict__ dcol, int R, int C, int border, int scan_rows, int* __restrict__ d2,
                                                                           int* __restrict__ near, int* __restrict__ colflag) {
   const int c = (int)(blockIdx.x * 64 + (threadIdx.x & 63u));
@@ -129,7 +127,6 @@ __global__ __launch_bounds__(PF_CL_THREADS) void k_clear_cols_outward_scan(const
   if (near) near[v] = brow < 0 ? -1 : brow * C + c + bd;
 }
 
-template <int PF_LATE = 0>
 __global__ __launch_bounds__(64) void k_clear_cols_lower_envelope(const int* __restrict__ dcol, int R, int C, int border, const int* __restrict__ colflag,
                                                                  int2* __restrict__ stack, int* __restrict__ d2, int* __restrict__ near) {
   const int c = (int)(blockIdx.x * 64 + threadIdx.x);
@@ -190,7 +187,6 @@ __global__ __launch_bounds__(64) void k_clear_cols_lower_envelope(const int* __r
   }
 }
 
-template <int PF_LATE = 0>
 __global__ __launch_bounds__(PF_CL_THREADS) void k_clear_info_reduce(const uint8_t* __restrict__ occ, const int* __restrict__ d2, int RC, unsigned long long* __restrict__ ctl) {
   unsigned long long best = 0ull;                                    // (a free cell's d2 is >= 1: its key is never 0)
   int obst = 0;
@@ -211,7 +207,6 @@ __global__ __launch_bounds__(PF_CL_THREADS) void k_clear_info_reduce(const uint8
   }
 }
 
-template <int PF_LATE = 0>
 __global__ void k_clear_write_info_block(const unsigned long long* __restrict__ ctl, int RC, long long* __restrict__ info) {
   if (blockIdx.x || threadIdx.x) return;
   const long long obst = (long long)ctl[1];
@@ -221,7 +216,6 @@ __global__ void k_clear_write_info_block(const unsigned long long* __restrict__ 
   info[3] = obst < RC ? (long long)(0xFFFFFFFFu - (unsigned)(ctl[0] & 0xFFFFFFFFull)) : -1;
 }
 
-template <int PF_LATE = 0>
 __global__ __launch_bounds__(64) void k_clear_paths_one_wave_per_row(const int* __restrict__ d2, int RC, int n, int path_cap, const int* __restrict__ cells,
                                                                     const int* __restrict__ len, int margin_d2, int* __restrict__ out, int* __restrict__ profile,
                                                                     int* __restrict__ status) {
@@ -265,7 +259,6 @@ __global__ __launch_bounds__(64) void k_clear_paths_one_wave_per_row(const int* 
   }
 }
 
-template <int PF_LATE = 0>
 __global__ __launch_bounds__(64) void k_clear_segments_lanes_on_major(const int* __restrict__ d2, int RC, int C, int touched, int n, const int* __restrict__ from,
                                                                      const int* __restrict__ to, int* __restrict__ dmin, int* __restrict__ dat) {
   const int p = (int)blockIdx.x, lane = (int)threadIdx.x;

@@ -79,7 +79,6 @@ __device__ __forceinline__ void cc_link(int* p, int a, int b) {
   }
 }
 
-template <int PF_LATE = 0>
 __global__ __launch_bounds__(PF_CC_THREADS) void k_cc_init_parent_lowest_back_neighbour(const uint8_t* __restrict__ occ, const uint8_t* __restrict__ mm, int RC, int C,
                                                                                        int* __restrict__ parent) {
   const int v = (int)(blockIdx.x * PF_CC_THREADS + threadIdx.x);
@@ -92,7 +91,6 @@ __global__ __launch_bounds__(PF_CC_THREADS) void k_cc_init_parent_lowest_back_ne
   parent[v] = p;
 }
 
-template <int PF_LATE = 0>
 __global__ __launch_bounds__(PF_CC_THREADS) void k_cc_link_forward_edges(const uint8_t* __restrict__ occ, const uint8_t* __restrict__ mm, int RC, int C, int* __restrict__ parent) {
   const int v = (int)(blockIdx.x * PF_CC_THREADS + threadIdx.x);
   if (v >= RC || occ[v] == 1) return;
@@ -107,7 +105,6 @@ __global__ __launch_bounds__(PF_CC_THREADS) void k_cc_link_forward_edges(const u
 // local ids lr * PF_CC_TW + lc, which order like the cell ids, with workgroup-scope atomics (LDS atomics never leave the workgroup) --
 // and writes parent[v] = the cell id of v's root within the tile; then one thread per cell links the forward edges that leave its
 // tile in HBM exactly as the global form does.  Cells of the tile beyond the grid count as obstacles.
-template <int PF_LATE = 0>
 __global__ __launch_bounds__(PF_CC_THREADS) void k_cc_label_tiles_in_lds(const uint8_t* __restrict__ occ, const uint8_t* __restrict__ mm, int R, int C, int* __restrict__ parent) {
   constexpr int N = PF_CC_TW * PF_CC_TH, PER = N / PF_CC_THREADS;
   __shared__ int lp[N];
@@ -152,7 +149,6 @@ __global__ __launch_bounds__(PF_CC_THREADS) void k_cc_label_tiles_in_lds(const u
   }
 }
 
-template <int PF_LATE = 0>
 __global__ __launch_bounds__(PF_CC_THREADS) void k_cc_link_tile_borders(const uint8_t* __restrict__ occ, const uint8_t* __restrict__ mm, int RC, int C, int* __restrict__ parent) {
   const int v = (int)(blockIdx.x * PF_CC_THREADS + threadIdx.x);
   if (v >= RC || occ[v] == 1) return;
@@ -182,7 +178,6 @@ __device__ __forceinline__ int cc_block_prefix(bool flag, int* wsum, int* total)
   return before + below;
 }
 
-template <int PF_LATE = 0>
 __global__ __launch_bounds__(PF_CC_THREADS) void k_cc_flatten_and_count_roots(int RC, const int* __restrict__ parent, int* __restrict__ root, int* __restrict__ block_roots) {
   __shared__ int wsum[PF_CC_THREADS / 64];
   const int v = (int)(blockIdx.x * PF_CC_THREADS + threadIdx.x);
@@ -198,7 +193,6 @@ __global__ __launch_bounds__(PF_CC_THREADS) void k_cc_flatten_and_count_roots(in
 }
 
 // in place: counts -> exclusive offsets; ctl[0] = the total
-template <int PF_LATE = 0>
 __global__ __launch_bounds__(PF_CC_SCAN_THREADS) void k_cc_scan_block_counts(int nblocks, int* __restrict__ block_roots, unsigned long long* __restrict__ ctl) {
   __shared__ int wsum[PF_CC_SCAN_THREADS / 64];
   __shared__ int carry_s;
@@ -223,7 +217,6 @@ __global__ __launch_bounds__(PF_CC_SCAN_THREADS) void k_cc_scan_block_counts(int
   if (tid == 0) ctl[0] = (unsigned long long)carry_s;
 }
 
-template <int PF_LATE = 0>
 __global__ __launch_bounds__(PF_CC_THREADS) void k_cc_rank_roots(int RC, const int* __restrict__ parent, const int* __restrict__ block_off, int* __restrict__ rank,
                                                                 int* __restrict__ size) {
   __shared__ int wsum[PF_CC_THREADS / 64];
@@ -234,7 +227,6 @@ __global__ __launch_bounds__(PF_CC_THREADS) void k_cc_rank_roots(int RC, const i
   if (is_root) { rank[v] = k; size[k] = 0; }
 }
 
-template <int PF_LATE = 0>
 __global__ __launch_bounds__(PF_CC_THREADS) void k_cc_write_labels(int RC, const int* __restrict__ rank, int* __restrict__ labels) {
   const int v = (int)(blockIdx.x * PF_CC_THREADS + threadIdx.x);
   if (v >= RC) return;
@@ -246,7 +238,7 @@ __global__ __launch_bounds__(PF_CC_THREADS) void k_cc_write_labels(int RC, const
 // the cell id, over unsigned words preset to 0xFFFFFFFF; nfree (or null): += the cells counted.  A wavefront walks PF_CC_HIST_PER
 // consecutive 64-cell groups and makes one atomic per distinct label of a group, from that label's lowest lane; the label of the
 // group's first counted lane is folded into a running (label, cells) pair instead, flushed when that label changes and at the end.
-template <typename T, int PF_LATE = 0>
+template <typename T>
 __global__ __launch_bounds__(PF_CC_THREADS) void k_cc_histogram(int RC, const int* __restrict__ labels, const unsigned long long* __restrict__ d_count, int count,
                                                                T* __restrict__ sizes, unsigned* __restrict__ first, unsigned long long* __restrict__ nfree) {
   const int lane = (int)(threadIdx.x & 63u);
@@ -287,7 +279,6 @@ __global__ __launch_bounds__(PF_CC_THREADS) void k_cc_histogram(int RC, const in
   }
 }
 
-template <int PF_LATE = 0>
 __global__ __launch_bounds__(PF_CC_THREADS) void k_cc_largest(const int* __restrict__ size, unsigned long long* __restrict__ ctl) {
   const int count = (int)ctl[0];
   unsigned long long best = 0ull;
@@ -300,13 +291,6 @@ __global__ __launch_bounds__(PF_CC_THREADS) void k_cc_largest(const int* __restr
   if ((threadIdx.x & 63u) == 0 && best) atomicMax(ctl + 2, best);
 }
 
-// A constraint the names carry: the total length of the kernel names in this library decides where the code
-// object's .rodata starts, in steps of 64 bytes per 16 characters, and the existing kernels reach their constants through
-// PC-relative literals.  k_cc_write_info_block and k_cc_fill_words_with_a_value are named so that .rodata keeps the previous
-// commit's residue modulo 256 and every older function disassembles byte for byte as before.  Renaming a kernel here, or adding
-// one, changes those literals (and nothing else) in about twenty older functions: harmless for the results, but the
-// function-by-function comparison of a later change then has to be read modulo the literals, or the names balanced again.
-template <int PF_LATE = 0>
 __global__ void k_cc_write_info_block(const unsigned long long* __restrict__ ctl, long long* __restrict__ info) {
   if (blockIdx.x || threadIdx.x) return;
   const long long count = (long long)ctl[0];
@@ -316,14 +300,13 @@ __global__ void k_cc_write_info_block(const unsigned long long* __restrict__ ctl
   info[3] = count ? (long long)(0xFFFFFFFFu - (unsigned)(ctl[2] & 0xFFFFFFFFull)) : -1;
 }
 
-template <typename T, int PF_LATE = 0>
+template <typename T>
 __global__ __launch_bounds__(PF_CC_THREADS) void k_cc_fill_words_with_a_value(T* __restrict__ dst, int n, T value) {
   const int i = (int)(blockIdx.x * PF_CC_THREADS + threadIdx.x);
   if (i < n) dst[i] = value;
 }
 
 // same[i] = 1 iff both ids lie in [0, RC), both labels are >= 0 and equal
-template <int PF_LATE = 0>
 __global__ __launch_bounds__(PF_CC_THREADS) void k_cc_same_pairs(int RC, const int* __restrict__ labels, int n, const int* __restrict__ a, const int* __restrict__ b,
                                                                 int* __restrict__ same) {
   const int i = (int)(blockIdx.x * PF_CC_THREADS + threadIdx.x);

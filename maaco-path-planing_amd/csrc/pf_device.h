@@ -34,6 +34,9 @@ struct __attribute__((aligned(16))) Rec {
 // helper.py:30-36 / MPA.py:71-77 move order
 __device__ __constant__ const int8_t HM_DR[8] = {0, 0, 1, -1, 1, 1, -1, -1};
 __device__ __constant__ const int8_t HM_DC[8] = {1, -1, 0, 0, 1, -1, 1, -1};
+// ... the same deltas from the move index without a table lookup
+PF_DEV int move_dr(int d) { return (int)((0x0A25u >> (2 * d)) & 3u) - 1; }   // {0,0,1,-1,1,1,-1,-1} + 1 packed
+PF_DEV int move_dc(int d) { return (int)((0x2252u >> (2 * d)) & 3u) - 1; }   // {1,-1,0,0,1,-1,1,-1} + 1 packed
 // MAACO.py:98 move order, and the helper-order bit each one corresponds to
 __device__ __constant__ const int8_t AM_DR[8] = {-1, -1, -1, 0, 0, 1, 1, 1};
 __device__ __constant__ const int8_t AM_DC[8] = {-1, 0, 1, -1, 1, -1, 0, 1};

@@ -1,4 +1,4 @@
-// pf_dist_field.h -- exact one-to-all path lengths from K source cells (pf_dist_field_batch): dijkstra.py's
+// pf_dist_field.h -- exact one-to-all path lengths from K source cells or sets (pf_dist_field_batch / _merged): dijkstra.py's
 // relaxation with no target, WITHOUT the pop order.
 //
 // Why this is exact.  The table dijkstra_host builds is the least fixed point of
@@ -9,7 +9,7 @@
 // buckets below i have been relaxed every cell whose label lies in bucket i = (int)D is final, and level i relaxes the cells
 // of bucket i in any order, in parallel, into buckets i + 1 and i + 2 (D[u] < i + 1 and w < 1.4143: never i + 3).
 //
-// Mapping.  One workgroup per source; gridDim.x workgroups loop over the sources b, b + gridDim.x, ...  Labels are
+// Mapping.  One workgroup per source set; gridDim.x workgroups loop over the sets b, b + gridDim.x, ...  Labels are
 // non-negative doubles, so their bit patterns order as unsigned 64-bit integers: ONE atomicMin on the label word of the output
 // row compares and updates, +inf is the initial value.  The thread whose atomic returns an old value of ANOTHER bucket than
 // its new one appends the cell to the new bucket's list (exactly one thread sees each transition).  A label only falls, so a
@@ -69,29 +69,39 @@ PF_DEV void df_offer(unsigned long long* D, int* L, int* cnt, int* err, int RC, 
   }
 }
 
-// info (or null): int64 [K][4] = {levels that held a live cell, cells with a finite label, relaxations offered, list appends}
-template <int PF_LATE = 0>
-__global__ __launch_bounds__(PF_DF_THREADS) void k_dist_field_level_synchronous(const uint8_t* __restrict__ occ, const uint8_t* __restrict__ mm, int RC, int C, int K,
-                                                                                const int* __restrict__ src, double* out, int* lists, long long* info, int* err) {
+// The one level-synchronous kernel: row b is the field of source set b, sets (device) = {off[B + 1], ids[off[B]]}; a single source
+// is a set of one (pf_dist_field_batch uploads off = 0..K).  Seeding: after the +inf fill, the release fence and the barrier the
+// threads stride over the set's sources, skip those on an obstacle and make one agent-scope atomic min of 0 on the label; the
+// thread that saw +inf appends the cell to list 0, so a source listed twice enters once, and a set with no free source leaves a
+// +inf row.  Why a seed of several cells is as exact as a seed of one: pf_nearest_field.h.
+// info (or null): int64 [B][4] = {levels that held a live cell, cells with a finite label, relaxations offered, list appends}, the
+// seeds counting as cells reached and as appends
+__global__ __launch_bounds__(PF_DF_THREADS) void k_dist_field_merged_source_sets(const uint8_t* __restrict__ occ, const uint8_t* __restrict__ mm, int RC, int C, int B,
+                                                                                      const int* __restrict__ off, const int* __restrict__ src, double* out, int* lists,
+                                                                                      long long* info, int* err) {
   __shared__ int cnt[4], live[4];
   __shared__ unsigned long long acc[3];
   const int tid = (int)threadIdx.x, sub = tid % PF_DF_LANES, grp = tid / PF_DF_LANES;
   int* const L = lists + (size_t)blockIdx.x * 3 * (size_t)RC;
   const int bound = 2 * RC + 4;                                      // (RC <= 2^24)
-  for (int k = (int)blockIdx.x; k < K; k += (int)gridDim.x) {
-    unsigned long long* const D = (unsigned long long*)(out + (size_t)k * (size_t)RC);
+  for (int b = (int)blockIdx.x; b < B; b += (int)gridDim.x) {
+    unsigned long long* const D = (unsigned long long*)(out + (size_t)b * (size_t)RC);
     if (tid == 0) { for (int i = 0; i < 4; ++i) { cnt[i] = 0; live[i] = 0; } acc[0] = acc[1] = acc[2] = 0ull; }
     for (int i = tid; i < RC; i += PF_DF_THREADS) D[i] = PF_DF_INF_BITS;
-    const int s = src[k];
-    const bool open = occ[s] != 1;                                   // a source ON an obstacle: the row stays +inf
     __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");               // the fill is in L2 before the first atomic lands there
     __syncthreads();
-    if (tid == 0 && open) {
-      __hip_atomic_store(&D[s], 0ull, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-      L[0] = s; cnt[0] = 1;
+    unsigned n_set = 0, n_off = 0, n_app = 0;
+    const int hi = off[b + 1];
+    for (int j = off[b] + tid; j < hi; j += PF_DF_THREADS) {         // the seeds: bucket 0
+      const int s = src[j];
+      if (occ[s] == 1) continue;                                     // a source ON an obstacle is no source
+      if (__hip_atomic_fetch_min(&D[s], 0ull, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != PF_DF_INF_BITS) continue;   // listed before
+      const int at = __hip_atomic_fetch_add(&cnt[0], 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+      if (at < RC) L[at] = s;
+      else *err = PF_DF_ERR_LIST;                                    // (cannot happen: a cell enters once)
+      n_set += 1; n_app += 1;
     }
     int levels = 0;                                                  // (thread 0's)
-    unsigned n_set = 0, n_off = 0, n_app = 0;
     for (int lv = 0;; ++lv) {
       __syncthreads();                                               // the appends and the label stores of level lv - 1 are done
       const int cur = lv & 3;
@@ -122,9 +132,9 @@ __global__ __launch_bounds__(PF_DF_THREADS) void k_dist_field_level_synchronous(
       if (n_app) __hip_atomic_fetch_add(&acc[2], (unsigned long long)n_app, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
     }
     __syncthreads();
-    if (tid == 0 && info) {                                          // the seed is one settled cell and one append
-      long long* o = info + 4 * (size_t)k;
-      o[0] = levels; o[1] = (long long)acc[0] + (open ? 1 : 0); o[2] = (long long)acc[1]; o[3] = (long long)acc[2] + (open ? 1 : 0);
+    if (tid == 0 && info) {
+      long long* o = info + 4 * (size_t)b;
+      o[0] = levels; o[1] = (long long)acc[0]; o[2] = (long long)acc[1]; o[3] = (long long)acc[2];
     }
   }
 }

@@ -30,7 +30,6 @@ namespace pf {
 #define PF_FP_SOURCE 8                          /* parent code of the source cell */
 #define PF_FP_NONE 255                          /* parent code of an obstacle / a cell out of reach */
 
-template <int PF_LATE = 0>
 __global__ __launch_bounds__(PF_FP_THREADS) void k_dist_field_parent_map_thread_per_cell(const uint8_t* __restrict__ mm, int RC, int C, int K,
                                                                                    const double* __restrict__ fields, uint8_t* __restrict__ parents, int* err) {
   const int v = (int)blockIdx.x * PF_FP_THREADS + (int)threadIdx.x;
@@ -62,7 +61,6 @@ __global__ __launch_bounds__(PF_FP_THREADS) void k_dist_field_parent_map_thread_
 }
 
 // status / length / chosen field per query; a row of d_cells is written only when the status is PF_ST_OK
-template <int PF_LATE = 0>
 __global__ __launch_bounds__(PF_FP_TRACE_THREADS) void k_dist_field_trace_query_lanes(const uint8_t* __restrict__ parents, const double* __restrict__ fields, int RC, int C,
                                                                                 int K, int n, const int* __restrict__ field_idx, const int* __restrict__ target,
                                                                                 int reverse, int path_cap, int* __restrict__ cells, int* __restrict__ len,

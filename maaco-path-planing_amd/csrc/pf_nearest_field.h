@@ -6,11 +6,9 @@
 // which any label-correcting schedule reaches bit for bit (fl(. + w) is monotone: pf_settle.h).  A chain of fl(. + w) that starts
 // at 0 in one source is a chain of that source's own field, so the fixed point is the elementwise minimum of the single-source
 // fields.  Nothing in pf_dist_field.h's bucket argument needs ONE cell of label 0: every weight is >= 1, so a label of bucket
-// i is set from a bucket below i, and level i relaxes bucket i into i + 1 and i + 2.  k_dist_field_merged_source_sets
-// is that kernel with another seeding step: after the +inf fill, the release fence and the barrier the threads stride over the
-// set's sources, skip those on an obstacle and make one agent-scope atomic min of 0 on the label; the thread that saw +inf
-// appends the cell to list 0, so a source listed twice enters once.  One workgroup per set on the handle's list slots; a row and
-// a slot belong to one workgroup; labels are read with agent-scope relaxed atomic loads.
+// i is set from a bucket below i, and level i relaxes bucket i into i + 1 and i + 2.  So k_dist_field_merged_source_sets
+// (pf_dist_field.h) seeds bucket 0 with every free source of the set and is the only level kernel: one workgroup per set on the
+// handle's list slots; a row and a slot belong to one workgroup.
 //
 // Owners.  pf_dist_field_parents turns the merged rows into parent maps (every D == 0 cell gets code 8): a forest, one tree
 // per free source cell, and the tree a cell hangs in is the tree a dijkstra.py-shaped search seeded with the whole set leaves
@@ -40,75 +38,8 @@ namespace pf {
 #define PF_NF_ERR_CHAIN 8                       /* *err: a chain longer than the bound */
 #define PF_NF_ERR_ROOT 16                       /* *err: a root that is no source of its set */
 
-// sets (device): {off[B + 1], ids[off[B]]}; info (or null): int64 [B][4] as k_dist_field_level_synchronous's, the seeds
-// counting as cells reached and as appends
-template <int PF_LATE = 0>
-__global__ __launch_bounds__(PF_DF_THREADS) void k_dist_field_merged_source_sets(const uint8_t* __restrict__ occ, const uint8_t* __restrict__ mm, int RC, int C, int B,
-                                                                                      const int* __restrict__ off, const int* __restrict__ src, double* out, int* lists,
-                                                                                      long long* info, int* err) {
-  __shared__ int cnt[4], live[4];
-  __shared__ unsigned long long acc[3];
-  const int tid = (int)threadIdx.x, sub = tid % PF_DF_LANES, grp = tid / PF_DF_LANES;
-  int* const L = lists + (size_t)blockIdx.x * 3 * (size_t)RC;
-  const int bound = 2 * RC + 4;                                      // (RC <= 2^24)
-  for (int b = (int)blockIdx.x; b < B; b += (int)gridDim.x) {
-    unsigned long long* const D = (unsigned long long*)(out + (size_t)b * (size_t)RC);
-    if (tid == 0) { for (int i = 0; i < 4; ++i) { cnt[i] = 0; live[i] = 0; } acc[0] = acc[1] = acc[2] = 0ull; }
-    for (int i = tid; i < RC; i += PF_DF_THREADS) D[i] = PF_DF_INF_BITS;
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");               // the fill is in L2 before the first atomic lands there
-    __syncthreads();
-    unsigned n_set = 0, n_off = 0, n_app = 0;
-    const int hi = off[b + 1];
-    for (int j = off[b] + tid; j < hi; j += PF_DF_THREADS) {         // the seeds: bucket 0
-      const int s = src[j];
-      if (occ[s] == 1) continue;                                     // a source ON an obstacle is no source
-      if (__hip_atomic_fetch_min(&D[s], 0ull, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != PF_DF_INF_BITS) continue;   // listed before
-      const int at = __hip_atomic_fetch_add(&cnt[0], 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-      if (at < RC) L[at] = s;
-      else *err = PF_DF_ERR_LIST;                                    // (cannot happen: a cell enters once)
-      n_set += 1; n_app += 1;
-    }
-    int levels = 0;                                                  // (thread 0's)
-    for (int lv = 0;; ++lv) {
-      __syncthreads();                                               // the appends and the label stores of level lv - 1 are done
-      const int cur = lv & 3;
-      const int n = cnt[cur];
-      const int waiting = n + cnt[(lv + 1) & 3] + cnt[(lv + 2) & 3];
-      if (tid == 0) { levels += live[(lv + 3) & 3]; live[(lv + 3) & 3] = 0; cnt[(lv + 3) & 3] = 0; }   // bucket lv - 1 is history
-      if (waiting == 0) break;
-      if (lv > bound) { if (tid == 0) *err = PF_DF_ERR_LEVELS; break; }
-      const int* const Lc = L + (size_t)(lv % 3) * (size_t)RC;
-      for (int e = grp; e < n; e += PF_DF_THREADS / PF_DF_LANES) {
-        const int u = Lc[e];
-        const double du = __builtin_bit_cast(double, __hip_atomic_load(&D[u], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT));
-        if ((int)du != lv) continue;                                 // stale: improved into bucket lv - 1 and relaxed there
-        if (sub == 0) live[cur] = 1;
-        const unsigned m = mm[u];
-#if PF_DF_LANES == 8
-        if ((m >> sub) & 1u) df_offer(D, L, cnt, err, RC, C, u, du, sub, n_set, n_off, n_app);
-#else
-#pragma unroll
-        for (int mv = 0; mv < 8; ++mv)
-          if ((m >> mv) & 1u) df_offer(D, L, cnt, err, RC, C, u, du, mv, n_set, n_off, n_app);
-#endif
-      }
-    }
-    if (info) {
-      if (n_set) __hip_atomic_fetch_add(&acc[0], (unsigned long long)n_set, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-      if (n_off) __hip_atomic_fetch_add(&acc[1], (unsigned long long)n_off, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-      if (n_app) __hip_atomic_fetch_add(&acc[2], (unsigned long long)n_app, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-    }
-    __syncthreads();
-    if (tid == 0 && info) {
-      long long* o = info + 4 * (size_t)b;
-      o[0] = levels; o[1] = (long long)acc[0]; o[2] = (long long)acc[1]; o[3] = (long long)acc[2];
-    }
-  }
-}
-
 PF_DEV void nf_raise(int* err, int bit) { __hip_atomic_fetch_or(err, bit, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }   // (the kinds add up)
 
-template <int PF_LATE = 0>
 __global__ __launch_bounds__(PF_NF_THREADS) void k_nearest_owner_links(const uint8_t* __restrict__ parents, int RC, int C, int B, int* __restrict__ link,
                                                                                    int* err) {
   const int v = (int)blockIdx.x * PF_NF_THREADS + (int)threadIdx.x;
@@ -128,7 +59,6 @@ __global__ __launch_bounds__(PF_NF_THREADS) void k_nearest_owner_links(const uin
 }
 
 // sets: {off[B + 1], ids[off[B]]}, every id inside [0, RC) (checked on the host)
-template <int PF_LATE = 0>
 __global__ __launch_bounds__(PF_NF_THREADS) void k_nearest_owner_stamp_ranks(int RC, int B, const int* __restrict__ off, const int* __restrict__ src, int* link) {
   for (int b = (int)blockIdx.y; b < B; b += (int)gridDim.y) {
     const int lo = off[b], hi = off[b + 1];
@@ -141,7 +71,6 @@ __global__ __launch_bounds__(PF_NF_THREADS) void k_nearest_owner_stamp_ranks(int
   }
 }
 
-template <int PF_LATE = 0>
 __global__ __launch_bounds__(PF_NF_THREADS) void k_nearest_owner_doubling(int RC, int B, const int* __restrict__ cur, int* __restrict__ next) {
   const int v = (int)blockIdx.x * PF_NF_THREADS + (int)threadIdx.x;
   if (v >= RC) return;
@@ -154,7 +83,6 @@ __global__ __launch_bounds__(PF_NF_THREADS) void k_nearest_owner_doubling(int RC
 }
 
 // count (or null): int64 [off[B]], zeroed by the caller
-template <int PF_LATE = 0>
 __global__ __launch_bounds__(PF_NF_THREADS) void k_nearest_owner_write_and_count(int RC, int B, const int* __restrict__ off, const int* __restrict__ link,
                                                                                 int* __restrict__ owner, unsigned long long* count, int* err) {
   const int v = (int)blockIdx.x * PF_NF_THREADS + (int)threadIdx.x;

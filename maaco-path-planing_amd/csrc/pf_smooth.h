@@ -82,7 +82,6 @@ __device__ __forceinline__ int sm_first_block(const uint8_t* __restrict__ occ, i
   return -1;
 }
 
-template <int PF_LATE = 0>
 __global__ __launch_bounds__(64) void k_line_of_sight_pairs_lanes_on_major(const uint8_t* __restrict__ occ, int RC, int C, int strict, int n, const int* __restrict__ from,
                                                             const int* __restrict__ to, int* __restrict__ vis, int* __restrict__ fblock) {
   const int q = (int)blockIdx.x, lane = (int)threadIdx.x;
@@ -122,7 +121,6 @@ __device__ __forceinline__ void sm_emit(SmOut& o, int i, int cell, int C, int la
   o.cnt += 1;
 }
 
-template <int PF_LATE = 0>
 __global__ __launch_bounds__(64) void k_smooth_paths_one_wave_per_row(const uint8_t* __restrict__ occ, int RC, int C, int strict, int n, int path_cap,
                                                      const int* __restrict__ cells, const int* __restrict__ len, int way_cap, int* __restrict__ way_cells,
                                                      int* __restrict__ way_idx, int* __restrict__ way_len, double* __restrict__ stats,

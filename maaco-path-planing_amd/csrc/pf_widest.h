@@ -72,7 +72,6 @@ __device__ __forceinline__ void wd_enqueue(int q, int* __restrict__ flag, int* _
     queue[__hip_atomic_fetch_add(count, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)] = q;
 }
 
-template <int PF_LATE = 0>
 __global__ __launch_bounds__(PF_WD_THREADS) void k_widest_seed_sets(const int* __restrict__ d2, int RC, int C, int tiles_x, int ntiles, int B,
                                                                           const int* __restrict__ off, const int* __restrict__ src, int* __restrict__ w_rows,
                                                                           int* __restrict__ flag, int* __restrict__ queue, int* __restrict__ count,
@@ -110,7 +109,6 @@ __device__ __forceinline__ int wd_row_scan(int w, int d, int lane) {
   return rw > lw_ ? rw : lw_;
 }
 
-template <int PF_LATE = 0>
 __global__ __launch_bounds__(PF_WD_THREADS) void k_widest_relax_tiles_in_lds(const int* __restrict__ d2, int R, int C, int allow_diag, int restrict_corner, int tiles_x,
                                                                             int tiles_y, int* w_rows, const int* __restrict__ queue, int nqueue, int first, int* flag_now, int* count_now,
                                                                             int* flag_next, int* __restrict__ queue_next, int* count_next,
@@ -206,7 +204,6 @@ __global__ __launch_bounds__(PF_WD_THREADS) void k_widest_relax_tiles_in_lds(con
 }
 
 // keys[b] = the smallest (w << 32) | id over the cells of row b with w >= 1 (preset to all ones), cells[b] += their number
-template <int PF_LATE = 0>
 __global__ __launch_bounds__(PF_WD_THREADS) void k_widest_info_sum(const int* __restrict__ w_rows, int RC, int B, unsigned long long* __restrict__ keys,
                                                                      unsigned long long* __restrict__ cells) {
   for (int b = (int)blockIdx.y; b < B; b += (int)gridDim.y) {
@@ -233,7 +230,6 @@ __global__ __launch_bounds__(PF_WD_THREADS) void k_widest_info_sum(const int* __
   }
 }
 
-template <int PF_LATE = 0>
 __global__ __launch_bounds__(PF_WD_THREADS) void k_widest_write_info(int B, const unsigned long long* __restrict__ keys, const unsigned long long* __restrict__ cells,
                                                                           const unsigned long long* __restrict__ nsrc, long long* __restrict__ info) {
   const int b = (int)(blockIdx.x * PF_WD_THREADS + threadIdx.x);
@@ -244,9 +240,5 @@ __global__ __launch_bounds__(PF_WD_THREADS) void k_widest_write_info(int B, cons
   info[4 * (size_t)b + 2] = n ? (long long)(keys[b] >> 32) : -1;
   info[4 * (size_t)b + 3] = n ? (long long)(keys[b] & 0xFFFFFFFFull) : -1;
 }
-
-// pf_components.h's note on kernel names applies here too: these four kernels, their names and their argument lists move the start of
-// the code object's .rodata, so 22 older functions differ from the previous commit in their PC-relative literals and in nothing else
-// (DESIGN.md 4.17 lists them); the names were not balanced against that.
 
 }  // namespace pf

@@ -8,6 +8,7 @@ import math
 
 import numpy as np
 
+from ._field import Field
 from ._lib import PathfitError
 from .dist_field import DistanceField
 from .engine import Engine
@@ -33,10 +34,11 @@ def margin_to_sq(margin):
     return n
 
 
-class WidestField:
+class WidestField(Field):
     """What Clearance.widest returns: w[b, r, c] = the largest margin_sq with which a robot gets from a source of set b to (r, c)
     (0: not at all), kept in HBM (`w_device`, int32 [B, R * C]); `info` int64 [B, 4] = (sources that counted, cells reached, the
     smallest w >= 1, the smallest cell id that attains it; -1, -1 when nothing is reached)."""
+    _bufs = ("w_device",)
 
     def __init__(self, clearance, w_device, info, kernel_ms):
         self.clearance, self.w_device, self.info, self.kernel_ms = clearance, w_device, info, kernel_ms
@@ -73,36 +75,18 @@ class WidestField:
         Clearance.inflated)."""
         return self.w >= Clearance._margin_sq(margin, margin_sq, 1)
 
-    def close(self):
-        buf, self.w_device = getattr(self, "w_device", None), None
-        if buf is not None:
-            buf.free()
 
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-
-class Clearance:
+class Clearance(Field):
     """d2[r, c] = the squared Euclidean distance between cell centres to the nearest obstacle cell (grid value 1), 0 on an obstacle,
     PF_CLEAR_NONE on a map without one.  border=True: the cells just outside the grid count as obstacles too (the reference's
     safety term does not: helper.py:67-80).  nearest=True also keeps the nearest obstacle cell per cell (the smallest id on a tie);
     it never names the border."""
+    _bufs = ("d2_device", "near_device", "ibuf")
 
     def __init__(self, grid, border=False, nearest=False, engine=None):
-        who = type(self).__name__
-        self.grid = np.array(grid, dtype=int)
-        if self.grid.ndim != 2:
-            raise ValueError(f"{who}: grid must be 2-D")
-        self.rows, self.cols = self.grid.shape
+        self._set_grid(grid)
         self.border, self.want_nearest = bool(border), bool(nearest)
-        if engine is not None and (engine.R, engine.C) != self.grid.shape:
-            raise ValueError(f"{who}: the engine's grid has another shape")
-        # every argument is checked: the device
-        self._own_engine = engine is None
-        self.engine = engine if engine is not None else Engine(self.grid)
+        self._set_engine(engine, Engine)                             # every argument is checked: the device
         self.d2_device = self.near_device = self.ibuf = None
         self.d2_device = self.engine.buf(self.rows * self.cols, np.int32)
         if self.want_nearest:
@@ -203,17 +187,6 @@ class Clearance:
                 raise ValueError(f"Clearance: paths[{i}][{int(bad[0])}] = cell {int(a[bad[0]])} is outside the {self.rows}x{self.cols} grid")
             out.append(a.astype(np.int32))
         return out
-
-    def _cell(self, what, p, inside):
-        try:
-            r, c = (int(v) for v in p)
-        except (TypeError, ValueError):
-            raise ValueError(f"Clearance: {what} must be an (r, c) pair, got {p!r}") from None
-        if not (0 <= r < self.rows and 0 <= c < self.cols):
-            if not inside:
-                return -1
-            raise ValueError(f"Clearance: {what} = {(r, c)} is outside the {self.rows}x{self.cols} grid")
-        return r * self.cols + c
 
     def path_clearance(self, paths, margin=None, margin_sq=None):
         """paths: a sequence of CellPath, lists of (r, c) or int32 cell arrays -> (int32 [n, 4], status int32 [n]).  Per path: the
@@ -419,18 +392,3 @@ class Clearance:
         self._pair("target", target)
         paths, ws = self.widest_paths(source, [target], allow_diagonal_moves, restrict_diagonal_near_obstacle)
         return (paths[0], int(ws[0])) if ws[0] > 0 else ([], 0)
-
-    def close(self):
-        for name in ("d2_device", "near_device", "ibuf"):
-            buf = getattr(self, name, None)
-            setattr(self, name, None)
-            if buf is not None:
-                buf.free()
-        if getattr(self, "_own_engine", False) and getattr(self, "engine", None) is not None:
-            self.engine.close()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass

@@ -4,28 +4,22 @@ other at all, how large each region is, and whether a and b are connected, for t
 `engine.update_grid`."""
 import numpy as np
 
+from ._field import Field
 from ._lib import PathfitError
 from .engine import Engine
 
 
-class Components:
+class Components(Field):
     """labels[r, c] = -1 on an obstacle, else the rank of the cell's component when the components are ordered by their smallest cell
     id r * C + c (so label 0 holds the first free cell).  Two free cells are adjacent iff the move policy allows the move between
     them; the START and TARGET markers are free cells."""
+    _bufs = ("labels_device", "ibuf")
 
     def __init__(self, grid, allow_diagonal_moves=True, restrict_diagonal_near_obstacle=True, engine=None):
-        who = type(self).__name__
-        self.grid = np.array(grid, dtype=int)
-        if self.grid.ndim != 2:
-            raise ValueError(f"{who}: grid must be 2-D")
-        self.rows, self.cols = self.grid.shape
+        self._set_grid(grid)
         self.allow_diagonal_moves = bool(allow_diagonal_moves)
         self.restrict_diagonal_near_obstacle = bool(restrict_diagonal_near_obstacle)
-        if engine is not None and (engine.R, engine.C) != self.grid.shape:
-            raise ValueError(f"{who}: the engine's grid has another shape")
-        # every argument is checked: the device
-        self._own_engine = engine is None
-        self.engine = engine if engine is not None else Engine(self.grid)
+        self._set_engine(engine, Engine)                             # every argument is checked: the device
         self.labels_device = self.ibuf = None
         self.labels_device = self.engine.buf(self.rows * self.cols, np.int32)
         self.ibuf = self.engine.buf(4, np.int64)
@@ -82,42 +76,14 @@ class Components:
         self._sizes_and_first()
         return [(int(v) // self.cols, int(v) % self.cols) for v in self._first]
 
-    def _ids(self, what, cells, inside):
-        """(r, c) pairs -> int32 cell ids; a pair beside the grid is an error when `inside`, else the id -1."""
-        who = type(self).__name__
-        try:
-            cells = list(cells)
-        except TypeError:
-            raise ValueError(f"{who}: {what} must be a list of (r, c) pairs, got {cells!r}") from None
-        ids = np.empty(len(cells), np.int32)
-        for i, p in enumerate(cells):
-            try:
-                r, c = (int(v) for v in p)
-            except (TypeError, ValueError):
-                raise ValueError(f"{who}: {what}[{i}] must be an (r, c) pair, got {p!r}") from None
-            ok = 0 <= r < self.rows and 0 <= c < self.cols
-            if inside and not ok:
-                raise ValueError(f"{who}: {what}[{i}] = {(r, c)} is outside the {self.rows}x{self.cols} grid")
-            ids[i] = r * self.cols + c if ok else -1
-        return ids
-
     def label_of(self, cells):
         """int32 per (r, c) pair: the cell's label, -1 on an obstacle."""
-        ids = self._ids("cells", cells, True)
+        ids = self._cell_ids("cells", cells)
         return self.labels.reshape(-1)[ids].astype(np.int32)
-
-    def _label_checked(self, label):
-        try:
-            ok = int(label) == label and not isinstance(label, bool) and 0 <= int(label) < self.count
-        except (TypeError, ValueError):
-            ok = False
-        if not ok:
-            raise ValueError(f"{type(self).__name__}: label = {label!r} is outside [0, {self.count})")
-        return int(label)
 
     def mask(self, label):
         """bool [R, C]: the cells of component `label`."""
-        return self.labels == self._label_checked(label)
+        return self.labels == self._index("label", label, self.count)
 
     def same(self, pairs):
         """bool per ((r, c), (r, c)) pair: both cells are free and lie in one component (a free cell is connected to itself; a cell
@@ -134,8 +100,8 @@ class Components:
                 ok = False
             if not ok:
                 raise ValueError(f"{who}: pairs[{i}] must be a pair of (r, c) cells, got {p!r}")
-        a = self._ids("pairs[.][0]", [p[0] for p in pairs], False)
-        b = self._ids("pairs[.][1]", [p[1] for p in pairs], False)
+        a = self._cell_ids("pairs[.][0]", [p[0] for p in pairs], False)
+        b = self._cell_ids("pairs[.][1]", [p[1] for p in pairs], False)
         n = len(pairs)
         if n == 0:
             return np.zeros(0, bool)
@@ -149,18 +115,3 @@ class Components:
         finally:
             for buf in (da, db, ds):
                 buf.free()
-
-    def close(self):
-        for name in ("labels_device", "ibuf"):
-            buf = getattr(self, name, None)
-            setattr(self, name, None)
-            if buf is not None:
-                buf.free()
-        if getattr(self, "_own_engine", False) and getattr(self, "engine", None) is not None:
-            self.engine.close()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass

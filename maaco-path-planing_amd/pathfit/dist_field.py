@@ -6,6 +6,7 @@ of many targets, cell for cell, out of one parent map (`parents`, pf_dist_field_
 import numpy as np
 
 from ._batch import _cells
+from ._field import Field
 from ._lib import PathfitError
 from .engine import Engine
 from .env import TARGET_NODE_VAL, find_marker
@@ -16,16 +17,14 @@ MOVE_DC = (1, -1, 0, 0, 1, -1, 1, -1)
 PARENT_SOURCE, PARENT_NONE = 8, 255
 
 
-class DistanceField:
+class DistanceField(Field):
     """fields[k, r, c] = the length of the shortest path from sources[k] to (r, c) under the move policy (inf: an obstacle, or out
     of reach), bit for bit what DijkstraSolver's relaxation leaves.  sources: (r, c) pairs, None = the grid's target marker."""
+    _bufs = ("buf", "pbuf")
 
     def __init__(self, grid, sources=None, allow_diagonal_moves=True, restrict_diagonal_near_obstacle=True, engine=None):
         who = type(self).__name__
-        self.grid = np.array(grid, dtype=int)
-        if self.grid.ndim != 2:
-            raise ValueError(f"{who}: grid must be 2-D")
-        self.rows, self.cols = self.grid.shape
+        self._set_grid(grid)
         if sources is None:
             try:
                 sources = [find_marker(self.grid, TARGET_NODE_VAL, who)]
@@ -41,11 +40,7 @@ class DistanceField:
         self.K = len(self.sources)
         self.allow_diagonal_moves = bool(allow_diagonal_moves)
         self.restrict_diagonal_near_obstacle = bool(restrict_diagonal_near_obstacle)
-        if engine is not None and (engine.R, engine.C) != self.grid.shape:
-            raise ValueError(f"{who}: the engine's grid has another shape")
-        # every argument is checked: the device
-        self._own_engine = engine is None
-        self.engine = engine if engine is not None else Engine(self.grid)
+        self._set_engine(engine, Engine)                             # every argument is checked: the device
         self._fields = None
         self._parents, self.pbuf = None, None
         self.chosen = np.zeros(0, np.int32)
@@ -104,30 +99,10 @@ class DistanceField:
         return self._parents
 
     def _k_checked(self, k):
-        try:
-            ok = int(k) == k and not isinstance(k, bool) and 0 <= int(k) < self.K
-        except (TypeError, ValueError):
-            ok = False
-        if not ok:
-            raise ValueError(f"{type(self).__name__}: k = {k!r} is outside [0, {self.K})")
-        return int(k)
+        return self._index("k", k, self.K)
 
     def _target_ids(self, targets):
-        who = type(self).__name__
-        try:
-            targets = list(targets)
-        except TypeError:
-            raise ValueError(f"{who}: targets must be a list of (r, c) pairs, got {targets!r}") from None
-        ids = np.empty(len(targets), np.int32)
-        for i, p in enumerate(targets):
-            try:
-                r, c = (int(v) for v in p)
-            except (TypeError, ValueError):
-                raise ValueError(f"{who}: targets[{i}] must be an (r, c) pair, got {p!r}") from None
-            if not (0 <= r < self.rows and 0 <= c < self.cols):
-                raise ValueError(f"{who}: targets[{i}] = {(r, c)} is outside the {self.rows}x{self.cols} grid")
-            ids[i] = r * self.cols + c
-        return ids
+        return self._cell_ids("targets", targets)
 
     def next_hop(self, k, cell):
         """The cell before `cell` (r, c) on the path from sources[k], i.e. an agent's next step towards that source; None at the
@@ -205,19 +180,3 @@ class DistanceField:
         finally:
             for b in (dc, dl, dst, dch):
                 b.free()
-
-    def close(self):
-        buf, self.buf = getattr(self, "buf", None), None
-        if buf is not None:
-            buf.free()
-        pbuf, self.pbuf = getattr(self, "pbuf", None), None
-        if pbuf is not None:
-            pbuf.free()
-        if getattr(self, "_own_engine", False) and getattr(self, "engine", None) is not None:
-            self.engine.close()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass

@@ -27,13 +27,11 @@ class NearestSourceField(DistanceField):
     the root of the tree a dijkstra.py-shaped search seeded with the whole set leaves -- the parent of a cell is the neighbour u with
     the smallest (D[u], u) that offers the cell's label, at every step.  It is NOT the lowest source index among the sources at the
     same distance; DistanceField.paths(k=None) keeps its own lowest-k rule.  The two agree on every length, not on every cell."""
+    _bufs = ("obuf", "cbuf", "ibuf") + DistanceField._bufs
 
     def __init__(self, grid, source_sets, allow_diagonal_moves=True, restrict_diagonal_near_obstacle=True, engine=None):
         who = type(self).__name__
-        self.grid = np.array(grid, dtype=int)
-        if self.grid.ndim != 2:
-            raise ValueError(f"{who}: grid must be 2-D")
-        self.rows, self.cols = self.grid.shape
+        self._set_grid(grid)
         try:
             sets = list(source_sets)
         except TypeError:
@@ -54,11 +52,7 @@ class NearestSourceField(DistanceField):
         self.B = self.K = len(self.source_sets)                       # (K: the inherited calls see B fields)
         self.allow_diagonal_moves = bool(allow_diagonal_moves)
         self.restrict_diagonal_near_obstacle = bool(restrict_diagonal_near_obstacle)
-        if engine is not None and (engine.R, engine.C) != self.grid.shape:
-            raise ValueError(f"{who}: the engine's grid has another shape")
-        # every argument is checked: the device
-        self._own_engine = engine is None
-        self.engine = engine if engine is not None else Engine(self.grid)
+        self._set_engine(engine, Engine)                             # every argument is checked: the device
         self._fields = self._parents = self._owners = self._counts = self._info = None
         self.pbuf = self.obuf = self.cbuf = self.ibuf = None
         self.chosen = np.zeros(0, np.int32)
@@ -70,13 +64,7 @@ class NearestSourceField(DistanceField):
         self.kernel_ms = self.engine.last_kernel_ms()
 
     def _k_checked(self, b):
-        try:
-            ok = int(b) == b and not isinstance(b, bool) and 0 <= int(b) < self.B
-        except (TypeError, ValueError):
-            ok = False
-        if not ok:
-            raise ValueError(f"{type(self).__name__}: b = {b!r} is outside [0, {self.B})")
-        return int(b)
+        return self._index("b", b, self.B)
 
     @property
     def info(self):
@@ -141,11 +129,3 @@ class NearestSourceField(DistanceField):
         out = self._paths_of(ids, np.full(len(ids), b, np.int32), reverse, path_cap)
         self.chosen = self.owners[b].reshape(-1)[ids] if len(ids) else np.zeros(0, np.int32)
         return out
-
-    def close(self):
-        for name in ("obuf", "cbuf", "ibuf"):
-            buf = getattr(self, name, None)
-            setattr(self, name, None)
-            if buf is not None:
-                buf.free()
-        super().close()

@@ -4,46 +4,28 @@ forward string pulling needs (pf_smooth_batch) and `smooth_device` does the same
 The occupancy is the engine's at call time: Engine.update_grid is seen by the next call."""
 import numpy as np
 
+from ._field import Field
 from ._lib import PathfitError
 from .engine import Engine
 from .paths import CellPath
 
 
-class PathSmoother:
+class PathSmoother(Field):
     """restrict_diagonal_near_obstacle: a segment that only touches an obstacle's corner is blocked too (on a single diagonal step
     this is the move policy's corner-cut rule); False is the permissive policy."""
 
     def __init__(self, grid, restrict_diagonal_near_obstacle=True, engine=None):
-        who = type(self).__name__
-        self.grid = np.array(grid, dtype=int)
-        if self.grid.ndim != 2:
-            raise ValueError(f"{who}: grid must be 2-D")
-        self.rows, self.cols = self.grid.shape
+        self._set_grid(grid)
         self.restrict_diagonal_near_obstacle = bool(restrict_diagonal_near_obstacle)
-        if engine is not None and (engine.R, engine.C) != self.grid.shape:
-            raise ValueError(f"{who}: the engine's grid has another shape")
         self._closed = False
         self.first_block = []
         self.indices, self.lengths, self.turns, self.status = [], np.zeros(0), np.zeros(0, np.int64), np.zeros(0, np.int32)
         self.kernel_ms = 0.0
-        # every argument is checked: the device
-        self._own_engine = engine is None
-        self.engine = engine if engine is not None else Engine(self.grid)
+        self._set_engine(engine, Engine)                             # every argument is checked: the device
 
     def _check_open(self):
         if getattr(self, "_closed", True):
             raise ValueError(f"{type(self).__name__}: the smoother is closed")
-
-    def _cell(self, what, p, inside=True):
-        try:
-            r, c = (int(v) for v in p)
-        except (TypeError, ValueError):
-            raise ValueError(f"PathSmoother: {what} must be an (r, c) pair, got {p!r}") from None
-        if not (0 <= r < self.rows and 0 <= c < self.cols):
-            if not inside:
-                return -1
-            raise ValueError(f"PathSmoother: {what} = {(r, c)} is outside the {self.rows}x{self.cols} grid")
-        return r * self.cols + c
 
     # ------------------------------------------------------------------ line of sight
     def visible(self, pairs):
@@ -169,11 +151,4 @@ class PathSmoother:
 
     def close(self):
         self._closed = True
-        if getattr(self, "_own_engine", False) and getattr(self, "engine", None) is not None:
-            self.engine.close()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
+        super().close()

@@ -131,6 +131,78 @@ def test_every_cell_of_fig7(ad, rs):
         e.close()
 
 
+# ---- 1b. the one level kernel behind both entry points: single sources are sets of one
+def wall_and_pocket():
+    """9 x 11: a wall across the map with a one-cell gap, and a sealed one-cell pocket."""
+    g = np.zeros((9, 11), np.uint8)
+    g[4, :] = 1
+    g[4, 7] = 0
+    g[0:3, 0:3] = 1
+    g[1, 1] = 0
+    return g
+
+
+@pytest.fixture(scope="module")
+def compute_units():
+    """torch.cuda.get_device_properties(0).multi_processor_count.  torch brings a HIP runtime of its own, and it finds no GPU once
+    the library's runtime has started in this process (whichever test ran first decides), so then a child process asks torch."""
+    import subprocess
+    import sys
+    ask = "import torch; print(torch.cuda.get_device_properties(0).multi_processor_count)"
+    try:
+        import torch
+        return int(torch.cuda.get_device_properties(0).multi_processor_count)
+    except RuntimeError:
+        return int(subprocess.run([sys.executable, "-c", ask], check=True, capture_output=True, text=True, timeout=120).stdout.split()[-1])
+
+
+@pytest.mark.parametrize("ad, rs", [(1, 1), (0, 0)])
+def test_more_sources_than_workgroups(compute_units, ad, rs):
+    """K = 2 CUs + 3 single sources: every workgroup loops at least twice and the control block {error word, off[K + 1], ids}
+    outgrows its first allocation of 64 words.  The sources cycle through all 99 cells: obstacle cells and repeats are among them."""
+    from pathfit.engine import Engine
+    g = wall_and_pocket()
+    K = 2 * compute_units + 3
+    sources = np.arange(K) % g.size
+    assert K > g.size and (g.reshape(-1)[sources] == 1).any()
+    e = Engine(g)
+    try:
+        got, info = check_against_heap(e, g, sources, ad, rs)
+        for k in np.flatnonzero(g.reshape(-1)[sources] == 1):
+            assert np.all(np.isinf(got[k])), k
+            assert info[k].tolist() == [0, 0, 0, 0], (k, info[k])
+    finally:
+        e.close()
+
+
+def test_unit_sets_equal_the_batch():
+    """pf_dist_field_merged with K sets of one source each against pf_dist_field_batch with the same K sources: the fields bytewise,
+    the schedule-independent info words (levels, cells reached, offers) exactly; a cell is appended at most twice."""
+    from pathfit.engine import Engine
+    g = wall_and_pocket()
+    C = g.shape[1]
+    sources = np.array([0 * C + 5, 1 * C + 1, 4 * C + 7, 4 * C + 2, 8 * C + 10, 0 * C + 5, 6 * C + 3], np.int32)   # the pocket, the gap, a wall cell, a repeat
+    assert len(sources) == 7 and g.reshape(-1)[sources[3]] == 1 and sources[5] == sources[0]
+    e = Engine(g)
+    try:
+        for ad, rs in POLICIES:
+            batch, binfo = e.dist_fields_host(sources, ad, rs, want_info=True)
+            out, dinfo = e.buf((7, g.size), np.float64), e.buf((7, 4), np.int64)
+            try:
+                e.dist_field_merged(np.arange(8), sources, out, ad, rs, dinfo)
+                merged, minfo = out.download(), dinfo.download()
+            finally:
+                out.free()
+                dinfo.free()
+            assert merged.tobytes() == batch.tobytes(), (ad, rs)
+            assert np.array_equal(minfo[:, :3], binfo[:, :3]), (ad, rs, minfo, binfo)
+            for info in (minfo, binfo):
+                assert np.all(info[:, 1] <= info[:, 3]) and np.all(info[:, 3] <= 2 * info[:, 1]), (ad, rs, info)
+            assert binfo[3].tolist() == [0, 0, 0, 0] and np.all(np.isinf(batch[3]))
+    finally:
+        e.close()
+
+
 # ---- 2. thin maps
 @pytest.mark.parametrize("R, C", [(1, 1), (1, 4095), (4095, 1), (2, 300), (3, 300)])
 def test_thin_maps(R, C):
