@@ -547,6 +547,44 @@ int pf_clearance_widest(pf_handle* h, int32_t allow_diag, int32_t restrict_corne
                         const int32_t* set_off, const int32_t* src, int32_t* d_out, int64_t* d_info);
 int pf_clearance_widest_work(pf_handle* h, int64_t* out4);
 
+/* ---- cost fields: exact weighted shortest paths over a per-cell cost map (pathfit.CostField) ----------------------------------
+ * d_cost: a double [R C] cost map c in HBM.  Every FREE cell (grid value not 1) needs a finite c with 1 <= c <= 2^20; the words
+ * on obstacle cells are ignored and never validated.  Legality of a move comes from the handle's mask byte of the policy, the
+ * one pf_dist_field_merged uses; occupancy and masks are read at call time (pf_update_grid keeps working).
+ * The weight of a legal move u -> v by move k:  w = m for k < 4,  w = fl(PF_SQRT2 m) for k >= 4,  m = fl(0.5 fl(c[u] + c[v])):
+ * symmetric, exactly 1 / sqrt(2) when c == 1; w is rounded to a double before it is added (no fused operation anywhere).
+ * pf_cost_field: B source sets in pf_dist_field_merged's host CSR form -> d_out[b * R C + v] = D[b][v], the least fixed point
+ * of  D[s] = 0 on the free sources of set b,  D[v] = min over legal moves u -> v of fl(D[u] + w(u, v))  elsewhere; +inf on
+ * obstacles and out of reach.  Every label is the left-to-right rounded cost of a real walk, what a heap Dijkstra leaves bit for
+ * bit; with c == 1 the rows are pf_dist_field_merged's.  A source on an obstacle is skipped, one listed twice counts once, a
+ * set without a usable source gives an all-inf row.  d_info (or NULL) int64 [B][4]: {the sources that counted, the cells with a
+ * finite label, the cell with the largest finite label (the smallest id on a tie; -1 when nothing is reached), 0}.
+ * A cost outside [1, 2^20] on a free cell, NaN and inf included, is an argument error (-1, the message names the cell) found by
+ * a validation kernel BEFORE any output is touched.  Like pf_clearance_widest, tiles of 64 x 16 cells are relaxed to their own
+ * fixed point in LDS, one launch per round over the queued (set, tile) pairs of all B sets; the rounds grow with the tiles an
+ * optimal walk crosses, not with its cells or its cost, and the host reads one 4-byte queue length per round.  The result is
+ * the least fixed point whatever the timing: identical run to run.  Scratch: pf_clearance_widest's block.
+ * pf_cost_field_work (host side): out4 = {launches of the tile kernel, tile visits, words lowered, 0} of the last call: figures
+ * for a probe that depend on the schedule, never part of a result.
+ * pf_cost_field_parents: pf_dist_field_parents under these weights: d_parents[k * R C + v] = 0..7 the move of the last step
+ * into v, 8 on a source, 255 without a route; the parent is the u with the smallest (D[u], u) among the cells with a legal move
+ * u -> v and fl(D[u] + w(u, v)) == D[v] -- what a heap Dijkstra with keys (g, cell id), strict-improvement came_from and all
+ * sources of the set seeded at 0 leaves.  pf_dist_field_paths and pf_dist_field_owners work on these maps unchanged.
+ * pf_cost_paths: n path rows laid out as pf_astar_batch's -> d_total[q] = the left-to-right double sum of w over the row's
+ * consecutive cells (0 for a one-cell row), d_bad[q] = -1; for a row with a step that is no king move between cells inside the
+ * grid d_bad[q] = the index of the first such step and d_total[q] = NaN; a row with d_len <= 0 or > path_cap, or a lone cell
+ * outside the grid, gives d_bad = 0 and NaN.  Occupancy is not consulted.  One wavefront per row.
+ * All: a null handle (-2); B < 1, bad offsets, an empty set, an id outside the grid, K < 1, n < 0, path_cap < 1 or a missing
+ * pointer (-1, with a message) is an argument error found before any launch; n == 0 returns 0.  Synchronous and ordered on the
+ * handle's stream; pf_last_kernel_ms reports the span of the kernels. */
+int pf_cost_field(pf_handle* h, int32_t allow_diag, int32_t restrict_corner, const double* d_cost, int32_t B,
+                  const int32_t* set_off, const int32_t* src, double* d_out, int64_t* d_info);
+int pf_cost_field_work(pf_handle* h, int64_t* out4);
+int pf_cost_field_parents(pf_handle* h, int32_t allow_diag, int32_t restrict_corner, const double* d_cost, int32_t K,
+                          const double* d_fields, uint8_t* d_parents);
+int pf_cost_paths(pf_handle* h, const double* d_cost, int32_t n, int32_t path_cap, const int32_t* d_cells,
+                  const int32_t* d_len, double* d_total, int32_t* d_bad);
+
 /* Tuning knobs (results never change): "components_phases" 0/1 pf_components records a HIP event after each phase
  * (pf_components_phase_ms; default 0); "maaco_pack8_min" ants per batch from which eight ants share a wavefront
  * (default 2048); "maaco_load_ahead" the packed walk kernel's load-ahead form (all of a step's loads issued together plus touches of the

@@ -1,5 +1,5 @@
 // pathfit_fields.hip -- the field family of libpathfit.so: distance fields, routing trees, nearest-source fields, smoothing,
-// connected components, clearance and widest paths.  A translation unit, and so a device code object, of its own (DESIGN.md
+// connected components, clearance, widest paths and cost fields.  A translation unit, and so a device code object, of its own (DESIGN.md
 // 4.18): it shares the handle and the error helpers with pathfit.hip (pf_host.h) and none of the solvers' device code.
 #include <algorithm>
 #include <string>
@@ -609,6 +609,156 @@ int pf_clearance_widest_work(pf_handle* h, int64_t* out4) {
   if (!out4) { failmsg(h, "pf_clearance_widest_work: bad arguments (the four words must not be null)"); return -1; }
   for (int i = 0; i < 4; ++i) out4[i] = h->widest_work[i];
   return 0;
+}
+
+}  // extern "C"
+
+// ---------------------------------------------------------------------------
+// Cost fields: exact weighted shortest paths over a per-cell cost map (pf_cost_field.h).  The occupancy and the
+// masks are read at call time (pf_update_grid keeps working).  The field call works in the widest paths' scratch block (nothing
+// in it outlives a call, each call lays it out anew); the handle keeps the last call's work counters.  The round loop is the
+// widest paths' in shape: one queue length read per launch.
+// ---------------------------------------------------------------------------
+#include "pf_cost_field.h"
+
+extern "C" {
+
+int pf_cost_field(pf_handle* h, int32_t allow_diag, int32_t restrict_corner, const double* d_cost, int32_t B, const int32_t* set_off, const int32_t* src,
+                  double* d_out, int64_t* d_info) {
+  if (!h) return -2;
+  const std::string me("pf_cost_field");
+  auto run = [&]() -> int {
+    std::vector<int> sets;
+    if (nearest_sets_check(h, me, B, set_off, src, sets)) return -2;
+    if (!d_cost || !d_out) return failmsg(h, me + ": bad arguments (the cost map and the rows must not be null)");
+    CK(hipSetDevice(h->device));
+    const int R = h->R, C = h->C, RC = h->RC;
+    const int tiles_x = (C + PF_WD_TW - 1) / PF_WD_TW, tiles_y = (R + PF_WD_TH - 1) / PF_WD_TH, ntiles = tiles_x * tiles_y;
+    if ((long long)B * ntiles >= 0x7FFFFFFFll) return failmsg(h, me + ": bad arguments (B times the number of tiles must stay below 2^31 - 1)");
+    const size_t T = (size_t)B * (size_t)ntiles, nsets = sets.size() - 1;   // (sets[0] is the nearest fields' error word: not uploaded)
+    // the block: {words lowered, spare} | largest [B] | cells [B] | sources [B] | queue lengths [2], the offending cell, spare | arg [B] | off [B + 1], ids | queues [2][T] | flags [2][T]
+    const size_t n64 = 2 + 3 * (size_t)B;
+    if (scratch(h, me, h->d_widest, &h->widest_bytes, sizeof(unsigned long long) * n64 + sizeof(int) * (4 + (size_t)B + nsets + 4 * T), "the scratch words", true)) return -2;
+    unsigned long long* const lowered = (unsigned long long*)h->d_widest;
+    unsigned long long* const largest = lowered + 2;
+    unsigned long long* const cells = largest + B;
+    unsigned long long* const nsrc = cells + B;
+    int* const count = (int*)(nsrc + B);
+    int* const arg = count + 4;
+    int* const d_off = arg + B;
+    int* const d_src = d_off + B + 1;
+    int* const queue = d_off + nsets;
+    int* const flag = queue + 2 * T;
+    h->cost_work[0] = h->cost_work[1] = h->cost_work[2] = h->cost_work[3] = 0;
+    const unsigned nb = (unsigned)((RC + PF_CF_THREADS - 1) / PF_CF_THREADS), gy = (unsigned)(B < 65535 ? B : 65535);
+    // the costs of the free cells, before any output is touched
+    int bad = 0x7FFFFFFF;
+    CK(hipMemcpyAsync(count + 2, &bad, sizeof(int), hipMemcpyHostToDevice, h->stream));
+    CK(hipStreamSynchronize(h->stream));
+    CK(hipEventRecord(h->ev0, h->stream));
+    hipLaunchKernelGGL(k_cost_validate_free_cells, dim3(nb < 2048u ? nb : 2048u), dim3(PF_CF_THREADS), 0, h->stream, (const uint8_t*)h->d_occ, d_cost, RC, count + 2);
+    CK(hipGetLastError());
+    CK(hipMemcpyAsync(&bad, count + 2, sizeof(int), hipMemcpyDeviceToHost, h->stream));
+    CK(hipStreamSynchronize(h->stream));
+    h->d2h_small += 1;
+    if (bad != 0x7FFFFFFF)
+      return failmsg(h, me + ": bad arguments (the cost of the free cell (" + std::to_string(bad / C) + ", " + std::to_string(bad % C) +
+                            ") is not a finite number in [1, 2^20])");
+    CK(hipMemsetAsync(lowered, 0, sizeof(unsigned long long) * n64 + sizeof(int) * 2, h->stream));   // counters, largest, cells, sources, queue lengths
+    CK(hipMemsetAsync(arg, 0x7F, sizeof(int) * (size_t)B, h->stream));   // (any word above every cell id: 2^24 cells at most, as the level kernel's)
+    CK(hipMemsetAsync(flag, 0, sizeof(int) * 2 * T, h->stream));
+    CK(hipMemcpyAsync(d_off, sets.data() + 1, sizeof(int) * nsets, hipMemcpyHostToDevice, h->stream));
+    CK(hipStreamSynchronize(h->stream));                            // (sets is pageable and leaves scope)
+    const size_t words = (size_t)B * (size_t)RC;
+    hipLaunchKernelGGL(k_cost_fill_inf, dim3((unsigned)std::min<size_t>((words + PF_CF_THREADS - 1) / PF_CF_THREADS, 4096)), dim3(PF_CF_THREADS), 0, h->stream,
+                       (unsigned long long*)d_out, words);
+    int most_src = 1;
+    for (int b = 0; b < B; ++b) most_src = std::max(most_src, set_off[b + 1] - set_off[b]);
+    hipLaunchKernelGGL(k_cost_seed_sets, dim3((unsigned)std::min((most_src + PF_CF_THREADS - 1) / PF_CF_THREADS, 64), gy), dim3(PF_CF_THREADS), 0, h->stream,
+                       (const uint8_t*)h->d_occ, RC, C, tiles_x, ntiles, (int)B, (const int*)d_off, (const int*)d_src, d_out, flag, queue, count, nsrc);
+    CK(hipGetLastError());
+    int n = 0;
+    CK(hipMemcpyAsync(&n, count, sizeof(int), hipMemcpyDeviceToHost, h->stream));
+    CK(hipStreamSynchronize(h->stream));
+    const uint8_t* mm = move_mask(h, allow_diag, restrict_corner);
+    long long launches = 0, visits = 0;
+    for (long long round = 0; n > 0; ++round) {
+      if (round > (long long)RC + 1) return failmsg(h, me + ": internal: round bound");
+      if (n < 0 || (size_t)n > T) return failmsg(h, me + ": internal: queue bound");
+      const int p = (int)(round & 1);
+      hipLaunchKernelGGL(k_cost_relax_tiles_in_lds, dim3((unsigned)n), dim3(PF_CF_THREADS), 0, h->stream, (const uint8_t*)h->d_occ, mm, d_cost, R, C, allow_diag ? 1 : 0, tiles_x, tiles_y, d_out,
+                         (const int*)(queue + (size_t)p * T), n, round == 0 ? 1 : 0, flag + (size_t)p * T, count + p, flag + (size_t)(p ^ 1) * T,
+                         queue + (size_t)(p ^ 1) * T, count + (p ^ 1), lowered);
+      CK(hipGetLastError());
+      launches += 1; visits += n;
+      CK(hipMemcpyAsync(&n, count + (p ^ 1), sizeof(int), hipMemcpyDeviceToHost, h->stream));
+      CK(hipStreamSynchronize(h->stream));
+    }
+    if (d_info) {
+      hipLaunchKernelGGL(k_cost_info_largest, dim3(nb < 1024u ? nb : 1024u, gy), dim3(PF_CF_THREADS), 0, h->stream, (const double*)d_out, RC, (int)B, largest, cells);
+      hipLaunchKernelGGL(k_cost_info_arg, dim3(nb < 1024u ? nb : 1024u, gy), dim3(PF_CF_THREADS), 0, h->stream, (const double*)d_out, RC, (int)B,
+                         (const unsigned long long*)largest, arg);
+      hipLaunchKernelGGL(k_cost_write_info, dim3(((unsigned)B + PF_CF_THREADS - 1) / PF_CF_THREADS), dim3(PF_CF_THREADS), 0, h->stream, (int)B,
+                         (const unsigned long long*)cells, (const unsigned long long*)nsrc, (const int*)arg, (long long*)d_info);
+      CK(hipGetLastError());
+    }
+    CK(hipEventRecord(h->ev1, h->stream));
+    unsigned long long fell = 0;
+    CK(hipMemcpyAsync(&fell, lowered, sizeof(fell), hipMemcpyDeviceToHost, h->stream));
+    CK(hipStreamSynchronize(h->stream));
+    CK(hipEventElapsedTime(&h->last_ms, h->ev0, h->ev1));
+    h->d2h_small += launches + 2;
+    h->cost_work[0] = launches; h->cost_work[1] = visits; h->cost_work[2] = (long long)fell;
+    return 0;
+  };
+  return run() ? -1 : 0;
+}
+
+int pf_cost_field_work(pf_handle* h, int64_t* out4) {
+  if (!h) return -2;
+  if (!out4) { failmsg(h, "pf_cost_field_work: bad arguments (the four words must not be null)"); return -1; }
+  for (int i = 0; i < 4; ++i) out4[i] = h->cost_work[i];
+  return 0;
+}
+
+int pf_cost_field_parents(pf_handle* h, int32_t allow_diag, int32_t restrict_corner, const double* d_cost, int32_t K, const double* d_fields, uint8_t* d_parents) {
+  if (!h) return -2;
+  if (K < 1 || !d_cost || !d_fields || !d_parents) {
+    failmsg(h, "pf_cost_field_parents: bad arguments (K >= 1; the cost map, the fields and the parents must not be null)");
+    return -1;
+  }
+  auto run = [&]() -> int {
+    CK(hipSetDevice(h->device));
+    if (scratch(h, "pf_cost_field_parents", h->d_df_ctl, &h->df_ctl_bytes, sizeof(int) * 64, "the error word", false)) return -2;
+    CK(hipMemsetAsync(h->d_df_ctl, 0, sizeof(int), h->stream));
+    const unsigned gx = (unsigned)((h->RC + PF_FP_THREADS - 1) / PF_FP_THREADS), gy = (unsigned)(K < 65535 ? K : 65535);
+    int err = 0;
+    const int rc = timed(h, [&] {
+      hipLaunchKernelGGL(k_cost_parent_map_thread_per_cell, dim3(gx, gy), dim3(PF_FP_THREADS), 0, h->stream, move_mask(h, allow_diag, restrict_corner), d_cost,
+                         h->RC, h->C, K, d_fields, d_parents, h->d_df_ctl);
+    }, h->d_df_ctl, &err);
+    if (rc) return rc;
+    if (err) return failmsg(h, "pf_cost_field_parents: a finite cell has no parent: the fields are no fixed point of this grid, policy and cost map");
+    return 0;
+  };
+  return run() ? -1 : 0;
+}
+
+int pf_cost_paths(pf_handle* h, const double* d_cost, int32_t n, int32_t path_cap, const int32_t* d_cells, const int32_t* d_len, double* d_total, int32_t* d_bad) {
+  if (!h) return -2;
+  if (n < 0 || path_cap < 1 || !d_cost || !d_cells || !d_len || !d_total || !d_bad) {
+    failmsg(h, "pf_cost_paths: bad arguments (n >= 0, path_cap >= 1; the cost map, the rows, the lengths, the totals and the step indices must not be null)");
+    return -1;
+  }
+  if (n == 0) return 0;
+  auto run = [&]() -> int {
+    CK(hipSetDevice(h->device));
+    return timed(h, [&] {
+      hipLaunchKernelGGL(k_cost_paths_one_wave_per_row, dim3((unsigned)n), dim3(64), 0, h->stream, d_cost, h->RC, h->C, (int)n, (int)path_cap, (const int*)d_cells,
+                         (const int*)d_len, d_total, (int*)d_bad);
+    });
+  };
+  return run() ? -1 : 0;
 }
 
 }  // extern "C"

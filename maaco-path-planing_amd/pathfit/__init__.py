@@ -21,3 +21,4 @@ from .nearest_field import NearestSourceField  # noqa: F401
 from .smooth import PathSmoother  # noqa: F401
 from .components import Components  # noqa: F401
 from .clearance import Clearance, PF_CLEAR_NONE  # noqa: F401
+from .cost_field import CostField  # noqa: F401

@@ -173,6 +173,10 @@ SYMBOLS = {
     "pf_clearance_segments": (C.c_int, [_vp, _vp, _i32, _i32, _vp, _vp, _vp, _vp]),
     "pf_clearance_widest": (C.c_int, [_vp, _i32, _i32, _vp, _i32, _vp, _vp, _vp, _vp]),
     "pf_clearance_widest_work": (C.c_int, [_vp, _vp]),
+    "pf_cost_field": (C.c_int, [_vp, _i32, _i32, _vp, _i32, _vp, _vp, _vp, _vp]),
+    "pf_cost_field_work": (C.c_int, [_vp, _vp]),
+    "pf_cost_field_parents": (C.c_int, [_vp, _i32, _i32, _vp, _i32, _vp, _vp]),
+    "pf_cost_paths": (C.c_int, [_vp, _vp, _i32, _i32, _vp, _vp, _vp, _vp]),
 }
 
 

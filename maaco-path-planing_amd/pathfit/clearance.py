@@ -34,6 +34,34 @@ def margin_to_sq(margin):
     return n
 
 
+def cost_map_of(d2, grid, margin=None, margin_sq=None, weight=1.0):
+    """Clearance.cost_map on a squared-distance field d2 and its grid, both [R, C] (numpy alone: no device)."""
+    if (margin is None) == (margin_sq is None):
+        raise ValueError("Clearance: give exactly one of margin and margin_sq")
+    if margin is not None:
+        try:
+            m = float(margin)
+        except (TypeError, ValueError):
+            m = math.nan
+        if isinstance(margin, bool) or not (0.0 < m < 46340.0):
+            raise ValueError(f"Clearance: margin must be a number in (0, 46340), got {margin!r}")
+    else:
+        m = math.sqrt(Clearance._margin_sq(None, margin_sq, 1))
+    try:
+        w = float(weight)
+    except (TypeError, ValueError):
+        w = math.nan
+    if isinstance(weight, bool) or not (0.0 <= w < math.inf):
+        raise ValueError(f"Clearance: weight must be a finite number >= 0, got {weight!r}")
+    d2, grid = np.asarray(d2), np.asarray(grid)
+    if d2.shape != grid.shape or d2.ndim != 2:
+        raise ValueError(f"Clearance: the field has shape {d2.shape}, the grid has {grid.shape}")
+    out = np.ones(d2.shape, np.float64)
+    near = (grid != 1) & (d2 != PF_CLEAR_NONE)
+    out[near] = np.minimum(1.0 + w * np.maximum(0.0, m - np.sqrt(d2[near].astype(np.float64))) ** 2, float(2 ** 20))
+    return out
+
+
 class WidestField(Field):
     """What Clearance.widest returns: w[b, r, c] = the largest margin_sq with which a robot gets from a source of set b to (r, c)
     (0: not at all), kept in HBM (`w_device`, int32 [B, R * C]); `info` int64 [B, 4] = (sources that counted, cells reached, the
@@ -162,6 +190,14 @@ class Clearance(Field):
         out = self.grid.copy()
         out[self.d2 < msq] = 1
         return out
+
+    def cost_map(self, margin=None, margin_sq=None, weight=1.0):
+        """float64 [R, C] for CostField: 1 + weight * max(0, m - sqrt(d2))^2 on a free cell, clipped to 2^20, with m = margin when
+        given, else sqrt(margin_sq); 1 on obstacles and on a map without obstacles.  Cells nearer than m to an obstacle grow dearer
+        with the square of the shortfall; cells at least m away cost 1.  This is the ADDITIVE form of the safety term: a route's
+        cost is its length plus the penalties it collects.  It is NOT the reference's fitness, which divides the safety penalty by
+        the path length (helper.py:67-80).  Runs in numpy on the downloaded field."""
+        return cost_map_of(self.d2, self.grid, margin, margin_sq, weight)
 
     # ------------------------------------------------------------------ path rows
     def _rows(self, paths):

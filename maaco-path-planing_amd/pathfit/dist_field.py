@@ -82,13 +82,17 @@ class DistanceField(Field):
         if self.pbuf is None:
             pbuf = self.engine.buf((self.K, self.rows, self.cols), np.uint8)
             try:
-                self.engine.dist_field_parents(self.K, self.buf, pbuf, self.allow_diagonal_moves, self.restrict_diagonal_near_obstacle)
+                self._compute_parents(pbuf)
             except Exception:
                 pbuf.free()
                 raise
             self.pbuf = pbuf
             self.parents_kernel_ms = self.engine.last_kernel_ms()
         return self.pbuf
+
+    def _compute_parents(self, pbuf):
+        """The parent maps of `buf` into pbuf (CostField computes them under its cost map)."""
+        self.engine.dist_field_parents(self.K, self.buf, pbuf, self.allow_diagonal_moves, self.restrict_diagonal_near_obstacle)
 
     @property
     def parents(self):

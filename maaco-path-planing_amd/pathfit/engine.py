@@ -368,6 +368,39 @@ class Engine:
         self._ck(self.L.pf_clearance_widest_work(self.h, out))
         return tuple(int(v) for v in out)
 
+    # ------------------------------------------------------------------ cost fields
+    def cost_field(self, d_cost, set_off, sources, d_out, allow_diag=True, restrict_corner=True, d_info=None):
+        """A cost map in HBM (float64 [R * C], in [1, 2^20] on every free cell) and source SETS (host int32 CSR, as
+        dist_field_merged's) -> d_out float64 [B, R * C]: the cost of the cheapest walk into each cell from a source of the set, a
+        move weighing the mean of its two cells' costs (times sqrt(2) for a diagonal), inf where none arrives; d_info int64 [B, 4] =
+        (sources that counted, cells reached, the cell with the largest finite label, 0) (pf_cost_field)."""
+        off = np.ascontiguousarray(set_off, np.int32).reshape(-1)
+        src = np.ascontiguousarray(sources, np.int32).reshape(-1)
+        self._ck(self.L.pf_cost_field(self.h, int(bool(allow_diag)), int(bool(restrict_corner)), d_cost.ptr if d_cost else None, int(off.size) - 1,
+                                      off.ctypes.data if off.size else None, src.ctypes.data if src.size else None, d_out.ptr if d_out else None,
+                                      d_info.ptr if d_info else None))
+        self._logk("cost_field")
+
+    def cost_field_work(self):
+        """(launches, tile visits, words lowered, 0) of the last cost_field call: they depend on the schedule (the probe's figures)."""
+        out = (C.c_int64 * 4)()
+        self._ck(self.L.pf_cost_field_work(self.h, out))
+        return tuple(int(v) for v in out)
+
+    def cost_field_parents(self, d_cost, K, d_fields, d_parents, allow_diag=True, restrict_corner=True):
+        """Parent maps of K cost fields (the cost map and policy they were computed under) -> d_parents [K, R * C] uint8, coded as
+        dist_field_parents' (pf_cost_field_parents); dist_field_paths and dist_field_owners take them unchanged."""
+        self._ck(self.L.pf_cost_field_parents(self.h, int(bool(allow_diag)), int(bool(restrict_corner)), d_cost.ptr if d_cost else None, int(K),
+                                              d_fields.ptr if d_fields else None, d_parents.ptr if d_parents else None))
+        self._logk("cost_field_parents")
+
+    def cost_paths(self, d_cost, n, path_cap, d_cells, d_len, d_total, d_bad):
+        """Rows of astar_batch's layout in HBM -> d_total float64 [n], the left-to-right sum of the moves' weights (NaN for a bad
+        row), and d_bad int32 [n], the first step that is no king move inside the grid or -1 (pf_cost_paths)."""
+        self._ck(self.L.pf_cost_paths(self.h, d_cost.ptr if d_cost else None, int(n), int(path_cap), d_cells.ptr if d_cells else None,
+                                      d_len.ptr if d_len else None, d_total.ptr if d_total else None, d_bad.ptr if d_bad else None))
+        self._logk("cost_paths")
+
     # ------------------------------------------------------------------ K1
     def score_batch(self, n, path_cap, d_cells, d_len, d_stats, sp):
         """Rows of astar_batch's layout in HBM -> d_stats [n, 5] doubles (pf_score_batch)."""

@@ -28,10 +28,17 @@ class NearestSourceField(DistanceField):
     the smallest (D[u], u) that offers the cell's label, at every step.  It is NOT the lowest source index among the sources at the
     same distance; DistanceField.paths(k=None) keeps its own lowest-k rule.  The two agree on every length, not on every cell."""
     _bufs = ("obuf", "cbuf", "ibuf") + DistanceField._bufs
+    _info_bounds_chains = True              # info[b, 0] (the levels) bounds the cells of a parent chain: the owner kernel's rounds
 
     def __init__(self, grid, source_sets, allow_diagonal_moves=True, restrict_diagonal_near_obstacle=True, engine=None):
-        who = type(self).__name__
         self._set_grid(grid)
+        self._set_source_sets(source_sets, allow_diagonal_moves, restrict_diagonal_near_obstacle)
+        self._set_engine(engine, Engine)                             # every argument is checked: the device
+        self._start()
+
+    def _set_source_sets(self, source_sets, allow_diagonal_moves, restrict_diagonal_near_obstacle):
+        """The sets and the policy, checked on the host."""
+        who = type(self).__name__
         try:
             sets = list(source_sets)
         except TypeError:
@@ -52,16 +59,22 @@ class NearestSourceField(DistanceField):
         self.B = self.K = len(self.source_sets)                       # (K: the inherited calls see B fields)
         self.allow_diagonal_moves = bool(allow_diagonal_moves)
         self.restrict_diagonal_near_obstacle = bool(restrict_diagonal_near_obstacle)
-        self._set_engine(engine, Engine)                             # every argument is checked: the device
+        self.set_off = np.concatenate([[0], np.cumsum([len(s) for s in self.source_sets])]).astype(np.int32)
+        self.ids = np.array([r * self.cols + c for s in self.source_sets for r, c in s], np.int32)
+
+    def _start(self):
+        """The buffers and the field rows, once the engine is set."""
         self._fields = self._parents = self._owners = self._counts = self._info = None
         self.pbuf = self.obuf = self.cbuf = self.ibuf = None
         self.chosen = np.zeros(0, np.int32)
-        self.set_off = np.concatenate([[0], np.cumsum([len(s) for s in self.source_sets])]).astype(np.int32)
-        self.ids = np.array([r * self.cols + c for s in self.source_sets for r, c in s], np.int32)
         self.buf = self.engine.buf((self.B, self.rows, self.cols), np.float64)
         self.ibuf = self.engine.buf((self.B, 4), np.int64)
-        self.engine.dist_field_merged(self.set_off, self.ids, self.buf, self.allow_diagonal_moves, self.restrict_diagonal_near_obstacle, self.ibuf)
+        self._compute_fields()
         self.kernel_ms = self.engine.last_kernel_ms()
+
+    def _compute_fields(self):
+        """The field rows into `buf`, their info block into `ibuf` (CostField computes them under its cost map)."""
+        self.engine.dist_field_merged(self.set_off, self.ids, self.buf, self.allow_diagonal_moves, self.restrict_diagonal_near_obstacle, self.ibuf)
 
     def _k_checked(self, b):
         return self._index("b", b, self.B)
@@ -81,7 +94,7 @@ class NearestSourceField(DistanceField):
             e = self.engine
             obuf, cbuf = e.buf((self.B, self.rows, self.cols), np.int32), e.buf(len(self.ids), np.int64)
             try:
-                e.dist_field_owners(self.set_off, self.ids, pbuf, obuf, self.ibuf, cbuf)
+                e.dist_field_owners(self.set_off, self.ids, pbuf, obuf, self.ibuf if self._info_bounds_chains else None, cbuf)
             except Exception:
                 obuf.free()
                 cbuf.free()
