@@ -585,6 +585,47 @@ int pf_cost_field_parents(pf_handle* h, int32_t allow_diag, int32_t restrict_cor
 int pf_cost_paths(pf_handle* h, const double* d_cost, int32_t n, int32_t path_cap, const int32_t* d_cells,
                   const int32_t* d_len, double* d_total, int32_t* d_bad);
 
+/* ---- turn fields: the exact optimum of length plus a turn penalty, over (cell, heading) states (pathfit.TurnField) ----------
+ * Moves, legality and the move weight w(u, v, k) are the cost fields'; d_cost NULL means c == 1 everywhere (no buffer is read,
+ * the same bits as a map of ones).  turn_weight is a finite double in [0, 2^20].  T[b][d][v] is the cheapest cost of a walk from
+ * a source of set b that ENTERS v by move d:  T[d][s] = 0 for all eight d on every free source (the first move of a path is no
+ * turn, as helper.py's count_turns has it);  elsewhere, with u = v - step(d) and the move u -> v legal,
+ *     T[d][v] = min over d' of fl(T[d'][u] + e),   e = w for d' == d,  e = fl(w + turn_weight) otherwise;
+ * +inf where the move is illegal, on obstacles and out of reach.  Every label is the left-to-right rounded cost of a real walk
+ * (which may pass a cell twice), and the least fixed point is what a heap Dijkstra over the states leaves, bit for bit.
+ * pf_turn_field: B source sets in pf_dist_field_merged's host CSR form -> d_states [B][8][R C] (plane-major) and d_best [B][R C],
+ * best[v] = min over d of T[d][v]: the least, over all paths from a source to v, of the path's length plus turn_weight per
+ * turn under the cost map; at turn_weight == 0 pf_cost_field's rows bit for bit.  d_info (or NULL) int64 [B][4] as
+ * pf_cost_field's, counted on best.  Sources on obstacles, duplicates and sets without a usable source as pf_cost_field.  A bad
+ * cost on a free cell (pf_cost_field's validation kernel) or a turn_weight outside [0, 2^20], NaN included, is an argument
+ * error (-1) found BEFORE any output is touched.  Tiles of 32 x 16 cells with nine doubles a cell in LDS are relaxed to their own
+ * fixed point, one launch per round over the queued (set, tile) pairs; one 4-byte queue length is read per round; at most
+ * 8 R C + 2 rounds, and a tile's sweeps are bounded by its states + 2: beyond either the call fails with a message (DESIGN.md
+ * 4.20).  Identical run to run.  Scratch: pf_clearance_widest's block.
+ * pf_turn_field_work (host side): out4 = {launches of the tile kernel, tile visits, state words lowered, 0} of the last call:
+ * figures for a probe that depend on the schedule, never part of a result.
+ * pf_turn_field_paths: n queries (d_set_idx[q], d_target[q]) -> rows laid out as pf_dist_field_paths', from the states alone (no
+ * parent map): start at the target with the heading of the smallest (T[d][t], d); at (v, d) step to u = v - step(d); stop when
+ * best[u] == 0 (a source); otherwise take the d' with the smallest (T[d'][u], d') among those with fl(T[d'][u] + e) == T[d][v]
+ * bit for bit.  The route's cost under pf_turn_paths equals best[target] bit for bit.  PF_ST_INFEASIBLE, length 0: no finite
+ * state at the target, a target id outside [0, R C) or a set index outside [0, B).  PF_ST_OVERFLOW, length 0, row untouched:
+ * more than path_cap cells -- or words that are no fixed point (no state offers the label, a step off the grid, more than R C
+ * cells): the walk is bounded whatever the words hold.  One lane per query.
+ * pf_turn_paths: n path rows laid out as pf_astar_batch's -> d_total[q] = the rule's cost summed left to right: a step weighs w,
+ * or fl(w + turn_weight) when its move differs from the move of the step before; d_turns[q] = the steps that turned
+ * (count_turns); d_bad[q] = -1.  Bad rows as pf_cost_paths: NaN, 0 turns and the first bad step.  One wavefront per row.
+ * All: a null handle (-2); B < 1, bad offsets, an empty set, an id outside the grid, n < 0, path_cap < 1, a bad turn_weight or a
+ * missing pointer (-1, with a message) is an argument error found before any launch; n == 0 returns 0.  Synchronous and ordered
+ * on the handle's stream; pf_last_kernel_ms reports the span of the kernels. */
+int pf_turn_field(pf_handle* h, int32_t allow_diag, int32_t restrict_corner, const double* d_cost, double turn_weight, int32_t B,
+                  const int32_t* set_off, const int32_t* src, double* d_states, double* d_best, int64_t* d_info);
+int pf_turn_field_work(pf_handle* h, int64_t* out4);
+int pf_turn_field_paths(pf_handle* h, const double* d_cost, double turn_weight, int32_t B, const double* d_states, int32_t n,
+                        const int32_t* d_set_idx, const int32_t* d_target, int32_t reverse, int32_t path_cap, int32_t* d_cells,
+                        int32_t* d_len, int32_t* d_status);
+int pf_turn_paths(pf_handle* h, const double* d_cost, double turn_weight, int32_t n, int32_t path_cap, const int32_t* d_cells,
+                  const int32_t* d_len, double* d_total, int32_t* d_turns, int32_t* d_bad);
+
 /* Tuning knobs (results never change): "components_phases" 0/1 pf_components records a HIP event after each phase
  * (pf_components_phase_ms; default 0); "maaco_pack8_min" ants per batch from which eight ants share a wavefront
  * (default 2048); "maaco_load_ahead" the packed walk kernel's load-ahead form (all of a step's loads issued together plus touches of the

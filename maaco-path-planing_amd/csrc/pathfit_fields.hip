@@ -1,5 +1,5 @@
 // pathfit_fields.hip -- the field family of libpathfit.so: distance fields, routing trees, nearest-source fields, smoothing,
-// connected components, clearance, widest paths and cost fields.  A translation unit, and so a device code object, of its own (DESIGN.md
+// connected components, clearance, widest paths, cost fields and turn fields.  A translation unit, and so a device code object, of its own (DESIGN.md
 // 4.18): it shares the handle and the error helpers with pathfit.hip (pf_host.h) and none of the solvers' device code.
 #include <algorithm>
 #include <string>
@@ -756,6 +756,165 @@ int pf_cost_paths(pf_handle* h, const double* d_cost, int32_t n, int32_t path_ca
     return timed(h, [&] {
       hipLaunchKernelGGL(k_cost_paths_one_wave_per_row, dim3((unsigned)n), dim3(64), 0, h->stream, d_cost, h->RC, h->C, (int)n, (int)path_cap, (const int*)d_cells,
                          (const int*)d_len, d_total, (int*)d_bad);
+    });
+  };
+  return run() ? -1 : 0;
+}
+
+}  // extern "C"
+
+// ---------------------------------------------------------------------------
+// Turn fields: the exact optimum of length plus a turn penalty over (cell, heading) states (pf_turn_field.h).
+// The cost fields' round loop over the turn tile (PF_TF_TW x PF_TF_TH); the scratch is the widest paths' block, laid out anew by
+// each call for this tile's queues; the handle keeps the last call's work counters.
+// ---------------------------------------------------------------------------
+#include "pf_turn_field.h"
+
+// a turn weight is a finite double in [0, 2^20] (NaN fails both comparisons)
+static int turn_weight_check(pf_handle* h, const std::string& me, double turn_weight) {
+  if (turn_weight >= 0.0 && turn_weight <= PF_TF_WEIGHT_MAX) return 0;
+  return failmsg(h, me + ": bad arguments (the turn weight is not a finite number in [0, 2^20])");
+}
+
+extern "C" {
+
+int pf_turn_field(pf_handle* h, int32_t allow_diag, int32_t restrict_corner, const double* d_cost, double turn_weight, int32_t B, const int32_t* set_off,
+                  const int32_t* src, double* d_states, double* d_best, int64_t* d_info) {
+  if (!h) return -2;
+  const std::string me("pf_turn_field");
+  auto run = [&]() -> int {
+    std::vector<int> sets;
+    if (nearest_sets_check(h, me, B, set_off, src, sets)) return -2;
+    if (!d_states || !d_best) return failmsg(h, me + ": bad arguments (the states and the best rows must not be null)");
+    if (turn_weight_check(h, me, turn_weight)) return -2;
+    CK(hipSetDevice(h->device));
+    const int R = h->R, C = h->C, RC = h->RC;
+    const int tiles_x = (C + PF_TF_TW - 1) / PF_TF_TW, tiles_y = (R + PF_TF_TH - 1) / PF_TF_TH, ntiles = tiles_x * tiles_y;
+    if ((long long)B * ntiles >= 0x7FFFFFFFll) return failmsg(h, me + ": bad arguments (B times the number of tiles must stay below 2^31 - 1)");
+    const size_t T = (size_t)B * (size_t)ntiles, nsets = sets.size() - 1;   // (sets[0] is the nearest fields' error word: not uploaded)
+    // the block: {words lowered, the sweep bound's error word} | largest [B] | cells [B] | sources [B] | queue lengths [2], the offending cell, spare | arg [B] | off [B + 1], ids | queues [2][T] | flags [2][T]
+    const size_t n64 = 2 + 3 * (size_t)B;
+    if (scratch(h, me, h->d_widest, &h->widest_bytes, sizeof(unsigned long long) * n64 + sizeof(int) * (4 + (size_t)B + nsets + 4 * T), "the scratch words", true)) return -2;
+    unsigned long long* const counters = (unsigned long long*)h->d_widest;
+    unsigned long long* const largest = counters + 2;
+    unsigned long long* const cells = largest + B;
+    unsigned long long* const nsrc = cells + B;
+    int* const count = (int*)(nsrc + B);
+    int* const arg = count + 4;
+    int* const d_off = arg + B;
+    int* const d_src = d_off + B + 1;
+    int* const queue = d_off + nsets;
+    int* const flag = queue + 2 * T;
+    h->turn_work[0] = h->turn_work[1] = h->turn_work[2] = h->turn_work[3] = 0;
+    const unsigned nb = (unsigned)((RC + PF_CF_THREADS - 1) / PF_CF_THREADS), gy = (unsigned)(B < 65535 ? B : 65535);
+    CK(hipEventRecord(h->ev0, h->stream));
+    if (d_cost) {                                                     // the costs of the free cells, before any output is touched
+      int bad = 0x7FFFFFFF;
+      CK(hipMemcpyAsync(count + 2, &bad, sizeof(int), hipMemcpyHostToDevice, h->stream));
+      CK(hipStreamSynchronize(h->stream));
+      hipLaunchKernelGGL(k_cost_validate_free_cells, dim3(nb < 2048u ? nb : 2048u), dim3(PF_CF_THREADS), 0, h->stream, (const uint8_t*)h->d_occ, d_cost, RC, count + 2);
+      CK(hipGetLastError());
+      CK(hipMemcpyAsync(&bad, count + 2, sizeof(int), hipMemcpyDeviceToHost, h->stream));
+      CK(hipStreamSynchronize(h->stream));
+      h->d2h_small += 1;
+      if (bad != 0x7FFFFFFF)
+        return failmsg(h, me + ": bad arguments (the cost of the free cell (" + std::to_string(bad / C) + ", " + std::to_string(bad % C) +
+                              ") is not a finite number in [1, 2^20])");
+    }
+    CK(hipMemsetAsync(counters, 0, sizeof(unsigned long long) * n64 + sizeof(int) * 2, h->stream));   // counters, largest, cells, sources, queue lengths
+    CK(hipMemsetAsync(arg, 0x7F, sizeof(int) * (size_t)B, h->stream));   // (any word above every cell id)
+    CK(hipMemsetAsync(flag, 0, sizeof(int) * 2 * T, h->stream));
+    CK(hipMemcpyAsync(d_off, sets.data() + 1, sizeof(int) * nsets, hipMemcpyHostToDevice, h->stream));
+    CK(hipStreamSynchronize(h->stream));                            // (sets is pageable and leaves scope)
+    const size_t words = (size_t)B * (size_t)RC;
+    hipLaunchKernelGGL(k_cost_fill_inf, dim3((unsigned)std::min<size_t>((8 * words + PF_CF_THREADS - 1) / PF_CF_THREADS, 4096)), dim3(PF_CF_THREADS), 0, h->stream,
+                       (unsigned long long*)d_states, 8 * words);
+    hipLaunchKernelGGL(k_cost_fill_inf, dim3((unsigned)std::min<size_t>((words + PF_CF_THREADS - 1) / PF_CF_THREADS, 4096)), dim3(PF_CF_THREADS), 0, h->stream,
+                       (unsigned long long*)d_best, words);
+    int most_src = 1;
+    for (int b = 0; b < B; ++b) most_src = std::max(most_src, set_off[b + 1] - set_off[b]);
+    hipLaunchKernelGGL(k_turn_seed_sets, dim3((unsigned)std::min((most_src + PF_TF_THREADS - 1) / PF_TF_THREADS, 64), gy), dim3(PF_TF_THREADS), 0, h->stream,
+                       (const uint8_t*)h->d_occ, RC, C, tiles_x, ntiles, (int)B, (const int*)d_off, (const int*)d_src, d_states, d_best, flag, queue, count, nsrc);
+    CK(hipGetLastError());
+    int n = 0;
+    CK(hipMemcpyAsync(&n, count, sizeof(int), hipMemcpyDeviceToHost, h->stream));
+    CK(hipStreamSynchronize(h->stream));
+    const uint8_t* mm = move_mask(h, allow_diag, restrict_corner);
+    long long launches = 0, visits = 0;
+    for (long long round = 0; n > 0; ++round) {
+      if (round > 8 * (long long)RC + 1) return failmsg(h, me + ": internal: round bound");
+      if (n < 0 || (size_t)n > T) return failmsg(h, me + ": internal: queue bound");
+      const int p = (int)(round & 1);
+      hipLaunchKernelGGL(k_turn_relax_tiles_in_lds, dim3((unsigned)n), dim3(PF_TF_THREADS), 0, h->stream, (const uint8_t*)h->d_occ, mm, d_cost, turn_weight, R, C,
+                         allow_diag ? 1 : 0, tiles_x, tiles_y, d_states, d_best, (const int*)(queue + (size_t)p * T), n, round == 0 ? 1 : 0, flag + (size_t)p * T, count + p,
+                         flag + (size_t)(p ^ 1) * T, queue + (size_t)(p ^ 1) * T, count + (p ^ 1), counters);
+      CK(hipGetLastError());
+      launches += 1; visits += n;
+      CK(hipMemcpyAsync(&n, count + (p ^ 1), sizeof(int), hipMemcpyDeviceToHost, h->stream));
+      CK(hipStreamSynchronize(h->stream));
+    }
+    if (d_info) {
+      hipLaunchKernelGGL(k_cost_info_largest, dim3(nb < 1024u ? nb : 1024u, gy), dim3(PF_CF_THREADS), 0, h->stream, (const double*)d_best, RC, (int)B, largest, cells);
+      hipLaunchKernelGGL(k_cost_info_arg, dim3(nb < 1024u ? nb : 1024u, gy), dim3(PF_CF_THREADS), 0, h->stream, (const double*)d_best, RC, (int)B,
+                         (const unsigned long long*)largest, arg);
+      hipLaunchKernelGGL(k_cost_write_info, dim3(((unsigned)B + PF_CF_THREADS - 1) / PF_CF_THREADS), dim3(PF_CF_THREADS), 0, h->stream, (int)B,
+                         (const unsigned long long*)cells, (const unsigned long long*)nsrc, (const int*)arg, (long long*)d_info);
+      CK(hipGetLastError());
+    }
+    CK(hipEventRecord(h->ev1, h->stream));
+    unsigned long long fell[2] = {0, 0};
+    CK(hipMemcpyAsync(fell, counters, sizeof(fell), hipMemcpyDeviceToHost, h->stream));
+    CK(hipStreamSynchronize(h->stream));
+    CK(hipEventElapsedTime(&h->last_ms, h->ev0, h->ev1));
+    h->d2h_small += launches + 2;
+    h->turn_work[0] = launches; h->turn_work[1] = visits; h->turn_work[2] = (long long)fell[0];
+    if (fell[1]) return failmsg(h, me + ": internal: sweep bound");
+    return 0;
+  };
+  return run() ? -1 : 0;
+}
+
+int pf_turn_field_work(pf_handle* h, int64_t* out4) {
+  if (!h) return -2;
+  if (!out4) { failmsg(h, "pf_turn_field_work: bad arguments (the four words must not be null)"); return -1; }
+  for (int i = 0; i < 4; ++i) out4[i] = h->turn_work[i];
+  return 0;
+}
+
+int pf_turn_field_paths(pf_handle* h, const double* d_cost, double turn_weight, int32_t B, const double* d_states, int32_t n, const int32_t* d_set_idx,
+                        const int32_t* d_target, int32_t reverse, int32_t path_cap, int32_t* d_cells, int32_t* d_len, int32_t* d_status) {
+  if (!h) return -2;
+  if (B < 1 || n < 0 || path_cap < 1 || !d_states || !d_set_idx || !d_target || !d_cells || !d_len || !d_status) {
+    failmsg(h, "pf_turn_field_paths: bad arguments (B >= 1, n >= 0, path_cap >= 1; the states, the set indices, the targets, the rows, the lengths and the statuses must not be null)");
+    return -1;
+  }
+  if (turn_weight_check(h, "pf_turn_field_paths", turn_weight)) return -1;
+  if (n == 0) return 0;
+  auto run = [&]() -> int {
+    CK(hipSetDevice(h->device));
+    return timed(h, [&] {
+      hipLaunchKernelGGL(k_turn_trace_query_lanes, dim3(((unsigned)n + PF_FP_TRACE_THREADS - 1) / PF_FP_TRACE_THREADS), dim3(PF_FP_TRACE_THREADS), 0, h->stream, d_cost,
+                         turn_weight, h->R, h->C, (int)B, d_states, (int)n, (const int*)d_set_idx, (const int*)d_target, reverse ? 1 : 0, (int)path_cap, (int*)d_cells,
+                         (int*)d_len, (int*)d_status);
+    });
+  };
+  return run() ? -1 : 0;
+}
+
+int pf_turn_paths(pf_handle* h, const double* d_cost, double turn_weight, int32_t n, int32_t path_cap, const int32_t* d_cells, const int32_t* d_len, double* d_total,
+                  int32_t* d_turns, int32_t* d_bad) {
+  if (!h) return -2;
+  if (n < 0 || path_cap < 1 || !d_cells || !d_len || !d_total || !d_turns || !d_bad) {
+    failmsg(h, "pf_turn_paths: bad arguments (n >= 0, path_cap >= 1; the rows, the lengths, the totals, the turn counts and the step indices must not be null)");
+    return -1;
+  }
+  if (turn_weight_check(h, "pf_turn_paths", turn_weight)) return -1;
+  if (n == 0) return 0;
+  auto run = [&]() -> int {
+    CK(hipSetDevice(h->device));
+    return timed(h, [&] {
+      hipLaunchKernelGGL(k_turn_paths_one_wave_per_row, dim3((unsigned)n), dim3(64), 0, h->stream, d_cost, turn_weight, h->RC, h->C, (int)n, (int)path_cap,
+                         (const int*)d_cells, (const int*)d_len, d_total, (int*)d_turns, (int*)d_bad);
     });
   };
   return run() ? -1 : 0;

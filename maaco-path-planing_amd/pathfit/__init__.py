@@ -22,3 +22,4 @@ from .smooth import PathSmoother  # noqa: F401
 from .components import Components  # noqa: F401
 from .clearance import Clearance, PF_CLEAR_NONE  # noqa: F401
 from .cost_field import CostField  # noqa: F401
+from .turn_field import TurnField  # noqa: F401

@@ -401,6 +401,42 @@ class Engine:
                                       d_len.ptr if d_len else None, d_total.ptr if d_total else None, d_bad.ptr if d_bad else None))
         self._logk("cost_paths")
 
+    # ------------------------------------------------------------------ turn fields
+    def turn_field(self, d_cost, turn_weight, set_off, sources, d_states, d_best, allow_diag=True, restrict_corner=True, d_info=None):
+        """Source SETS (host int32 CSR, as dist_field_merged's), a cost map in HBM or None (cost 1 everywhere) and a turn weight in
+        [0, 2^20] -> d_states float64 [B, 8, R * C]: the cheapest cost of a walk from a source of the set that enters the cell by
+        move d, a move weighing as cost_field's plus turn_weight when it differs from the move before; d_best float64 [B, R * C]:
+        the smallest of the eight; d_info int64 [B, 4] as cost_field's, counted on d_best (pf_turn_field)."""
+        off = np.ascontiguousarray(set_off, np.int32).reshape(-1)
+        src = np.ascontiguousarray(sources, np.int32).reshape(-1)
+        self._ck(self.L.pf_turn_field(self.h, int(bool(allow_diag)), int(bool(restrict_corner)), d_cost.ptr if d_cost else None, float(turn_weight),
+                                      int(off.size) - 1, off.ctypes.data if off.size else None, src.ctypes.data if src.size else None,
+                                      d_states.ptr if d_states else None, d_best.ptr if d_best else None, d_info.ptr if d_info else None))
+        self._logk("turn_field")
+
+    def turn_field_work(self):
+        """(launches, tile visits, state words lowered, 0) of the last turn_field call: they depend on the schedule (the probe's figures)."""
+        out = (C.c_int64 * 4)()
+        self._ck(self.L.pf_turn_field_work(self.h, out))
+        return tuple(int(v) for v in out)
+
+    def turn_field_paths(self, d_cost, turn_weight, B, d_states, d_set_idx, d_target, n, path_cap, d_cells, d_len, d_status, reverse=False):
+        """n queries (d_set_idx[q], d_target[q]) chased through the states of turn_field (the same cost map and turn weight) into
+        rows laid out as astar_batch's: the route whose cost is d_best at the target (pf_turn_field_paths)."""
+        self._ck(self.L.pf_turn_field_paths(self.h, d_cost.ptr if d_cost else None, float(turn_weight), int(B), d_states.ptr if d_states else None, int(n),
+                                            d_set_idx.ptr if d_set_idx else None, d_target.ptr if d_target else None, int(bool(reverse)), int(path_cap),
+                                            d_cells.ptr if d_cells else None, d_len.ptr if d_len else None, d_status.ptr if d_status else None))
+        self._logk("turn_field_paths")
+
+    def turn_paths(self, d_cost, turn_weight, n, path_cap, d_cells, d_len, d_total, d_turns, d_bad):
+        """Rows of astar_batch's layout in HBM -> d_total float64 [n], the left-to-right sum of the moves' weights plus turn_weight
+        per turn (NaN for a bad row), d_turns int32 [n], the turns, and d_bad int32 [n], the first step that is no king move
+        inside the grid or -1 (pf_turn_paths)."""
+        self._ck(self.L.pf_turn_paths(self.h, d_cost.ptr if d_cost else None, float(turn_weight), int(n), int(path_cap), d_cells.ptr if d_cells else None,
+                                      d_len.ptr if d_len else None, d_total.ptr if d_total else None, d_turns.ptr if d_turns else None,
+                                      d_bad.ptr if d_bad else None))
+        self._logk("turn_paths")
+
     # ------------------------------------------------------------------ K1
     def score_batch(self, n, path_cap, d_cells, d_len, d_stats, sp):
         """Rows of astar_batch's layout in HBM -> d_stats [n, 5] doubles (pf_score_batch)."""
