@@ -521,9 +521,109 @@ int pf_clearance_segments(pf_handle* h, const int32_t* d_d2, int32_t touched, in
 }  // extern "C"
 
 // ---------------------------------------------------------------------------
+// The tile-queue engine's host half (pf_tile_queue.h), shared by the widest, cost and turn fields: one call's
+// view of the handle's scratch block, the round loop that reads a queue length after every launch, and the call's closing.  The
+// block is the handle's (grown when a call needs more); nothing in it outlives a call and every call lays it out anew for its own
+// B and tile.  A field's entry point supplies its checks, the fill of its rows, its seed launch, its relax launch and its info.
+// ---------------------------------------------------------------------------
+#include "pf_tile_queue.h"
+
+struct TileCall {
+  int B, tiles_x, tiles_y, ntiles;
+  size_t T, nsets;                                                  // queue entries (B * ntiles); words of off [B + 1] and ids
+  unsigned long long *moved, *top, *cells, *nsrc;                   // {words moved, an error word} | a field's own [B] | cells [B] | sources [B]
+  int *count, *arg, *d_off, *d_src, *queue, *flag;                  // queue lengths [2], the offending cell, spare | arg [B] | off, ids | queues [2][T] | flags [2][T]
+  unsigned seed_gx, gy;                                             // the seed kernel's grid for 256 threads, and the sets' grid dimension
+  long long* work;                                                  // the handle's work words of this entry point
+  long long launches = 0, visits = 0;
+  unsigned long long end[2] = {0, 0};                               // the two words at `moved` when the call ends
+};
+
+// one round's kernel arguments: the current queue, and the queue, flags and length the launch fills
+struct TileRound { const int* queue; int n, first; int *flag_now, *count_now, *flag_next, *queue_next, *count_next; };
+
+// Lays the block out for B sets and a tile of TW x TH cells and clears the work words (sets: nearest_sets_check's)
+static int tile_call(pf_handle* h, const std::string& me, int B, const std::vector<int>& sets, int TW, int TH, long long* work, TileCall& k) {
+  k.B = B;
+  k.tiles_x = (h->C + TW - 1) / TW; k.tiles_y = (h->R + TH - 1) / TH; k.ntiles = k.tiles_x * k.tiles_y;
+  if ((long long)B * k.ntiles >= 0x7FFFFFFFll) return failmsg(h, me + ": bad arguments (B times the number of tiles must stay below 2^31 - 1)");
+  k.T = (size_t)B * (size_t)k.ntiles; k.nsets = sets.size() - 1;     // (sets[0] is the nearest fields' error word: not uploaded)
+  const size_t n64 = 2 + 3 * (size_t)B;
+  if (scratch(h, me, h->d_widest, &h->widest_bytes, sizeof(unsigned long long) * n64 + sizeof(int) * (4 + (size_t)B + k.nsets + 4 * k.T), "the scratch words", true)) return -2;
+  k.moved = (unsigned long long*)h->d_widest;
+  k.top = k.moved + 2;
+  k.cells = k.top + B;
+  k.nsrc = k.cells + B;
+  k.count = (int*)(k.nsrc + B);
+  k.arg = k.count + 4;
+  k.d_off = k.arg + B;
+  k.d_src = k.d_off + B + 1;
+  k.queue = k.d_off + k.nsets;
+  k.flag = k.queue + 2 * k.T;
+  int most_src = 1;
+  for (int b = 0; b < B; ++b) most_src = std::max(most_src, sets[b + 2] - sets[b + 1]);
+  k.seed_gx = (unsigned)std::min((most_src + 255) / 256, 64);
+  k.gy = (unsigned)(B < 65535 ? B : 65535);
+  k.work = work;
+  work[0] = work[1] = work[2] = work[3] = 0;
+  return 0;
+}
+
+// Clears the block's counters, queue lengths and flags (the field's own [B] words to top_byte) and uploads the sets
+static int tile_upload(pf_handle* h, const TileCall& k, const std::vector<int>& sets, int top_byte) {
+  CK(hipMemsetAsync(k.moved, 0, sizeof(unsigned long long) * (2 + 3 * (size_t)k.B) + sizeof(int) * 2, h->stream));   // counters, top, cells, sources, queue lengths
+  if (top_byte) CK(hipMemsetAsync(k.top, top_byte, sizeof(unsigned long long) * (size_t)k.B, h->stream));
+  CK(hipMemsetAsync(k.arg, 0x7F, sizeof(int) * (size_t)k.B, h->stream));   // (any word above every cell id: 2^24 cells at most, as the level kernel's)
+  CK(hipMemsetAsync(k.flag, 0, sizeof(int) * 2 * k.T, h->stream));
+  CK(hipMemcpyAsync(k.d_off, sets.data() + 1, sizeof(int) * k.nsets, hipMemcpyHostToDevice, h->stream));
+  CK(hipStreamSynchronize(h->stream));                              // (sets is pageable and leaves scope)
+  return 0;
+}
+
+// The rounds, after the seed launch: launch(r) enqueues one relax kernel over r.n queued tiles; the host reads the next queue's
+// length after each and stops at 0.  Queues, flags and lengths alternate by the round's parity.
+template <typename F>
+static int tile_rounds(pf_handle* h, const std::string& me, TileCall& k, long long round_bound, F&& launch) {
+  CK(hipGetLastError());
+  int n = 0;
+  CK(hipMemcpyAsync(&n, k.count, sizeof(int), hipMemcpyDeviceToHost, h->stream));
+  CK(hipStreamSynchronize(h->stream));
+  for (long long round = 0; n > 0; ++round) {
+    if (round > round_bound) return failmsg(h, me + ": internal: round bound");
+    if (n < 0 || (size_t)n > k.T) return failmsg(h, me + ": internal: queue bound");
+    const size_t now = (size_t)(round & 1) * k.T, next = k.T - now;
+    const int p = (int)(round & 1);
+    launch(TileRound{k.queue + now, n, round == 0 ? 1 : 0, k.flag + now, k.count + p, k.flag + next, k.queue + next, k.count + (p ^ 1)});
+    CK(hipGetLastError());
+    k.launches += 1; k.visits += n;
+    CK(hipMemcpyAsync(&n, k.count + (p ^ 1), sizeof(int), hipMemcpyDeviceToHost, h->stream));
+    CK(hipStreamSynchronize(h->stream));
+  }
+  return 0;
+}
+
+// The end of a call: ev1, the block's two counters, last_ms, the copies made (one per launch, the seed's and this one) and the work words
+static int tile_finish(pf_handle* h, TileCall& k) {
+  CK(hipGetLastError());
+  CK(hipEventRecord(h->ev1, h->stream));
+  CK(hipMemcpyAsync(k.end, k.moved, sizeof(k.end), hipMemcpyDeviceToHost, h->stream));
+  CK(hipStreamSynchronize(h->stream));
+  CK(hipEventElapsedTime(&h->last_ms, h->ev0, h->ev1));
+  h->d2h_small += k.launches + 2;
+  k.work[0] = k.launches; k.work[1] = k.visits; k.work[2] = (long long)k.end[0];
+  return 0;
+}
+
+static int tile_work(pf_handle* h, const char* who, const long long* work, int64_t* out4) {
+  if (!h) return -2;
+  if (!out4) { failmsg(h, std::string(who) + ": bad arguments (the four words must not be null)"); return -1; }
+  for (int i = 0; i < 4; ++i) out4[i] = work[i];
+  return 0;
+}
+
+// ---------------------------------------------------------------------------
 // Widest-path fields over a clearance field (pf_widest.h).  Reads the caller's d2 only, never the handle's
-// occupancy or masks; the handle keeps the scratch block (grown when a call needs more) and the last call's work counters.
-// The round loop reads a queue length after every launch, so its timing stays spelled out here.
+// occupancy or masks; the handle keeps the last call's work counters.  Rounds and scratch: the tile-queue engine's, above.
 // ---------------------------------------------------------------------------
 #include "pf_widest.h"
 
@@ -539,87 +639,75 @@ int pf_clearance_widest(pf_handle* h, int32_t allow_diag, int32_t restrict_corne
     if (!d_d2 || !d_out) return failmsg(h, me + ": bad arguments (the field and the rows must not be null)");
     CK(hipSetDevice(h->device));
     const int R = h->R, C = h->C, RC = h->RC;
-    const int tiles_x = (C + PF_WD_TW - 1) / PF_WD_TW, tiles_y = (R + PF_WD_TH - 1) / PF_WD_TH, ntiles = tiles_x * tiles_y;
-    if ((long long)B * ntiles >= 0x7FFFFFFFll) return failmsg(h, me + ": bad arguments (B times the number of tiles must stay below 2^31 - 1)");
-    const size_t T = (size_t)B * (size_t)ntiles, nsets = sets.size() - 1;   // (sets[0] is the nearest fields' error word: not uploaded)
-    // the block: {words raised, spare} | keys [B] | cells [B] | sources [B] | queue lengths [2] + 2 spare | off [B + 1], ids | queues [2][T] | flags [2][T]
-    const size_t n64 = 2 + 3 * (size_t)B;
-    if (scratch(h, me, h->d_widest, &h->widest_bytes, sizeof(unsigned long long) * n64 + sizeof(int) * (4 + nsets + 4 * T), "the scratch words", true)) return -2;
-    unsigned long long* const raised = (unsigned long long*)h->d_widest;
-    unsigned long long* const keys = raised + 2;
-    unsigned long long* const cells = keys + B;
-    unsigned long long* const nsrc = cells + B;
-    int* const count = (int*)(nsrc + B);
-    int* const d_off = count + 4;
-    int* const d_src = d_off + B + 1;
-    int* const queue = d_off + nsets;
-    int* const flag = queue + 2 * T;
-    h->widest_work[0] = h->widest_work[1] = h->widest_work[2] = h->widest_work[3] = 0;
+    TileCall k;                                                       // top: the smallest (w << 32) | id per set, preset to all ones
+    if (const int rc = tile_call(h, me, B, sets, PF_WD_TW, PF_WD_TH, h->widest_work, k)) return rc;
     CK(hipEventRecord(h->ev0, h->stream));
-    CK(hipMemsetAsync(raised, 0, sizeof(unsigned long long) * 2, h->stream));
-    CK(hipMemsetAsync(keys, 0xFF, sizeof(unsigned long long) * (size_t)B, h->stream));
-    CK(hipMemsetAsync(cells, 0, sizeof(unsigned long long) * 2 * (size_t)B + sizeof(int) * 4, h->stream));   // cells, sources, queue lengths
-    CK(hipMemsetAsync(flag, 0, sizeof(int) * 2 * T, h->stream));
     CK(hipMemsetAsync(d_out, 0, sizeof(int) * (size_t)B * (size_t)RC, h->stream));
-    CK(hipMemcpyAsync(d_off, sets.data() + 1, sizeof(int) * nsets, hipMemcpyHostToDevice, h->stream));
-    CK(hipStreamSynchronize(h->stream));                            // (sets is pageable and leaves scope)
-    int most_src = 1;
-    for (int b = 0; b < B; ++b) most_src = std::max(most_src, set_off[b + 1] - set_off[b]);
-    const unsigned gy = (unsigned)(B < 65535 ? B : 65535);
-    hipLaunchKernelGGL(k_widest_seed_sets, dim3((unsigned)std::min((most_src + PF_WD_THREADS - 1) / PF_WD_THREADS, 64), gy), dim3(PF_WD_THREADS), 0, h->stream,
-                       (const int*)d_d2, RC, C, tiles_x, ntiles, (int)B, (const int*)d_off, (const int*)d_src, (int*)d_out, flag, queue, count, nsrc);
-    CK(hipGetLastError());
-    int n = 0;
-    CK(hipMemcpyAsync(&n, count, sizeof(int), hipMemcpyDeviceToHost, h->stream));
-    CK(hipStreamSynchronize(h->stream));
-    long long launches = 0, visits = 0;
-    for (long long round = 0; n > 0; ++round) {
-      if (round > (long long)RC) return failmsg(h, me + ": internal: round bound");
-      if (n < 0 || (size_t)n > T) return failmsg(h, me + ": internal: queue bound");
-      const int p = (int)(round & 1);
-      hipLaunchKernelGGL(k_widest_relax_tiles_in_lds, dim3((unsigned)n), dim3(PF_WD_THREADS), 0, h->stream, (const int*)d_d2, R, C, allow_diag ? 1 : 0,
-                         restrict_corner ? 1 : 0, tiles_x, tiles_y, (int*)d_out, (const int*)(queue + (size_t)p * T), n, round == 0 ? 1 : 0, flag + (size_t)p * T, count + p,
-                         flag + (size_t)(p ^ 1) * T, queue + (size_t)(p ^ 1) * T, count + (p ^ 1), raised);
-      CK(hipGetLastError());
-      launches += 1; visits += n;
-      CK(hipMemcpyAsync(&n, count + (p ^ 1), sizeof(int), hipMemcpyDeviceToHost, h->stream));
-      CK(hipStreamSynchronize(h->stream));
-    }
+    if (tile_upload(h, k, sets, 0xFF)) return -2;
+    hipLaunchKernelGGL(k_widest_seed_sets, dim3(k.seed_gx, k.gy), dim3(PF_WD_THREADS), 0, h->stream, (const int*)d_d2, RC, C, k.tiles_x, k.ntiles, (int)B,
+                       (const int*)k.d_off, (const int*)k.d_src, (int*)d_out, k.flag, k.queue, k.count, k.nsrc);
+    if (const int rc = tile_rounds(h, me, k, RC, [&](const TileRound& r) {
+          hipLaunchKernelGGL(k_widest_relax_tiles_in_lds, dim3((unsigned)r.n), dim3(PF_WD_THREADS), 0, h->stream, (const int*)d_d2, R, C, allow_diag ? 1 : 0,
+                             restrict_corner ? 1 : 0, k.tiles_x, k.tiles_y, (int*)d_out, r.queue, r.n, r.first, r.flag_now, r.count_now, r.flag_next, r.queue_next,
+                             r.count_next, k.moved);
+        })) return rc;
     if (d_info) {
       const unsigned nb = (unsigned)((RC + PF_WD_THREADS - 1) / PF_WD_THREADS);
-      hipLaunchKernelGGL(k_widest_info_sum, dim3(nb < 1024u ? nb : 1024u, gy), dim3(PF_WD_THREADS), 0, h->stream, (const int*)d_out, RC, (int)B, keys, cells);
+      hipLaunchKernelGGL(k_widest_info_sum, dim3(nb < 1024u ? nb : 1024u, k.gy), dim3(PF_WD_THREADS), 0, h->stream, (const int*)d_out, RC, (int)B, k.top, k.cells);
       hipLaunchKernelGGL(k_widest_write_info, dim3(((unsigned)B + PF_WD_THREADS - 1) / PF_WD_THREADS), dim3(PF_WD_THREADS), 0, h->stream, (int)B,
-                         (const unsigned long long*)keys, (const unsigned long long*)cells, (const unsigned long long*)nsrc, (long long*)d_info);
-      CK(hipGetLastError());
+                         (const unsigned long long*)k.top, (const unsigned long long*)k.cells, (const unsigned long long*)k.nsrc, (long long*)d_info);
     }
-    CK(hipEventRecord(h->ev1, h->stream));
-    unsigned long long words = 0;
-    CK(hipMemcpyAsync(&words, raised, sizeof(words), hipMemcpyDeviceToHost, h->stream));
-    CK(hipStreamSynchronize(h->stream));
-    CK(hipEventElapsedTime(&h->last_ms, h->ev0, h->ev1));
-    h->d2h_small += launches + 2;
-    h->widest_work[0] = launches; h->widest_work[1] = visits; h->widest_work[2] = (long long)words;
-    return 0;
+    return tile_finish(h, k);
   };
   return run() ? -1 : 0;
 }
 
-int pf_clearance_widest_work(pf_handle* h, int64_t* out4) {
-  if (!h) return -2;
-  if (!out4) { failmsg(h, "pf_clearance_widest_work: bad arguments (the four words must not be null)"); return -1; }
-  for (int i = 0; i < 4; ++i) out4[i] = h->widest_work[i];
-  return 0;
-}
+int pf_clearance_widest_work(pf_handle* h, int64_t* out4) { return tile_work(h, "pf_clearance_widest_work", h ? h->widest_work : nullptr, out4); }
 
 }  // extern "C"
 
 // ---------------------------------------------------------------------------
 // Cost fields: exact weighted shortest paths over a per-cell cost map (pf_cost_field.h).  The occupancy and the
-// masks are read at call time (pf_update_grid keeps working).  The field call works in the widest paths' scratch block (nothing
-// in it outlives a call, each call lays it out anew); the handle keeps the last call's work counters.  The round loop is the
-// widest paths' in shape: one queue length read per launch.
+// masks are read at call time (pf_update_grid keeps working).  The handle keeps the last call's work counters.  Rounds and
+// scratch: the tile-queue engine's, over the widest paths' tile.
 // ---------------------------------------------------------------------------
 #include "pf_cost_field.h"
+
+// The costs of the free cells, before any output is touched: `word` (device) takes the smallest offending cell.  ev0, where given,
+// is recorded behind the upload of the word.  One small copy back.
+static int cost_map_check(pf_handle* h, const std::string& me, const double* d_cost, int* word, hipEvent_t ev0) {
+  const int RC = h->RC, C = h->C;
+  const unsigned nb = (unsigned)((RC + PF_CF_THREADS - 1) / PF_CF_THREADS);
+  int bad = 0x7FFFFFFF;
+  CK(hipMemcpyAsync(word, &bad, sizeof(int), hipMemcpyHostToDevice, h->stream));
+  CK(hipStreamSynchronize(h->stream));
+  if (ev0) CK(hipEventRecord(ev0, h->stream));
+  hipLaunchKernelGGL(k_cost_validate_free_cells, dim3(nb < 2048u ? nb : 2048u), dim3(PF_CF_THREADS), 0, h->stream, (const uint8_t*)h->d_occ, d_cost, RC, word);
+  CK(hipGetLastError());
+  CK(hipMemcpyAsync(&bad, word, sizeof(int), hipMemcpyDeviceToHost, h->stream));
+  CK(hipStreamSynchronize(h->stream));
+  h->d2h_small += 1;
+  if (bad != 0x7FFFFFFF)
+    return failmsg(h, me + ": bad arguments (the cost of the free cell (" + std::to_string(bad / C) + ", " + std::to_string(bad % C) +
+                          ") is not a finite number in [1, 2^20])");
+  return 0;
+}
+
+// rows [n] become +inf
+static void cost_fill_inf(pf_handle* h, double* rows, size_t n) {
+  hipLaunchKernelGGL(k_cost_fill_inf, dim3((unsigned)std::min<size_t>((n + PF_CF_THREADS - 1) / PF_CF_THREADS, 4096)), dim3(PF_CF_THREADS), 0, h->stream,
+                     (unsigned long long*)rows, n);
+}
+
+// info [B][4] of the rows [B][RC] of a call: top takes the largest finite label per set
+static void cost_info(pf_handle* h, const TileCall& k, const double* rows, int64_t* d_info) {
+  const int RC = h->RC;
+  const unsigned nb = (unsigned)((RC + PF_CF_THREADS - 1) / PF_CF_THREADS);
+  hipLaunchKernelGGL(k_cost_info_largest, dim3(nb < 1024u ? nb : 1024u, k.gy), dim3(PF_CF_THREADS), 0, h->stream, rows, RC, k.B, k.top, k.cells);
+  hipLaunchKernelGGL(k_cost_info_arg, dim3(nb < 1024u ? nb : 1024u, k.gy), dim3(PF_CF_THREADS), 0, h->stream, rows, RC, k.B, (const unsigned long long*)k.top, k.arg);
+  hipLaunchKernelGGL(k_cost_write_info, dim3(((unsigned)k.B + PF_CF_THREADS - 1) / PF_CF_THREADS), dim3(PF_CF_THREADS), 0, h->stream, k.B,
+                     (const unsigned long long*)k.cells, (const unsigned long long*)k.nsrc, (const int*)k.arg, (long long*)d_info);
+}
 
 extern "C" {
 
@@ -633,93 +721,26 @@ int pf_cost_field(pf_handle* h, int32_t allow_diag, int32_t restrict_corner, con
     if (!d_cost || !d_out) return failmsg(h, me + ": bad arguments (the cost map and the rows must not be null)");
     CK(hipSetDevice(h->device));
     const int R = h->R, C = h->C, RC = h->RC;
-    const int tiles_x = (C + PF_WD_TW - 1) / PF_WD_TW, tiles_y = (R + PF_WD_TH - 1) / PF_WD_TH, ntiles = tiles_x * tiles_y;
-    if ((long long)B * ntiles >= 0x7FFFFFFFll) return failmsg(h, me + ": bad arguments (B times the number of tiles must stay below 2^31 - 1)");
-    const size_t T = (size_t)B * (size_t)ntiles, nsets = sets.size() - 1;   // (sets[0] is the nearest fields' error word: not uploaded)
-    // the block: {words lowered, spare} | largest [B] | cells [B] | sources [B] | queue lengths [2], the offending cell, spare | arg [B] | off [B + 1], ids | queues [2][T] | flags [2][T]
-    const size_t n64 = 2 + 3 * (size_t)B;
-    if (scratch(h, me, h->d_widest, &h->widest_bytes, sizeof(unsigned long long) * n64 + sizeof(int) * (4 + (size_t)B + nsets + 4 * T), "the scratch words", true)) return -2;
-    unsigned long long* const lowered = (unsigned long long*)h->d_widest;
-    unsigned long long* const largest = lowered + 2;
-    unsigned long long* const cells = largest + B;
-    unsigned long long* const nsrc = cells + B;
-    int* const count = (int*)(nsrc + B);
-    int* const arg = count + 4;
-    int* const d_off = arg + B;
-    int* const d_src = d_off + B + 1;
-    int* const queue = d_off + nsets;
-    int* const flag = queue + 2 * T;
-    h->cost_work[0] = h->cost_work[1] = h->cost_work[2] = h->cost_work[3] = 0;
-    const unsigned nb = (unsigned)((RC + PF_CF_THREADS - 1) / PF_CF_THREADS), gy = (unsigned)(B < 65535 ? B : 65535);
-    // the costs of the free cells, before any output is touched
-    int bad = 0x7FFFFFFF;
-    CK(hipMemcpyAsync(count + 2, &bad, sizeof(int), hipMemcpyHostToDevice, h->stream));
-    CK(hipStreamSynchronize(h->stream));
-    CK(hipEventRecord(h->ev0, h->stream));
-    hipLaunchKernelGGL(k_cost_validate_free_cells, dim3(nb < 2048u ? nb : 2048u), dim3(PF_CF_THREADS), 0, h->stream, (const uint8_t*)h->d_occ, d_cost, RC, count + 2);
-    CK(hipGetLastError());
-    CK(hipMemcpyAsync(&bad, count + 2, sizeof(int), hipMemcpyDeviceToHost, h->stream));
-    CK(hipStreamSynchronize(h->stream));
-    h->d2h_small += 1;
-    if (bad != 0x7FFFFFFF)
-      return failmsg(h, me + ": bad arguments (the cost of the free cell (" + std::to_string(bad / C) + ", " + std::to_string(bad % C) +
-                            ") is not a finite number in [1, 2^20])");
-    CK(hipMemsetAsync(lowered, 0, sizeof(unsigned long long) * n64 + sizeof(int) * 2, h->stream));   // counters, largest, cells, sources, queue lengths
-    CK(hipMemsetAsync(arg, 0x7F, sizeof(int) * (size_t)B, h->stream));   // (any word above every cell id: 2^24 cells at most, as the level kernel's)
-    CK(hipMemsetAsync(flag, 0, sizeof(int) * 2 * T, h->stream));
-    CK(hipMemcpyAsync(d_off, sets.data() + 1, sizeof(int) * nsets, hipMemcpyHostToDevice, h->stream));
-    CK(hipStreamSynchronize(h->stream));                            // (sets is pageable and leaves scope)
-    const size_t words = (size_t)B * (size_t)RC;
-    hipLaunchKernelGGL(k_cost_fill_inf, dim3((unsigned)std::min<size_t>((words + PF_CF_THREADS - 1) / PF_CF_THREADS, 4096)), dim3(PF_CF_THREADS), 0, h->stream,
-                       (unsigned long long*)d_out, words);
-    int most_src = 1;
-    for (int b = 0; b < B; ++b) most_src = std::max(most_src, set_off[b + 1] - set_off[b]);
-    hipLaunchKernelGGL(k_cost_seed_sets, dim3((unsigned)std::min((most_src + PF_CF_THREADS - 1) / PF_CF_THREADS, 64), gy), dim3(PF_CF_THREADS), 0, h->stream,
-                       (const uint8_t*)h->d_occ, RC, C, tiles_x, ntiles, (int)B, (const int*)d_off, (const int*)d_src, d_out, flag, queue, count, nsrc);
-    CK(hipGetLastError());
-    int n = 0;
-    CK(hipMemcpyAsync(&n, count, sizeof(int), hipMemcpyDeviceToHost, h->stream));
-    CK(hipStreamSynchronize(h->stream));
+    TileCall k;                                                       // top: the largest finite label's bits per set
+    if (const int rc = tile_call(h, me, B, sets, PF_WD_TW, PF_WD_TH, h->cost_work, k)) return rc;
+    if (const int rc = cost_map_check(h, me, d_cost, k.count + 2, h->ev0)) return rc;
+    if (tile_upload(h, k, sets, 0)) return -2;
+    cost_fill_inf(h, d_out, (size_t)B * (size_t)RC);
+    hipLaunchKernelGGL(k_cost_seed_sets, dim3(k.seed_gx, k.gy), dim3(PF_CF_THREADS), 0, h->stream, (const uint8_t*)h->d_occ, RC, C, k.tiles_x, k.ntiles, (int)B,
+                       (const int*)k.d_off, (const int*)k.d_src, d_out, k.flag, k.queue, k.count, k.nsrc);
     const uint8_t* mm = move_mask(h, allow_diag, restrict_corner);
-    long long launches = 0, visits = 0;
-    for (long long round = 0; n > 0; ++round) {
-      if (round > (long long)RC + 1) return failmsg(h, me + ": internal: round bound");
-      if (n < 0 || (size_t)n > T) return failmsg(h, me + ": internal: queue bound");
-      const int p = (int)(round & 1);
-      hipLaunchKernelGGL(k_cost_relax_tiles_in_lds, dim3((unsigned)n), dim3(PF_CF_THREADS), 0, h->stream, (const uint8_t*)h->d_occ, mm, d_cost, R, C, allow_diag ? 1 : 0, tiles_x, tiles_y, d_out,
-                         (const int*)(queue + (size_t)p * T), n, round == 0 ? 1 : 0, flag + (size_t)p * T, count + p, flag + (size_t)(p ^ 1) * T,
-                         queue + (size_t)(p ^ 1) * T, count + (p ^ 1), lowered);
-      CK(hipGetLastError());
-      launches += 1; visits += n;
-      CK(hipMemcpyAsync(&n, count + (p ^ 1), sizeof(int), hipMemcpyDeviceToHost, h->stream));
-      CK(hipStreamSynchronize(h->stream));
-    }
-    if (d_info) {
-      hipLaunchKernelGGL(k_cost_info_largest, dim3(nb < 1024u ? nb : 1024u, gy), dim3(PF_CF_THREADS), 0, h->stream, (const double*)d_out, RC, (int)B, largest, cells);
-      hipLaunchKernelGGL(k_cost_info_arg, dim3(nb < 1024u ? nb : 1024u, gy), dim3(PF_CF_THREADS), 0, h->stream, (const double*)d_out, RC, (int)B,
-                         (const unsigned long long*)largest, arg);
-      hipLaunchKernelGGL(k_cost_write_info, dim3(((unsigned)B + PF_CF_THREADS - 1) / PF_CF_THREADS), dim3(PF_CF_THREADS), 0, h->stream, (int)B,
-                         (const unsigned long long*)cells, (const unsigned long long*)nsrc, (const int*)arg, (long long*)d_info);
-      CK(hipGetLastError());
-    }
-    CK(hipEventRecord(h->ev1, h->stream));
-    unsigned long long fell = 0;
-    CK(hipMemcpyAsync(&fell, lowered, sizeof(fell), hipMemcpyDeviceToHost, h->stream));
-    CK(hipStreamSynchronize(h->stream));
-    CK(hipEventElapsedTime(&h->last_ms, h->ev0, h->ev1));
-    h->d2h_small += launches + 2;
-    h->cost_work[0] = launches; h->cost_work[1] = visits; h->cost_work[2] = (long long)fell;
-    return 0;
+    if (const int rc = tile_rounds(h, me, k, (long long)RC + 1, [&](const TileRound& r) {
+          hipLaunchKernelGGL(k_cost_relax_tiles_in_lds, dim3((unsigned)r.n), dim3(PF_CF_THREADS), 0, h->stream, (const uint8_t*)h->d_occ, mm, d_cost, R, C,
+                             allow_diag ? 1 : 0, k.tiles_x, k.tiles_y, d_out, r.queue, r.n, r.first, r.flag_now, r.count_now, r.flag_next, r.queue_next, r.count_next,
+                             k.moved);
+        })) return rc;
+    if (d_info) cost_info(h, k, d_out, d_info);
+    return tile_finish(h, k);
   };
   return run() ? -1 : 0;
 }
 
-int pf_cost_field_work(pf_handle* h, int64_t* out4) {
-  if (!h) return -2;
-  if (!out4) { failmsg(h, "pf_cost_field_work: bad arguments (the four words must not be null)"); return -1; }
-  for (int i = 0; i < 4; ++i) out4[i] = h->cost_work[i];
-  return 0;
-}
+int pf_cost_field_work(pf_handle* h, int64_t* out4) { return tile_work(h, "pf_cost_field_work", h ? h->cost_work : nullptr, out4); }
 
 int pf_cost_field_parents(pf_handle* h, int32_t allow_diag, int32_t restrict_corner, const double* d_cost, int32_t K, const double* d_fields, uint8_t* d_parents) {
   if (!h) return -2;
@@ -765,10 +786,12 @@ int pf_cost_paths(pf_handle* h, const double* d_cost, int32_t n, int32_t path_ca
 
 // ---------------------------------------------------------------------------
 // Turn fields: the exact optimum of length plus a turn penalty over (cell, heading) states (pf_turn_field.h).
-// The cost fields' round loop over the turn tile (PF_TF_TW x PF_TF_TH); the scratch is the widest paths' block, laid out anew by
-// each call for this tile's queues; the handle keeps the last call's work counters.
+// The handle keeps the last call's work counters.  Rounds and scratch: the tile-queue engine's, over the turn tile (PF_TF_TW x
+// PF_TF_TH).
 // ---------------------------------------------------------------------------
 #include "pf_turn_field.h"
+
+static_assert(PF_WD_THREADS == 256 && PF_CF_THREADS == 256 && PF_TF_THREADS == 256, "tile_call sizes the seed grids for 256 threads");
 
 // a turn weight is a finite double in [0, 2^20] (NaN fails both comparisons)
 static int turn_weight_check(pf_handle* h, const std::string& me, double turn_weight) {
@@ -789,97 +812,32 @@ int pf_turn_field(pf_handle* h, int32_t allow_diag, int32_t restrict_corner, con
     if (turn_weight_check(h, me, turn_weight)) return -2;
     CK(hipSetDevice(h->device));
     const int R = h->R, C = h->C, RC = h->RC;
-    const int tiles_x = (C + PF_TF_TW - 1) / PF_TF_TW, tiles_y = (R + PF_TF_TH - 1) / PF_TF_TH, ntiles = tiles_x * tiles_y;
-    if ((long long)B * ntiles >= 0x7FFFFFFFll) return failmsg(h, me + ": bad arguments (B times the number of tiles must stay below 2^31 - 1)");
-    const size_t T = (size_t)B * (size_t)ntiles, nsets = sets.size() - 1;   // (sets[0] is the nearest fields' error word: not uploaded)
-    // the block: {words lowered, the sweep bound's error word} | largest [B] | cells [B] | sources [B] | queue lengths [2], the offending cell, spare | arg [B] | off [B + 1], ids | queues [2][T] | flags [2][T]
-    const size_t n64 = 2 + 3 * (size_t)B;
-    if (scratch(h, me, h->d_widest, &h->widest_bytes, sizeof(unsigned long long) * n64 + sizeof(int) * (4 + (size_t)B + nsets + 4 * T), "the scratch words", true)) return -2;
-    unsigned long long* const counters = (unsigned long long*)h->d_widest;
-    unsigned long long* const largest = counters + 2;
-    unsigned long long* const cells = largest + B;
-    unsigned long long* const nsrc = cells + B;
-    int* const count = (int*)(nsrc + B);
-    int* const arg = count + 4;
-    int* const d_off = arg + B;
-    int* const d_src = d_off + B + 1;
-    int* const queue = d_off + nsets;
-    int* const flag = queue + 2 * T;
-    h->turn_work[0] = h->turn_work[1] = h->turn_work[2] = h->turn_work[3] = 0;
-    const unsigned nb = (unsigned)((RC + PF_CF_THREADS - 1) / PF_CF_THREADS), gy = (unsigned)(B < 65535 ? B : 65535);
+    TileCall k;                                                       // top: the largest finite best label's bits per set; moved[1]: the sweep bound's error word
+    if (const int rc = tile_call(h, me, B, sets, PF_TF_TW, PF_TF_TH, h->turn_work, k)) return rc;
     CK(hipEventRecord(h->ev0, h->stream));
-    if (d_cost) {                                                     // the costs of the free cells, before any output is touched
-      int bad = 0x7FFFFFFF;
-      CK(hipMemcpyAsync(count + 2, &bad, sizeof(int), hipMemcpyHostToDevice, h->stream));
-      CK(hipStreamSynchronize(h->stream));
-      hipLaunchKernelGGL(k_cost_validate_free_cells, dim3(nb < 2048u ? nb : 2048u), dim3(PF_CF_THREADS), 0, h->stream, (const uint8_t*)h->d_occ, d_cost, RC, count + 2);
-      CK(hipGetLastError());
-      CK(hipMemcpyAsync(&bad, count + 2, sizeof(int), hipMemcpyDeviceToHost, h->stream));
-      CK(hipStreamSynchronize(h->stream));
-      h->d2h_small += 1;
-      if (bad != 0x7FFFFFFF)
-        return failmsg(h, me + ": bad arguments (the cost of the free cell (" + std::to_string(bad / C) + ", " + std::to_string(bad % C) +
-                              ") is not a finite number in [1, 2^20])");
-    }
-    CK(hipMemsetAsync(counters, 0, sizeof(unsigned long long) * n64 + sizeof(int) * 2, h->stream));   // counters, largest, cells, sources, queue lengths
-    CK(hipMemsetAsync(arg, 0x7F, sizeof(int) * (size_t)B, h->stream));   // (any word above every cell id)
-    CK(hipMemsetAsync(flag, 0, sizeof(int) * 2 * T, h->stream));
-    CK(hipMemcpyAsync(d_off, sets.data() + 1, sizeof(int) * nsets, hipMemcpyHostToDevice, h->stream));
-    CK(hipStreamSynchronize(h->stream));                            // (sets is pageable and leaves scope)
+    if (d_cost)
+      if (const int rc = cost_map_check(h, me, d_cost, k.count + 2, nullptr)) return rc;
+    if (tile_upload(h, k, sets, 0)) return -2;
     const size_t words = (size_t)B * (size_t)RC;
-    hipLaunchKernelGGL(k_cost_fill_inf, dim3((unsigned)std::min<size_t>((8 * words + PF_CF_THREADS - 1) / PF_CF_THREADS, 4096)), dim3(PF_CF_THREADS), 0, h->stream,
-                       (unsigned long long*)d_states, 8 * words);
-    hipLaunchKernelGGL(k_cost_fill_inf, dim3((unsigned)std::min<size_t>((words + PF_CF_THREADS - 1) / PF_CF_THREADS, 4096)), dim3(PF_CF_THREADS), 0, h->stream,
-                       (unsigned long long*)d_best, words);
-    int most_src = 1;
-    for (int b = 0; b < B; ++b) most_src = std::max(most_src, set_off[b + 1] - set_off[b]);
-    hipLaunchKernelGGL(k_turn_seed_sets, dim3((unsigned)std::min((most_src + PF_TF_THREADS - 1) / PF_TF_THREADS, 64), gy), dim3(PF_TF_THREADS), 0, h->stream,
-                       (const uint8_t*)h->d_occ, RC, C, tiles_x, ntiles, (int)B, (const int*)d_off, (const int*)d_src, d_states, d_best, flag, queue, count, nsrc);
-    CK(hipGetLastError());
-    int n = 0;
-    CK(hipMemcpyAsync(&n, count, sizeof(int), hipMemcpyDeviceToHost, h->stream));
-    CK(hipStreamSynchronize(h->stream));
+    cost_fill_inf(h, d_states, 8 * words);
+    cost_fill_inf(h, d_best, words);
+    hipLaunchKernelGGL(k_turn_seed_sets, dim3(k.seed_gx, k.gy), dim3(PF_TF_THREADS), 0, h->stream, (const uint8_t*)h->d_occ, RC, C, k.tiles_x, k.ntiles, (int)B,
+                       (const int*)k.d_off, (const int*)k.d_src, d_states, d_best, k.flag, k.queue, k.count, k.nsrc);
     const uint8_t* mm = move_mask(h, allow_diag, restrict_corner);
-    long long launches = 0, visits = 0;
-    for (long long round = 0; n > 0; ++round) {
-      if (round > 8 * (long long)RC + 1) return failmsg(h, me + ": internal: round bound");
-      if (n < 0 || (size_t)n > T) return failmsg(h, me + ": internal: queue bound");
-      const int p = (int)(round & 1);
-      hipLaunchKernelGGL(k_turn_relax_tiles_in_lds, dim3((unsigned)n), dim3(PF_TF_THREADS), 0, h->stream, (const uint8_t*)h->d_occ, mm, d_cost, turn_weight, R, C,
-                         allow_diag ? 1 : 0, tiles_x, tiles_y, d_states, d_best, (const int*)(queue + (size_t)p * T), n, round == 0 ? 1 : 0, flag + (size_t)p * T, count + p,
-                         flag + (size_t)(p ^ 1) * T, queue + (size_t)(p ^ 1) * T, count + (p ^ 1), counters);
-      CK(hipGetLastError());
-      launches += 1; visits += n;
-      CK(hipMemcpyAsync(&n, count + (p ^ 1), sizeof(int), hipMemcpyDeviceToHost, h->stream));
-      CK(hipStreamSynchronize(h->stream));
-    }
-    if (d_info) {
-      hipLaunchKernelGGL(k_cost_info_largest, dim3(nb < 1024u ? nb : 1024u, gy), dim3(PF_CF_THREADS), 0, h->stream, (const double*)d_best, RC, (int)B, largest, cells);
-      hipLaunchKernelGGL(k_cost_info_arg, dim3(nb < 1024u ? nb : 1024u, gy), dim3(PF_CF_THREADS), 0, h->stream, (const double*)d_best, RC, (int)B,
-                         (const unsigned long long*)largest, arg);
-      hipLaunchKernelGGL(k_cost_write_info, dim3(((unsigned)B + PF_CF_THREADS - 1) / PF_CF_THREADS), dim3(PF_CF_THREADS), 0, h->stream, (int)B,
-                         (const unsigned long long*)cells, (const unsigned long long*)nsrc, (const int*)arg, (long long*)d_info);
-      CK(hipGetLastError());
-    }
-    CK(hipEventRecord(h->ev1, h->stream));
-    unsigned long long fell[2] = {0, 0};
-    CK(hipMemcpyAsync(fell, counters, sizeof(fell), hipMemcpyDeviceToHost, h->stream));
-    CK(hipStreamSynchronize(h->stream));
-    CK(hipEventElapsedTime(&h->last_ms, h->ev0, h->ev1));
-    h->d2h_small += launches + 2;
-    h->turn_work[0] = launches; h->turn_work[1] = visits; h->turn_work[2] = (long long)fell[0];
-    if (fell[1]) return failmsg(h, me + ": internal: sweep bound");
+    if (const int rc = tile_rounds(h, me, k, 8 * (long long)RC + 1, [&](const TileRound& r) {
+          hipLaunchKernelGGL(k_turn_relax_tiles_in_lds, dim3((unsigned)r.n), dim3(PF_TF_THREADS), 0, h->stream, (const uint8_t*)h->d_occ, mm, d_cost, turn_weight, R, C,
+                             allow_diag ? 1 : 0, k.tiles_x, k.tiles_y, d_states, d_best, r.queue, r.n, r.first, r.flag_now, r.count_now, r.flag_next, r.queue_next,
+                             r.count_next, k.moved);
+        })) return rc;
+    if (d_info) cost_info(h, k, d_best, d_info);
+    if (const int rc = tile_finish(h, k)) return rc;
+    if (k.end[1]) return failmsg(h, me + ": internal: sweep bound");
     return 0;
   };
   return run() ? -1 : 0;
 }
 
-int pf_turn_field_work(pf_handle* h, int64_t* out4) {
-  if (!h) return -2;
-  if (!out4) { failmsg(h, "pf_turn_field_work: bad arguments (the four words must not be null)"); return -1; }
-  for (int i = 0; i < 4; ++i) out4[i] = h->turn_work[i];
-  return 0;
-}
+int pf_turn_field_work(pf_handle* h, int64_t* out4) { return tile_work(h, "pf_turn_field_work", h ? h->turn_work : nullptr, out4); }
 
 int pf_turn_field_paths(pf_handle* h, const double* d_cost, double turn_weight, int32_t B, const double* d_states, int32_t n, const int32_t* d_set_idx,
                         const int32_t* d_target, int32_t reverse, int32_t path_cap, int32_t* d_cells, int32_t* d_len, int32_t* d_status) {

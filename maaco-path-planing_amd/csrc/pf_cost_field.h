@@ -11,7 +11,7 @@
 //   k_cost_validate_free_cells     a reduction over the free cells: the smallest cell id whose cost is not in [1, 2^20] (NaN fails
 //                                  both comparisons).  The host reads the word before anything is written: a refused call leaves
 //                                  every output untouched.
-//   k_cost_fill_inf / k_cost_seed_sets   the rows become +inf; one thread per listed source: skipped on an obstacle, an atomic
+//   k_cost_fill_inf / k_cost_seed_sets   the rows become +inf; one thread per listed source (tq_seed_sets): skipped on an obstacle, an atomic
 //                                  min of 0 on the label (the one that found +inf counts the source: listed twice counts once),
 //                                  and the source's tile goes on the first queue.
 //   k_cost_relax_tiles_in_lds      one workgroup per queued (set, tile), the tile of pf_widest.h (64 x 16 cells, four per thread):
@@ -22,9 +22,8 @@
 //                                  neighbour labels of its cells and forms min fl(D[u] + w); barrier; the cells that fell are
 //                                  written; barrier -- until one whole sweep lowers nothing: the tile's own fixed point under the
 //                                  halo it read.  It stores the words that fell and queues, for the next launch, the neighbour
-//                                  tiles that hold a lowered cell in their halo (a diagonal neighbour for a corner cell when
-//                                  diagonals are allowed).  In the first launch a tile also reports the seeds on its border.
-//                                  Queue entries are deduplicated by one flag word per (set, tile) and parity (wd_enqueue).
+//                                  tiles that hold a lowered cell in their halo.  Opening and closing the visit, the queues,
+//                                  flags and parity are pf_tile_queue.h's.
 //   k_cost_info_largest / _arg / k_cost_write_info   cells with a finite label and the largest finite label per set (one atomic
 //                                  max on the label's bits: non-negative doubles order as their bits), then the smallest cell
 //                                  that attains it, then the four words.
@@ -43,11 +42,10 @@
 // rounded cost of a real walk from a source.  Along any walk, fl(. + w) is monotone, so by induction over an OPTIMAL walk's
 // prefix order no walk's rounded cost lies below the least fixed point's label of its end: every stored value is >= the answer.
 // Nothing is ever summed ahead: there is no segment scan here (a pre-summed segment rounds differently).  (2) A halo word that
-// the neighbour tile is lowering in the same launch may be read old or new: the loads into LDS and the stores of the lowered
-// words are whole-word 64-bit agent-scope relaxed atomics and a label has ONE writer per launch (the flags admit a (set, tile)
-// once), so what is read was stored, and by (1) it is a valid upper bound.  Whoever lowers a border cell queues every tile that
-// holds it in its halo for the NEXT launch, and the kernel boundary makes the store visible.  When no tile is queued, every tile
-// was last relaxed from halo words that did not change afterwards: the whole row is a fixed point above the seeds.  (3) A fixed
+// the neighbour tile is lowering in the same launch may be read old or new: what is read was stored (cf_load, cf_store and the
+// seed's minimum are whole-word 64-bit agent-scope relaxed atomics), and by (1) it is a valid upper bound.  pf_tile_queue.h has
+// the rest of this half -- one writer per (set, tile) per launch, whoever lowers a border cell queues its readers for the next
+// launch, no other synchronisation --: when no tile is queued, the whole row is a fixed point above the seeds.  (3) A fixed
 // point with D[s] = 0 on the seeds is <= the least one's label along every optimal walk (induction along the walk, fl monotone),
 // so with (1) it IS the least fixed point, whatever the timing: identical run to run, bit for bit.
 //
@@ -96,21 +94,11 @@ __global__ __launch_bounds__(PF_CF_THREADS) void k_cost_seed_sets(const uint8_t*
                                                                     const int* __restrict__ off, const int* __restrict__ src, double* __restrict__ rows,
                                                                     int* __restrict__ flag, int* __restrict__ queue, int* __restrict__ count,
                                                                     unsigned long long* __restrict__ nsrc) {
-  for (int b = (int)blockIdx.y; b < B; b += (int)gridDim.y) {
-    const int end = off[b + 1];
-    int counted = 0;
-    for (int j = off[b] + (int)(blockIdx.x * PF_CF_THREADS + threadIdx.x); j < end; j += (int)(gridDim.x * PF_CF_THREADS)) {
-      const int s = src[j];
-      if ((unsigned)s >= (unsigned)RC) continue;                     // (the host has checked the ids)
-      if (occ[s] == 1) continue;                                     // a source ON an obstacle is no source
-      unsigned long long* const word = (unsigned long long*)(rows + (size_t)b * (size_t)RC + (size_t)s);
-      if (__hip_atomic_fetch_min(word, 0ull, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != PF_DF_INF_BITS) continue;   // listed twice
-      counted += 1;
-      const int r = s / C, c = s - r * C;
-      wd_enqueue(b * ntiles + (r / PF_WD_TH) * tiles_x + c / PF_WD_TW, flag, queue, count);
-    }
-    if (counted) atomicAdd(nsrc + b, (unsigned long long)counted);
-  }
+  tq_seed_sets<PF_CF_THREADS, PF_WD_TW, PF_WD_TH>(RC, C, tiles_x, ntiles, B, off, src, flag, queue, count, nsrc, [&](int b, int s) {
+    if (occ[s] == 1) return false;                                   // a source ON an obstacle is no source
+    unsigned long long* const word = (unsigned long long*)(rows + (size_t)b * (size_t)RC + (size_t)s);
+    return __hip_atomic_fetch_min(word, 0ull, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == PF_DF_INF_BITS;   // otherwise: listed twice
+  });
 }
 
 __global__ __launch_bounds__(PF_CF_THREADS) void k_cost_relax_tiles_in_lds(const uint8_t* __restrict__ occ, const uint8_t* __restrict__ mm, const double* __restrict__ cost, int R, int C, int allow_diag,
@@ -120,16 +108,13 @@ __global__ __launch_bounds__(PF_CF_THREADS) void k_cost_relax_tiles_in_lds(const
   constexpr int PER = PF_WD_TW * PF_WD_TH / PF_CF_THREADS, LW = PF_WD_LW, LN = PF_WD_LW * PF_WD_LH;
   __shared__ double ld[LN];
   __shared__ double lc[LN];
-  __shared__ int sides_s, lowered_s;
   if ((int)blockIdx.x >= nqueue) return;
   const int tid = (int)threadIdx.x;
-  const int q = queue[blockIdx.x], ntiles = tiles_x * tiles_y;
-  const int b = q / ntiles, t = q - b * ntiles, ty = t / tiles_x, tx = t - ty * tiles_x;
-  const int r0 = ty * PF_WD_TH, c0 = tx * PF_WD_TW;
-  double* const D = d_rows + (size_t)b * (size_t)R * (size_t)C;
+  const tq_visit visit = tq_entry(queue, tiles_x, tiles_y);
+  const int r0 = visit.ty * PF_WD_TH, c0 = visit.tx * PF_WD_TW;
+  double* const D = d_rows + (size_t)visit.b * (size_t)R * (size_t)C;
   const double inf = __builtin_bit_cast(double, PF_DF_INF_BITS);
-  if (tid == 0) { flag_now[q] = 0; sides_s = 0; lowered_s = 0; }
-  if (tid == 0 && blockIdx.x == 0) *count_now = 0;                   // the host has read this queue's length: the word is the launch after next's
+  tq_open(visit, flag_now, count_now);
   for (int i = tid; i < LN; i += PF_CF_THREADS) {
     const int r = r0 + i / LW - 1, c = c0 + i % LW - 1;
     double dv = inf, cv = 1.0;
@@ -190,19 +175,9 @@ __global__ __launch_bounds__(PF_CF_THREADS) void k_cost_relax_tiles_in_lds(const
       cf_store(D + (size_t)(r0 + lr) * (size_t)C + (size_t)(c0 + lcn), cur[j]);
       lowered += 1;
     }
-    const int n = lr == 0, s = lr == PF_WD_TH - 1, wst = lcn == 0, e = lcn == PF_WD_TW - 1;
-    sides |= n | (s << 1) | (wst << 2) | (e << 3) | ((n & wst) << 4) | ((n & e) << 5) | ((s & wst) << 6) | ((s & e) << 7);
+    sides |= tq_side_bits<PF_WD_TW, PF_WD_TH>(lr, lcn);
   }
-  if (sides) atomicOr(&sides_s, sides);
-  if (lowered) atomicAdd(&lowered_s, lowered);
-  __syncthreads();
-  if (tid < (allow_diag ? 8 : 4) && ((sides_s >> tid) & 1)) {
-    const int dy = (tid == 0 || tid == 4 || tid == 5) ? -1 : (tid == 1 || tid == 6 || tid == 7) ? 1 : 0;
-    const int dx = (tid == 2 || tid == 4 || tid == 6) ? -1 : (tid == 3 || tid == 5 || tid == 7) ? 1 : 0;
-    const int ny = ty + dy, nx = tx + dx;
-    if (ny >= 0 && ny < tiles_y && nx >= 0 && nx < tiles_x) wd_enqueue(b * ntiles + ny * tiles_x + nx, flag_next, queue_next, count_next);
-  }
-  if (tid == 0 && lowered_s) atomicAdd(lowered_total, (unsigned long long)lowered_s);
+  tq_close(visit, sides, lowered, allow_diag, tiles_x, tiles_y, flag_next, queue_next, count_next, lowered_total);
 }
 
 // largest[b] = the largest finite label's bits of row b (preset to 0), cells[b] += the cells with a finite label
@@ -297,36 +272,51 @@ __global__ __launch_bounds__(PF_FP_THREADS) void k_cost_parent_map_thread_per_ce
   }
 }
 
-// total[p] = the left-to-right sum of the weights of row p's steps, bad[p] = -1; or NaN and the first step that is no king move
-// between cells inside the grid (0 for an empty row, a length beyond path_cap or a lone cell outside the grid)
-__global__ __launch_bounds__(64) void k_cost_paths_one_wave_per_row(const double* __restrict__ cost, int RC, int C, int n, int path_cap, const int* __restrict__ cells,
-                                                                      const int* __restrict__ len, double* __restrict__ total, int* __restrict__ bad) {
-  const int p = (int)blockIdx.x, lane = (int)threadIdx.x;
-  if (p >= n) return;
-  const int L = len[p];
-  const int* const row = cells + (size_t)p * (size_t)path_cap;
-  int at = -1;
+// The path-row scorer, one wavefront per row (also pf_turn_field.h's): the lanes form the weights of 64 consecutive steps and
+// check them, then the sum is taken left to right.  -> the sum; at = -1, or the first step that is no king move between cells
+// inside the grid (0 for an empty row, a length beyond path_cap or a lone cell outside the grid; the sum means nothing then).
+// UNIT_IF_NULL: a null cost map is a map of ones.  step(i, a, dr, dc, w, mark) -> what step i = a -> a + (dr, dc) of weight w adds
+// to the sum, and may set the lane's mark (0 before); trip(mark) runs once for every 64 steps that passed the check.
+template <bool UNIT_IF_NULL, typename Step, typename Trip>
+__device__ __forceinline__ double cf_score_row(const double* __restrict__ cost, int RC, int C, const int* __restrict__ row, int L, int path_cap, int lane, int& at,
+                                               Step step, Trip trip) {
   double sum = 0.0;
+  at = -1;
   if (L < 1 || L > path_cap) at = 0;
   else if (L == 1 && (unsigned)row[0] >= (unsigned)RC) at = 0;
   for (int base = 0; at < 0 && base + 1 < L; base += 64) {           // (uniform: the whole wavefront)
     const int i = base + lane;                                       // the step row[i] -> row[i + 1]
-    double w = 0.0;
-    int off = 0;
+    double e = 0.0;
+    int off = 0, mark = 0;
     if (i + 1 < L) {
       const int a = row[i], b = row[i + 1];
       if ((unsigned)a >= (unsigned)RC || (unsigned)b >= (unsigned)RC) off = 1;
       else {
         const int dr = b / C - a / C, dc = b % C - a % C;
         if (dr < -1 || dr > 1 || dc < -1 || dc > 1 || (dr == 0 && dc == 0)) off = 1;
-        else w = cf_weight(cost[a], cost[b], (dr != 0 && dc != 0) ? 4 : 0);
+        else {
+          const bool unit = UNIT_IF_NULL && !cost;
+          e = step(i, a, dr, dc, cf_weight(unit ? 1.0 : cost[a], unit ? 1.0 : cost[b], (dr != 0 && dc != 0) ? 4 : 0), mark);
+        }
       }
     }
     const unsigned long long offs = __ballot(off);
     if (offs) { at = base + __builtin_ctzll(offs); break; }
+    trip(mark);
     const int steps = L - 1 - base < 64 ? L - 1 - base : 64;
-    for (int t = 0; t < steps; ++t) sum += __shfl(w, t);             // one rounded addition per step, in the row's order
+    for (int t = 0; t < steps; ++t) sum += __shfl(e, t);             // one rounded addition per step, in the row's order
   }
+  return sum;
+}
+
+// total[p] = the left-to-right sum of the weights of row p's steps, bad[p] = -1; or NaN and the first bad step (cf_score_row)
+__global__ __launch_bounds__(64) void k_cost_paths_one_wave_per_row(const double* __restrict__ cost, int RC, int C, int n, int path_cap, const int* __restrict__ cells,
+                                                                      const int* __restrict__ len, double* __restrict__ total, int* __restrict__ bad) {
+  const int p = (int)blockIdx.x, lane = (int)threadIdx.x;
+  if (p >= n) return;
+  int at;
+  const double sum = cf_score_row<false>(cost, RC, C, cells + (size_t)p * (size_t)path_cap, len[p], path_cap, lane, at,
+                                         [](int, int, int, int, double w, int&) { return w; }, [](int) {});
   if (lane == 0) {
     total[p] = at >= 0 ? __builtin_bit_cast(double, 0x7FF8000000000000ull) : sum;
     bad[p] = at;

@@ -20,7 +20,8 @@
 //                                  two words T[d][u] and M[u] of u = v - step(d); barrier; the states that fell and the new M are
 //                                  written; barrier -- until one whole sweep lowers nothing.  The words that fell are stored (the
 //                                  states and best) and the neighbour tiles that hold a lowered cell in their halo are queued for
-//                                  the next launch.  Queue flags, parity and lengths are pf_widest.h's (wd_enqueue).
+//                                  the next launch.  Opening and closing the visit, the queues, flags and parity are
+//                                  pf_tile_queue.h's.
 //   k_turn_trace_query_lanes       the route rule, one lane per query, the field alone: at the target the heading with the smallest
 //                                  (T[d][t], d); at (v, d) step to u = v - step(d); stop when M[u] == 0; otherwise the d' with the
 //                                  smallest (T[d'][u], d') among those with fl(T[d'][u] + e(d', d)) == T[d][v] bit for bit.  Labels
@@ -35,12 +36,11 @@
 // real walk from a source that enters v by d (a walk may pass a cell twice: into (v, d) when u is a dead end reachable only through
 // v).  fl(. + e) is monotone, so by induction over an optimal walk's prefixes no walk's rounded cost lies below the least fixed
 // point's label of its end state: every stored value is >= the answer.  M is a minimum of such values.  Nothing is summed ahead.
-// (2) A halo word that the neighbour tile is lowering in the same launch may be read old or new: the loads into LDS and the
-// stores of the lowered words are whole-word 64-bit agent-scope relaxed atomics and a word has ONE writer per launch (the flags
-// admit a (set, tile) once), so what is read was stored and by (1) is a valid upper bound; the eight words of a halo cell may be
-// of different ages, each is valid on its own and so is their minimum.  Whoever lowers a border cell's state queues every tile
-// that holds the cell in its halo for the NEXT launch.  When no tile is queued, every tile was last relaxed from halo words that
-// did not change afterwards: the whole array is a fixed point above the seeds.  (3) A fixed point with T[.][s] = 0 on the seeds
+// (2) A halo word that the neighbour tile is lowering in the same launch may be read old or new: what is read was stored (whole
+// 64-bit words, cf_load and cf_store) and by (1) is a valid upper bound; the eight words of a halo cell may be of different ages,
+// each is valid on its own and so is their minimum.  pf_tile_queue.h has the rest of this half -- one writer per (set, tile) per
+// launch, whoever lowers a border cell's state queues its readers for the next launch, no other synchronisation --: when no tile
+// is queued, the whole array is a fixed point above the seeds.  (3) A fixed point with T[.][s] = 0 on the seeds
 // is <= the least one's label along every optimal walk (induction along the walk), so with (1) it IS the least fixed point,
 // whatever the timing: identical run to run, bit for bit.
 //
@@ -71,23 +71,15 @@ __global__ __launch_bounds__(PF_TF_THREADS) void k_turn_seed_sets(const uint8_t*
                                                                     const int* __restrict__ off, const int* __restrict__ src, double* __restrict__ states,
                                                                     double* __restrict__ best, int* __restrict__ flag, int* __restrict__ queue,
                                                                     int* __restrict__ count, unsigned long long* __restrict__ nsrc) {
-  for (int b = (int)blockIdx.y; b < B; b += (int)gridDim.y) {
-    const int end = off[b + 1];
-    int counted = 0;
-    for (int j = off[b] + (int)(blockIdx.x * PF_TF_THREADS + threadIdx.x); j < end; j += (int)(gridDim.x * PF_TF_THREADS)) {
-      const int s = src[j];
-      if ((unsigned)s >= (unsigned)RC) continue;                     // (the host has checked the ids)
-      if (occ[s] == 1) continue;                                     // a source ON an obstacle is no source
-      unsigned long long* const word = (unsigned long long*)(best + (size_t)b * (size_t)RC + (size_t)s);
-      if (__hip_atomic_fetch_min(word, 0ull, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != PF_DF_INF_BITS) continue;   // listed twice
-      counted += 1;
+  tq_seed_sets<PF_TF_THREADS, PF_TF_TW, PF_TF_TH>(RC, C, tiles_x, ntiles, B, off, src, flag, queue, count, nsrc, [&](int b, int s) {
+    if (occ[s] == 1) return false;                                   // a source ON an obstacle is no source
+    unsigned long long* const word = (unsigned long long*)(best + (size_t)b * (size_t)RC + (size_t)s);
+    if (__hip_atomic_fetch_min(word, 0ull, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != PF_DF_INF_BITS) return false;   // listed twice
+    double* state = states + (size_t)b * 8 * (size_t)RC + (size_t)s;
 #pragma unroll
-      for (int d = 0; d < 8; ++d) cf_store(states + ((size_t)b * 8 + (size_t)d) * (size_t)RC + (size_t)s, 0.0);
-      const int r = s / C, c = s - r * C;
-      wd_enqueue(b * ntiles + (r / PF_TF_TH) * tiles_x + c / PF_TF_TW, flag, queue, count);
-    }
-    if (counted) atomicAdd(nsrc + b, (unsigned long long)counted);
-  }
+    for (int d = 0; d < 8; ++d, state += RC) cf_store(state, 0.0);
+    return true;
+  });
 }
 
 // counters[0] += the state words lowered; counters[1] = 1 when a tile hit the sweep bound
@@ -97,18 +89,15 @@ __global__ __launch_bounds__(PF_TF_THREADS) void k_turn_relax_tiles_in_lds(const
                                                                              int* __restrict__ queue_next, int* count_next, unsigned long long* __restrict__ counters) {
   constexpr int PER = PF_TF_PER, LW = PF_TF_LW, LN = PF_TF_LW * PF_TF_LH;
   __shared__ double lt[9][LN];                                       // planes 0..7: T[d]; plane 8: M (and, before the labels come, the costs)
-  __shared__ int sides_s, lowered_s;
   if ((int)blockIdx.x >= nqueue) return;
   const int tid = (int)threadIdx.x;
-  const int q = queue[blockIdx.x], ntiles = tiles_x * tiles_y;
-  const int b = q / ntiles, t = q - b * ntiles, ty = t / tiles_x, tx = t - ty * tiles_x;
-  const int r0 = ty * PF_TF_TH, c0 = tx * PF_TF_TW;
+  const tq_visit visit = tq_entry(queue, tiles_x, tiles_y);
+  const int r0 = visit.ty * PF_TF_TH, c0 = visit.tx * PF_TF_TW;
   const size_t RC = (size_t)R * (size_t)C;
-  double* const T = d_states + (size_t)b * 8 * RC;
-  double* const Mg = d_best + (size_t)b * RC;
+  double* const T = d_states + (size_t)visit.b * 8 * RC;
+  double* const Mg = d_best + (size_t)visit.b * RC;
   const double inf = __builtin_bit_cast(double, PF_DF_INF_BITS);
-  if (tid == 0) { flag_now[q] = 0; sides_s = 0; lowered_s = 0; }
-  if (tid == 0 && blockIdx.x == 0) *count_now = 0;                   // the host has read this queue's length: the word is the launch after next's
+  tq_open(visit, flag_now, count_now);
   for (int i = tid; i < LN; i += PF_TF_THREADS) {
     const int r = r0 + i / LW - 1, c = c0 + i % LW - 1;
     double cv = 1.0;
@@ -202,19 +191,9 @@ __global__ __launch_bounds__(PF_TF_THREADS) void k_turn_relax_tiles_in_lds(const
       if ((fell[j] >> d) & 1u) cf_store(T + (size_t)d * RC + v, cur[j][d]);
     if (fell[j] & 256u) cf_store(Mg + v, curm[j]);
     lowered += __builtin_popcount(fell[j] & 255u);
-    const int n = lr == 0, s = lr == PF_TF_TH - 1, wst = lcn == 0, e = lcn == PF_TF_TW - 1;
-    sides |= n | (s << 1) | (wst << 2) | (e << 3) | ((n & wst) << 4) | ((n & e) << 5) | ((s & wst) << 6) | ((s & e) << 7);
+    sides |= tq_side_bits<PF_TF_TW, PF_TF_TH>(lr, lcn);
   }
-  if (sides) atomicOr(&sides_s, sides);
-  if (lowered) atomicAdd(&lowered_s, lowered);
-  __syncthreads();
-  if (tid < (allow_diag ? 8 : 4) && ((sides_s >> tid) & 1)) {
-    const int dy = (tid == 0 || tid == 4 || tid == 5) ? -1 : (tid == 1 || tid == 6 || tid == 7) ? 1 : 0;
-    const int dx = (tid == 2 || tid == 4 || tid == 6) ? -1 : (tid == 3 || tid == 5 || tid == 7) ? 1 : 0;
-    const int ny = ty + dy, nx = tx + dx;
-    if (ny >= 0 && ny < tiles_y && nx >= 0 && nx < tiles_x) wd_enqueue(b * ntiles + ny * tiles_x + nx, flag_next, queue_next, count_next);
-  }
-  if (tid == 0 && lowered_s) atomicAdd(counters, (unsigned long long)lowered_s);
+  tq_close(visit, sides, lowered, allow_diag, tiles_x, tiles_y, flag_next, queue_next, count_next, counters);
   if (tid == 0 && stuck) counters[1] = 1ull;
 }
 
@@ -289,38 +268,17 @@ __global__ __launch_bounds__(64) void k_turn_paths_one_wave_per_row(const double
                                                                       const int* __restrict__ len, double* __restrict__ total, int* __restrict__ turns, int* __restrict__ bad) {
   const int p = (int)blockIdx.x, lane = (int)threadIdx.x;
   if (p >= n) return;
-  const int L = len[p];
   const int* const row = cells + (size_t)p * (size_t)path_cap;
-  int at = -1, nturns = 0;
-  double sum = 0.0;
-  if (L < 1 || L > path_cap) at = 0;
-  else if (L == 1 && (unsigned)row[0] >= (unsigned)RC) at = 0;
-  for (int base = 0; at < 0 && base + 1 < L; base += 64) {           // (uniform: the whole wavefront)
-    const int i = base + lane;                                       // the step row[i] -> row[i + 1]
-    double e = 0.0;
-    int off = 0, turn = 0;
-    if (i + 1 < L) {
-      const int a = row[i], b = row[i + 1];
-      if ((unsigned)a >= (unsigned)RC || (unsigned)b >= (unsigned)RC) off = 1;
-      else {
-        const int dr = b / C - a / C, dc = b % C - a % C;
-        if (dr < -1 || dr > 1 || dc < -1 || dc > 1 || (dr == 0 && dc == 0)) off = 1;
-        else {
-          const double w = cf_weight(cost ? cost[a] : 1.0, cost ? cost[b] : 1.0, (dr != 0 && dc != 0) ? 4 : 0);
-          if (i >= 1) {                                              // (a bad step before this one ends the row at that step)
-            const int z = row[i - 1];
-            if ((unsigned)z < (unsigned)RC) turn = (a / C - z / C != dr) || (a % C - z % C != dc);
-          }
-          e = turn ? w + wt : w;
-        }
-      }
-    }
-    const unsigned long long offs = __ballot(off);
-    if (offs) { at = base + __builtin_ctzll(offs); break; }
-    nturns += __builtin_popcountll(__ballot(turn));
-    const int steps = L - 1 - base < 64 ? L - 1 - base : 64;
-    for (int t = 0; t < steps; ++t) sum += __shfl(e, t);             // one rounded addition per step, in the row's order
-  }
+  int at, nturns = 0;
+  const double sum = cf_score_row<true>(cost, RC, C, row, len[p], path_cap, lane, at,
+                                        [&](int i, int a, int dr, int dc, double w, int& turn) {
+                                          if (i >= 1) {              // (a bad step before this one ends the row at that step)
+                                            const int z = row[i - 1];
+                                            if ((unsigned)z < (unsigned)RC) turn = (a / C - z / C != dr) || (a % C - z % C != dc);
+                                          }
+                                          return turn ? w + wt : w;
+                                        },
+                                        [&](int turn) { nturns += __builtin_popcountll(__ballot(turn)); });
   if (lane == 0) {
     total[p] = at >= 0 ? __builtin_bit_cast(double, 0x7FF8000000000000ull) : sum;
     turns[p] = at >= 0 ? 0 : nturns;

@@ -9,19 +9,17 @@
 // and a sweep reads nothing but the eight neighbours' w.  Equivalently, for every t >= 1: w[b][v] >= t iff v and a source of set
 // b lie in one component of the map whose obstacles are the cells with d2 < t.  d2 is read only; the occupancy never is.
 //
-//   k_widest_seed_sets              one thread per listed source: an atomic exchange of d2[s] into w[b][s] (the first one to find 0
-//                                   there counts the source: a source listed twice counts once, one with d2 == 0 never), and the
-//                                   source's tile goes on the first queue.
+//   k_widest_seed_sets              one thread per listed source (tq_seed_sets): an atomic exchange of d2[s] into w[b][s] (the first one
+//                                   to find 0 there counts the source: a source listed twice counts once, one with d2 == 0 never),
+//                                   and the source's tile goes on the first queue.
 //   k_widest_relax_tiles_in_lds     one workgroup per queued (set, tile), a tile being PF_WD_TW x PF_WD_TH cells, four per thread:
 //                                   loads its cells and a one-cell halo of w and d2 into LDS (0 beyond the grid: such a cell offers
 //                                   and takes nothing), sweeps until one whole sweep raises nothing -- the tile's own fixed point
 //                                   under the halo it read; a sweep relaxes a cell from its eight neighbours and then carries w
-//                                   along the tile row by a wave-wide (max, min) scan (wd_row_scan; -DPF_WD_ROW_SCAN=0: without) --, stores the words that rose and queues, for the next launch, the
-//                                   neighbour tiles that hold a risen cell in their halo (N, S, W, E for a risen border row or
-//                                   column, a diagonal neighbour for a risen corner cell when diagonals are allowed).  A tile does
-//                                   not queue itself: it is at its fixed point until a halo word rises, and whoever raises one
-//                                   queues it.  In the first launch a tile also reports the seeds on its border, which rose in the
-//                                   seeding kernel.  Queue entries are deduplicated by one flag word per (set, tile) and parity.
+//                                   along the tile row by a wave-wide (max, min) scan (wd_row_scan; -DPF_WD_ROW_SCAN=0: without) --,
+//                                   stores the words that rose and queues, for the next launch, the neighbour tiles that hold a
+//                                   risen cell in their halo.  Opening and closing the visit, the queues, flags and parity are
+//                                   pf_tile_queue.h's.
 //   k_widest_info_sum / k_widest_write_info   the cells with w >= 1 and the smallest such w with the smallest cell id that
 //                                   attains it, as one 64-bit atomic min of (w << 32) | id per set; then the four words of `info`.
 //
@@ -33,23 +31,13 @@
 // fewer than R C borders, which is the bound the host enforces.  A tile may be visited again whenever a wider route reaches its
 // halo later than a narrower one; pf_clearance_widest_work reports launches, tile visits and words raised.
 //
-// Visibility.  Per-XCD L2s are not coherent with each other and a CU's L1 is never refreshed by another CU's stores, so a halo word
-// that the neighbour tile is raising in the same launch may be read old or new.  That is harmless, for three reasons.  Values
-// only rise: every value ever stored in w[v] is the capacity of some real walk from a source to v, so an old value is a valid lower
-// bound and a tile relaxed from old halo words ends at or below the fixed point, never above it.  A word is written whole: w[v]
-// has ONE writer, the workgroup of v's tile (two workgroups never hold the same (set, tile) in one launch: the flags), and it
-// stores aligned 32-bit words, so a reader sees a value that was stored, never a mixture.  Whoever raised it re-queues the reader:
-// a workgroup that raises a border cell queues every tile that holds the cell in its halo for the NEXT launch, and the kernel
-// boundary in between makes the store visible, so a reader that saw the old word runs again and sees the new one.  At the end no
-// tile is queued, hence every tile was last relaxed from halo words that did not change afterwards: the whole array is a fixed
-// point, at or below the least one by the first reason and at or above it because it is a fixed point above the seeds.  The least
-// fixed point is unique, so the result does not depend on timing and is identical run to run.
-// Which accesses have to be agent-scope atomics for this: the loads of w into LDS and the stores of the risen words (relaxed
-// __hip_atomic_load / __hip_atomic_store: whole words, not cached across the launch in a way the compiler may assume stable), the
-// exchange on the flag word and the add on the next queue's length.  d2, the current queue and this round's flags are written by
-// nobody else in the launch: a workgroup clears its own current flag, and the first one the current queue's length, which the host
-// has read already and which is the launch after next's.  Kernel boundaries are the only synchronisation: no spin-wait, no
-// cooperative launch, no fence across workgroups.
+// Why this is exact.  Values only rise: every value ever stored in w[v] is the capacity of some real walk from a source to v, so a
+// halo word read old (the neighbour tile may be raising it in the same launch) is a valid lower bound, and a tile relaxed from old
+// halo words ends at or below the least fixed point, never above it.  w[v] is an aligned 32-bit word with one writer per launch,
+// and whoever raises a border cell queues its readers for the next launch (pf_tile_queue.h has this half of the argument, and
+// which accesses are agent-scope atomics: here wd_load, wd_store and the seed's exchange): at the end the whole array is a fixed
+// point above the seeds, at or below the least one by the first half and at or above it because it is a fixed point above the
+// seeds.  The least fixed point is unique, so the result does not depend on timing and is identical run to run.
 #pragma once
 
 namespace pf {
@@ -66,31 +54,14 @@ namespace pf {
 __device__ __forceinline__ int wd_load(const int* p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
 __device__ __forceinline__ void wd_store(int* p, int v) { __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
 
-// (set, tile) q goes on the queue whose length is *count, once: the flag word says it is there already
-__device__ __forceinline__ void wd_enqueue(int q, int* __restrict__ flag, int* __restrict__ queue, int* __restrict__ count) {
-  if (__hip_atomic_exchange(flag + q, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == 0)
-    queue[__hip_atomic_fetch_add(count, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)] = q;
-}
-
 __global__ __launch_bounds__(PF_WD_THREADS) void k_widest_seed_sets(const int* __restrict__ d2, int RC, int C, int tiles_x, int ntiles, int B,
                                                                           const int* __restrict__ off, const int* __restrict__ src, int* __restrict__ w_rows,
                                                                           int* __restrict__ flag, int* __restrict__ queue, int* __restrict__ count,
                                                                           unsigned long long* __restrict__ nsrc) {
-  for (int b = (int)blockIdx.y; b < B; b += (int)gridDim.y) {
-    const int end = off[b + 1];
-    int counted = 0;
-    for (int j = off[b] + (int)(blockIdx.x * PF_WD_THREADS + threadIdx.x); j < end; j += (int)(gridDim.x * PF_WD_THREADS)) {
-      const int s = src[j];
-      if ((unsigned)s >= (unsigned)RC) continue;                     // (the host has checked the ids)
-      const int dv = d2[s];
-      if (dv < 1) continue;
-      if (__hip_atomic_exchange(w_rows + (size_t)b * (size_t)RC + (size_t)s, dv, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != 0) continue;   // listed twice
-      counted += 1;
-      const int r = s / C, c = s - r * C;
-      wd_enqueue(b * ntiles + (r / PF_WD_TH) * tiles_x + c / PF_WD_TW, flag, queue, count);
-    }
-    if (counted) atomicAdd(nsrc + b, (unsigned long long)counted);
-  }
+  tq_seed_sets<PF_WD_THREADS, PF_WD_TW, PF_WD_TH>(RC, C, tiles_x, ntiles, B, off, src, flag, queue, count, nsrc, [&](int b, int s) {
+    const int dv = d2[s];
+    return dv >= 1 && __hip_atomic_exchange(w_rows + (size_t)b * (size_t)RC + (size_t)s, dv, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == 0;   // != 0: listed twice
+  });
 }
 
 // The 64 cells of a tile row lie in the 64 lanes of one wavefront.  Straight moves along the row alone carry w[j] to cell i at
@@ -116,16 +87,13 @@ __global__ __launch_bounds__(PF_WD_THREADS) void k_widest_relax_tiles_in_lds(con
   constexpr int PER = PF_WD_TW * PF_WD_TH / PF_WD_THREADS, LW = PF_WD_LW, LN = PF_WD_LW * PF_WD_LH;
   __shared__ int lw[LN];
   __shared__ int ld[LN];
-  __shared__ int sides_s, raised_s;
   if ((int)blockIdx.x >= nqueue) return;
   const int tid = (int)threadIdx.x;
   [[maybe_unused]] const int lane = tid & 63;
-  const int q = queue[blockIdx.x], ntiles = tiles_x * tiles_y;
-  const int b = q / ntiles, t = q - b * ntiles, ty = t / tiles_x, tx = t - ty * tiles_x;
-  const int r0 = ty * PF_WD_TH, c0 = tx * PF_WD_TW;
-  int* const w = w_rows + (size_t)b * (size_t)R * (size_t)C;
-  if (tid == 0) { flag_now[q] = 0; sides_s = 0; raised_s = 0; }
-  if (tid == 0 && blockIdx.x == 0) *count_now = 0;                   // the host has read this queue's length: the word is the launch after next's
+  const tq_visit visit = tq_entry(queue, tiles_x, tiles_y);
+  const int r0 = visit.ty * PF_WD_TH, c0 = visit.tx * PF_WD_TW;
+  int* const w = w_rows + (size_t)visit.b * (size_t)R * (size_t)C;
+  tq_open(visit, flag_now, count_now);
   for (int i = tid; i < LN; i += PF_WD_THREADS) {
     const int r = r0 + i / LW - 1, c = c0 + i % LW - 1;
     int dv = 0, wv = 0;
@@ -188,19 +156,9 @@ __global__ __launch_bounds__(PF_WD_THREADS) void k_widest_relax_tiles_in_lds(con
       wd_store(w + (size_t)(r0 + lr) * (size_t)C + (size_t)(c0 + lc), cur[j]);
       raised += 1;
     }
-    const int n = lr == 0, s = lr == PF_WD_TH - 1, wst = lc == 0, e = lc == PF_WD_TW - 1;
-    sides |= n | (s << 1) | (wst << 2) | (e << 3) | ((n & wst) << 4) | ((n & e) << 5) | ((s & wst) << 6) | ((s & e) << 7);
+    sides |= tq_side_bits<PF_WD_TW, PF_WD_TH>(lr, lc);
   }
-  if (sides) atomicOr(&sides_s, sides);
-  if (raised) atomicAdd(&raised_s, raised);
-  __syncthreads();
-  if (tid < (allow_diag ? 8 : 4) && ((sides_s >> tid) & 1)) {
-    const int dy = (tid == 0 || tid == 4 || tid == 5) ? -1 : (tid == 1 || tid == 6 || tid == 7) ? 1 : 0;
-    const int dx = (tid == 2 || tid == 4 || tid == 6) ? -1 : (tid == 3 || tid == 5 || tid == 7) ? 1 : 0;
-    const int ny = ty + dy, nx = tx + dx;
-    if (ny >= 0 && ny < tiles_y && nx >= 0 && nx < tiles_x) wd_enqueue(b * ntiles + ny * tiles_x + nx, flag_next, queue_next, count_next);
-  }
-  if (tid == 0 && raised_s) atomicAdd(raised_total, (unsigned long long)raised_s);
+  tq_close(visit, sides, raised, allow_diag, tiles_x, tiles_y, flag_next, queue_next, count_next, raised_total);
 }
 
 // keys[b] = the smallest (w << 32) | id over the cells of row b with w >= 1 (preset to all ones), cells[b] += their number
