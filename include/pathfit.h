@@ -580,6 +580,28 @@ int pf_clearance_widest_work(pf_handle* h, int64_t* out4);
 int pf_cost_field(pf_handle* h, int32_t allow_diag, int32_t restrict_corner, const double* d_cost, int32_t B,
                   const int32_t* set_off, const int32_t* src, double* d_out, int64_t* d_info);
 int pf_cost_field_work(pf_handle* h, int64_t* out4);
+/* pf_cost_field_repair: the exact update of cost fields after a few cells changed.  d_rows [B][R C] holds what
+ * pf_cost_field (or an earlier repair) left for the same sets and policy, computed on an occupancy and a cost map that differ
+ * from the handle's present occupancy (after pf_update_grid) and from d_cost at most on the n_changed cells of `changed`, a HOST
+ * array of flat cell ids; duplicates are fine, and so are cells that in fact did not change.  On return the rows, and d_info (or
+ * NULL), are bit for bit what pf_cost_field would write now.  Two phases on the tile-queue engine: labels that lost their support
+ * -- no legal move u -> v of the new mask with fl(D[u] + w_new(u, v)) == D[v], and every finite label on an obstacle -- are
+ * raised to +inf, tile by tile from the 3 x 3 blocks about the listed cells, until nothing changes; every free source takes 0;
+ * then pf_cost_field's relax kernel lowers from the tiles that had a word raised, that meet such a block or that hold a new
+ * seed.  The work follows the tiles the invalid region crosses, not the map (the validation of d_cost and d_info still read the
+ * map once); a change next to a source may cost as much as a fresh field or more, two phases crossing the same tiles.  The result
+ * does not depend on the timing.  If the caller breaks the contract the result is unspecified, but the call ends within the
+ * round bounds (R C + 1 launches a phase) and accesses nothing out of range.
+ * n_changed == 0: the rows stay untouched and no tile kernel is launched; d_info is still written when given.  n_changed < 0, a
+ * null `changed` with n_changed > 0, an id outside [0, R C) (the message names its index) and every argument error of
+ * pf_cost_field: -1 with a message, found on the host before any launch; a bad cost on a free cell: -1, found by the validation
+ * kernel BEFORE anything is written; a null handle: -2.  Afterwards pf_cost_field_work reports {tile launches of both phases,
+ * tile visits of both, words lowered, words raised}: the labels that were finite before and +inf after the raise phase, a figure
+ * that does not depend on the schedule (after pf_cost_field the fourth word stays 0).  pf_last_kernel_ms spans both phases.
+ * Scratch: pf_clearance_widest's block, grown by one word per (set, tile) and by the device copy of the list. */
+int pf_cost_field_repair(pf_handle* h, int32_t allow_diag, int32_t restrict_corner, const double* d_cost, int32_t n_changed,
+                         const int32_t* changed, int32_t B, const int32_t* set_off, const int32_t* src, double* d_rows,
+                         int64_t* d_info);
 int pf_cost_field_parents(pf_handle* h, int32_t allow_diag, int32_t restrict_corner, const double* d_cost, int32_t K,
                           const double* d_fields, uint8_t* d_parents);
 int pf_cost_paths(pf_handle* h, const double* d_cost, int32_t n, int32_t path_cap, const int32_t* d_cells,

@@ -542,14 +542,16 @@ struct TileCall {
 // one round's kernel arguments: the current queue, and the queue, flags and length the launch fills
 struct TileRound { const int* queue; int n, first; int *flag_now, *count_now, *flag_next, *queue_next, *count_next; };
 
-// Lays the block out for B sets and a tile of TW x TH cells and clears the work words (sets: nearest_sets_check's)
-static int tile_call(pf_handle* h, const std::string& me, int B, const std::vector<int>& sets, int TW, int TH, long long* work, TileCall& k) {
+// Lays the block out for B sets and a tile of TW x TH cells and clears the work words (sets: nearest_sets_check's).  A call may ask
+// for extra_flags more words per (set, tile) and extra_ints more words behind the flags (the cost repair's: k.flag + 2 * k.T on).
+static int tile_call(pf_handle* h, const std::string& me, int B, const std::vector<int>& sets, int TW, int TH, long long* work, TileCall& k,
+                     size_t extra_flags = 0, size_t extra_ints = 0) {
   k.B = B;
   k.tiles_x = (h->C + TW - 1) / TW; k.tiles_y = (h->R + TH - 1) / TH; k.ntiles = k.tiles_x * k.tiles_y;
   if ((long long)B * k.ntiles >= 0x7FFFFFFFll) return failmsg(h, me + ": bad arguments (B times the number of tiles must stay below 2^31 - 1)");
   k.T = (size_t)B * (size_t)k.ntiles; k.nsets = sets.size() - 1;     // (sets[0] is the nearest fields' error word: not uploaded)
   const size_t n64 = 2 + 3 * (size_t)B;
-  if (scratch(h, me, h->d_widest, &h->widest_bytes, sizeof(unsigned long long) * n64 + sizeof(int) * (4 + (size_t)B + k.nsets + 4 * k.T), "the scratch words", true)) return -2;
+  if (scratch(h, me, h->d_widest, &h->widest_bytes, sizeof(unsigned long long) * n64 + sizeof(int) * (4 + (size_t)B + k.nsets + (4 + extra_flags) * k.T + extra_ints), "the scratch words", true)) return -2;
   k.moved = (unsigned long long*)h->d_widest;
   k.top = k.moved + 2;
   k.cells = k.top + B;
@@ -672,6 +674,7 @@ int pf_clearance_widest_work(pf_handle* h, int64_t* out4) { return tile_work(h, 
 // scratch: the tile-queue engine's, over the widest paths' tile.
 // ---------------------------------------------------------------------------
 #include "pf_cost_field.h"
+#include "pf_cost_repair.h"
 
 // The costs of the free cells, before any output is touched: `word` (device) takes the smallest offending cell.  ev0, where given,
 // is recorded behind the upload of the word.  One small copy back.
@@ -741,6 +744,74 @@ int pf_cost_field(pf_handle* h, int32_t allow_diag, int32_t restrict_corner, con
 }
 
 int pf_cost_field_work(pf_handle* h, int64_t* out4) { return tile_work(h, "pf_cost_field_work", h ? h->cost_work : nullptr, out4); }
+
+// Cost-field repair (pf_cost_repair.h): the raise phase and the lower phase, each a run of tile_rounds over the
+// same queues (a phase ends with both queue lengths and every flag at 0: the next one starts at parity 0 again).  The block grows
+// by the touched flags [T] and the device copy of the changed list, behind the flags.  moved[1] takes the words raised.
+int pf_cost_field_repair(pf_handle* h, int32_t allow_diag, int32_t restrict_corner, const double* d_cost, int32_t n_changed, const int32_t* changed, int32_t B,
+                         const int32_t* set_off, const int32_t* src, double* d_rows, int64_t* d_info) {
+  if (!h) return -2;
+  const std::string me("pf_cost_field_repair");
+  auto run = [&]() -> int {
+    std::vector<int> listed;
+    if (nearest_sets_check(h, me, B, set_off, src, listed)) return -2;
+    if (!d_cost || !d_rows) return failmsg(h, me + ": bad arguments (the cost map and the rows must not be null)");
+    if (n_changed < 0) return failmsg(h, me + ": bad arguments (n_changed = " + std::to_string(n_changed) + ": the number of changed cells must not be negative)");
+    if (n_changed > 0 && !changed) return failmsg(h, me + ": bad arguments (the changed cells must not be null when n_changed > 0)");
+    for (int i = 0; i < n_changed; ++i)
+      if (changed[i] < 0 || changed[i] >= h->RC)
+        return failmsg(h, me + ": changed[" + std::to_string(i) + "] = " + std::to_string(changed[i]) + " lies outside the grid");
+    std::vector<int> sets(1, 0);                                      // the sets with every source once: {error word, off [B + 1], ids}
+    {
+      std::vector<int> off(1, 0), ids;
+      for (int b = 0; b < B; ++b) {
+        std::vector<int> s(src + set_off[b], src + set_off[b + 1]);
+        std::sort(s.begin(), s.end());
+        s.erase(std::unique(s.begin(), s.end()), s.end());
+        ids.insert(ids.end(), s.begin(), s.end());
+        off.push_back((int)ids.size());
+      }
+      sets.insert(sets.end(), off.begin(), off.end());
+      sets.insert(sets.end(), ids.begin(), ids.end());
+    }
+    CK(hipSetDevice(h->device));
+    const int R = h->R, C = h->C, RC = h->RC;
+    TileCall k;                                                       // top: the largest finite label's bits per set
+    if (const int rc = tile_call(h, me, B, sets, PF_WD_TW, PF_WD_TH, h->cost_work, k, 1, (size_t)n_changed)) return rc;
+    int* const touched = k.flag + 2 * k.T;
+    int* const d_changed = touched + k.T;
+    if (const int rc = cost_map_check(h, me, d_cost, k.count + 2, h->ev0)) return rc;
+    CK(hipMemsetAsync(touched, 0, sizeof(int) * k.T, h->stream));
+    if (n_changed) CK(hipMemcpyAsync(d_changed, changed, sizeof(int) * (size_t)n_changed, hipMemcpyHostToDevice, h->stream));
+    if (tile_upload(h, k, sets, 0)) return -2;                        // (it synchronises: the caller's list may leave scope)
+    const uint8_t* occ = h->d_occ;
+    const uint8_t* mm = move_mask(h, allow_diag, restrict_corner);
+    const int most = std::max(std::max((int)std::min<size_t>(k.T, 0x7FFFFFFF), (int)n_changed), sets[B + 1]);
+    const dim3 qgrid((unsigned)std::min((n_changed + PF_CF_THREADS - 1) / PF_CF_THREADS, 256), k.gy);
+    const dim3 lgrid((unsigned)std::min((most + PF_CF_THREADS - 1) / PF_CF_THREADS, 256), k.gy);
+    if (n_changed) {
+      hipLaunchKernelGGL(k_repair_queue_changed_blocks, qgrid, dim3(PF_CF_THREADS), 0, h->stream, R, C, k.tiles_x, k.ntiles, (int)B, (int)n_changed, (const int*)d_changed,
+                         k.flag, k.queue, k.count);
+      if (const int rc = tile_rounds(h, me, k, (long long)RC + 1, [&](const TileRound& r) {
+            hipLaunchKernelGGL(k_cost_raise_tiles_in_lds, dim3((unsigned)r.n), dim3(PF_CF_THREADS), 0, h->stream, occ, mm, d_cost, R, C, allow_diag ? 1 : 0, k.tiles_x,
+                               k.tiles_y, d_rows, r.queue, r.n, r.flag_now, r.count_now, r.flag_next, r.queue_next, r.count_next, touched, k.moved + 1);
+          })) return rc;
+    }
+    if (n_changed || d_info)                                          // (nothing listed: it only counts the sources, for the info)
+      hipLaunchKernelGGL(k_repair_queue_lower, lgrid, dim3(PF_CF_THREADS), 0, h->stream, occ, R, C, k.tiles_x, k.ntiles, (int)B, (int)k.T, (const int*)touched,
+                       (int)n_changed, (const int*)d_changed, (const int*)k.d_off, (const int*)k.d_src, n_changed ? 1 : 0, d_rows, k.flag, k.queue, k.count, k.nsrc);
+    if (n_changed)
+      if (const int rc = tile_rounds(h, me, k, (long long)RC + 1, [&](const TileRound& r) {
+            hipLaunchKernelGGL(k_cost_relax_tiles_in_lds, dim3((unsigned)r.n), dim3(PF_CF_THREADS), 0, h->stream, occ, mm, d_cost, R, C, allow_diag ? 1 : 0, k.tiles_x,
+                               k.tiles_y, d_rows, r.queue, r.n, r.first, r.flag_now, r.count_now, r.flag_next, r.queue_next, r.count_next, k.moved);
+          })) return rc;
+    if (d_info) cost_info(h, k, d_rows, d_info);
+    if (const int rc = tile_finish(h, k)) return rc;
+    k.work[3] = (long long)k.end[1];
+    return 0;
+  };
+  return run() ? -1 : 0;
+}
 
 int pf_cost_field_parents(pf_handle* h, int32_t allow_diag, int32_t restrict_corner, const double* d_cost, int32_t K, const double* d_fields, uint8_t* d_parents) {
   if (!h) return -2;

@@ -3,7 +3,8 @@ terrain, a lane next to a wall, a zone to avoid unless there is no other way.  A
 costs, times sqrt(2) for a diagonal; with cost == 1 everywhere the field is NearestSourceField's bit for bit.  Everything a
 NearestSourceField offers (parents, next_hop, owners, territory_sizes, nearest, paths) works on the weighted field through the same
 trace and owner kernels; `path_costs` scores any path rows under the cost map (pf_cost_paths).  The cost map stays in HBM
-(`cost_device`); `refresh` recomputes after `engine.update_grid` or with a new cost map."""
+(`cost_device`); `refresh` recomputes after `engine.update_grid` or with a new cost map, `repair` updates the field it holds for the
+cells that changed (pf_cost_field_repair), with the same result."""
 import numpy as np
 
 from .engine import DevBuf, Engine
@@ -26,6 +27,17 @@ def checked_cost(who, grid, cost):
         r, k = (int(v) for v in bad[0])
         raise ValueError(f"{who}: cost[{r}, {k}] = {float(c[r, k])!r} on a free cell is not a finite number in [1, 2^20]")
     return np.ascontiguousarray(c)
+
+
+def changed_cells(grid0, cost0, grid1, cost1):
+    """int32 flat ids, ascending: the cells whose free / obstacle state differs between the two grids, or that are free in both
+    with another cost (what lies under an obstacle is never compared: it may be NaN)."""
+    free0, free1 = np.asarray(grid0) != 1, np.asarray(grid1) != 1
+    if free0.shape != free1.shape or np.shape(cost0) != free0.shape or np.shape(cost1) != free0.shape:
+        raise ValueError(f"changed_cells: the shapes differ ({free0.shape}, {np.shape(cost0)}, {free1.shape}, {np.shape(cost1)})")
+    both = free0 & free1
+    differs = (free0 != free1) | (both & (np.where(both, cost0, 0.0) != np.where(both, cost1, 0.0)))
+    return np.flatnonzero(differs.reshape(-1)).astype(np.int32)
 
 
 class CostField(NearestSourceField):
@@ -81,6 +93,38 @@ class CostField(NearestSourceField):
         self.chosen = np.zeros(0, np.int32)
         self._compute_fields()
         self.kernel_ms = self.engine.last_kernel_ms()
+        return self
+
+    def repair(self, cost=None):
+        """refresh(cost), done incrementally (pf_cost_field_repair): the field held here is repaired for the map the engine holds now
+        (after engine.update_grid) and, when given, a new cost map.  The cells that differ (changed_cells) are found here; the labels
+        that lost their support are raised to inf on the device and lowered again from there, at a cost that follows the tiles the
+        invalid region crosses instead of the map.  The fields are bit for bit refresh's.  With nothing changed it returns at once and
+        keeps everything derived; otherwise fields, parents and owners are dropped as refresh drops them.  work: (launches of both
+        phases, tile visits of both, words lowered, words raised).  A change next to a source may invalidate most of the field: the
+        repair then crosses the same tiles twice and can take as long as refresh, or longer (DESIGN.md 4.22 has the figures)."""
+        self._check_open()
+        held = getattr(self.engine, "grid_u8", None)
+        grid = np.array(held, dtype=int) if held is not None else self.grid
+        new = checked_cost(type(self).__name__, grid, self.cost if cost is None else cost)
+        changed = changed_cells(self.grid, self.cost, grid, new)
+        if changed.size == 0:
+            return self
+        if cost is not None:
+            self.cost_device.upload(new.reshape(-1))
+        for name in ("pbuf", "obuf", "cbuf"):
+            buf = getattr(self, name)
+            setattr(self, name, None)
+            if buf is not None:
+                buf.free()
+        self._fields = self._parents = self._owners = self._counts = self._info = None
+        self.chosen = np.zeros(0, np.int32)
+        e = self.engine
+        e.cost_field_repair(self.cost_device, changed, self.set_off, self.ids, self.buf, self.allow_diagonal_moves, self.restrict_diagonal_near_obstacle,
+                            self.ibuf)
+        self.grid, self.cost = grid, new
+        self.work = e.cost_field_work()
+        self.kernel_ms = e.last_kernel_ms()
         return self
 
     def path_costs(self, paths):

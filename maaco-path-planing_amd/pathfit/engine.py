@@ -381,8 +381,23 @@ class Engine:
                                       d_info.ptr if d_info else None))
         self._logk("cost_field")
 
+    def cost_field_repair(self, d_cost, changed, set_off, sources, d_rows, allow_diag=True, restrict_corner=True, d_info=None):
+        """d_rows float64 [B, R * C]: what cost_field (or an earlier repair) left for the same sets and policy on a map and a cost map
+        that differ from the engine's present grid and d_cost at most on the flat cell ids of `changed` (host; duplicates and cells
+        that did not change are fine) -> the rows, and d_info, bit for bit as cost_field would write them now: the labels that lost
+        their support are raised to inf, then lowered from there (pf_cost_field_repair).  cost_field_work then reports (launches of
+        both phases, tile visits of both, words lowered, words raised)."""
+        off = np.ascontiguousarray(set_off, np.int32).reshape(-1)
+        src = np.ascontiguousarray(sources, np.int32).reshape(-1)
+        chg = np.ascontiguousarray(changed, np.int32).reshape(-1)
+        self._ck(self.L.pf_cost_field_repair(self.h, int(bool(allow_diag)), int(bool(restrict_corner)), d_cost.ptr if d_cost else None, int(chg.size),
+                                             chg.ctypes.data if chg.size else None, int(off.size) - 1, off.ctypes.data if off.size else None,
+                                             src.ctypes.data if src.size else None, d_rows.ptr if d_rows else None, d_info.ptr if d_info else None))
+        self._logk("cost_field_repair")
+
     def cost_field_work(self):
-        """(launches, tile visits, words lowered, 0) of the last cost_field call: they depend on the schedule (the probe's figures)."""
+        """(launches, tile visits, words lowered, words raised) of the last cost_field or cost_field_repair call (0 words raised after
+        cost_field); the first three depend on the schedule (the probe's figures)."""
         out = (C.c_int64 * 4)()
         self._ck(self.L.pf_cost_field_work(self.h, out))
         return tuple(int(v) for v in out)
