@@ -642,6 +642,29 @@ int pf_cost_paths(pf_handle* h, const double* d_cost, int32_t n, int32_t path_ca
 int pf_turn_field(pf_handle* h, int32_t allow_diag, int32_t restrict_corner, const double* d_cost, double turn_weight, int32_t B,
                   const int32_t* set_off, const int32_t* src, double* d_states, double* d_best, int64_t* d_info);
 int pf_turn_field_work(pf_handle* h, int64_t* out4);
+/* pf_turn_field_repair: the exact update of a turn field after a few cells changed.  d_states [B][8][R C] and
+ * d_best [B][R C] hold what pf_turn_field (or an earlier repair) left for the same sets, policy and turn_weight, computed on an
+ * occupancy and a cost map that differ from the handle's present occupancy (after pf_update_grid) and from d_cost (NULL: ones) at
+ * most on the n_changed cells of `changed`, a HOST array of flat cell ids; duplicates are fine, and so are cells that in fact did
+ * not change.  On return the states, best and d_info (or NULL) are bit for bit what pf_turn_field would write now.  Two phases on
+ * the tile-queue engine over the turn tile: the finite states that lost their support -- no d' with
+ * fl(T[d'][u] + e(d', d)) == T[d][v] over a legal move u -> v of the new mask, u = v - step(d), and every finite state on an
+ * obstacle -- are raised to +inf, tile by tile from the 3 x 3 blocks about the listed cells, until nothing changes, and best is
+ * rewritten as the minimum of what survives (it may rise to a finite value); every free source takes 0 in its nine words; then
+ * pf_turn_field's relax kernel lowers from the tiles that had a state raised, that meet such a block or that hold a new seed.
+ * The work follows the tiles the invalid region crosses, not the map; a change next to a source may cost as much as a fresh field
+ * or more.  The result does not depend on the timing.  If the caller breaks the contract the result is unspecified, but the call
+ * ends within the round bounds (8 R C + 1 launches a phase) and the sweep bound, and accesses nothing out of range.
+ * n_changed == 0: the rows stay untouched and no tile kernel is launched; d_info is still written when given.  n_changed < 0, a
+ * null `changed` with n_changed > 0, an id outside [0, R C) (the message names its index) and every argument error of
+ * pf_turn_field: -1 with a message, found on the host before any launch; a bad cost on a free cell: -1, found by the validation
+ * kernel BEFORE anything is written; a null handle: -2.  Afterwards pf_turn_field_work reports {tile launches of both phases,
+ * tile visits of both, state words lowered, state words raised}: the states that were finite before and +inf after the raise
+ * phase, a figure that does not depend on the schedule (after pf_turn_field the fourth word stays 0).  pf_last_kernel_ms spans
+ * everything.  Scratch: pf_clearance_widest's block, grown by one word per (set, tile), six words and the device copy of the list. */
+int pf_turn_field_repair(pf_handle* h, int32_t allow_diag, int32_t restrict_corner, const double* d_cost, double turn_weight,
+                         int32_t n_changed, const int32_t* changed, int32_t B, const int32_t* set_off, const int32_t* src,
+                         double* d_states, double* d_best, int64_t* d_info);
 int pf_turn_field_paths(pf_handle* h, const double* d_cost, double turn_weight, int32_t B, const double* d_states, int32_t n,
                         const int32_t* d_set_idx, const int32_t* d_target, int32_t reverse, int32_t path_cap, int32_t* d_cells,
                         int32_t* d_len, int32_t* d_status);

@@ -861,6 +861,7 @@ int pf_cost_paths(pf_handle* h, const double* d_cost, int32_t n, int32_t path_ca
 // PF_TF_TH).
 // ---------------------------------------------------------------------------
 #include "pf_turn_field.h"
+#include "pf_turn_repair.h"
 
 static_assert(PF_WD_THREADS == 256 && PF_CF_THREADS == 256 && PF_TF_THREADS == 256, "tile_call sizes the seed grids for 256 threads");
 
@@ -909,6 +910,85 @@ int pf_turn_field(pf_handle* h, int32_t allow_diag, int32_t restrict_corner, con
 }
 
 int pf_turn_field_work(pf_handle* h, int64_t* out4) { return tile_work(h, "pf_turn_field_work", h ? h->turn_work : nullptr, out4); }
+
+// Turn-field repair (pf_turn_repair.h): pf_cost_field_repair's two runs of tile_rounds over the turn tile.  The
+// block grows by the touched flags [T], the raise phase's two words {state words raised, its sweep bound's error word} -- moved[1]
+// is the relax kernel's error word in turn calls -- and the device copy of the changed list, behind the flags.
+int pf_turn_field_repair(pf_handle* h, int32_t allow_diag, int32_t restrict_corner, const double* d_cost, double turn_weight, int32_t n_changed, const int32_t* changed,
+                         int32_t B, const int32_t* set_off, const int32_t* src, double* d_states, double* d_best, int64_t* d_info) {
+  if (!h) return -2;
+  const std::string me("pf_turn_field_repair");
+  auto run = [&]() -> int {
+    std::vector<int> listed;
+    if (nearest_sets_check(h, me, B, set_off, src, listed)) return -2;
+    if (!d_states || !d_best) return failmsg(h, me + ": bad arguments (the states and the best rows must not be null)");
+    if (turn_weight_check(h, me, turn_weight)) return -2;
+    if (n_changed < 0) return failmsg(h, me + ": bad arguments (n_changed = " + std::to_string(n_changed) + ": the number of changed cells must not be negative)");
+    if (n_changed > 0 && !changed) return failmsg(h, me + ": bad arguments (the changed cells must not be null when n_changed > 0)");
+    for (int i = 0; i < n_changed; ++i)
+      if (changed[i] < 0 || changed[i] >= h->RC)
+        return failmsg(h, me + ": changed[" + std::to_string(i) + "] = " + std::to_string(changed[i]) + " lies outside the grid");
+    std::vector<int> sets(1, 0);                                      // the sets with every source once: {error word, off [B + 1], ids}
+    {
+      std::vector<int> off(1, 0), ids;
+      for (int b = 0; b < B; ++b) {
+        std::vector<int> s(src + set_off[b], src + set_off[b + 1]);
+        std::sort(s.begin(), s.end());
+        s.erase(std::unique(s.begin(), s.end()), s.end());
+        ids.insert(ids.end(), s.begin(), s.end());
+        off.push_back((int)ids.size());
+      }
+      sets.insert(sets.end(), off.begin(), off.end());
+      sets.insert(sets.end(), ids.begin(), ids.end());
+    }
+    CK(hipSetDevice(h->device));
+    const int R = h->R, C = h->C, RC = h->RC;
+    TileCall k;                                                       // top: the largest finite best label's bits per set; moved[1]: the relax kernel's sweep-bound word
+    if (const int rc = tile_call(h, me, B, sets, PF_TF_TW, PF_TF_TH, h->turn_work, k, 1, (size_t)n_changed + 6)) return rc;
+    int* const touched = k.flag + 2 * k.T;
+    unsigned long long* const rwords = (unsigned long long*)(((uintptr_t)(touched + k.T) + 7u) & ~(uintptr_t)7u);   // (8-byte aligned: at most one word of the six is skipped)
+    int* const d_changed = (int*)(rwords + 2);
+    CK(hipEventRecord(h->ev0, h->stream));
+    if (d_cost)
+      if (const int rc = cost_map_check(h, me, d_cost, k.count + 2, nullptr)) return rc;
+    CK(hipMemsetAsync(touched, 0, sizeof(int) * k.T, h->stream));
+    CK(hipMemsetAsync(rwords, 0, sizeof(unsigned long long) * 2, h->stream));
+    if (n_changed) CK(hipMemcpyAsync(d_changed, changed, sizeof(int) * (size_t)n_changed, hipMemcpyHostToDevice, h->stream));
+    if (tile_upload(h, k, sets, 0)) return -2;                        // (it synchronises: the caller's list may leave scope)
+    const uint8_t* occ = h->d_occ;
+    const uint8_t* mm = move_mask(h, allow_diag, restrict_corner);
+    const int most = std::max(std::max((int)std::min<size_t>(k.T, 0x7FFFFFFF), (int)n_changed), sets[B + 1]);
+    const dim3 qgrid((unsigned)std::min((n_changed + PF_TF_THREADS - 1) / PF_TF_THREADS, 256), k.gy);
+    const dim3 lgrid((unsigned)std::min((most + PF_TF_THREADS - 1) / PF_TF_THREADS, 256), k.gy);
+    if (n_changed) {
+      hipLaunchKernelGGL(k_turn_repair_queue_changed_blocks, qgrid, dim3(PF_TF_THREADS), 0, h->stream, R, C, k.tiles_x, k.ntiles, (int)B, (int)n_changed,
+                         (const int*)d_changed, k.flag, k.queue, k.count);
+      if (const int rc = tile_rounds(h, me, k, 8 * (long long)RC + 1, [&](const TileRound& r) {
+            hipLaunchKernelGGL(k_turn_raise_tiles_in_lds, dim3((unsigned)r.n), dim3(PF_TF_THREADS), 0, h->stream, occ, mm, d_cost, turn_weight, R, C, allow_diag ? 1 : 0,
+                               k.tiles_x, k.tiles_y, d_states, d_best, r.queue, r.n, r.flag_now, r.count_now, r.flag_next, r.queue_next, r.count_next, touched, rwords);
+          })) return rc;
+    }
+    if (n_changed || d_info)                                          // (nothing listed: it only counts the sources, for the info)
+      hipLaunchKernelGGL(k_turn_repair_queue_lower, lgrid, dim3(PF_TF_THREADS), 0, h->stream, occ, R, C, k.tiles_x, k.ntiles, (int)B, (int)k.T, (const int*)touched,
+                         (int)n_changed, (const int*)d_changed, (const int*)k.d_off, (const int*)k.d_src, n_changed ? 1 : 0, d_states, d_best, k.flag, k.queue, k.count,
+                         k.nsrc);
+    if (n_changed)
+      if (const int rc = tile_rounds(h, me, k, 8 * (long long)RC + 1, [&](const TileRound& r) {
+            hipLaunchKernelGGL(k_turn_relax_tiles_in_lds, dim3((unsigned)r.n), dim3(PF_TF_THREADS), 0, h->stream, occ, mm, d_cost, turn_weight, R, C, allow_diag ? 1 : 0,
+                               k.tiles_x, k.tiles_y, d_states, d_best, r.queue, r.n, r.first, r.flag_now, r.count_now, r.flag_next, r.queue_next, r.count_next, k.moved);
+          })) return rc;
+    if (d_info) cost_info(h, k, d_best, d_info);
+    if (const int rc = tile_finish(h, k)) return rc;
+    unsigned long long rw[2] = {0, 0};
+    CK(hipMemcpyAsync(rw, rwords, sizeof(rw), hipMemcpyDeviceToHost, h->stream));
+    CK(hipStreamSynchronize(h->stream));
+    h->d2h_small += 1;
+    k.work[3] = (long long)rw[0];
+    if (k.end[1] || rw[1]) return failmsg(h, me + ": internal: sweep bound");
+    return 0;
+  };
+  return run() ? -1 : 0;
+}
 
 int pf_turn_field_paths(pf_handle* h, const double* d_cost, double turn_weight, int32_t B, const double* d_states, int32_t n, const int32_t* d_set_idx,
                         const int32_t* d_target, int32_t reverse, int32_t path_cap, int32_t* d_cells, int32_t* d_len, int32_t* d_status) {

@@ -180,6 +180,7 @@ SYMBOLS = {
     "pf_cost_paths": (C.c_int, [_vp, _vp, _i32, _i32, _vp, _vp, _vp, _vp]),
     "pf_turn_field": (C.c_int, [_vp, _i32, _i32, _vp, _dbl, _i32, _vp, _vp, _vp, _vp, _vp]),
     "pf_turn_field_work": (C.c_int, [_vp, _vp]),
+    "pf_turn_field_repair": (C.c_int, [_vp, _i32, _i32, _vp, _dbl, _i32, _vp, _i32, _vp, _vp, _vp, _vp, _vp]),
     "pf_turn_field_paths": (C.c_int, [_vp, _vp, _dbl, _i32, _vp, _i32, _vp, _vp, _i32, _i32, _vp, _vp, _vp]),
     "pf_turn_paths": (C.c_int, [_vp, _vp, _dbl, _i32, _i32, _vp, _vp, _vp, _vp, _vp]),
 }

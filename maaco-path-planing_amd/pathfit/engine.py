@@ -429,8 +429,25 @@ class Engine:
                                       d_states.ptr if d_states else None, d_best.ptr if d_best else None, d_info.ptr if d_info else None))
         self._logk("turn_field")
 
+    def turn_field_repair(self, d_cost, turn_weight, changed, set_off, sources, d_states, d_best, allow_diag=True, restrict_corner=True, d_info=None):
+        """d_states float64 [B, 8, R * C] and d_best float64 [B, R * C]: what turn_field (or an earlier repair) left for the same sets,
+        policy and turn weight on a map and a cost map that differ from the engine's present grid and d_cost (None: ones) at most on
+        the flat cell ids of `changed` (host; duplicates and cells that did not change are fine) -> the states, best and d_info, bit
+        for bit as turn_field would write them now: the states that lost their support are raised to inf, then lowered from there
+        (pf_turn_field_repair).  turn_field_work then reports (launches of both phases, tile visits of both, state words lowered,
+        state words raised)."""
+        off = np.ascontiguousarray(set_off, np.int32).reshape(-1)
+        src = np.ascontiguousarray(sources, np.int32).reshape(-1)
+        chg = np.ascontiguousarray(changed, np.int32).reshape(-1)
+        self._ck(self.L.pf_turn_field_repair(self.h, int(bool(allow_diag)), int(bool(restrict_corner)), d_cost.ptr if d_cost else None, float(turn_weight),
+                                             int(chg.size), chg.ctypes.data if chg.size else None, int(off.size) - 1, off.ctypes.data if off.size else None,
+                                             src.ctypes.data if src.size else None, d_states.ptr if d_states else None, d_best.ptr if d_best else None,
+                                             d_info.ptr if d_info else None))
+        self._logk("turn_field_repair")
+
     def turn_field_work(self):
-        """(launches, tile visits, state words lowered, 0) of the last turn_field call: they depend on the schedule (the probe's figures)."""
+        """(launches, tile visits, state words lowered, state words raised) of the last turn_field or turn_field_repair call (0 words
+        raised after turn_field); the first three depend on the schedule (the probe's figures)."""
         out = (C.c_int64 * 4)()
         self._ck(self.L.pf_turn_field_work(self.h, out))
         return tuple(int(v) for v in out)

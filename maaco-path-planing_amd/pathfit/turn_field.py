@@ -4,12 +4,13 @@ states[b, d, r, c] is the cheapest cost of a walk from a source of set b that en
 move weighing as CostField's and turn_weight more when it differs from the move before; best[b, r, c] is the smallest of the eight.
 At turn_weight == 0 best is CostField's field bit for bit.  `paths` reads the route out of the states alone (pf_turn_field_paths);
 `path_costs` scores any path rows under the same rule (pf_turn_paths).  Everything stays in HBM; `refresh` recomputes after
-`engine.update_grid`, under a new cost map or a new turn weight."""
+`engine.update_grid`, under a new cost map or a new turn weight; `repair` updates the field it holds for the cells that changed
+(pf_turn_field_repair), with the same result."""
 import numpy as np
 
 from ._field import Field
 from ._lib import PathfitError
-from .cost_field import CostField, checked_cost
+from .cost_field import CostField, changed_cells, checked_cost
 from .engine import Engine
 from .nearest_field import NearestSourceField
 from .paths import CellPath
@@ -33,7 +34,8 @@ class TurnField(Field):
     the timing of the device.
 
     info: int64 [B, 4] = (sources that counted, cells reached, the cell id with the largest finite best -- the smallest on a tie, -1
-    when nothing is reached --, 0).  work: (launches of the tile kernel, tile visits, state words lowered, 0) of the last computation."""
+    when nothing is reached --, 0).  work: (launches of the tile kernel, tile visits, state words lowered, 0) of the last computation
+    ((launches of both phases, tile visits of both, state words lowered, state words raised) after `repair`)."""
     _bufs = ("cost_device", "sbuf", "bbuf", "ibuf")
     _set_source_sets = NearestSourceField._set_source_sets
 
@@ -178,4 +180,41 @@ class TurnField(Field):
             else:
                 self.cost_device.upload(new.reshape(-1))
         self._compute()
+        return self
+
+    def repair(self, cost=None):
+        """refresh(cost), done incrementally (pf_turn_field_repair): the field held here is repaired for the map the engine holds now
+        (after engine.update_grid) and, when given, a new cost map; the turn weight is not changed here (that is refresh).  The cells
+        that differ (cost_field.changed_cells; a field without a cost map compares against ones, and takes a cost map here as refresh
+        does) are found here; the states that lost their support are raised to inf on the device, best is rewritten, and both are
+        lowered again from there, at a cost that follows the tiles the invalid region crosses instead of the map.  States, best and
+        info are bit for bit refresh's.  With nothing changed it returns at once and keeps what was downloaded; otherwise states,
+        best and info are dropped as refresh drops them.  work: (launches of both phases, tile visits of both, state words lowered,
+        state words raised).  A change next to a source may invalidate most of the field: the repair then crosses the same tiles
+        twice and can take as long as refresh, or longer (DESIGN.md 4.23 has the figures)."""
+        who = type(self).__name__
+        self._check_open()
+        held = getattr(self.engine, "grid_u8", None)
+        grid = np.array(held, dtype=int) if held is not None else self.grid
+        new = self.cost if cost is None else cost
+        if new is not None:
+            new = checked_cost(who, grid, new)
+        ones = np.ones(grid.shape)
+        changed = changed_cells(self.grid, ones if self.cost is None else self.cost, grid, ones if new is None else new)
+        if changed.size == 0:
+            return self
+        if cost is not None:
+            if self.cost_device is None:
+                self.cost_device = self.engine.put(new.reshape(-1), np.float64)
+            else:
+                self.cost_device.upload(new.reshape(-1))
+        self._states = self._best = self._info = None
+        e = self.engine
+        e.turn_field_repair(self.cost_device, self.turn_weight, changed, self.set_off, self.ids, self.sbuf, self.bbuf, self.allow_diagonal_moves,
+                            self.restrict_diagonal_near_obstacle, self.ibuf)
+        self.grid = grid
+        if cost is not None:
+            self.cost = new
+        self.work = e.turn_field_work()
+        self.kernel_ms = e.last_kernel_ms()
         return self
