@@ -671,6 +671,37 @@ int pf_turn_field_paths(pf_handle* h, const double* d_cost, double turn_weight, 
 int pf_turn_paths(pf_handle* h, const double* d_cost, double turn_weight, int32_t n, int32_t path_cap, const int32_t* d_cells,
                   const int32_t* d_len, double* d_total, int32_t* d_turns, int32_t* d_bad);
 
+/* ---- visibility fields: what each viewpoint sees, exposure counts, the exposure of path rows (pathfit.Visibility) -----------
+ * The rule is the smoothing section's visible(a, b, restrict_corner), evaluated from one cell to all: the cells
+ * of the bounding box with |2k| < s are crossed, those with |2k| == s touched; b is seen from a iff no crossed cell is an
+ * obstacle and, with restrict_corner != 0, no touched one either; a == b is seen iff the cell is free; the endpoints are
+ * crossed.  So a viewpoint on an obstacle sees nothing, an obstacle is never seen, and the relation is symmetric.  With
+ * max_range_sq >= 0 a cell counts only if dr^2 + dc^2 <= max_range_sq (integers); -1 means no limit.  `view` is a HOST array of
+ * K cell ids (as pf_dist_field_batch's sources); the occupancy is read at call time (pf_update_grid keeps working).
+ * pf_visibility_field: d_seen[k * R C + v] = 1 where view[k] sees v within the range, else 0; every byte of the K rows is
+ * written.  d_info (or NULL) int64 [K][4]: {cells seen, the largest dr^2 + dc^2 among them, the smallest cell id that attains
+ * it, 0}; {0, -1, -1, 0} when nothing is seen.  One lane per target, 64 consecutive cells per wavefront: a lane walks its own
+ * sight line and leaves at the first blocker.
+ * pf_visibility_count: d_count[v] = the number of k with view[k] seeing v (a viewpoint listed twice counts twice); the K masks
+ * are never materialised.  d_info (or NULL) int64 [4]: {free cells with count > 0, free cells, the largest count over the free
+ * cells, the smallest free cell id that attains it}; the last two -1 on a map without a free cell.  Integer sums (a lane per (viewpoint,
+ * cell) pair and one integer atomic per seen pair): identical run to run.
+ * pf_visibility_paths: n path rows laid out as pf_astar_batch's against counts in HBM (int32 [R C]) -> d_out[i * 4 ..] = {the
+ * sum of the counts over the row's cells, the largest count, the position of the first cell that attains it, the cells with
+ * count > 0}; d_profile (or NULL) [n * path_cap]: the count per cell, words beyond d_len[i] untouched.  d_status: 0 ok; 1 = an
+ * empty row, a length beyond path_cap or a cell outside [0, R C): d_out = {0, -1, -1, 0}, the profile row untouched, nothing read
+ * out of range.  One wavefront per row.
+ * A null handle (-2); K < 1, max_range_sq < -1, a viewpoint outside [0, R C) (the message names its index), R^2 + C^2 >= 2^31 - 1,
+ * a missing required pointer, n < 0 or path_cap < 1 (-1, with a message) is an argument error found before any launch; n == 0
+ * returns 0 and launches nothing.  All three are synchronous and ordered on the handle's stream; pf_last_kernel_ms reports the
+ * kernels.  Scratch: the distance fields' control block (the viewpoints and a few 64-bit words). */
+int pf_visibility_field(pf_handle* h, int32_t restrict_corner, int32_t max_range_sq, int32_t K, const int32_t* view,
+                        uint8_t* d_seen, int64_t* d_info);
+int pf_visibility_count(pf_handle* h, int32_t restrict_corner, int32_t max_range_sq, int32_t K, const int32_t* view,
+                        int32_t* d_count, int64_t* d_info);
+int pf_visibility_paths(pf_handle* h, const int32_t* d_count, int32_t n, int32_t path_cap, const int32_t* d_cells,
+                        const int32_t* d_len, int64_t* d_out, int32_t* d_profile, int32_t* d_status);
+
 /* Tuning knobs (results never change): "components_phases" 0/1 pf_components records a HIP event after each phase
  * (pf_components_phase_ms; default 0); "maaco_pack8_min" ants per batch from which eight ants share a wavefront
  * (default 2048); "maaco_load_ahead" the packed walk kernel's load-ahead form (all of a step's loads issued together plus touches of the

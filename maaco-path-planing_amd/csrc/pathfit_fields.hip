@@ -1,5 +1,5 @@
 // pathfit_fields.hip -- the field family of libpathfit.so: distance fields, routing trees, nearest-source fields, smoothing,
-// connected components, clearance, widest paths, cost fields and turn fields.  A translation unit, and so a device code object, of its own (DESIGN.md
+// connected components, clearance, widest paths, cost fields, turn fields and visibility fields.  A translation unit, and so a device code object, of its own (DESIGN.md
 // 4.18): it shares the handle and the error helpers with pathfit.hip (pf_host.h) and none of the solvers' device code.
 #include <algorithm>
 #include <string>
@@ -1024,6 +1024,113 @@ int pf_turn_paths(pf_handle* h, const double* d_cost, double turn_weight, int32_
     return timed(h, [&] {
       hipLaunchKernelGGL(k_turn_paths_one_wave_per_row, dim3((unsigned)n), dim3(64), 0, h->stream, d_cost, turn_weight, h->RC, h->C, (int)n, (int)path_cap,
                          (const int*)d_cells, (const int*)d_len, d_total, (int*)d_turns, (int*)d_bad);
+    });
+  };
+  return run() ? -1 : 0;
+}
+
+}  // extern "C"
+
+// ---------------------------------------------------------------------------
+// Visibility fields: what each viewpoint sees, exposure counts and the exposure of path rows (pf_visibility.h).
+// The rule is the smoothing section's, one-to-all.  The occupancy is read at call time (pf_update_grid keeps working); the
+// viewpoints and the info keys of a call live in the distance fields' control block, and nothing in it outlives the call.
+// ---------------------------------------------------------------------------
+#include "pf_visibility.h"
+
+// The checks of the two one-to-all calls, then the call's view of the control block: n64 zeroed 64-bit words in front, the
+// viewpoints behind them.
+static int visibility_views(pf_handle* h, const std::string& me, int max_range_sq, int K, const int32_t* view, const void* d_out, size_t n64,
+                            unsigned long long*& keys, int*& d_view) {
+  if (K < 1) return failmsg(h, me + ": bad arguments (K = " + std::to_string(K) + ": at least one viewpoint is needed)");
+  if (max_range_sq < -1) return failmsg(h, me + ": bad arguments (max_range_sq = " + std::to_string(max_range_sq) + ": -1 means no limit, else >= 0)");
+  if (!view || !d_out) return failmsg(h, me + ": bad arguments (the viewpoints and the output must not be null)");
+  if ((long long)h->R * h->R + (long long)h->C * h->C >= 0x7FFFFFFFll) return failmsg(h, me + ": bad arguments (R^2 + C^2 must stay below 2^31 - 1)");
+  for (int k = 0; k < K; ++k)
+    if (view[k] < 0 || view[k] >= h->RC)
+      return failmsg(h, me + ": viewpoint " + std::to_string(k) + " = " + std::to_string(view[k]) + " lies outside the grid");
+  CK(hipSetDevice(h->device));
+  if (scratch(h, me, h->d_df_ctl, &h->df_ctl_bytes, std::max<size_t>(sizeof(unsigned long long) * n64 + sizeof(int) * (size_t)K, 256), "the viewpoints", false)) return -2;
+  keys = (unsigned long long*)h->d_df_ctl;                            // (in front: 8-byte aligned)
+  d_view = (int*)(keys + n64);
+  CK(hipMemcpyAsync(d_view, view, sizeof(int) * (size_t)K, hipMemcpyHostToDevice, h->stream));
+  CK(hipStreamSynchronize(h->stream));                                // (view is pageable and the caller's)
+  return 0;
+}
+
+extern "C" {
+
+int pf_visibility_field(pf_handle* h, int32_t restrict_corner, int32_t max_range_sq, int32_t K, const int32_t* view, uint8_t* d_seen, int64_t* d_info) {
+  if (!h) return -2;
+  const std::string me("pf_visibility_field");
+  auto run = [&]() -> int {
+    unsigned long long* keys = nullptr;
+    int* d_view = nullptr;
+    if (const int rc = visibility_views(h, me, max_range_sq, K, view, d_seen, 2 * (size_t)(K > 0 ? K : 0), keys, d_view)) return rc;
+    const int RC = h->RC, C = h->C;
+    const unsigned gy = (unsigned)(K < 65535 ? K : 65535);
+    return timed(h, [&]() -> int {
+#if PF_VIS_WAVE_PER_TARGET
+      hipLaunchKernelGGL(k_visibility_field_wave_per_target, dim3(((unsigned)RC + PF_VIS_THREADS / 64 - 1) / (PF_VIS_THREADS / 64), gy), dim3(PF_VIS_THREADS), 0, h->stream,
+                         (const uint8_t*)h->d_occ, RC, C, restrict_corner ? 1 : 0, (int)max_range_sq, (int)K, (const int*)d_view, d_seen);
+#else
+      hipLaunchKernelGGL(k_visibility_field_lane_per_target, dim3(((unsigned)RC + PF_VIS_THREADS - 1) / PF_VIS_THREADS, gy), dim3(PF_VIS_THREADS), 0, h->stream,
+                         (const uint8_t*)h->d_occ, RC, C, restrict_corner ? 1 : 0, (int)max_range_sq, (int)K, (const int*)d_view, d_seen);
+#endif
+      if (d_info) {
+        CK(hipMemsetAsync(keys, 0, sizeof(unsigned long long) * 2 * (size_t)K, h->stream));
+        const unsigned nb = ((unsigned)RC + PF_VIS_THREADS - 1) / PF_VIS_THREADS;
+        hipLaunchKernelGGL(k_visibility_field_info_reduce, dim3(nb < 256u ? nb : 256u, gy), dim3(PF_VIS_THREADS), 0, h->stream, (const uint8_t*)d_seen, RC, C, (int)K,
+                           (const int*)d_view, keys);
+        hipLaunchKernelGGL(k_visibility_field_write_info, dim3(((unsigned)K + PF_VIS_THREADS - 1) / PF_VIS_THREADS), dim3(PF_VIS_THREADS), 0, h->stream, (int)K,
+                           (const unsigned long long*)keys, (long long*)d_info);
+      }
+      return 0;
+    });
+  };
+  return run() ? -1 : 0;
+}
+
+int pf_visibility_count(pf_handle* h, int32_t restrict_corner, int32_t max_range_sq, int32_t K, const int32_t* view, int32_t* d_count, int64_t* d_info) {
+  if (!h) return -2;
+  const std::string me("pf_visibility_count");
+  auto run = [&]() -> int {
+    unsigned long long* ctl = nullptr;
+    int* d_view = nullptr;
+    if (const int rc = visibility_views(h, me, max_range_sq, K, view, d_count, 4, ctl, d_view)) return rc;
+    const int RC = h->RC, C = h->C;
+    const int per = vis_count_per(RC, K);
+    const unsigned chunks = (unsigned)((K + per - 1) / per);
+    const unsigned nb = ((unsigned)RC + PF_VIS_THREADS - 1) / PF_VIS_THREADS;
+    return timed(h, [&]() -> int {
+      CK(hipMemsetAsync(d_count, 0, sizeof(int) * (size_t)RC, h->stream));
+      hipLaunchKernelGGL(k_visibility_count_lanes_on_targets, dim3(nb, chunks < 65535u ? chunks : 65535u), dim3(PF_VIS_THREADS), 0, h->stream, (const uint8_t*)h->d_occ, RC, C,
+                         restrict_corner ? 1 : 0, (int)max_range_sq, (int)K, per, (const int*)d_view, (int*)d_count);
+      if (d_info) {
+        CK(hipMemsetAsync(ctl, 0, sizeof(unsigned long long) * 4, h->stream));
+        hipLaunchKernelGGL(k_visibility_count_info_reduce, dim3(nb < 1024u ? nb : 1024u), dim3(PF_VIS_THREADS), 0, h->stream, (const uint8_t*)h->d_occ, (const int*)d_count, RC,
+                           ctl);
+        hipLaunchKernelGGL(k_visibility_count_write_info, dim3(1), dim3(64), 0, h->stream, (const unsigned long long*)ctl, (long long*)d_info);
+      }
+      return 0;
+    });
+  };
+  return run() ? -1 : 0;
+}
+
+int pf_visibility_paths(pf_handle* h, const int32_t* d_count, int32_t n, int32_t path_cap, const int32_t* d_cells, const int32_t* d_len, int64_t* d_out,
+                        int32_t* d_profile, int32_t* d_status) {
+  if (!h) return -2;
+  if (n < 0 || path_cap < 1 || !d_count || !d_cells || !d_len || !d_out || !d_status) {
+    failmsg(h, "pf_visibility_paths: bad arguments (n >= 0, path_cap >= 1; the counts, the rows, the lengths, the results and the statuses must not be null)");
+    return -1;
+  }
+  if (n == 0) return 0;
+  auto run = [&]() -> int {
+    CK(hipSetDevice(h->device));
+    return timed(h, [&] {
+      hipLaunchKernelGGL(k_visibility_paths_one_wave_per_row, dim3((unsigned)n), dim3(64), 0, h->stream, (const int*)d_count, h->RC, (int)n, (int)path_cap, (const int*)d_cells,
+                         (const int*)d_len, (long long*)d_out, (int*)d_profile, (int*)d_status);
     });
   };
   return run() ? -1 : 0;

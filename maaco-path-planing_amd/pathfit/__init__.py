@@ -23,3 +23,4 @@ from .components import Components  # noqa: F401
 from .clearance import Clearance, PF_CLEAR_NONE  # noqa: F401
 from .cost_field import CostField  # noqa: F401
 from .turn_field import TurnField  # noqa: F401
+from .visibility import Visibility  # noqa: F401

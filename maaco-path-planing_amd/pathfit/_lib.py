@@ -183,6 +183,9 @@ SYMBOLS = {
     "pf_turn_field_repair": (C.c_int, [_vp, _i32, _i32, _vp, _dbl, _i32, _vp, _i32, _vp, _vp, _vp, _vp, _vp]),
     "pf_turn_field_paths": (C.c_int, [_vp, _vp, _dbl, _i32, _vp, _i32, _vp, _vp, _i32, _i32, _vp, _vp, _vp]),
     "pf_turn_paths": (C.c_int, [_vp, _vp, _dbl, _i32, _i32, _vp, _vp, _vp, _vp, _vp]),
+    "pf_visibility_field": (C.c_int, [_vp, _i32, _i32, _i32, _vp, _vp, _vp]),
+    "pf_visibility_count": (C.c_int, [_vp, _i32, _i32, _i32, _vp, _vp, _vp]),
+    "pf_visibility_paths": (C.c_int, [_vp, _vp, _i32, _i32, _vp, _vp, _vp, _vp, _vp]),
 }
 
 

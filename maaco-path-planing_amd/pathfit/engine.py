@@ -469,6 +469,35 @@ class Engine:
                                       d_bad.ptr if d_bad else None))
         self._logk("turn_paths")
 
+    # ------------------------------------------------------------------ visibility fields
+    def visibility_field(self, viewpoints, d_seen, restrict_corner=True, max_range_sq=-1, d_info=None):
+        """What each of the K cells `viewpoints` (host int32 ids) sees, on the map the handle holds now -> d_seen uint8 [K, R * C] in
+        HBM (1 where the segment between the centres meets no obstacle; with restrict_corner, touches none in a corner either; and
+        dr^2 + dc^2 <= max_range_sq unless that is -1); d_info int64 [K, 4] = (cells seen, the largest dr^2 + dc^2 among them, the
+        smallest cell id that attains it, 0), (0, -1, -1, 0) when nothing is seen (pf_visibility_field)."""
+        view = np.ascontiguousarray(viewpoints, np.int32).reshape(-1)
+        self._ck(self.L.pf_visibility_field(self.h, int(bool(restrict_corner)), int(max_range_sq), int(view.size), view.ctypes.data if view.size else None,
+                                            d_seen.ptr if d_seen else None, d_info.ptr if d_info else None))
+        self._logk("visibility_field")
+
+    def visibility_count(self, viewpoints, d_count, restrict_corner=True, max_range_sq=-1, d_info=None):
+        """-> d_count int32 [R * C] in HBM: how many of the viewpoints see each cell (one listed twice counts twice), without the K
+        masks; d_info int64 [4] = (free cells with count > 0, free cells, the largest count over the free cells, the smallest free
+        cell id that attains it) (pf_visibility_count)."""
+        view = np.ascontiguousarray(viewpoints, np.int32).reshape(-1)
+        self._ck(self.L.pf_visibility_count(self.h, int(bool(restrict_corner)), int(max_range_sq), int(view.size), view.ctypes.data if view.size else None,
+                                            d_count.ptr if d_count else None, d_info.ptr if d_info else None))
+        self._logk("visibility_count")
+
+    def visibility_paths(self, d_count, n, path_cap, d_cells, d_len, d_out, d_status, d_profile=None):
+        """Rows of astar_batch's layout in HBM against counts in HBM -> d_out int64 [n, 4] = (the sum of the counts over the row's
+        cells, the largest count, the first position that attains it, the cells with count > 0), d_profile int32 [n, path_cap] the
+        count per cell, d_status (0 ok, 1 bad row: d_out = (0, -1, -1, 0)) (pf_visibility_paths)."""
+        self._ck(self.L.pf_visibility_paths(self.h, d_count.ptr if d_count else None, int(n), int(path_cap), d_cells.ptr if d_cells else None,
+                                            d_len.ptr if d_len else None, d_out.ptr if d_out else None, d_profile.ptr if d_profile else None,
+                                            d_status.ptr if d_status else None))
+        self._logk("visibility_paths")
+
     # ------------------------------------------------------------------ K1
     def score_batch(self, n, path_cap, d_cells, d_len, d_stats, sp):
         """Rows of astar_batch's layout in HBM -> d_stats [n, 5] doubles (pf_score_batch)."""
