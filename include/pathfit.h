@@ -702,6 +702,64 @@ int pf_visibility_count(pf_handle* h, int32_t restrict_corner, int32_t max_range
 int pf_visibility_paths(pf_handle* h, const int32_t* d_count, int32_t n, int32_t path_cap, const int32_t* d_cells,
                         const int32_t* d_len, int64_t* d_out, int32_t* d_profile, int32_t* d_status);
 
+/* ---- space-time fields: arrival ticks and routes among moving obstacles (pathfit.SpaceTime) ---------------------------------
+ * Time runs in ticks 0..T (the horizon, 0 <= T <= 2^20).  In a tick a robot waits or makes one move of the policy (allow_diag,
+ * restrict_corner, as pf_dist_field_batch's); every move takes one tick.  S is the handle's static occupancy at call time
+ * (pf_update_grid keeps working), D[t] the dynamic plane of tick t, A[t] = S | D[t].  The planes are the device buffer d_occ,
+ * uint64 [T + 1][R][Wc] with Wc = ceil(C / 64): cell (r, c) is bit c & 63 of word r Wc + (c >> 6); the bits at c >= C are 0.
+ * A robot at u at tick t may be at v at tick t + 1 iff
+ *   1. v is inside the grid and A[t + 1][v] == 0 (vertex);
+ *   2. v == u (wait), or u -> v is a straight step, or a diagonal step when allow_diag;
+ *   3. for a move, not both D[t][v] and D[t + 1][u] are set (swap / pass-through; the test is on the planes, so two different
+ *      obstacles that set the two bits forbid the move too);
+ *   4. for a diagonal move under restrict_corner, neither (v.r, u.c) nor (u.r, v.c) is set in A[t] | A[t + 1].
+ * With every D[t] zero, rules 1, 2 and 4 are the handle's move-mask byte of the policy.  reach[0] = the sources free in A[0];
+ * reach[t + 1][v] = some u of reach[t] may be at v at tick t + 1.  reach is not monotone in t.  arrive[v] = the least t <= T with
+ * reach[t][v], -1 if none; the hold tick of v = the least t with reach[t][v] and D[t'][v] == 0 for every t <= t' <= T.
+ * pf_spacetime_stamp: ORs n path rows laid out as pf_astar_batch's into d_occ: the cell at position j of row i at tick
+ * d_t0[i] + j (d_t0 NULL: 0).  after_end != 0: the last cell stays occupied to tick T, else the obstacle vanishes.  corners != 0:
+ * a unit diagonal step over t -> t + 1 also stamps its two orthogonal corner cells at ticks t and t + 1 (the swept footprint);
+ * other steps stamp none.  clear != 0 zeroes the planes first.  Ticks beyond T are dropped; consecutive cells need not be
+ * adjacent.  d_status: 0 ok; 1 = an empty row, a length beyond path_cap, a cell outside [0, R C) or a t0 outside [0, T]: nothing
+ * of the row is stamped, nothing is read out of range.  64-bit atomic ORs: rows may overlap.
+ * pf_spacetime_field: B source sets in pf_dist_field_merged's host CSR form (an empty set is legal) -> d_arrive int32 [B][R C],
+ * every word written; d_reach (or NULL) uint64 [B][T + 1][R Wc], every word written; d_info (or NULL) int64 [B][4] = {cells
+ * reached, the largest arrival tick, the smallest cell id that attains it, 0}, {0, -1, -1, 0} when nothing is reached.  A source
+ * on a cell occupied at tick 0 is skipped, one listed twice counts once, a set without a usable source reaches nothing.  One
+ * workgroup per set, min(B, CUs) of them, the tick loop inside the kernel, 64 cells to a word; the three live planes of a
+ * workgroup lie in LDS where 3 R Wc 8 bytes fit 60 KiB, else in the handle's scratch in HBM.
+ * pf_spacetime_paths: n queries (d_set_idx[q], d_target[q], d_tick[q]) through d_reach (B sets) and d_occ -> rows d_cells
+ * [n][path_cap], d_len, d_status and d_tick_out (or NULL), the tick used (-1 where none).  d_tick[q] == -1: the earliest arrival;
+ * -2: the hold tick; >= 0: that tick; d_tick NULL: all -1.  A row holds tick + 1 cells, cell j the position at tick j.  From (tick,
+ * target) the walk goes back: at (t, v), t > 0, the first u with reach[t - 1][u] and u -> v allowed over t - 1 -> t among
+ * u = v - step(d), d = 0..7 in pf_dist_field_parents' move order, then u = v (the wait last).  PF_ST_INFEASIBLE, length 0: the
+ * reach bit is not set, the tick lies beyond T or below -2, no hold tick exists, or the target or the set index is out of range.
+ * PF_ST_OVERFLOW, length 0, row untouched: tick + 1 > path_cap, or some tick has no predecessor (planes that pf_spacetime_field
+ * did not produce on this map).  A walk makes at most `tick` steps and reads inside the planes whatever the words hold.
+ * pf_spacetime_conflicts: n rows of the same layout, starting at d_t0[i] (NULL: 0), against S, d_occ and the policy -> d_out
+ * int32 [n][4] = {the first conflicting tick or -1, its kind (0: none), the cell the robot would enter or -1, the number of
+ * conflicting steps}.  Kinds, by precedence at one step: 1 static (the cell is a static obstacle, or the step is neither a wait
+ * nor a move of the policy on the static map), 2 vertex, 3 swap, 4 corner.  The row's first cell is checked as a vertex at t0 (on a
+ * static obstacle: kind 1); a step t -> t + 1 reports tick t + 1.  hold != 0 also checks the last cell as a vertex at every later
+ * tick up to T, each such tick one conflicting step.  d_status: 0 ok; 1 a bad row as the stamp's (d_out = {-1, 0, -1, 0}); 2 the row
+ * runs past the horizon: checked up to T, the steps beyond not counted, no hold check.
+ * A null handle (-2); T outside [0, 2^20], B < 1, offsets that do not start at 0 or that decrease, a source outside [0, R C) (the
+ * message names its index), n < 0, path_cap < 1 or a missing required pointer (-1, with a message) is an argument error found
+ * before any launch: no output is touched; n == 0 returns 0 and launches nothing.  All four are synchronous and ordered on the
+ * handle's stream; pf_last_kernel_ms reports the kernels. */
+int pf_spacetime_stamp(pf_handle* h, int32_t T, uint64_t* d_occ, int32_t n, int32_t path_cap, const int32_t* d_cells,
+                       const int32_t* d_len, const int32_t* d_t0, int32_t after_end, int32_t corners, int32_t clear,
+                       int32_t* d_status);
+int pf_spacetime_field(pf_handle* h, int32_t allow_diag, int32_t restrict_corner, int32_t T, const uint64_t* d_occ, int32_t B,
+                       const int32_t* set_off, const int32_t* src, int32_t* d_arrive, uint64_t* d_reach, int64_t* d_info);
+int pf_spacetime_paths(pf_handle* h, int32_t allow_diag, int32_t restrict_corner, int32_t T, const uint64_t* d_occ, int32_t B,
+                       const uint64_t* d_reach, int32_t n, const int32_t* d_set_idx, const int32_t* d_target,
+                       const int32_t* d_tick, int32_t path_cap, int32_t* d_cells, int32_t* d_len, int32_t* d_status,
+                       int32_t* d_tick_out);
+int pf_spacetime_conflicts(pf_handle* h, int32_t allow_diag, int32_t restrict_corner, int32_t T, const uint64_t* d_occ, int32_t n,
+                           int32_t path_cap, const int32_t* d_cells, const int32_t* d_len, const int32_t* d_t0, int32_t hold,
+                           int32_t* d_out, int32_t* d_status);
+
 /* Tuning knobs (results never change): "components_phases" 0/1 pf_components records a HIP event after each phase
  * (pf_components_phase_ms; default 0); "maaco_pack8_min" ants per batch from which eight ants share a wavefront
  * (default 2048); "maaco_load_ahead" the packed walk kernel's load-ahead form (all of a step's loads issued together plus touches of the

@@ -1,5 +1,5 @@
 // pathfit_fields.hip -- the field family of libpathfit.so: distance fields, routing trees, nearest-source fields, smoothing,
-// connected components, clearance, widest paths, cost fields, turn fields and visibility fields.  A translation unit, and so a device code object, of its own (DESIGN.md
+// connected components, clearance, widest paths, cost fields, turn fields, visibility fields and space-time fields.  A translation unit, and so a device code object, of its own (DESIGN.md
 // 4.18): it shares the handle and the error helpers with pathfit.hip (pf_host.h) and none of the solvers' device code.
 #include <algorithm>
 #include <string>
@@ -1131,6 +1131,144 @@ int pf_visibility_paths(pf_handle* h, const int32_t* d_count, int32_t n, int32_t
     return timed(h, [&] {
       hipLaunchKernelGGL(k_visibility_paths_one_wave_per_row, dim3((unsigned)n), dim3(64), 0, h->stream, (const int*)d_count, h->RC, (int)n, (int)path_cap, (const int*)d_cells,
                          (const int*)d_len, (long long*)d_out, (int*)d_profile, (int*)d_status);
+    });
+  };
+  return run() ? -1 : 0;
+}
+
+}  // extern "C"
+
+// ---------------------------------------------------------------------------
+// Space-time fields: arrival ticks and routes among moving obstacles (pf_spacetime.h).  The dynamic planes are the
+// caller's buffer; the static occupancy is read at call time (pf_update_grid keeps working).  Scratch: the source table in the
+// distance fields' control block; the static bit plane and, where the live planes do not fit LDS, three planes per workgroup
+// in the tile-queue block.  Nothing in either outlives a call.
+// ---------------------------------------------------------------------------
+#include "pf_spacetime.h"
+
+#define PF_STF_T_MAX (1 << 20)
+
+static std::string spacetime_horizon(const std::string& me, int T) {
+  return me + ": bad arguments (T = " + std::to_string(T) + ": the horizon must lie in [0, 2^20])";
+}
+
+extern "C" {
+
+int pf_spacetime_stamp(pf_handle* h, int32_t T, uint64_t* d_occ, int32_t n, int32_t path_cap, const int32_t* d_cells, const int32_t* d_len, const int32_t* d_t0,
+                       int32_t after_end, int32_t corners, int32_t clear, int32_t* d_status) {
+  if (!h) return -2;
+  const std::string me("pf_spacetime_stamp");
+  if (T < 0 || T > PF_STF_T_MAX) { failmsg(h, spacetime_horizon(me, T)); return -1; }
+  if (n < 0 || path_cap < 1 || !d_occ || !d_cells || !d_len || !d_status) {
+    failmsg(h, me + ": bad arguments (n >= 0, path_cap >= 1; the planes, the rows, the lengths and the statuses must not be null)");
+    return -1;
+  }
+  if (n == 0) return 0;
+  auto run = [&]() -> int {
+    CK(hipSetDevice(h->device));
+    const int Wc = (h->C + 63) / 64;
+    return timed(h, [&]() -> int {
+      if (clear) CK(hipMemsetAsync(d_occ, 0, sizeof(uint64_t) * ((size_t)T + 1) * (size_t)h->R * (size_t)Wc, h->stream));
+      hipLaunchKernelGGL(k_spacetime_stamp_one_wave_per_row, dim3((unsigned)n), dim3(64), 0, h->stream, (st_u64*)d_occ, h->R, h->C, Wc, (int)T, (int)n, (int)path_cap,
+                         (const int*)d_cells, (const int*)d_len, (const int*)d_t0, after_end ? 1 : 0, corners ? 1 : 0, (int*)d_status);
+      return 0;
+    });
+  };
+  return run() ? -1 : 0;
+}
+
+int pf_spacetime_field(pf_handle* h, int32_t allow_diag, int32_t restrict_corner, int32_t T, const uint64_t* d_occ, int32_t B, const int32_t* set_off, const int32_t* src,
+                       int32_t* d_arrive, uint64_t* d_reach, int64_t* d_info) {
+  if (!h) return -2;
+  const std::string me("pf_spacetime_field");
+  auto run = [&]() -> int {
+    if (B < 1) return failmsg(h, me + ": bad arguments (B = " + std::to_string(B) + ": at least one source set is needed)");
+    if (T < 0 || T > PF_STF_T_MAX) return failmsg(h, spacetime_horizon(me, T));
+    if (!d_occ || !set_off || !d_arrive) return failmsg(h, me + ": bad arguments (the planes, the set offsets and the arrival rows must not be null)");
+    if (set_off[0] != 0) return failmsg(h, me + ": bad arguments (the set offsets must start at 0)");
+    for (int b = 0; b < B; ++b)
+      if (set_off[b + 1] < set_off[b]) return failmsg(h, me + ": bad arguments (the offsets of set " + std::to_string(b) + " decrease)");
+    const int ns = set_off[B];
+    if (ns > 0 && !src) return failmsg(h, me + ": bad arguments (the sources must not be null)");
+    for (int i = 0; i < ns; ++i)
+      if (src[i] < 0 || src[i] >= h->RC) return failmsg(h, me + ": source " + std::to_string(i) + " = " + std::to_string(src[i]) + " lies outside the grid");
+    CK(hipSetDevice(h->device));
+    if (h->df_cus < 1) {
+      int cus = 0;
+      if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, h->device) != hipSuccess || cus < 1) cus = 256;
+      h->df_cus = cus;
+    }
+    const int R = h->R, C = h->C, Wc = (C + 63) / 64, W = R * Wc;
+    const size_t plane = sizeof(st_u64) * (size_t)W;
+    const bool lds = PF_STF_LDS_BYTES > 0 && 3 * plane <= (size_t)PF_STF_LDS_BYTES;
+    int G = B < h->df_cus ? B : h->df_cus;
+    if (!lds) {                                                       // three planes per workgroup in HBM: at most 1 GiB of them
+      const size_t fit = ((size_t)1 << 30) / (3 * plane);
+      if ((size_t)G > fit) G = fit < 1 ? 1 : (int)fit;
+    }
+    if (scratch(h, me, h->d_df_ctl, &h->df_ctl_bytes, sizeof(int) * std::max<size_t>((size_t)B + 1 + (size_t)ns, 64), "the source table", false)) return -2;
+    if (scratch(h, me, h->d_widest, &h->widest_bytes, plane * (1 + (lds ? 0 : 3 * (size_t)G)), "the live planes", true)) return -2;
+    int* const d_off = h->d_df_ctl;
+    int* const d_src = d_off + B + 1;
+    CK(hipMemcpyAsync(d_off, set_off, sizeof(int) * ((size_t)B + 1), hipMemcpyHostToDevice, h->stream));
+    if (ns) CK(hipMemcpyAsync(d_src, src, sizeof(int) * (size_t)ns, hipMemcpyHostToDevice, h->stream));
+    CK(hipStreamSynchronize(h->stream));                              // (the arrays are pageable and the caller's)
+    st_u64* const d_S = (st_u64*)h->d_widest;
+    const unsigned nt = (unsigned)std::min<int>(PF_STF_THREADS, (W + 63) / 64 * 64);
+    return timed(h, [&] {
+      hipLaunchKernelGGL(k_spacetime_pack_static, dim3(((unsigned)W + 255) / 256), dim3(256), 0, h->stream, (const uint8_t*)h->d_occ, R, C, Wc, d_S);
+      if (lds)
+        hipLaunchKernelGGL(k_spacetime_field_group_per_set<true>, dim3((unsigned)G), dim3(nt), 3 * plane, h->stream, (const st_u64*)d_S, (const st_u64*)d_occ, R, C, Wc, (int)T,
+                           allow_diag ? 1 : 0, restrict_corner ? 1 : 0, (int)B, (const int*)d_off, (const int*)d_src, (int*)d_arrive, (st_u64*)d_reach, (long long*)d_info,
+                           (st_u64*)nullptr);
+      else
+        hipLaunchKernelGGL(k_spacetime_field_group_per_set<false>, dim3((unsigned)G), dim3(nt), 0, h->stream, (const st_u64*)d_S, (const st_u64*)d_occ, R, C, Wc, (int)T,
+                           allow_diag ? 1 : 0, restrict_corner ? 1 : 0, (int)B, (const int*)d_off, (const int*)d_src, (int*)d_arrive, (st_u64*)d_reach, (long long*)d_info,
+                           d_S + W);
+    });
+  };
+  return run() ? -1 : 0;
+}
+
+int pf_spacetime_paths(pf_handle* h, int32_t allow_diag, int32_t restrict_corner, int32_t T, const uint64_t* d_occ, int32_t B, const uint64_t* d_reach, int32_t n,
+                       const int32_t* d_set_idx, const int32_t* d_target, const int32_t* d_tick, int32_t path_cap, int32_t* d_cells, int32_t* d_len, int32_t* d_status,
+                       int32_t* d_tick_out) {
+  if (!h) return -2;
+  const std::string me("pf_spacetime_paths");
+  if (T < 0 || T > PF_STF_T_MAX) { failmsg(h, spacetime_horizon(me, T)); return -1; }
+  if (B < 1 || n < 0 || path_cap < 1 || !d_occ || !d_reach || !d_set_idx || !d_target || !d_cells || !d_len || !d_status) {
+    failmsg(h, me + ": bad arguments (B >= 1, n >= 0, path_cap >= 1; the planes, the reach planes, the set indices, the targets, the rows, the lengths and the statuses "
+                    "must not be null)");
+    return -1;
+  }
+  if (n == 0) return 0;
+  auto run = [&]() -> int {
+    CK(hipSetDevice(h->device));
+    return timed(h, [&] {
+      hipLaunchKernelGGL(k_spacetime_paths_lane_per_query, dim3(((unsigned)n + 63) / 64), dim3(64), 0, h->stream, (const uint8_t*)h->d_occ, (const st_u64*)d_occ,
+                         (const st_u64*)d_reach, h->R, h->C, (h->C + 63) / 64, (int)T, allow_diag ? 1 : 0, restrict_corner ? 1 : 0, (int)B, (int)n, (const int*)d_set_idx,
+                         (const int*)d_target, (const int*)d_tick, (int)path_cap, (int*)d_cells, (int*)d_len, (int*)d_status, (int*)d_tick_out);
+    });
+  };
+  return run() ? -1 : 0;
+}
+
+int pf_spacetime_conflicts(pf_handle* h, int32_t allow_diag, int32_t restrict_corner, int32_t T, const uint64_t* d_occ, int32_t n, int32_t path_cap, const int32_t* d_cells,
+                           const int32_t* d_len, const int32_t* d_t0, int32_t hold, int32_t* d_out, int32_t* d_status) {
+  if (!h) return -2;
+  const std::string me("pf_spacetime_conflicts");
+  if (T < 0 || T > PF_STF_T_MAX) { failmsg(h, spacetime_horizon(me, T)); return -1; }
+  if (n < 0 || path_cap < 1 || !d_occ || !d_cells || !d_len || !d_out || !d_status) {
+    failmsg(h, me + ": bad arguments (n >= 0, path_cap >= 1; the planes, the rows, the lengths, the results and the statuses must not be null)");
+    return -1;
+  }
+  if (n == 0) return 0;
+  auto run = [&]() -> int {
+    CK(hipSetDevice(h->device));
+    return timed(h, [&] {
+      hipLaunchKernelGGL(k_spacetime_conflicts_one_wave_per_row, dim3((unsigned)n), dim3(64), 0, h->stream, (const uint8_t*)h->d_occ, (const st_u64*)d_occ, h->R, h->C,
+                         (h->C + 63) / 64, (int)T, allow_diag ? 1 : 0, restrict_corner ? 1 : 0, (int)n, (int)path_cap, (const int*)d_cells, (const int*)d_len,
+                         (const int*)d_t0, hold ? 1 : 0, (int*)d_out, (int*)d_status);
     });
   };
   return run() ? -1 : 0;

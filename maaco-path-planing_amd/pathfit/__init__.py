@@ -24,3 +24,4 @@ from .clearance import Clearance, PF_CLEAR_NONE  # noqa: F401
 from .cost_field import CostField  # noqa: F401
 from .turn_field import TurnField  # noqa: F401
 from .visibility import Visibility  # noqa: F401
+from .spacetime import SpaceTime  # noqa: F401

@@ -498,6 +498,50 @@ class Engine:
                                             d_status.ptr if d_status else None))
         self._logk("visibility_paths")
 
+    # ------------------------------------------------------------------ space-time fields
+    def spacetime_stamp(self, horizon, d_occ, n, path_cap, d_cells, d_len, d_status, d_t0=None, after_end=True, corners=False, clear=False):
+        """ORs n path rows of astar_batch's layout into the dynamic planes d_occ uint64 [T + 1, R, ceil(C / 64)]: the cell at position
+        j of row i at tick d_t0[i] + j (None: 0); after_end: the last cell stays to tick T; corners: a unit diagonal step also stamps
+        its two corner cells at both ticks; clear: the planes are zeroed first; d_status 0 ok, 1 a bad row, of which nothing is
+        stamped (pf_spacetime_stamp)."""
+        self._ck(self.L.pf_spacetime_stamp(self.h, int(horizon), d_occ.ptr if d_occ else None, int(n), int(path_cap), d_cells.ptr if d_cells else None,
+                                           d_len.ptr if d_len else None, d_t0.ptr if d_t0 else None, int(bool(after_end)), int(bool(corners)), int(bool(clear)),
+                                           d_status.ptr if d_status else None))
+        self._logk("spacetime_stamp")
+
+    def spacetime_field(self, horizon, d_occ, set_off, sources, d_arrive, allow_diag=True, restrict_corner=True, d_reach=None, d_info=None):
+        """One arrival field per source SET (host int32 CSR as dist_field_merged's) against the planes -> d_arrive int32 [B, R * C]
+        (the least tick a robot can be on the cell, -1: never within the horizon), d_reach uint64 [B, T + 1, R * ceil(C / 64)] the
+        reach planes, d_info int64 [B, 4] = (cells reached, the largest arrival tick, the smallest cell id that attains it, 0)
+        (pf_spacetime_field)."""
+        off = np.ascontiguousarray(set_off, np.int32).reshape(-1)
+        src = np.ascontiguousarray(sources, np.int32).reshape(-1)
+        self._ck(self.L.pf_spacetime_field(self.h, int(allow_diag), int(restrict_corner), int(horizon), d_occ.ptr if d_occ else None, int(off.size) - 1,
+                                           off.ctypes.data if off.size else None, src.ctypes.data if src.size else None, d_arrive.ptr if d_arrive else None,
+                                           d_reach.ptr if d_reach else None, d_info.ptr if d_info else None))
+        self._logk("spacetime_field")
+
+    def spacetime_paths(self, horizon, d_occ, B, d_reach, n, d_set_idx, d_target, path_cap, d_cells, d_len, d_status, d_tick=None, d_tick_out=None,
+                        allow_diag=True, restrict_corner=True):
+        """n queries (d_set_idx[q], d_target[q], d_tick[q]: -1 the earliest arrival, -2 the hold tick, >= 0 that tick; None: all -1)
+        walked back through the reach planes into rows of tick + 1 cells, cell j the position at tick j; d_tick_out takes the tick
+        used (pf_spacetime_paths)."""
+        self._ck(self.L.pf_spacetime_paths(self.h, int(allow_diag), int(restrict_corner), int(horizon), d_occ.ptr if d_occ else None, int(B),
+                                           d_reach.ptr if d_reach else None, int(n), d_set_idx.ptr if d_set_idx else None, d_target.ptr if d_target else None,
+                                           d_tick.ptr if d_tick else None, int(path_cap), d_cells.ptr if d_cells else None, d_len.ptr if d_len else None,
+                                           d_status.ptr if d_status else None, d_tick_out.ptr if d_tick_out else None))
+        self._logk("spacetime_paths")
+
+    def spacetime_conflicts(self, horizon, d_occ, n, path_cap, d_cells, d_len, d_out, d_status, d_t0=None, hold=False, allow_diag=True,
+                            restrict_corner=True):
+        """n rows starting at d_t0 (None: 0) against the static map, the planes and the policy -> d_out int32 [n, 4] = (the first
+        conflicting tick or -1, its kind 1 static / 2 vertex / 3 swap / 4 corner, the cell entered, the conflicting steps); d_status 0
+        ok, 1 a bad row, 2 the row runs past the horizon (pf_spacetime_conflicts)."""
+        self._ck(self.L.pf_spacetime_conflicts(self.h, int(allow_diag), int(restrict_corner), int(horizon), d_occ.ptr if d_occ else None, int(n), int(path_cap),
+                                               d_cells.ptr if d_cells else None, d_len.ptr if d_len else None, d_t0.ptr if d_t0 else None, int(bool(hold)),
+                                               d_out.ptr if d_out else None, d_status.ptr if d_status else None))
+        self._logk("spacetime_conflicts")
+
     # ------------------------------------------------------------------ K1
     def score_batch(self, n, path_cap, d_cells, d_len, d_stats, sp):
         """Rows of astar_batch's layout in HBM -> d_stats [n, 5] doubles (pf_score_batch)."""
