@@ -760,7 +760,40 @@ int pf_spacetime_conflicts(pf_handle* h, int32_t allow_diag, int32_t restrict_co
                            int32_t path_cap, const int32_t* d_cells, const int32_t* d_len, const int32_t* d_t0, int32_t hold,
                            int32_t* d_out, int32_t* d_status);
 
-/* Tuning knobs (results never change): "components_phases" 0/1 pf_components records a HIP event after each phase
+/* ---- tours: the exact best order through up to 16 stops (pathfit.Tour) -------------------------------------------------------
+ * A problem is an n x n matrix d of doubles, d[i n + j] the cost of going from node i to node j: not necessarily symmetric,
+ * +inf = no way, the diagonal never read.  Node 0 is the start.  mode 0 (open): the tour may end anywhere; 1 (return): it comes
+ * back to node 0; 2 (last): it ends at node n - 1.  The middle nodes M are the others: m = n - 1, or n - 2 in mode 2; 0 <= m <= 16.
+ * need[j] (HOST uint32 [n], or NULL: none) is the set of nodes that must come before j; bit 0 is always satisfied, the end's own
+ * needs are always met, and in mode 2 a middle node that needs node n - 1 can never be placed.  For S a subset of M and j in S
+ * 
+ *   f[S][j] = +inf if need[j] & M is no subset of S \ {j}, or if a middle j needs the end; else d[0][j] if S == {j}; else the
+ *             minimum over i in S \ {j} of fl(f[S \ {j}][i] + d[i][j]), one fp64 addition per candidate;
+ *   total   = min_j f[M][j] (mode 0), min_j fl(f[M][j] + d[j][0]) (mode 1), min_j fl(f[M][j] + d[j][n - 1]) (mode 2).
+ * The order is read back by one rule: the last middle node is the smallest j whose closing value equals total as a 64-bit word;
+ * from (S, j) the predecessor is the smallest i in S \ {j} with fl(f[S \ {j}][i] + d[i][j]) == f[S][j] as words.  fp64 addition
+ * is monotone, so total is bit for bit the minimum over all admissible permutations of the legs' left-to-right sum, and the
+ * returned order's left-to-right sum is total.  m == 0: total 0 and order [0] (n == 1), or total d[0][1] and order [0, 1] (mode 2).
+ * pf_tour_matrix: d_mat[i n + j] = d_fields[i R C + stops[j]] for n HOST cell ids `stops` and n field rows in HBM (row i the field
+ * from stop i, as pf_dist_field_batch or pf_cost_field leave them): a plain gather, neither symmetrised nor cleaned.
+ * pf_tour_solve: B problems d_mat [B][n][n] that share n, mode and need -> d_total [B]; d_order int32 [B][n], the nodes in
+ * visiting order (it begins with 0, does not repeat 0 in mode 1, ends with n - 1 in mode 2); d_status [B], 0 or 1 = infeasible
+ * (total == +inf: a stop out of reach, cyclic needs; the order row is all -1); d_info (or NULL) int64 [B][4] = {the number of
+ * finite f[S][j], the last middle node or -1, 0, 0}.  One layer per set size with a lane per state; for m <= 9 a workgroup per
+ * problem keeps the table in LDS with the layer loop in the kernel, above that the tables lie in the handle's scratch (2^m m 8
+ * bytes each) with one launch per layer, at most "tour_tables" problems in flight (pf_set_option; 0 = as many as fit 256 MiB),
+ * the batch running in chunks.  Results never depend on the form, the chunks or the timing.
+ * Every off-diagonal entry must be >= 0 or +inf: a NaN or a negative entry is -1 with a message naming (b, i, j), found by a
+ * validation kernel BEFORE anything is written.  A null handle (-2); n < 1, mode 2 with n < 2, m > 16, a mode outside 0..2,
+ * B < 1, need[0] != 0, a node needing itself, a need bit >= n, a stop outside [0, R C) (the message names its index) or a missing
+ * required pointer (-1, with a message) is an argument error found on the host before any launch: no output is touched.  Both
+ * are synchronous and ordered on the handle's stream; pf_last_kernel_ms reports the kernels (the validation included). */
+int pf_tour_matrix(pf_handle* h, int32_t n, const int32_t* stops, const double* d_fields, double* d_mat);
+int pf_tour_solve(pf_handle* h, int32_t mode, int32_t n, const uint32_t* need, int32_t B, const double* d_mat, double* d_total,
+                  int32_t* d_order, int32_t* d_status, int64_t* d_info);
+
+/* Tuning knobs (results never change): "tour_tables" the most Held-Karp tables pf_tour_solve keeps in flight in HBM (default 0:
+ * as many as fit 256 MiB); "components_phases" 0/1 pf_components records a HIP event after each phase
  * (pf_components_phase_ms; default 0); "maaco_pack8_min" ants per batch from which eight ants share a wavefront
  * (default 2048); "maaco_load_ahead" the packed walk kernel's load-ahead form (all of a step's loads issued together plus touches of the
  * records two steps ahead): -1 (default) for batches of at most one wavefront per SIMD, 0 never, 1 always;

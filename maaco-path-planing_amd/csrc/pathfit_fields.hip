@@ -1,5 +1,5 @@
 // pathfit_fields.hip -- the field family of libpathfit.so: distance fields, routing trees, nearest-source fields, smoothing,
-// connected components, clearance, widest paths, cost fields, turn fields, visibility fields and space-time fields.  A translation unit, and so a device code object, of its own (DESIGN.md
+// connected components, clearance, widest paths, cost fields, turn fields, visibility fields, space-time fields and tours.  A translation unit, and so a device code object, of its own (DESIGN.md
 // 4.18): it shares the handle and the error helpers with pathfit.hip (pf_host.h) and none of the solvers' device code.
 #include <algorithm>
 #include <string>
@@ -1270,6 +1270,135 @@ int pf_spacetime_conflicts(pf_handle* h, int32_t allow_diag, int32_t restrict_co
                          (h->C + 63) / 64, (int)T, allow_diag ? 1 : 0, restrict_corner ? 1 : 0, (int)n, (int)path_cap, (const int*)d_cells, (const int*)d_len,
                          (const int*)d_t0, hold ? 1 : 0, (int*)d_out, (int*)d_status);
     });
+  };
+  return run() ? -1 : 0;
+}
+
+}  // extern "C"
+
+// ---------------------------------------------------------------------------
+// Tours: the exact best order through up to 16 stops (pf_tour.h).  pf_tour_matrix gathers the stop-to-stop
+// matrix out of fields in HBM; pf_tour_solve runs the Held-Karp table over B problems.  Scratch: the stops in the distance
+// fields' control block; the first offending entry's index, the finite-state counters and, for m > PF_TOUR_LDS_M, the tables
+// of the problems in flight in the tile-queue block.  Nothing in either outlives a call.
+// ---------------------------------------------------------------------------
+#include "pf_tour.h"
+
+#define PF_TOUR_TABLE_BYTES ((size_t)256 << 20)   /* what the tables in flight may take when "tour_tables" is 0 */
+
+long long g_tour_tables = 0;
+
+extern "C" {
+
+int pf_tour_matrix(pf_handle* h, int32_t n, const int32_t* stops, const double* d_fields, double* d_mat) {
+  if (!h) return -2;
+  const std::string me("pf_tour_matrix");
+  auto run = [&]() -> int {
+    if (n < 1 || n > 32768) return failmsg(h, me + ": bad arguments (n = " + std::to_string(n) + ": the number of stops must lie in [1, 32768])");
+    if (!stops || !d_fields || !d_mat) return failmsg(h, me + ": bad arguments (the stops, the fields and the matrix must not be null)");
+    for (int j = 0; j < n; ++j)
+      if (stops[j] < 0 || stops[j] >= h->RC) return failmsg(h, me + ": stop " + std::to_string(j) + " = " + std::to_string(stops[j]) + " lies outside the grid");
+    CK(hipSetDevice(h->device));
+    if (scratch(h, me, h->d_df_ctl, &h->df_ctl_bytes, sizeof(int) * std::max<size_t>((size_t)n, 64), "the stops", false)) return -2;
+    CK(hipMemcpyAsync(h->d_df_ctl, stops, sizeof(int) * (size_t)n, hipMemcpyHostToDevice, h->stream));
+    CK(hipStreamSynchronize(h->stream));                              // (stops is pageable and the caller's)
+    const long long nn = (long long)n * n;
+    return timed(h, [&] {
+      hipLaunchKernelGGL(k_tour_matrix_gather, dim3((unsigned)((nn + PF_TOUR_THREADS - 1) / PF_TOUR_THREADS)), dim3(PF_TOUR_THREADS), 0, h->stream, d_fields,
+                         (const int*)h->d_df_ctl, h->RC, (int)n, d_mat);
+    });
+  };
+  return run() ? -1 : 0;
+}
+
+int pf_tour_solve(pf_handle* h, int32_t mode, int32_t n, const uint32_t* need, int32_t B, const double* d_mat, double* d_total, int32_t* d_order, int32_t* d_status,
+                  int64_t* d_info) {
+  if (!h) return -2;
+  const std::string me("pf_tour_solve");
+  auto run = [&]() -> int {
+    if (mode < 0 || mode > 2) return failmsg(h, me + ": bad arguments (mode = " + std::to_string(mode) + ": 0 open, 1 return, 2 last)");
+    if (n < 1 || (mode == 2 && n < 2))
+      return failmsg(h, me + ": bad arguments (n = " + std::to_string(n) + ": at least " + (mode == 2 ? "two nodes are needed in mode 2)" : "one node is needed)"));
+    const int m = mode == 2 ? n - 2 : n - 1;
+    if (m > PF_TOUR_M_MAX)
+      return failmsg(h, me + ": bad arguments (n = " + std::to_string(n) + " in mode " + std::to_string(mode) + " leaves " + std::to_string(m) +
+                            " middle nodes: at most 16 are solved)");
+    if (B < 1) return failmsg(h, me + ": bad arguments (B = " + std::to_string(B) + ": at least one problem is needed)");
+    if (!d_mat || !d_total || !d_order || !d_status) return failmsg(h, me + ": bad arguments (the matrices, the totals, the orders and the statuses must not be null)");
+    TourNeed nd;
+    for (int k = 0; k < PF_TOUR_M_MAX; ++k) nd.nm[k] = 0u;
+    if (need) {
+      if (need[0] != 0u) return failmsg(h, me + ": bad arguments (need[0] = " + std::to_string(need[0]) + ": the start needs nothing)");
+      for (int j = 0; j < n; ++j) {
+        if ((need[j] >> j) & 1u) return failmsg(h, me + ": bad arguments (need[" + std::to_string(j) + "]: node " + std::to_string(j) + " needs itself)");
+        if (n < 32 && (need[j] >> n) != 0u)
+          return failmsg(h, me + ": bad arguments (need[" + std::to_string(j) + "] = " + std::to_string(need[j]) + " names a node >= n = " + std::to_string(n) + ")");
+      }
+      for (int k = 0; k < m; ++k)                                     // (the end's own needs are always met)
+        nd.nm[k] = (mode == 2 && ((need[k + 1] >> (n - 1)) & 1u)) ? PF_TOUR_BLOCKED : ((need[k + 1] >> 1) & ((1u << m) - 1u));
+    }
+    CK(hipSetDevice(h->device));
+    if (h->df_cus < 1) {
+      int cus = 0;
+      if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, h->device) != hipSuccess || cus < 1) cus = 256;
+      h->df_cus = cus;
+    }
+    const bool lds = m >= 1 && m <= PF_TOUR_LDS_M;
+    const size_t states = m >= 1 ? ((size_t)1 << m) * (size_t)m : 0;
+    long long tables = 0;                                             // the problems in flight of the HBM form
+    if (m >= 1 && !lds) {
+      tables = g_tour_tables > 0 ? g_tour_tables : (long long)std::max<size_t>(PF_TOUR_TABLE_BYTES / (sizeof(double) * states), 1);
+      tables = std::min<long long>(tables, B);
+    }
+    // the block: {the first bad entry, finite[tables]} in front (8-byte words), the tables behind
+    if (scratch(h, me, h->d_widest, &h->widest_bytes, sizeof(unsigned long long) * (1 + (size_t)tables) + sizeof(double) * states * (size_t)tables, "the tables", true))
+      return -2;
+    unsigned long long* const d_bad = (unsigned long long*)h->d_widest;
+    unsigned long long* const d_finite = d_bad + 1;
+    double* const d_tab = (double*)(d_finite + tables);
+    // the entries, before any output is touched
+    const long long nn = (long long)n * n, entries = nn * B;
+    unsigned long long bad = ~0ull;
+    CK(hipMemcpyAsync(d_bad, &bad, sizeof(bad), hipMemcpyHostToDevice, h->stream));
+    CK(hipStreamSynchronize(h->stream));
+    CK(hipEventRecord(h->ev0, h->stream));
+    hipLaunchKernelGGL(k_tour_validate_entries, dim3((unsigned)std::min<long long>((entries + PF_TOUR_THREADS - 1) / PF_TOUR_THREADS, 2048)), dim3(PF_TOUR_THREADS), 0,
+                       h->stream, d_mat, (int)n, entries, d_bad);
+    CK(hipGetLastError());
+    CK(hipMemcpyAsync(&bad, d_bad, sizeof(bad), hipMemcpyDeviceToHost, h->stream));
+    CK(hipStreamSynchronize(h->stream));
+    h->d2h_small += 1;
+    if (bad != ~0ull) {
+      const long long e = (long long)bad;
+      return failmsg(h, me + ": bad arguments (the entry (b, i, j) = (" + std::to_string(e / nn) + ", " + std::to_string(e % nn / n) + ", " + std::to_string(e % n) +
+                            ") is neither >= 0 nor +inf)");
+    }
+    long long* const info = (long long*)d_info;
+    if (m == 0) {
+      hipLaunchKernelGGL(k_tour_no_middle_nodes, dim3(((unsigned)B + 63) / 64), dim3(64), 0, h->stream, d_mat, (int)mode, (int)n, (int)B, d_total, (int*)d_order,
+                         (int*)d_status, info);
+    } else if (lds) {
+      hipLaunchKernelGGL(k_tour_layers_in_lds_group_per_problem, dim3((unsigned)std::min<long long>(B, 8ll * h->df_cus)), dim3(PF_TOUR_THREADS), 0, h->stream, d_mat,
+                         (int)mode, (int)n, m, (int)B, nd, d_total, (int*)d_order, (int*)d_status, info);
+    } else {
+      const unsigned gx = (unsigned)((states + PF_TOUR_THREADS - 1) / PF_TOUR_THREADS);
+      for (long long b0 = 0; b0 < B; b0 += tables) {                  // a chunk of problems: their tables, layer by layer, then the orders
+        const int nb = (int)std::min<long long>(tables, B - b0);
+        const double* const mat = d_mat + (size_t)b0 * (size_t)nn;
+        CK(hipMemsetAsync(d_finite, 0, sizeof(unsigned long long) * (size_t)nb, h->stream));
+        for (int c = 1; c <= m; ++c)
+          hipLaunchKernelGGL(k_tour_layer_lane_per_state, dim3(gx, (unsigned)std::min(nb, 65535)), dim3(PF_TOUR_THREADS), 0, h->stream, mat, (int)n, m, c, nb, nd, d_tab,
+                             d_finite);
+        hipLaunchKernelGGL(k_tour_trace_lane_per_problem, dim3(((unsigned)nb + 63) / 64), dim3(64), 0, h->stream, mat, (int)mode, (int)n, m, nb, (const double*)d_tab,
+                           (const unsigned long long*)d_finite, d_total + b0, (int*)d_order + (size_t)b0 * (size_t)n, (int*)d_status + b0,
+                           info ? info + (size_t)b0 * 4 : nullptr);
+      }
+    }
+    CK(hipGetLastError());
+    CK(hipEventRecord(h->ev1, h->stream));
+    CK(hipStreamSynchronize(h->stream));
+    CK(hipEventElapsedTime(&h->last_ms, h->ev0, h->ev1));
+    return 0;
   };
   return run() ? -1 : 0;
 }

@@ -101,6 +101,7 @@ inline const uint8_t* move_mask(const pf_handle* h, int allow_diag, int restrict
 }
 
 PF_INTERNAL extern bool g_cc_phases;   // pf_components records one HIP event per phase (pf_set_option "components_phases": the probe's spans)
+PF_INTERNAL extern long long g_tour_tables;   // pf_tour_solve: the most tables in flight in HBM (pf_set_option "tour_tables"; 0: sized from 256 MiB)
 
 // K single-source distance fields -> rows d_out[k][RC] for the K host cells src[k] (pathfit_fields.hip); `who` names the caller
 // in the messages.  The MPA bound tables are built with it ("mpa_bounds_device").

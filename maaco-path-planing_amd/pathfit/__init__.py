@@ -25,3 +25,4 @@ from .cost_field import CostField  # noqa: F401
 from .turn_field import TurnField  # noqa: F401
 from .visibility import Visibility  # noqa: F401
 from .spacetime import SpaceTime  # noqa: F401
+from .tour import Tour  # noqa: F401

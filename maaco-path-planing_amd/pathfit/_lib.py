@@ -190,6 +190,8 @@ SYMBOLS = {
     "pf_spacetime_field": (C.c_int, [_vp, _i32, _i32, _i32, _vp, _i32, _vp, _vp, _vp, _vp, _vp]),
     "pf_spacetime_paths": (C.c_int, [_vp, _i32, _i32, _i32, _vp, _i32, _vp, _i32, _vp, _vp, _vp, _i32, _vp, _vp, _vp, _vp]),
     "pf_spacetime_conflicts": (C.c_int, [_vp, _i32, _i32, _i32, _vp, _i32, _i32, _vp, _vp, _vp, _i32, _vp, _vp]),
+    "pf_tour_matrix": (C.c_int, [_vp, _i32, _vp, _vp, _vp]),
+    "pf_tour_solve": (C.c_int, [_vp, _i32, _i32, _vp, _i32, _vp, _vp, _vp, _vp, _vp]),
 }
 
 

@@ -543,6 +543,26 @@ class Engine:
         self._logk("spacetime_conflicts")
 
     # ------------------------------------------------------------------ K1
+    # ------------------------------------------------------------------ tours
+    def tour_matrix(self, stops, d_fields, d_mat):
+        """The stop-to-stop matrix out of n field rows in HBM (d_fields float64 [n, R * C], row i the field from stops[i]; `stops`
+        host int32 cell ids) -> d_mat float64 [n, n], d_mat[i, j] = d_fields[i, stops[j]]: a plain gather (pf_tour_matrix)."""
+        st = np.ascontiguousarray(stops, np.int32).reshape(-1)
+        self._ck(self.L.pf_tour_matrix(self.h, int(st.size), st.ctypes.data if st.size else None, d_fields.ptr if d_fields else None,
+                                       d_mat.ptr if d_mat else None))
+        self._logk("tour_matrix")
+
+    def tour_solve(self, mode, n, B, d_mat, d_total, d_order, d_status, need=None, d_info=None):
+        """B problems d_mat float64 [B, n, n] (entries >= 0 or +inf) that share n, mode (0 open, 1 return, 2 last) and need (host
+        uint32 [n]: the nodes that must come before each node, or None) -> d_total float64 [B], the exact optimum; d_order int32
+        [B, n], the nodes in visiting order (all -1 where infeasible); d_status int32 [B], 0 or 1 = infeasible; d_info int64 [B, 4] =
+        (finite table states, the last middle node or -1, 0, 0) (pf_tour_solve)."""
+        nd = None if need is None else np.ascontiguousarray(need, np.uint32).reshape(-1)
+        self._ck(self.L.pf_tour_solve(self.h, int(mode), int(n), nd.ctypes.data if nd is not None and nd.size else None, int(B),
+                                      d_mat.ptr if d_mat else None, d_total.ptr if d_total else None, d_order.ptr if d_order else None,
+                                      d_status.ptr if d_status else None, d_info.ptr if d_info else None))
+        self._logk("tour_solve")
+
     def score_batch(self, n, path_cap, d_cells, d_len, d_stats, sp):
         """Rows of astar_batch's layout in HBM -> d_stats [n, 5] doubles (pf_score_batch)."""
         self._ck(self.L.pf_score_batch(self.h, C.byref(sp), int(n), int(path_cap), d_cells.ptr, d_len.ptr, d_stats.ptr))
