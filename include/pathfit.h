@@ -792,6 +792,50 @@ int pf_tour_matrix(pf_handle* h, int32_t n, const int32_t* stops, const double* 
 int pf_tour_solve(pf_handle* h, int32_t mode, int32_t n, const uint32_t* need, int32_t B, const double* d_mat, double* d_total,
                   int32_t* d_order, int32_t* d_status, int64_t* d_info);
 
+/* ---- assignments: the exact best robot-to-task matching (pathfit.Assignment) --------------------------------------------------
+ * A problem is an n x m matrix a of doubles, row-major.  Rows are robots and columns are tasks, with 1 <= n <= m <= 1024
+ * (PF_ASSIGN_MAX).  +inf means no way.  Every other entry is finite with |x| <= 2^1000.  Negative entries are allowed.  NaN and
+ * -inf are errors.  There are three modes.
+ * Mode 0, "sum".  Rows are inserted in order i = 0 .. n-1.  The state is: potentials u[n] and v[m], all 0 at the start; p[m], the
+ * row matched to each column, -1 at the start.  Per inserted row, set minv[j] = +inf, way[j] = -1, used[j] = false, i0 = i,
+ * j0 = -1.  Then repeat tree steps.  One tree step is:
+ *   1. For every unused j in ascending order: cur = fl(fl(x - u[i0]) - v[j]), where x = a[i0][j], or +inf if x > limit.  If
+ *      cur < minv[j], set minv[j] = cur and way[j] = j0.  The comparison is strict.
+ *   2. delta is the smallest minv[j] over the unused j, and j1 is the smallest such j.  If there is none, or delta == +inf, the
+ *      row cannot be placed and the problem is infeasible.
+ *   3. u[i] += delta.  For every used j: u[p[j]] += delta and v[j] -= delta.  For every unused j: minv[j] -= delta.
+ *   4. j0 = j1, used[j0] = true.  If p[j0] < 0, the tree ends.  Otherwise i0 = p[j0].
+ * After the tree ends, augment along way from j0 back to -1: p[j0] = p[way[j0]], and the first column receives row i.  Each line
+ * is one fp64 operation in the order written.  No multiplication occurs, so nothing can contract.  limit is +inf in mode 0.
+ * Mode 1, "max" (bottleneck, the makespan).  The loop is the same without potentials: cur = a[i0][j], there is no step 3, and
+ * t = max(t, delta) with t = -inf at the start.  Only comparisons occur.  t is exactly the smallest possible largest entry over
+ * all assignments.
+ * Mode 2, "max_sum".  Run mode 1.  Then run mode 0 from fresh state with limit = t.  The result is the cheapest assignment among
+ * those with the best makespan.
+ * Results.  col[i] is the column of row i.  value = {sum, max}: sum is the left-to-right fp64 sum of a[i][col[i]] for
+ * i = 0 .. n-1, max is the largest of those entries.  dual holds u then v; it is all zeros in mode 1.  info = {tree steps of the
+ * sum phase, tree steps of the max phase, the first row that could not be placed or -1, 0}; a step that finds no column counts.
+ * An infeasible problem has status 1, col all -1, value = {+inf, +inf}, and dual all zeros.
+ * The device's col, value, dual and info equal the rule's as 64-bit words, on every run and in every kernel form.  Mode 1's t is
+ * exact on any input.  Mode 0's sum is the exact minimum over all assignments wherever every operation is exact (integer-valued
+ * and dyadic matrices of moderate size); on other matrices it is the left-to-right sum of some assignment, never below the
+ * brute-force minimum of left-to-right sums, and the reduced costs a - u - v can fall below zero by rounding.
+ * pf_assign_matrix: d_mat[(row0 + i) ld + j] = d_fields[i R C + cols[j]] for i < n_rows field rows in HBM (a chunk: i counts
+ * within it) and n_cols HOST cell ids `cols`; with `transpose` the value goes to d_mat[j ld + row0 + i].  A plain gather.
+ * pf_assign_solve: B problems d_mat [B][n][m] that share n, m and mode -> d_col int32 [B][n], d_value [B][2], d_status [B],
+ * d_dual [B][n + m] (or NULL), d_info int64 [B][4] (or NULL).  Up to 64 columns a wavefront solves a problem, column j in lane j;
+ * above that a workgroup does, a thread holding its columns in registers.  One launch per call, whatever B.
+ * A null handle (-2); n < 1, m < n, m > 1024, a mode outside 0..2, B < 1, a missing required pointer; for pf_assign_matrix a
+ * count outside [1, 32768], row0 < 0, ld shorter than a row of the matrix or a cell outside [0, R C) (-1, with a message) is an
+ * argument error found on the host before any launch.  A bad entry is -1 with a message naming the first (b, i, j), found by a
+ * validation kernel BEFORE anything is written.  Both are synchronous and ordered on the handle's stream; pf_last_kernel_ms
+ * reports the kernels (the validation included). */
+#define PF_ASSIGN_MAX 1024
+int pf_assign_matrix(pf_handle* h, int32_t n_rows, int32_t n_cols, const int32_t* cols, const double* d_fields, int32_t row0,
+                     int32_t ld, int32_t transpose, double* d_mat);
+int pf_assign_solve(pf_handle* h, int32_t mode, int32_t n, int32_t m, int32_t B, const double* d_mat, int32_t* d_col,
+                    double* d_value, int32_t* d_status, double* d_dual, int64_t* d_info);
+
 /* Tuning knobs (results never change): "tour_tables" the most Held-Karp tables pf_tour_solve keeps in flight in HBM (default 0:
  * as many as fit 256 MiB); "components_phases" 0/1 pf_components records a HIP event after each phase
  * (pf_components_phase_ms; default 0); "maaco_pack8_min" ants per batch from which eight ants share a wavefront

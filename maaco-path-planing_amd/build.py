@@ -12,7 +12,8 @@ IEEE double and bit-exact path parity depends on it.
 also builds the stress variants of the A* open list (VARIANTS below) into lib/stress/libpathfit_<name>.so: the shipped code under
 a bucket geometry that makes its rare branches common, with the branch counters of -DPF_OPEN_PATHS compiled in
 (tests/test_gpu_open_list_stress.py runs tests/open_list_cases.py against each), and the stress variants of the parallel closed-set
-engine (SETTLE_VARIANTS: tests/test_gpu_settle_stress.py runs tests/settle_cases.py against each).
+engine (SETTLE_VARIANTS: tests/test_gpu_settle_stress.py runs tests/settle_cases.py against each), and the assignment solver's
+workgroup form at every m (ASSIGN_VARIANTS: tests/test_gpu_assign.py holds it against the shipped library).
 """
 import os
 import subprocess
@@ -44,6 +45,11 @@ SETTLE_VARIANTS = {
     "st_touch": ["-DPF_ST_TOUCH_NUM=1", "-DPF_ST_TOUCH_DEN=4"],                           # the touched list filling up on the far pairs
     "st_wide2": ["-DPF_ST_WIDE=2", "-DPF_ST_Q=1.0"],                                       # two nodes per lane and trip
 }
+# The stress variant of the assignment solver (pf_assign.h): a workgroup per problem at every m, where the shipped library runs a
+# wavefront per problem up to 64 columns -- the workgroup form with one to sixty-four live columns and idle wavefronts.
+ASSIGN_VARIANTS = {
+    "as_group": ["-DPF_ASSIGN_WAVE_M=0"],
+}
 VARIANT_COMMON = ["-DPF_OPEN_PATHS"]
 MAX_JOBS = 16
 
@@ -72,7 +78,10 @@ def variant_path(name):
 
 
 def variant_flags(name):
-    return VARIANT_COMMON + (VARIANTS[name] if name in VARIANTS else SETTLE_VARIANTS[name])
+    for group in (VARIANTS, SETTLE_VARIANTS, ASSIGN_VARIANTS):
+        if name in group:
+            return VARIANT_COMMON + group[name]
+    raise KeyError(name)
 
 
 def build_variant(name, force=False, verbose=False):
@@ -82,7 +91,7 @@ def build_variant(name, force=False, verbose=False):
 
 def build_variants(names=None, force=False, verbose=False):
     """Several variants at once: one hipcc child each, at most MAX_JOBS at a time."""
-    names = list(VARIANTS) + list(SETTLE_VARIANTS) if names is None else list(names)
+    names = list(VARIANTS) + list(SETTLE_VARIANTS) + list(ASSIGN_VARIANTS) if names is None else list(names)
     outs = [variant_path(n) for n in names]
     os.makedirs(os.path.dirname(variant_path("x")), exist_ok=True)
     todo = [(n, o) for n, o in zip(names, outs) if force or _stale(o)]

@@ -1,5 +1,5 @@
 // pathfit_fields.hip -- the field family of libpathfit.so: distance fields, routing trees, nearest-source fields, smoothing,
-// connected components, clearance, widest paths, cost fields, turn fields, visibility fields, space-time fields and tours.  A translation unit, and so a device code object, of its own (DESIGN.md
+// connected components, clearance, widest paths, cost fields, turn fields, visibility fields, space-time fields, tours and assignments.  A translation unit, and so a device code object, of its own (DESIGN.md
 // 4.18): it shares the handle and the error helpers with pathfit.hip (pf_host.h) and none of the solvers' device code.
 #include <algorithm>
 #include <string>
@@ -1393,6 +1393,99 @@ int pf_tour_solve(pf_handle* h, int32_t mode, int32_t n, const uint32_t* need, i
                            (const unsigned long long*)d_finite, d_total + b0, (int*)d_order + (size_t)b0 * (size_t)n, (int*)d_status + b0,
                            info ? info + (size_t)b0 * 4 : nullptr);
       }
+    }
+    CK(hipGetLastError());
+    CK(hipEventRecord(h->ev1, h->stream));
+    CK(hipStreamSynchronize(h->stream));
+    CK(hipEventElapsedTime(&h->last_ms, h->ev0, h->ev1));
+    return 0;
+  };
+  return run() ? -1 : 0;
+}
+
+}  // extern "C"
+
+// ---------------------------------------------------------------------------
+// Assignments: the exact best robot-to-task matching (pf_assign.h).  pf_assign_matrix gathers a rectangular
+// robot-to-task matrix out of a chunk of fields in HBM; pf_assign_solve runs the shortest-augmenting-path rule over B problems, a
+// wavefront per problem up to 64 columns and a workgroup per problem above, one launch whatever B.  Scratch: the task cells in the
+// distance fields' control block, the first offending entry's index in the tile-queue block.  Nothing in either outlives a call.
+// ---------------------------------------------------------------------------
+#include "pf_assign.h"
+
+extern "C" {
+
+int pf_assign_matrix(pf_handle* h, int32_t n_rows, int32_t n_cols, const int32_t* cols, const double* d_fields, int32_t row0, int32_t ld, int32_t transpose,
+                     double* d_mat) {
+  if (!h) return -2;
+  const std::string me("pf_assign_matrix");
+  auto run = [&]() -> int {
+    if (n_rows < 1 || n_rows > 32768 || n_cols < 1 || n_cols > 32768)
+      return failmsg(h, me + ": bad arguments (n_rows = " + std::to_string(n_rows) + ", n_cols = " + std::to_string(n_cols) + ": both must lie in [1, 32768])");
+    if (row0 < 0 || row0 > 32768) return failmsg(h, me + ": bad arguments (row0 = " + std::to_string(row0) + " must lie in [0, 32768])");
+    const long long need = transpose ? (long long)row0 + n_rows : (long long)n_cols;
+    if ((long long)ld < need)
+      return failmsg(h, me + ": bad arguments (ld = " + std::to_string(ld) + " is shorter than a row of the matrix: " + std::to_string(need) + ")");
+    if (!cols || !d_fields || !d_mat) return failmsg(h, me + ": bad arguments (the cells, the fields and the matrix must not be null)");
+    for (int j = 0; j < n_cols; ++j)
+      if (cols[j] < 0 || cols[j] >= h->RC) return failmsg(h, me + ": cell " + std::to_string(j) + " = " + std::to_string(cols[j]) + " lies outside the grid");
+    CK(hipSetDevice(h->device));
+    if (scratch(h, me, h->d_df_ctl, &h->df_ctl_bytes, sizeof(int) * std::max<size_t>((size_t)n_cols, 64), "the cells", false)) return -2;
+    CK(hipMemcpyAsync(h->d_df_ctl, cols, sizeof(int) * (size_t)n_cols, hipMemcpyHostToDevice, h->stream));
+    CK(hipStreamSynchronize(h->stream));                              // (cols is pageable and the caller's)
+    const long long nn = (long long)n_rows * n_cols;
+    return timed(h, [&] {
+      hipLaunchKernelGGL(k_assign_matrix_gather, dim3((unsigned)((nn + PF_ASSIGN_GATHER_THREADS - 1) / PF_ASSIGN_GATHER_THREADS)), dim3(PF_ASSIGN_GATHER_THREADS), 0,
+                         h->stream, d_fields, (const int*)h->d_df_ctl, h->RC, (int)n_rows, (int)n_cols, (int)row0, (int)ld, transpose ? 1 : 0, d_mat);
+    });
+  };
+  return run() ? -1 : 0;
+}
+
+int pf_assign_solve(pf_handle* h, int32_t mode, int32_t n, int32_t m, int32_t B, const double* d_mat, int32_t* d_col, double* d_value, int32_t* d_status,
+                    double* d_dual, int64_t* d_info) {
+  if (!h) return -2;
+  const std::string me("pf_assign_solve");
+  auto run = [&]() -> int {
+    if (mode < 0 || mode > 2) return failmsg(h, me + ": bad arguments (mode = " + std::to_string(mode) + ": 0 sum, 1 max, 2 max_sum)");
+    if (n < 1) return failmsg(h, me + ": bad arguments (n = " + std::to_string(n) + ": at least one row is needed)");
+    if (m < n) return failmsg(h, me + ": bad arguments (m = " + std::to_string(m) + " < n = " + std::to_string(n) + ": rows must not outnumber columns)");
+    if (m > PF_ASSIGN_MAX) return failmsg(h, me + ": bad arguments (m = " + std::to_string(m) + ": at most " + std::to_string(PF_ASSIGN_MAX) + " columns are solved)");
+    if (B < 1) return failmsg(h, me + ": bad arguments (B = " + std::to_string(B) + ": at least one problem is needed)");
+    if (!d_mat || !d_col || !d_value || !d_status) return failmsg(h, me + ": bad arguments (the matrices, the columns, the values and the statuses must not be null)");
+    CK(hipSetDevice(h->device));
+    if (h->df_cus < 1) {
+      int cus = 0;
+      if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, h->device) != hipSuccess || cus < 1) cus = 256;
+      h->df_cus = cus;
+    }
+    if (scratch(h, me, h->d_widest, &h->widest_bytes, sizeof(unsigned long long) * 8, "the entry index", false)) return -2;
+    unsigned long long* const d_bad = (unsigned long long*)h->d_widest;
+    // the entries, before any output is touched
+    const long long nm = (long long)n * m, entries = nm * B;
+    unsigned long long bad = ~0ull;
+    CK(hipMemcpyAsync(d_bad, &bad, sizeof(bad), hipMemcpyHostToDevice, h->stream));
+    CK(hipStreamSynchronize(h->stream));
+    CK(hipEventRecord(h->ev0, h->stream));
+    hipLaunchKernelGGL(k_assign_validate_entries, dim3((unsigned)std::min<long long>((entries + PF_ASSIGN_GATHER_THREADS - 1) / PF_ASSIGN_GATHER_THREADS, 2048)),
+                       dim3(PF_ASSIGN_GATHER_THREADS), 0, h->stream, d_mat, entries, d_bad);
+    CK(hipGetLastError());
+    CK(hipMemcpyAsync(&bad, d_bad, sizeof(bad), hipMemcpyDeviceToHost, h->stream));
+    CK(hipStreamSynchronize(h->stream));
+    h->d2h_small += 1;
+    if (bad != ~0ull) {
+      const long long e = (long long)bad;
+      return failmsg(h, me + ": bad arguments (the entry (b, i, j) = (" + std::to_string(e / nm) + ", " + std::to_string(e % nm / m) + ", " + std::to_string(e % m) +
+                            ") is neither +inf nor finite within 2^1000)");
+    }
+    long long* const info = (long long*)d_info;
+    if (m <= PF_ASSIGN_WAVE_M) {
+      hipLaunchKernelGGL(k_assign_wave_per_problem, dim3((unsigned)(((long long)B + PF_ASSIGN_WAVES - 1) / PF_ASSIGN_WAVES)), dim3(64 * PF_ASSIGN_WAVES), 0, h->stream, d_mat,
+                         (int)mode, (int)n, (int)m, (int)B, (int*)d_col, d_value, (int*)d_status, d_dual, info);
+    } else {
+      const long long groups = (long long)(PF_ASSIGN_THREADS == 256 ? 8 : 2) * h->df_cus;
+      hipLaunchKernelGGL(k_assign_group_per_problem<PF_ASSIGN_THREADS>, dim3((unsigned)std::min<long long>(B, groups)), dim3(PF_ASSIGN_THREADS), 0, h->stream, d_mat,
+                         (int)mode, (int)n, (int)m, (int)B, (int*)d_col, d_value, (int*)d_status, d_dual, info);
     }
     CK(hipGetLastError());
     CK(hipEventRecord(h->ev1, h->stream));

@@ -26,3 +26,4 @@ from .turn_field import TurnField  # noqa: F401
 from .visibility import Visibility  # noqa: F401
 from .spacetime import SpaceTime  # noqa: F401
 from .tour import Tour  # noqa: F401
+from .assignment import Assignment  # noqa: F401

@@ -563,6 +563,26 @@ class Engine:
                                       d_status.ptr if d_status else None, d_info.ptr if d_info else None))
         self._logk("tour_solve")
 
+    # ------------------------------------------------------------------ assignments
+    def assign_matrix(self, n_rows, cols, d_fields, d_mat, row0=0, ld=None, transpose=False):
+        """A chunk of n_rows field rows in HBM (d_fields float64 [n_rows, R * C]) gathered at the host int32 cell ids `cols` ->
+        d_mat[(row0 + i) * ld + j] = d_fields[i, cols[j]], or d_mat[j * ld + row0 + i] with `transpose`; ld defaults to len(cols)
+        (pf_assign_matrix)."""
+        cl = np.ascontiguousarray(cols, np.int32).reshape(-1)
+        self._ck(self.L.pf_assign_matrix(self.h, int(n_rows), int(cl.size), cl.ctypes.data if cl.size else None, d_fields.ptr if d_fields else None,
+                                         int(row0), int(cl.size if ld is None else ld), int(bool(transpose)), d_mat.ptr if d_mat else None))
+        self._logk("assign_matrix")
+
+    def assign_solve(self, mode, n, m, B, d_mat, d_col, d_value, d_status, d_dual=None, d_info=None):
+        """B problems d_mat float64 [B, n, m] (n <= m <= 1024; +inf = no way) under mode 0 sum, 1 max or 2 max_sum -> d_col int32
+        [B, n], the column of each row (all -1 where infeasible); d_value float64 [B, 2] = (left-to-right sum, max); d_status int32
+        [B], 0 or 1 = infeasible; d_dual float64 [B, n + m] = u then v; d_info int64 [B, 4] = (tree steps of the sum phase, of the
+        max phase, the first row that could not be placed or -1, 0) (pf_assign_solve)."""
+        self._ck(self.L.pf_assign_solve(self.h, int(mode), int(n), int(m), int(B), d_mat.ptr if d_mat else None, d_col.ptr if d_col else None,
+                                        d_value.ptr if d_value else None, d_status.ptr if d_status else None, d_dual.ptr if d_dual else None,
+                                        d_info.ptr if d_info else None))
+        self._logk("assign_solve")
+
     def score_batch(self, n, path_cap, d_cells, d_len, d_stats, sp):
         """Rows of astar_batch's layout in HBM -> d_stats [n, 5] doubles (pf_score_batch)."""
         self._ck(self.L.pf_score_batch(self.h, C.byref(sp), int(n), int(path_cap), d_cells.ptr, d_len.ptr, d_stats.ptr))
