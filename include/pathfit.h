@@ -836,6 +836,48 @@ int pf_assign_matrix(pf_handle* h, int32_t n_rows, int32_t n_cols, const int32_t
 int pf_assign_solve(pf_handle* h, int32_t mode, int32_t n, int32_t m, int32_t B, const double* d_mat, int32_t* d_col,
                     double* d_value, int32_t* d_status, double* d_dual, int64_t* d_info);
 
+/* ---- tour search: 2-opt local search for tours of up to 1 024 stops (pathfit.TourSearch) --------------------------------------
+ * A problem is an n x n matrix d of doubles, 1 <= n <= 1024 (PF_TOUR_SEARCH_MAX).  Node 0 is the start.  
+ * Weights.  The rule reads the upper triangle only: w(x, y) = d[min(x, y) n + max(x, y)] for x != y.  The lower triangle and the
+ * diagonal are never read, so the weights are symmetric as 64-bit words.  w(x, none) = +0.0, and w(x, x) = +0.0 (the closing leg
+ * of n == 1 in mode 1, the only place a node meets itself).
+ * Modes are pf_tour_solve's.  Mode 0, open: the tour ends anywhere.  Mode 1, return: it comes back to node 0.  Mode 2, last: it
+ * ends at node n - 1.
+ * The order row.  order[0 .. n-1] is a permutation of the nodes with order[0] = 0; in mode 2, order[n-1] = n - 1.  order[n]
+ * stands for order[0] in mode 1 and for "none" in modes 0 and 2.  The movable positions are 1 .. hi, with hi = n - 1 in modes 0
+ * and 1, and hi = n - 2 in mode 2.
+ * n = 1 is a problem in every mode (in mode 2 node 0 is the start and the end): no pair, one sweep, status 0, value {+0.0, +0.0}.
+ * One sweep.  For every pair 1 <= i < j <= hi take a = order[i-1], b = order[i], c = order[j], e = order[j+1] and
+ *   delta(i, j) = fl( fl(w(a,c) + w(b,e)) - fl(w(a,b) + w(c,e)) ).
+ * That is three fp64 operations in the order written; nothing can contract.  The move of the sweep is the pair with the smallest
+ * delta.  On a tie it is the one with the smallest i, then the smallest j.  If that delta is < 0 (strictly) and fewer than
+ * max_moves moves were applied, positions i .. j are reversed.  That is one move.  Then sweep again.
+ * Stopping.  A sweep that finds no delta < 0 (or no pair at all) ends the search: the order is a local optimum, status 0.  A
+ * sweep that finds one after max_moves moves ends it too: status 2, the order is whatever the moves so far made.  So a call runs
+ * at most max_moves + 1 sweeps per start, 0 <= max_moves <= 2^20, and status 2 says that an improving move exists.  fl is
+ * monotone, so an accepted move strictly shortens the real-number length of the tour and the search ends without the cap.
+ * Results per start.  value = {total after, total before}.  Each is the left-to-right fp64 sum of w(order[k], order[k+1]) for
+ * k = 0 .. n-1, where the last term is the closing leg in mode 1 and +0.0 otherwise.  info = {moves, sweeps, 0, 0}.
+ * Entries.  Every upper-triangle entry must be >= 0 and either <= 2^1000 or +inf.  The rule needs finite weights: a problem with
+ * a +inf entry anywhere in its upper triangle is NOT searched.  Every start over it has status 1, an order row of all -1,
+ * value = {+inf, +inf} and info all 0.  The other problems of the batch are searched.
+ * pf_tour_improve: B starts d_order int32 [B][n], in and out, over one matrix d_mat [n][n] (shared = 1) or over d_mat [B][n][n]
+ * (shared = 0) -> d_value [B][2], d_status [B], d_info int64 [B][4] (or NULL).  One workgroup of 1024 threads per start holds
+ * the order row and its legs in LDS and runs the move loop inside the kernel.  The pairs are dealt evenly to its threads, the
+ * minimum is one lexicographic reduction over (delta, i, j), the reversal is applied by the threads in parallel.  The matrix is
+ * read through the caches.  One launch per call, whatever B.  The device's orders, values, statuses and infos equal the rule's
+ * as 64-bit words, on every run and for every assignment of starts to workgroups.
+ * A null handle (-2); n outside [1, 1024], B < 1, a mode outside 0..2, shared outside 0..1, max_moves outside [0, 2^20] or a
+ * missing required pointer (-1, with a message) is an argument error found on the host before any launch.  A NaN, a negative
+ * entry or a finite entry above 2^1000 in an upper triangle is -1 with a message naming the first (b, i, j).  A start row that
+ * is no permutation of 0 .. n-1 with node 0 first (and node n - 1 last in mode 2) is -1 with a message naming the first
+ * (b, position): the first position whose node lies outside [0, n), repeats the node of a smaller position or breaks a fixed
+ * end.  Two validation kernels find both BEFORE anything is written.  The call is synchronous and ordered on the handle's stream;
+ * pf_last_kernel_ms reports the kernels (the validations included). */
+#define PF_TOUR_SEARCH_MAX 1024
+int pf_tour_improve(pf_handle* h, int32_t mode, int32_t n, int32_t B, int32_t shared, const double* d_mat, int32_t max_moves,
+                    int32_t* d_order, double* d_value, int32_t* d_status, int64_t* d_info);
+
 /* Tuning knobs (results never change): "tour_tables" the most Held-Karp tables pf_tour_solve keeps in flight in HBM (default 0:
  * as many as fit 256 MiB); "components_phases" 0/1 pf_components records a HIP event after each phase
  * (pf_components_phase_ms; default 0); "maaco_pack8_min" ants per batch from which eight ants share a wavefront

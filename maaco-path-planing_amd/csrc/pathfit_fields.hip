@@ -1497,3 +1497,81 @@ int pf_assign_solve(pf_handle* h, int32_t mode, int32_t n, int32_t m, int32_t B,
 }
 
 }  // extern "C"
+
+// ---------------------------------------------------------------------------
+// Tour search: best-improvement 2-opt over up to 1024 stops (pf_tour_search.h).  pf_tour_improve takes B start
+// orders over one shared matrix or over B matrices, checks the entries and the start rows with two validation kernels, and runs
+// the move loops in one launch, a workgroup per start.  Scratch: the first offending index and the matrices' "holds +inf" words in
+// the tile-queue block (h->d_widest, h->widest_bytes).  Nothing in it outlives a call.
+// ---------------------------------------------------------------------------
+#include "pf_tour_search.h"
+
+extern "C" {
+
+int pf_tour_improve(pf_handle* h, int32_t mode, int32_t n, int32_t B, int32_t shared, const double* d_mat, int32_t max_moves, int32_t* d_order, double* d_value,
+                    int32_t* d_status, int64_t* d_info) {
+  if (!h) return -2;
+  const std::string me("pf_tour_improve");
+  auto run = [&]() -> int {
+    if (mode < 0 || mode > 2) return failmsg(h, me + ": bad arguments (mode = " + std::to_string(mode) + ": 0 open, 1 return, 2 last)");
+    if (n < 1 || n > PF_TOUR_SEARCH_MAX)
+      return failmsg(h, me + ": bad arguments (n = " + std::to_string(n) + ": the number of nodes must lie in [1, " + std::to_string(PF_TOUR_SEARCH_MAX) + "])");
+    if (B < 1) return failmsg(h, me + ": bad arguments (B = " + std::to_string(B) + ": at least one start is needed)");
+    if (shared != 0 && shared != 1) return failmsg(h, me + ": bad arguments (shared = " + std::to_string(shared) + ": 0 a matrix per start, 1 one matrix for all)");
+    if (max_moves < 0 || max_moves > (1 << 20))
+      return failmsg(h, me + ": bad arguments (max_moves = " + std::to_string(max_moves) + " must lie in [0, 2^20])");
+    if (!d_mat || !d_order || !d_value || !d_status) return failmsg(h, me + ": bad arguments (the matrices, the orders, the values and the statuses must not be null)");
+    CK(hipSetDevice(h->device));
+    if (h->df_cus < 1) {
+      int cus = 0;
+      if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, h->device) != hipSuccess || cus < 1) cus = 256;
+      h->df_cus = cus;
+    }
+    const long long mats = shared ? 1 : (long long)B;
+    // the block: {the first bad index, a spare word} in front, the matrices' "holds +inf" words behind
+    if (scratch(h, me, h->d_widest, &h->widest_bytes, sizeof(unsigned long long) * 2 + sizeof(int) * (size_t)mats, "the entry index", false)) return -2;
+    unsigned long long* const d_bad = (unsigned long long*)h->d_widest;
+    int* const d_inf = (int*)(d_bad + 2);
+    const long long nn = (long long)n * n, entries = nn * mats;
+    unsigned long long bad = ~0ull;
+    CK(hipMemcpyAsync(d_bad, &bad, sizeof(bad), hipMemcpyHostToDevice, h->stream));
+    CK(hipMemsetAsync(d_inf, 0, sizeof(int) * (size_t)mats, h->stream));
+    CK(hipStreamSynchronize(h->stream));
+    CK(hipEventRecord(h->ev0, h->stream));
+    // the entries, then the start rows, before any output is touched
+    hipLaunchKernelGGL(k_tour_search_validate_entries, dim3((unsigned)std::min<long long>((entries + PF_TOUR_SEARCH_THREADS - 1) / PF_TOUR_SEARCH_THREADS, 2048)),
+                       dim3(PF_TOUR_SEARCH_THREADS), 0, h->stream, d_mat, (int)n, entries, d_bad, d_inf);
+    CK(hipGetLastError());
+    CK(hipMemcpyAsync(&bad, d_bad, sizeof(bad), hipMemcpyDeviceToHost, h->stream));
+    CK(hipStreamSynchronize(h->stream));
+    h->d2h_small += 1;
+    if (bad != ~0ull) {
+      const long long e = (long long)bad;
+      return failmsg(h, me + ": bad arguments (the entry (b, i, j) = (" + std::to_string(e / nn) + ", " + std::to_string(e % nn / n) + ", " + std::to_string(e % n) +
+                            ") is neither +inf nor a number in [0, 2^1000])");
+    }
+    hipLaunchKernelGGL(k_tour_search_validate_orders, dim3((unsigned)std::min<long long>(B, 8ll * h->df_cus)), dim3(PF_TOUR_SEARCH_THREADS), 0, h->stream,
+                       (const int*)d_order, (int)mode, (int)n, (int)B, d_bad);
+    CK(hipGetLastError());
+    CK(hipMemcpyAsync(&bad, d_bad, sizeof(bad), hipMemcpyDeviceToHost, h->stream));
+    CK(hipStreamSynchronize(h->stream));
+    h->d2h_small += 1;
+    if (bad != ~0ull) {
+      const long long e = (long long)bad;
+      return failmsg(h, me + ": bad arguments (the start (b, position) = (" + std::to_string(e / n) + ", " + std::to_string(e % n) +
+                            ") is no permutation of the nodes with node 0 first" + (mode == 2 ? " and node n - 1 last)" : ")"));
+    }
+    long long* const info = (long long*)d_info;
+    const long long groups = (long long)(32 * 64 / PF_TOUR_SEARCH_GROUP) * h->df_cus;               // what is resident at once
+    hipLaunchKernelGGL(k_tour_search_group_per_start, dim3((unsigned)std::min<long long>(B, groups)), dim3(PF_TOUR_SEARCH_GROUP), 0, h->stream, d_mat, (const int*)d_inf,
+                       (int)mode, (int)n, (int)B, (int)shared, (int)max_moves, (int*)d_order, d_value, (int*)d_status, info);
+    CK(hipGetLastError());
+    CK(hipEventRecord(h->ev1, h->stream));
+    CK(hipStreamSynchronize(h->stream));
+    CK(hipEventElapsedTime(&h->last_ms, h->ev0, h->ev1));
+    return 0;
+  };
+  return run() ? -1 : 0;
+}
+
+}  // extern "C"

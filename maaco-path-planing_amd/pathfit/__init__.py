@@ -27,3 +27,4 @@ from .visibility import Visibility  # noqa: F401
 from .spacetime import SpaceTime  # noqa: F401
 from .tour import Tour  # noqa: F401
 from .assignment import Assignment  # noqa: F401
+from .tour_search import TourSearch  # noqa: F401

@@ -563,6 +563,17 @@ class Engine:
                                       d_status.ptr if d_status else None, d_info.ptr if d_info else None))
         self._logk("tour_solve")
 
+    def tour_improve(self, mode, n, B, shared, d_mat, max_moves, d_order, d_value, d_status, d_info=None):
+        """B start orders d_order int32 [B, n] (in and out) over one matrix d_mat float64 [n, n] (`shared`) or over [B, n, n], of
+        which the upper triangles are read, under mode 0 open, 1 return or 2 last: best-improvement 2-opt, at most max_moves moves
+        a start -> d_value float64 [B, 2] = (total after, total before); d_status int32 [B], 0 a local optimum, 1 not searched (a
+        +inf weight: the order row is all -1), 2 stopped by the cap; d_info int64 [B, 4] = (moves, sweeps, 0, 0)
+        (pf_tour_improve)."""
+        self._ck(self.L.pf_tour_improve(self.h, int(mode), int(n), int(B), int(bool(shared)), d_mat.ptr if d_mat else None, int(max_moves),
+                                        d_order.ptr if d_order else None, d_value.ptr if d_value else None, d_status.ptr if d_status else None,
+                                        d_info.ptr if d_info else None))
+        self._logk("tour_improve")
+
     # ------------------------------------------------------------------ assignments
     def assign_matrix(self, n_rows, cols, d_fields, d_mat, row0=0, ld=None, transpose=False):
         """A chunk of n_rows field rows in HBM (d_fields float64 [n_rows, R * C]) gathered at the host int32 cell ids `cols` ->
