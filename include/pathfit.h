@@ -878,6 +878,66 @@ int pf_assign_solve(pf_handle* h, int32_t mode, int32_t n, int32_t m, int32_t B,
 int pf_tour_improve(pf_handle* h, int32_t mode, int32_t n, int32_t B, int32_t shared, const double* d_mat, int32_t max_moves,
                     int32_t* d_order, double* d_value, int32_t* d_status, int64_t* d_info);
 
+/* ---- fleet routes: k robots over n tasks, 2-opt and segment relocation (pathfit.FleetTours) ------------------------------------
+ * A problem is k robots and n tasks, k >= 1, n >= 1, N = k + n <= 1024 (PF_FLEET_MAX).  Nodes 0 .. k-1 are the robots' start
+ * cells, nodes k .. N-1 are the tasks.  The weights are an N x N matrix d of doubles.  
+ * Weights.  The rule reads the upper triangle only: w(x, y) = d[min(x, y) N + max(x, y)] for x != y.  w(x, x) = +0.0 and
+ * w(x, none) = +0.0.  The robot-robot entries, the diagonal and the lower triangle are never read.
+ * The route row.  route[0 .. N-1] is a permutation of the nodes.  route[0] = 0, and the robots appear in increasing order: robot
+ * r's marker stands before robot r+1's.  The tasks between marker r and the next marker (or the end of the row) are robot r's
+ * route, in visiting order.  A route may be empty.  rob(p) is the robot whose stretch holds position p.  cnt[r] is the number of
+ * tasks of robot r.  nxt(p) is route[p+1] if p+1 < N and that node is a task; otherwise it is END(rob(p)).  END(r) is "none" in
+ * mode 0 (open: a route ends at its last task) and node r in mode 1 (return: each robot comes back to its own start).
+ * Capacity.  cap[r] >= 0 is an optional int32 per robot, shared by the batch; NULL means unlimited.  A row is valid only if
+ * cnt[r] <= cap[r] for every r.
+ * One sweep evaluates two families of candidates.
+ * Family code 0, 2-opt inside a route.  For every 1 <= i < j <= N-1 with the positions i .. j all tasks take a = route[i-1],
+ * b = route[i], c = route[j], e = nxt(j) and
+ *   delta = fl( fl(w(a,c) + w(b,e)) - fl(w(a,b) + w(c,e)) ),
+ * pf_tour_improve's form.  Applying it reverses the positions i .. j.
+ * Family code L = 1, 2, 3, relocate a segment.  The positions i .. i+L-1 must all be tasks.  j may be any position with j < i-1
+ * or j > i+L-1, markers included: j can be the head of another robot's route, or an empty route.  The candidate is admissible
+ * iff rob(j) == rob(i) or cnt[rob(j)] + L <= cap[rob(j)].  Take a = route[i-1], s1 = route[i], sL = route[i+L-1], b = nxt(i+L-1),
+ * p = route[j], q = nxt(j) and
+ *   rem   = fl( fl(w(a,s1) + w(sL,b)) - w(a,b) ),
+ *   add   = fl( fl(w(p,s1) + w(sL,q)) - w(p,q) ),
+ *   delta = fl( add - rem ).
+ * Each line is fp64 operations in the order written; nothing can contract.  Applying it takes the segment out and puts it back,
+ * in the same direction, directly behind position j's node.
+ * The move of the sweep is the admissible candidate with the smallest (delta, family code, i, j), compared lexicographically.  It
+ * is applied iff its delta is < 0 (strictly) and fewer than max_moves moves were applied.  Then sweep again.
+ * Stopping.  Status 0: a sweep found no delta < 0.  Status 2: a sweep found one after max_moves moves, 0 <= max_moves <= 2^20.  So
+ * a call runs at most max_moves + 1 sweeps per start.  The relocate delta is nested roundings (add and rem are rounded before
+ * they meet), so an accepted move need NOT shorten the real-number total, and a search can walk in a circle among rows whose
+ * totals agree to a rounding: termination rests on the cap, not on monotonicity.
+ * Results per start.  len[r] is robot r's length: the left-to-right fp64 sum of w(route[p], nxt(p)) over the positions of its
+ * stretch from its marker on, the END leg last (an empty route is the one leg w(r, END) = +0.0).  value = {total after, total
+ * before, makespan after}: total is the left-to-right sum of len[0 .. k-1], makespan the largest len.  info = {moves, sweeps, 2-opt
+ * moves, relocate moves}.
+ * Entries.  Every readable entry (i < j, j a task) must be >= 0 and either <= 2^1000 or +inf.  A problem with a +inf readable
+ * entry is NOT searched: status 1, a route row of all -1, value = {+inf, +inf, +inf}, len all +inf, info all 0.  The other
+ * problems of the batch are searched.
+ * pf_fleet_improve: B starts d_route int32 [B][N], in and out, over one matrix d_mat [N][N] (shared = 1) or over d_mat [B][N][N]
+ * (shared = 0), under d_cap int32 [k] (or NULL) -> d_len [B][k], d_value [B][3], d_status [B], d_info int64 [B][4] (or NULL).
+ * One workgroup of 1024 threads per start runs the move loop inside the kernel; LDS holds the route row, rob per position, cnt
+ * and cap, nxt and the legs w(route[p], nxt(p)) of the row as it stands and rem per (L, i).  The candidates are dealt evenly to
+ * the threads, the minimum is one lexicographic reduction over (delta, code, i, j), the move is applied by the threads in parallel,
+ * the lengths are summed by one thread per robot.  The matrix is read through the caches.  One launch per call, whatever B.  The
+ * device's routes, lengths, values, statuses and infos equal the rule's as 64-bit words, on every run and for every assignment
+ * of starts to workgroups.
+ * A null handle (-2); k < 1, n < 1, k + n > 1024, B < 1, a mode outside 0..1, shared outside 0..1, max_moves outside [0, 2^20], a
+ * negative cap[r] (the k words are read back first) or a missing required pointer (-1, with a message) is an argument error
+ * found on the host before any launch.  A NaN, a negative entry or a finite entry above 2^1000 among the readable entries is -1
+ * with a message naming the first (b, i, j).  A start row is -1 with a message naming the first (b, position) whose node lies
+ * outside [0, N), repeats the node of a smaller position, is not node 0 at position 0, or is a robot r >= 1 that robot r-1 does
+ * not stand in front of.  A robot with more tasks than its capacity is -1 with a message naming the first (b, robot).  Three
+ * validation kernels find these, in this order, BEFORE anything is written.  The call is synchronous and ordered on the handle's
+ * stream; pf_last_kernel_ms reports the kernels (the validations included). */
+#define PF_FLEET_MAX 1024
+int pf_fleet_improve(pf_handle* h, int32_t mode, int32_t k, int32_t n, int32_t B, int32_t shared, const double* d_mat,
+                     const int32_t* d_cap, int32_t max_moves, int32_t* d_route, double* d_len, double* d_value, int32_t* d_status,
+                     int64_t* d_info);
+
 /* Tuning knobs (results never change): "tour_tables" the most Held-Karp tables pf_tour_solve keeps in flight in HBM (default 0:
  * as many as fit 256 MiB); "components_phases" 0/1 pf_components records a HIP event after each phase
  * (pf_components_phase_ms; default 0); "maaco_pack8_min" ants per batch from which eight ants share a wavefront

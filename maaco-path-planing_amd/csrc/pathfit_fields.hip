@@ -1575,3 +1575,103 @@ int pf_tour_improve(pf_handle* h, int32_t mode, int32_t n, int32_t B, int32_t sh
 }
 
 }  // extern "C"
+
+// ---------------------------------------------------------------------------
+// Fleet routes: best-improvement 2-opt and segment relocation over k robots and n tasks (pf_fleet.h).
+// pf_fleet_improve takes B start rows over one shared matrix or over B matrices, checks the entries, the rows and the capacities
+// with validation kernels, and runs the move loops in one launch, a workgroup per start.  Scratch: the first offending index and
+// the matrices' "holds +inf" words in the tile-queue block (h->d_widest, h->widest_bytes).  Nothing in it outlives a call.
+// ---------------------------------------------------------------------------
+#include "pf_fleet.h"
+
+extern "C" {
+
+int pf_fleet_improve(pf_handle* h, int32_t mode, int32_t k, int32_t n, int32_t B, int32_t shared, const double* d_mat, const int32_t* d_cap, int32_t max_moves,
+                     int32_t* d_route, double* d_len, double* d_value, int32_t* d_status, int64_t* d_info) {
+  if (!h) return -2;
+  const std::string me("pf_fleet_improve");
+  auto run = [&]() -> int {
+    if (mode < 0 || mode > 1) return failmsg(h, me + ": bad arguments (mode = " + std::to_string(mode) + ": 0 open, 1 return)");
+    if (k < 1) return failmsg(h, me + ": bad arguments (k = " + std::to_string(k) + ": at least one robot is needed)");
+    if (n < 1) return failmsg(h, me + ": bad arguments (n = " + std::to_string(n) + ": at least one task is needed)");
+    if ((long long)k + (long long)n > PF_FLEET_MAX)
+      return failmsg(h, me + ": bad arguments (k + n = " + std::to_string((long long)k + (long long)n) + ": robots and tasks together must not exceed " +
+                            std::to_string(PF_FLEET_MAX) + ")");
+    if (B < 1) return failmsg(h, me + ": bad arguments (B = " + std::to_string(B) + ": at least one start is needed)");
+    if (shared != 0 && shared != 1) return failmsg(h, me + ": bad arguments (shared = " + std::to_string(shared) + ": 0 a matrix per start, 1 one matrix for all)");
+    if (max_moves < 0 || max_moves > (1 << 20))
+      return failmsg(h, me + ": bad arguments (max_moves = " + std::to_string(max_moves) + " must lie in [0, 2^20])");
+    if (!d_mat || !d_route || !d_len || !d_value || !d_status)
+      return failmsg(h, me + ": bad arguments (the matrices, the routes, the lengths, the values and the statuses must not be null)");
+    CK(hipSetDevice(h->device));
+    const int N = k + n;
+    if (d_cap) {                                // the capacities are k words: read back and checked on the host before any launch
+      std::vector<int32_t> cap((size_t)k);
+      CK(hipMemcpyAsync(cap.data(), d_cap, sizeof(int32_t) * (size_t)k, hipMemcpyDeviceToHost, h->stream));
+      CK(hipStreamSynchronize(h->stream));
+      h->d2h_small += 1;
+      for (int r = 0; r < k; ++r)
+        if (cap[(size_t)r] < 0) return failmsg(h, me + ": bad arguments (cap[" + std::to_string(r) + "] = " + std::to_string(cap[(size_t)r]) + " is negative)");
+    }
+    if (h->df_cus < 1) {
+      int cus = 0;
+      if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, h->device) != hipSuccess || cus < 1) cus = 256;
+      h->df_cus = cus;
+    }
+    const long long mats = shared ? 1 : (long long)B;
+    // the block: {the first bad index, a spare word} in front, the matrices' "holds +inf" words behind
+    if (scratch(h, me, h->d_widest, &h->widest_bytes, sizeof(unsigned long long) * 2 + sizeof(int) * (size_t)mats, "the entry index", false)) return -2;
+    unsigned long long* const d_bad = (unsigned long long*)h->d_widest;
+    int* const d_inf = (int*)(d_bad + 2);
+    const long long nn = (long long)N * N, entries = nn * mats;
+    unsigned long long bad = ~0ull;
+    CK(hipMemcpyAsync(d_bad, &bad, sizeof(bad), hipMemcpyHostToDevice, h->stream));
+    CK(hipMemsetAsync(d_inf, 0, sizeof(int) * (size_t)mats, h->stream));
+    CK(hipStreamSynchronize(h->stream));
+    CK(hipEventRecord(h->ev0, h->stream));
+    // the entries, then the start rows, then the capacities, before any output is touched
+    auto first_bad = [&]() -> int {
+      CK(hipGetLastError());
+      CK(hipMemcpyAsync(&bad, d_bad, sizeof(bad), hipMemcpyDeviceToHost, h->stream));
+      CK(hipStreamSynchronize(h->stream));
+      h->d2h_small += 1;
+      return 0;
+    };
+    const dim3 rows_grid((unsigned)std::min<long long>(B, 8ll * h->df_cus));
+    hipLaunchKernelGGL(k_fleet_validate_entries, dim3((unsigned)std::min<long long>((entries + PF_FLEET_THREADS - 1) / PF_FLEET_THREADS, 2048)), dim3(PF_FLEET_THREADS), 0,
+                       h->stream, d_mat, (int)k, N, entries, d_bad, d_inf);
+    if (first_bad()) return -1;
+    if (bad != ~0ull) {
+      const long long e = (long long)bad;
+      return failmsg(h, me + ": bad arguments (the entry (b, i, j) = (" + std::to_string(e / nn) + ", " + std::to_string(e % nn / N) + ", " + std::to_string(e % N) +
+                            ") is neither +inf nor a number in [0, 2^1000])");
+    }
+    hipLaunchKernelGGL(k_fleet_validate_rows, rows_grid, dim3(PF_FLEET_THREADS), 0, h->stream, (const int*)d_route, (int)k, N, (int)B, d_bad);
+    if (first_bad()) return -1;
+    if (bad != ~0ull) {
+      const long long e = (long long)bad;
+      return failmsg(h, me + ": bad arguments (the start (b, position) = (" + std::to_string(e / N) + ", " + std::to_string(e % N) +
+                            ") is no permutation of the nodes with node 0 first and the robots in increasing order)");
+    }
+    if (d_cap) {
+      hipLaunchKernelGGL(k_fleet_validate_caps, rows_grid, dim3(PF_FLEET_THREADS), 0, h->stream, (const int*)d_route, (const int*)d_cap, (int)k, N, (int)B, d_bad);
+      if (first_bad()) return -1;
+      if (bad != ~0ull) {
+        const long long e = (long long)bad;
+        return failmsg(h, me + ": bad arguments (the start (b, robot) = (" + std::to_string(e / k) + ", " + std::to_string(e % k) + ") holds more tasks than its capacity)");
+      }
+    }
+    long long* const info = (long long*)d_info;
+    const long long groups = (long long)(32 * 64 / PF_FLEET_GROUP) * h->df_cus;                    // what is resident at once
+    hipLaunchKernelGGL(k_fleet_group_per_start, dim3((unsigned)std::min<long long>(B, groups)), dim3(PF_FLEET_GROUP), 0, h->stream, d_mat, (const int*)d_inf,
+                       (const int*)d_cap, (int)mode, (int)k, N, (int)B, (int)shared, (int)max_moves, (int*)d_route, d_len, d_value, (int*)d_status, info);
+    CK(hipGetLastError());
+    CK(hipEventRecord(h->ev1, h->stream));
+    CK(hipStreamSynchronize(h->stream));
+    CK(hipEventElapsedTime(&h->last_ms, h->ev0, h->ev1));
+    return 0;
+  };
+  return run() ? -1 : 0;
+}
+
+}  // extern "C"

@@ -28,3 +28,4 @@ from .spacetime import SpaceTime  # noqa: F401
 from .tour import Tour  # noqa: F401
 from .assignment import Assignment  # noqa: F401
 from .tour_search import TourSearch  # noqa: F401
+from .fleet import FleetTours  # noqa: F401

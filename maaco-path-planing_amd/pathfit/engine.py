@@ -574,6 +574,19 @@ class Engine:
                                         d_info.ptr if d_info else None))
         self._logk("tour_improve")
 
+    def fleet_improve(self, mode, k, n, B, shared, d_mat, d_cap, max_moves, d_route, d_len, d_value, d_status, d_info=None):
+        """B start rows d_route int32 [B, k + n] (in and out: node 0 first, the robots 0 .. k - 1 in increasing order, the tasks
+        behind a robot its route) over one matrix d_mat float64 [k + n, k + n] (`shared`) or over [B, k + n, k + n], of which the
+        upper triangles are read, under mode 0 open or 1 return and the capacities d_cap int32 [k] (None: unlimited):
+        best-improvement 2-opt and segment relocation, at most max_moves moves a start -> d_len float64 [B, k], each robot's
+        length; d_value float64 [B, 3] = (total after, total before, makespan after); d_status int32 [B], 0 no improving move
+        is left, 1 not searched (a +inf weight: the row is all -1), 2 stopped by the cap; d_info int64 [B, 4] = (moves, sweeps,
+        2-opt moves, relocate moves) (pf_fleet_improve)."""
+        self._ck(self.L.pf_fleet_improve(self.h, int(mode), int(k), int(n), int(B), int(bool(shared)), d_mat.ptr if d_mat else None,
+                                         d_cap.ptr if d_cap else None, int(max_moves), d_route.ptr if d_route else None, d_len.ptr if d_len else None,
+                                         d_value.ptr if d_value else None, d_status.ptr if d_status else None, d_info.ptr if d_info else None))
+        self._logk("fleet_improve")
+
     # ------------------------------------------------------------------ assignments
     def assign_matrix(self, n_rows, cols, d_fields, d_mat, row0=0, ld=None, transpose=False):
         """A chunk of n_rows field rows in HBM (d_fields float64 [n_rows, R * C]) gathered at the host int32 cell ids `cols` ->
