@@ -938,6 +938,70 @@ int pf_fleet_improve(pf_handle* h, int32_t mode, int32_t k, int32_t n, int32_t B
                      const int32_t* d_cap, int32_t max_moves, int32_t* d_route, double* d_len, double* d_value, int32_t* d_status,
                      int64_t* d_info);
 
+/* ---- placement: which p of m candidate sites to open for n demands, additions and swaps (pathfit.Placement) ---------------------
+ * 
+ * The problem.
+ * - There are m sites, n demands and p slots.
+ * - The limits are 1 <= m <= 1 024 (PF_PLACE_SITES_MAX), 1 <= n <= 4 096 (PF_PLACE_DEMANDS_MAX) and 1 <= p <= min(m, 64)
+ *   (PF_PLACE_OPEN_MAX).
+ * - `fixed` lies in [0, p].
+ * - The matrix a is [m][n], row-major.  a[i][j] is what demand j pays at site i.
+ * - Every entry is +inf, or finite with +0.0 <= x <= 2^1000.
+ * - A NaN, a negative entry, a finite entry above 2^1000 and -0.0 are errors, named by (b, i, j).  The validation tests the sign
+ *   bit, because a minimum over +-0.0 would not be a function of the words.
+ * - No multiplication occurs anywhere, so nothing can contract.
+ * The row.
+ * - sel[0 .. p-1]: each entry is -1 (an empty slot) or a site.
+ * - No site stands twice.
+ * - The slots below `fixed` are not empty and never change.
+ * Nearest site.
+ * - near(sel, j) is the smallest a[sel[s]][j] over the non-empty slots, or +inf with none.
+ * - own(sel, j) is the smallest slot attaining it where it is finite, and -1 otherwise.
+ * Cost.  cost(sel) = (uns, sum, max), with uns = 0, sum = +0.0 and max = +0.0 at the start.  Walk j = 0 .. n-1 in order:
+ * - If near is +inf, uns += 1.
+ * - Otherwise sum = fl(sum + near), and max takes the larger of the two.
+ * Key.
+ * - Mode 0, "sum": (uns, sum).
+ * - Mode 1, "max": (uns, max, sum).
+ * - Keys compare lexicographically.  The integer comes first.
+ * One sweep.
+ * - For every slot o in [fixed, p) and every site i that is not in the row, the candidate is the row with sel[o] = i.
+ * - Its key is the key of its cost, computed exactly as above.
+ * - The move of the sweep is the candidate with the smallest (key, o, i).
+ * - It is applied iff its key is strictly smaller than the row's own key and fewer than max_moves moves were applied.
+ * - An empty slot is an ordinary o.  That candidate is an addition.  So the greedy construction from the all-empty row and the
+ *   swap search are one rule.
+ * Stopping.
+ * - Status 0: no candidate was strictly better, or there was no candidate at all (fixed == p, or every site is in the row).
+ * - Status 2: a strictly better candidate was found after max_moves moves, with 0 <= max_moves <= 2^20.
+ * - Every applied move lowers the key strictly and there are finitely many rows.  So the search ends without the cap.
+ * - A call runs at most max_moves + 1 sweeps per start.
+ * - A row may end with empty slots, where no addition changes the key.
+ * Results per start.
+ * - The row.
+ * - owner[j] = sel[own(sel, j)], or -1.
+ * - value = {sum after, max after, sum before, max before}.
+ * - info = {moves, sweeps, uns after, uns before}.
+ * pf_place_improve: B starts d_sel int32 [B][p], in and out, over one matrix d_mat [m][n] (shared = 1) or over d_mat [B][m][n]
+ * (shared = 0) -> d_owner int32 [B][n] (or NULL), d_value [B][4], d_status [B], d_info int64 [B][4] (or NULL).  One workgroup of
+ * 1024 threads per start runs the move loop inside the kernel; LDS holds, per demand, the smallest value over the row with its
+ * smallest slot and the second smallest value, so that a candidate's term at j is one minimum; a lane takes a candidate (o, i) --
+ * 64 / P sites share a wavefront, P the power of two >= p -- and walks the demands in order; the minimum is one lexicographic
+ * reduction over (key, o, i).  One launch per call, whatever B.  The device's rows, owners, values, statuses and infos equal the rule's as 64-bit words, on every run and for every
+ * assignment of starts to workgroups.
+ * A null handle (-2); m, n or p out of range, `fixed` outside [0, p], a mode outside 0..1, shared outside 0..1, B < 1, max_moves
+ * outside [0, 2^20] or a missing required pointer (-1, with a message) is an argument error found on the host before any launch.
+ * A bad entry is -1 with a message naming the first (b, i, j).  A bad row is -1 with a message naming the first (b, slot): the
+ * first slot that lies outside [-1, m), repeats the site of a smaller slot, or is empty below `fixed`.  Two validation kernels find
+ * these, in this order, BEFORE anything is written: after an error no output is touched.  The call is synchronous and ordered on
+ * the handle's stream; pf_last_kernel_ms reports the kernels (the validations included). */
+#define PF_PLACE_SITES_MAX 1024
+#define PF_PLACE_DEMANDS_MAX 4096
+#define PF_PLACE_OPEN_MAX 64
+int pf_place_improve(pf_handle* h, int32_t mode, int32_t m, int32_t n, int32_t p, int32_t fixed, int32_t B, int32_t shared,
+                     const double* d_mat, int32_t max_moves, int32_t* d_sel, int32_t* d_owner, double* d_value,
+                     int32_t* d_status, int64_t* d_info);
+
 /* Tuning knobs (results never change): "tour_tables" the most Held-Karp tables pf_tour_solve keeps in flight in HBM (default 0:
  * as many as fit 256 MiB); "components_phases" 0/1 pf_components records a HIP event after each phase
  * (pf_components_phase_ms; default 0); "maaco_pack8_min" ants per batch from which eight ants share a wavefront

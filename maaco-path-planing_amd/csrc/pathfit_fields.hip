@@ -1675,3 +1675,83 @@ int pf_fleet_improve(pf_handle* h, int32_t mode, int32_t k, int32_t n, int32_t B
 }
 
 }  // extern "C"
+
+// ---------------------------------------------------------------------------
+// Placement: which p of m candidate sites to open for n demands (pf_place.h).  pf_place_improve takes B start
+// rows over one shared matrix or over B matrices, checks the entries and the rows with two validation kernels, and runs the move
+// loops in one launch, a workgroup per start.  Scratch: the first offending index in the tile-queue block (h->d_widest,
+// h->widest_bytes).  Nothing in it outlives a call.
+// ---------------------------------------------------------------------------
+#include "pf_place.h"
+
+extern "C" {
+
+int pf_place_improve(pf_handle* h, int32_t mode, int32_t m, int32_t n, int32_t p, int32_t fixed, int32_t B, int32_t shared, const double* d_mat, int32_t max_moves,
+                     int32_t* d_sel, int32_t* d_owner, double* d_value, int32_t* d_status, int64_t* d_info) {
+  if (!h) return -2;
+  const std::string me("pf_place_improve");
+  auto run = [&]() -> int {
+    if (mode < 0 || mode > 1) return failmsg(h, me + ": bad arguments (mode = " + std::to_string(mode) + ": 0 sum, 1 max)");
+    if (m < 1 || m > PF_PLACE_SITES_MAX)
+      return failmsg(h, me + ": bad arguments (m = " + std::to_string(m) + ": the number of sites must lie in [1, " + std::to_string(PF_PLACE_SITES_MAX) + "])");
+    if (n < 1 || n > PF_PLACE_DEMANDS_MAX)
+      return failmsg(h, me + ": bad arguments (n = " + std::to_string(n) + ": the number of demands must lie in [1, " + std::to_string(PF_PLACE_DEMANDS_MAX) + "])");
+    if (p < 1 || p > std::min<int>(m, PF_PLACE_OPEN_MAX))
+      return failmsg(h, me + ": bad arguments (p = " + std::to_string(p) + ": the number of slots must lie in [1, min(m, " + std::to_string(PF_PLACE_OPEN_MAX) + ")])");
+    if (fixed < 0 || fixed > p) return failmsg(h, me + ": bad arguments (fixed = " + std::to_string(fixed) + " must lie in [0, p])");
+    if (B < 1) return failmsg(h, me + ": bad arguments (B = " + std::to_string(B) + ": at least one start is needed)");
+    if (shared != 0 && shared != 1) return failmsg(h, me + ": bad arguments (shared = " + std::to_string(shared) + ": 0 a matrix per start, 1 one matrix for all)");
+    if (max_moves < 0 || max_moves > (1 << 20))
+      return failmsg(h, me + ": bad arguments (max_moves = " + std::to_string(max_moves) + " must lie in [0, 2^20])");
+    if (!d_mat || !d_sel || !d_value || !d_status) return failmsg(h, me + ": bad arguments (the matrices, the rows, the values and the statuses must not be null)");
+    CK(hipSetDevice(h->device));
+    if (h->df_cus < 1) {
+      int cus = 0;
+      if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, h->device) != hipSuccess || cus < 1) cus = 256;
+      h->df_cus = cus;
+    }
+    if (scratch(h, me, h->d_widest, &h->widest_bytes, sizeof(unsigned long long) * 2, "the entry index", false)) return -2;
+    unsigned long long* const d_bad = (unsigned long long*)h->d_widest;
+    const long long mn = (long long)m * n, entries = mn * (shared ? 1 : (long long)B), slots = (long long)B * p;
+    unsigned long long bad = ~0ull;
+    CK(hipMemcpyAsync(d_bad, &bad, sizeof(bad), hipMemcpyHostToDevice, h->stream));
+    CK(hipStreamSynchronize(h->stream));
+    CK(hipEventRecord(h->ev0, h->stream));
+    // the entries, then the rows, before any output is touched
+    auto first_bad = [&]() -> int {
+      CK(hipGetLastError());
+      CK(hipMemcpyAsync(&bad, d_bad, sizeof(bad), hipMemcpyDeviceToHost, h->stream));
+      CK(hipStreamSynchronize(h->stream));
+      h->d2h_small += 1;
+      return 0;
+    };
+    hipLaunchKernelGGL(k_place_validate_entries, dim3((unsigned)std::min<long long>((entries + PF_PLACE_THREADS - 1) / PF_PLACE_THREADS, 2048)), dim3(PF_PLACE_THREADS), 0,
+                       h->stream, d_mat, entries, d_bad);
+    if (first_bad()) return -1;
+    if (bad != ~0ull) {
+      const long long e = (long long)bad;
+      return failmsg(h, me + ": bad arguments (the entry (b, i, j) = (" + std::to_string(e / mn) + ", " + std::to_string(e % mn / n) + ", " + std::to_string(e % n) +
+                            ") is neither +inf nor a number in [+0.0, 2^1000])");
+    }
+    hipLaunchKernelGGL(k_place_validate_rows, dim3((unsigned)std::min<long long>((slots + PF_PLACE_THREADS - 1) / PF_PLACE_THREADS, 2048)), dim3(PF_PLACE_THREADS), 0,
+                       h->stream, (const int*)d_sel, (int)m, (int)p, (int)fixed, slots, d_bad);
+    if (first_bad()) return -1;
+    if (bad != ~0ull) {
+      const long long e = (long long)bad;
+      return failmsg(h, me + ": bad arguments (the row (b, slot) = (" + std::to_string(e / p) + ", " + std::to_string(e % p) +
+                            ") lies outside [-1, m), repeats the site of a smaller slot or is empty below fixed)");
+    }
+    const size_t lds = (size_t)n * (2 * sizeof(double) + 1);          // d1, d2 and n1 per demand
+    CK(hipFuncSetAttribute((const void*)k_place_group_per_start, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    hipLaunchKernelGGL(k_place_group_per_start, dim3((unsigned)std::min<long long>(B, 2ll * h->df_cus)), dim3(PF_PLACE_GROUP), lds, h->stream, d_mat, (int)mode, (int)m,
+                       (int)n, (int)p, (int)fixed, (int)B, (int)shared, (int)max_moves, (int*)d_sel, (int*)d_owner, d_value, (int*)d_status, (long long*)d_info);
+    CK(hipGetLastError());
+    CK(hipEventRecord(h->ev1, h->stream));
+    CK(hipStreamSynchronize(h->stream));
+    CK(hipEventElapsedTime(&h->last_ms, h->ev0, h->ev1));
+    return 0;
+  };
+  return run() ? -1 : 0;
+}
+
+}  // extern "C"

@@ -29,3 +29,4 @@ from .tour import Tour  # noqa: F401
 from .assignment import Assignment  # noqa: F401
 from .tour_search import TourSearch  # noqa: F401
 from .fleet import FleetTours  # noqa: F401
+from .placement import Placement  # noqa: F401

@@ -587,6 +587,18 @@ class Engine:
                                          d_value.ptr if d_value else None, d_status.ptr if d_status else None, d_info.ptr if d_info else None))
         self._logk("fleet_improve")
 
+    def place_improve(self, mode, m, n, p, fixed, B, shared, d_mat, max_moves, d_sel, d_owner, d_value, d_status, d_info=None):
+        """B start rows d_sel int32 [B, p] (in and out: sites of [0, m), -1 an empty slot, no site twice, the slots below `fixed`
+        not empty and kept) over one matrix d_mat float64 [m, n] (`shared`) or over [B, m, n] (entries +inf or in [+0.0, 2^1000]),
+        under mode 0 sum or 1 max: best-improvement additions and swaps, at most max_moves moves a start -> d_owner int32 [B, n]
+        (or None), the open site nearest to each demand or -1; d_value float64 [B, 4] = (sum after, max after, sum before, max
+        before); d_status int32 [B], 0 no better candidate is left, 2 stopped by the cap; d_info int64 [B, 4] = (moves, sweeps,
+        unserved after, unserved before) (pf_place_improve)."""
+        self._ck(self.L.pf_place_improve(self.h, int(mode), int(m), int(n), int(p), int(fixed), int(B), int(bool(shared)), d_mat.ptr if d_mat else None,
+                                         int(max_moves), d_sel.ptr if d_sel else None, d_owner.ptr if d_owner else None, d_value.ptr if d_value else None,
+                                         d_status.ptr if d_status else None, d_info.ptr if d_info else None))
+        self._logk("place_improve")
+
     # ------------------------------------------------------------------ assignments
     def assign_matrix(self, n_rows, cols, d_fields, d_mat, row0=0, ld=None, transpose=False):
         """A chunk of n_rows field rows in HBM (d_fields float64 [n_rows, R * C]) gathered at the host int32 cell ids `cols` ->
