@@ -1002,6 +1002,81 @@ int pf_place_improve(pf_handle* h, int32_t mode, int32_t m, int32_t n, int32_t p
                      const double* d_mat, int32_t max_moves, int32_t* d_sel, int32_t* d_owner, double* d_value,
                      int32_t* d_status, int64_t* d_info);
 
+/* ---- coverage: which p of m sites see or reach the most of n elements, additions, swaps and drops (pathfit.Coverage) -----------
+ * 
+ * Inputs.
+ * - There are m sites, n elements and p slots.
+ * - The limits are 1 <= m <= 1 024 (PF_COVER_SITES_MAX), 1 <= n <= 2^20 (PF_COVER_ELEMS_MAX) and 1 <= p <= min(m, 64)
+ *   (PF_COVER_OPEN_MAX).
+ * - `fixed` lies in [0, p].
+ * - W = ceil(n / 64).
+ * - Site i has a mask M[i], uint64 [W].  Element j is bit j & 63 of word j >> 6.
+ * - A set bit at j >= n is an error, named by (b, i).
+ * - An all-zero mask is legal.
+ * - Everything is an integer: no result depends on the order of any sum.
+ * The row.
+ * - sel[0 .. p-1]: each entry is -1 (an empty slot) or a site.
+ * - No site stands twice.
+ * - The slots below `fixed` are not empty and never change.  This is pf_place_improve's row.
+ * Key.
+ * - cnt(sel, j) is the number of non-empty slots s with bit j set in M[sel[s]].
+ * - cov(sel) is the number of j in [0, n) with cnt(sel, j) > 0.
+ * - open(sel) is the number of non-empty slots.
+ * - The key is (n - cov, open).  Keys compare lexicographically.
+ * One sweep.
+ * - For every slot o in [fixed, p) and every site i that is not in the row, the candidate is the row with sel[o] = i.  It is an
+ *   addition if slot o is empty and a swap otherwise.
+ * - For every non-empty slot o in [fixed, p), the candidate is the row with sel[o] = -1, a drop.  A drop is written as i = m.
+ * - The move of the sweep is the candidate with the smallest (key, o, i).
+ * - It is applied iff its key is strictly smaller than the row's own key and fewer than max_moves moves were applied.
+ * Stopping.
+ * - Status 0: no candidate was strictly better, or there was no candidate at all.
+ * - Status 2: a strictly better candidate was found after max_moves moves, with 0 <= max_moves <= 2^20.
+ * - Every applied move lowers the key strictly and there are finitely many rows.  So the search ends without the cap.
+ * - A call runs at most max_moves + 1 sweeps per start.
+ * Consequences.
+ * - The greedy construction, the swap search and the removal of redundant sites are one rule.
+ * - A swap with equal coverage never applies: its key equals the row's.
+ * - An addition applies only if it covers something new: otherwise open grows and cov does not.  So a row may end with empty
+ *   slots.
+ * - A site that has become redundant is dropped: the drop keeps cov and lowers open.
+ * - Every empty slot has the same candidates with the same keys, and the smallest o wins the tie.  So the additions of the
+ *   smallest empty slot decide.
+ * - With p = min(m, 64) and an all-empty start the rule answers "how few sites cover everything that can be covered": it adds
+ *   while something new is covered, and swaps and drops afterwards.
+ * Results per start.
+ * - The row.
+ * - covered = the union of the row's masks, uint64 [W].
+ * - value = {cov after, open after, cov before, open before}.
+ * - info = {moves, sweeps, elements with cnt == 1 after, drops among the moves}.
+ * pf_cover_improve: B starts d_sel int32 [B][p], in and out, over one mask set d_mask uint64 [m][W] (shared = 1) or over d_mask
+ * [B][m][W] (shared = 0) -> d_covered uint64 [B][W] (or NULL), d_value int64 [B][4], d_status [B], d_info int64 [B][4] (or NULL).
+ * One workgroup of 1024 threads per start runs the move loop inside the kernel; per start two planes of W words hold the union
+ * and the elements covered exactly once, in LDS up to W = 4 096 and in the handle's scratch above, so that a swap's coverage is
+ * sum_w popc((any & ~(once & M[sel o])) | M[i]); a wavefront takes a site, its lanes the words.  One launch per call, whatever B.
+ * The device's rows, planes, values, statuses and infos equal the rule's, on every run and for every assignment of starts to
+ * workgroups.
+ * A null handle (-2); m, n or p out of range, `fixed` outside [0, p], shared outside 0..1, B < 1, max_moves outside [0, 2^20] or a
+ * missing required pointer (-1, with a message) is an argument error found on the host before any launch.  A set tail bit is -1
+ * with a message naming the first (b, i); a bad row is -1 with a message naming the first (b, slot), as pf_place_improve's.  Two
+ * validation kernels find these, in this order, BEFORE anything is written: after an error no output is touched.
+ * pf_cover_pack: the masks' builder.  K source rows d_src of leading dimension ld, read at the n cells d_targets (int32 [n] on the
+ * device, each in [0, ld)), fill the rows row0 .. row0 + K - 1 of d_mask [.][W].  kind 0: the source is uint8 and the bit is
+ * byte != 0 (pf_visibility_field's rows).  kind 1: the source is double and the bit is x <= radius (the fields' rows; +inf and NaN
+ * give 0; radius is finite and >= 0).  The tail bits of the last word are 0.  A null handle (-2); a kind outside 0..1, K, n or ld
+ * < 1, n above 2^20, a row range that leaves [0, 1 024], a bad radius or a missing pointer (-1, with a message) is found before
+ * any launch; a target outside [0, ld) is -1 with a message naming the first, found by a validation kernel before any write.
+ * Both calls are synchronous and ordered on the handle's stream; pf_last_kernel_ms reports the kernels (the validations
+ * included). */
+#define PF_COVER_SITES_MAX 1024
+#define PF_COVER_ELEMS_MAX 1048576
+#define PF_COVER_OPEN_MAX 64
+int pf_cover_pack(pf_handle* h, int32_t kind, int32_t K, int32_t n, const void* d_src, int32_t ld, const int32_t* d_targets,
+                  double radius, int32_t row0, uint64_t* d_mask);
+int pf_cover_improve(pf_handle* h, int32_t m, int32_t n, int32_t p, int32_t fixed, int32_t B, int32_t shared,
+                     const uint64_t* d_mask, int32_t max_moves, int32_t* d_sel, uint64_t* d_covered, int64_t* d_value,
+                     int32_t* d_status, int64_t* d_info);
+
 /* Tuning knobs (results never change): "tour_tables" the most Held-Karp tables pf_tour_solve keeps in flight in HBM (default 0:
  * as many as fit 256 MiB); "components_phases" 0/1 pf_components records a HIP event after each phase
  * (pf_components_phase_ms; default 0); "maaco_pack8_min" ants per batch from which eight ants share a wavefront

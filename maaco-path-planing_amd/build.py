@@ -12,8 +12,9 @@ IEEE double and bit-exact path parity depends on it.
 also builds the stress variants of the A* open list (VARIANTS below) into lib/stress/libpathfit_<name>.so: the shipped code under
 a bucket geometry that makes its rare branches common, with the branch counters of -DPF_OPEN_PATHS compiled in
 (tests/test_gpu_open_list_stress.py runs tests/open_list_cases.py against each), and the stress variants of the parallel closed-set
-engine (SETTLE_VARIANTS: tests/test_gpu_settle_stress.py runs tests/settle_cases.py against each), and the assignment solver's
-workgroup form at every m (ASSIGN_VARIANTS: tests/test_gpu_assign.py holds it against the shipped library).
+engine (SETTLE_VARIANTS: tests/test_gpu_settle_stress.py runs tests/settle_cases.py against each), the assignment solver's
+workgroup form at every m (ASSIGN_VARIANTS: tests/test_gpu_assign.py holds it against the shipped library), and the coverage
+search's other deal with the planes in HBM from three words on (COVER_VARIANTS: tests/test_gpu_cover.py does the same).
 """
 import os
 import subprocess
@@ -50,6 +51,11 @@ SETTLE_VARIANTS = {
 ASSIGN_VARIANTS = {
     "as_group": ["-DPF_ASSIGN_WAVE_M=0"],
 }
+# The stress variant of the coverage search (pf_cover.h): the deal that is not shipped (a lane per (site group, slot) walking the
+# words), and the planes of a start in the handle's scratch instead of LDS from W = 3 on, so that small cases run the HBM form.
+COVER_VARIANTS = {
+    "cv_lanes": ["-DPF_COVER_DEAL=0", "-DPF_COVER_LDS_WORDS=2"],
+}
 VARIANT_COMMON = ["-DPF_OPEN_PATHS"]
 MAX_JOBS = 16
 
@@ -78,7 +84,7 @@ def variant_path(name):
 
 
 def variant_flags(name):
-    for group in (VARIANTS, SETTLE_VARIANTS, ASSIGN_VARIANTS):
+    for group in (VARIANTS, SETTLE_VARIANTS, ASSIGN_VARIANTS, COVER_VARIANTS):
         if name in group:
             return VARIANT_COMMON + group[name]
     raise KeyError(name)
@@ -91,7 +97,7 @@ def build_variant(name, force=False, verbose=False):
 
 def build_variants(names=None, force=False, verbose=False):
     """Several variants at once: one hipcc child each, at most MAX_JOBS at a time."""
-    names = list(VARIANTS) + list(SETTLE_VARIANTS) + list(ASSIGN_VARIANTS) if names is None else list(names)
+    names = list(VARIANTS) + list(SETTLE_VARIANTS) + list(ASSIGN_VARIANTS) + list(COVER_VARIANTS) if names is None else list(names)
     outs = [variant_path(n) for n in names]
     os.makedirs(os.path.dirname(variant_path("x")), exist_ok=True)
     todo = [(n, o) for n, o in zip(names, outs) if force or _stale(o)]

@@ -2,6 +2,7 @@
 // connected components, clearance, widest paths, cost fields, turn fields, visibility fields, space-time fields, tours and assignments.  A translation unit, and so a device code object, of its own (DESIGN.md
 // 4.18): it shares the handle and the error helpers with pathfit.hip (pf_host.h) and none of the solvers' device code.
 #include <algorithm>
+#include <limits>
 #include <string>
 #include <type_traits>
 #include <vector>
@@ -1745,6 +1746,148 @@ int pf_place_improve(pf_handle* h, int32_t mode, int32_t m, int32_t n, int32_t p
     CK(hipFuncSetAttribute((const void*)k_place_group_per_start, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
     hipLaunchKernelGGL(k_place_group_per_start, dim3((unsigned)std::min<long long>(B, 2ll * h->df_cus)), dim3(PF_PLACE_GROUP), lds, h->stream, d_mat, (int)mode, (int)m,
                        (int)n, (int)p, (int)fixed, (int)B, (int)shared, (int)max_moves, (int*)d_sel, (int*)d_owner, d_value, (int*)d_status, (long long*)d_info);
+    CK(hipGetLastError());
+    CK(hipEventRecord(h->ev1, h->stream));
+    CK(hipStreamSynchronize(h->stream));
+    CK(hipEventElapsedTime(&h->last_ms, h->ev0, h->ev1));
+    return 0;
+  };
+  return run() ? -1 : 0;
+}
+
+}  // extern "C"
+
+// ---------------------------------------------------------------------------
+// Coverage: which p of m sites see or reach the most of n elements (pf_cover.h).  pf_cover_pack turns a chunk of
+// visibility rows (bytes) or field rows (doubles) in HBM into rows of the bit masks, 64 targets a word; pf_cover_improve takes B
+// start rows over one shared mask set or over B of them, checks the tail bits and the rows with two validation kernels, and runs
+// the move loops in one launch, a workgroup per start.  Scratch: the first offending index and, where the two planes of a start
+// do not fit LDS, a block of 2 W words per workgroup (one workgroup a CU then), both in the tile-queue block (h->d_widest, h->widest_bytes).  Nothing in it
+// outlives a call.
+// ---------------------------------------------------------------------------
+#include "pf_cover.h"
+
+extern "C" {
+
+int pf_cover_pack(pf_handle* h, int32_t kind, int32_t K, int32_t n, const void* d_src, int32_t ld, const int32_t* d_targets, double radius, int32_t row0,
+                  uint64_t* d_mask) {
+  if (!h) return -2;
+  const std::string me("pf_cover_pack");
+  auto run = [&]() -> int {
+    if (kind < 0 || kind > 1) return failmsg(h, me + ": bad arguments (kind = " + std::to_string(kind) + ": 0 bytes != 0, 1 doubles <= radius)");
+    if (K < 1 || K > PF_COVER_SITES_MAX)
+      return failmsg(h, me + ": bad arguments (K = " + std::to_string(K) + ": the number of source rows must lie in [1, " + std::to_string(PF_COVER_SITES_MAX) + "])");
+    if (n < 1 || n > PF_COVER_ELEMS_MAX)
+      return failmsg(h, me + ": bad arguments (n = " + std::to_string(n) + ": the number of elements must lie in [1, " + std::to_string(PF_COVER_ELEMS_MAX) + "])");
+    if (ld < 1) return failmsg(h, me + ": bad arguments (ld = " + std::to_string(ld) + ": a source row holds at least one entry)");
+    if (row0 < 0 || (long long)row0 + K > PF_COVER_SITES_MAX)
+      return failmsg(h, me + ": bad arguments (row0 = " + std::to_string(row0) + ", K = " + std::to_string(K) + ": the rows must lie in [0, " +
+                            std::to_string(PF_COVER_SITES_MAX) + "])");
+    if (kind == 1 && !(radius >= 0.0 && radius < std::numeric_limits<double>::infinity()))
+      return failmsg(h, me + ": bad arguments (radius = " + std::to_string(radius) + " must be finite and >= 0)");
+    if (!d_src || !d_targets || !d_mask) return failmsg(h, me + ": bad arguments (the source rows, the targets and the masks must not be null)");
+    CK(hipSetDevice(h->device));
+    if (scratch(h, me, h->d_widest, &h->widest_bytes, sizeof(unsigned long long) * 2, "the target index", false)) return -2;
+    unsigned long long* const d_bad = (unsigned long long*)h->d_widest;
+    unsigned long long bad = ~0ull;
+    CK(hipMemcpyAsync(d_bad, &bad, sizeof(bad), hipMemcpyHostToDevice, h->stream));
+    CK(hipStreamSynchronize(h->stream));
+    CK(hipEventRecord(h->ev0, h->stream));
+    // the targets, before any source entry is read
+    hipLaunchKernelGGL(k_cover_validate_targets, dim3((unsigned)std::min<long long>(((long long)n + PF_COVER_THREADS - 1) / PF_COVER_THREADS, 2048)), dim3(PF_COVER_THREADS), 0,
+                       h->stream, (const int*)d_targets, (int)n, (int)ld, d_bad);
+    CK(hipGetLastError());
+    CK(hipMemcpyAsync(&bad, d_bad, sizeof(bad), hipMemcpyDeviceToHost, h->stream));
+    CK(hipStreamSynchronize(h->stream));
+    h->d2h_small += 1;
+    if (bad != ~0ull) return failmsg(h, me + ": bad arguments (target " + std::to_string((long long)bad) + " lies outside [0, ld))");
+    const int W = (n + 63) / 64, per = PF_COVER_THREADS / 64;
+    const dim3 grid((unsigned)((W + per - 1) / per), (unsigned)K);
+    if (kind == 0)
+      hipLaunchKernelGGL(k_cover_pack<0>, grid, dim3(PF_COVER_THREADS), 0, h->stream, d_src, (const int*)d_targets, (int)n, (int)ld, radius, (int)row0,
+                         (unsigned long long*)d_mask);
+    else
+      hipLaunchKernelGGL(k_cover_pack<1>, grid, dim3(PF_COVER_THREADS), 0, h->stream, d_src, (const int*)d_targets, (int)n, (int)ld, radius, (int)row0,
+                         (unsigned long long*)d_mask);
+    CK(hipGetLastError());
+    CK(hipEventRecord(h->ev1, h->stream));
+    CK(hipStreamSynchronize(h->stream));
+    CK(hipEventElapsedTime(&h->last_ms, h->ev0, h->ev1));
+    return 0;
+  };
+  return run() ? -1 : 0;
+}
+
+int pf_cover_improve(pf_handle* h, int32_t m, int32_t n, int32_t p, int32_t fixed, int32_t B, int32_t shared, const uint64_t* d_mask, int32_t max_moves, int32_t* d_sel,
+                     uint64_t* d_covered, int64_t* d_value, int32_t* d_status, int64_t* d_info) {
+  if (!h) return -2;
+  const std::string me("pf_cover_improve");
+  auto run = [&]() -> int {
+    if (m < 1 || m > PF_COVER_SITES_MAX)
+      return failmsg(h, me + ": bad arguments (m = " + std::to_string(m) + ": the number of sites must lie in [1, " + std::to_string(PF_COVER_SITES_MAX) + "])");
+    if (n < 1 || n > PF_COVER_ELEMS_MAX)
+      return failmsg(h, me + ": bad arguments (n = " + std::to_string(n) + ": the number of elements must lie in [1, " + std::to_string(PF_COVER_ELEMS_MAX) + "])");
+    if (p < 1 || p > std::min<int>(m, PF_COVER_OPEN_MAX))
+      return failmsg(h, me + ": bad arguments (p = " + std::to_string(p) + ": the number of slots must lie in [1, min(m, " + std::to_string(PF_COVER_OPEN_MAX) + ")])");
+    if (fixed < 0 || fixed > p) return failmsg(h, me + ": bad arguments (fixed = " + std::to_string(fixed) + " must lie in [0, p])");
+    if (B < 1) return failmsg(h, me + ": bad arguments (B = " + std::to_string(B) + ": at least one start is needed)");
+    if (shared != 0 && shared != 1) return failmsg(h, me + ": bad arguments (shared = " + std::to_string(shared) + ": 0 a mask set per start, 1 one mask set for all)");
+    if (max_moves < 0 || max_moves > (1 << 20))
+      return failmsg(h, me + ": bad arguments (max_moves = " + std::to_string(max_moves) + " must lie in [0, 2^20])");
+    if (!d_mask || !d_sel || !d_value || !d_status) return failmsg(h, me + ": bad arguments (the masks, the rows, the values and the statuses must not be null)");
+    CK(hipSetDevice(h->device));
+    if (h->df_cus < 1) {
+      int cus = 0;
+      if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, h->device) != hipSuccess || cus < 1) cus = 256;
+      h->df_cus = cus;
+    }
+    const int W = (n + 63) / 64;
+    const bool lds = W <= PF_COVER_LDS_WORDS;
+    // two workgroups a CU in the LDS form; the HBM form's registers leave room for one, so a second half of the grid would only queue
+    const long long G = std::min<long long>(B, (lds ? 2ll : 1ll) * h->df_cus);
+    const size_t plane_bytes = lds ? 0 : sizeof(unsigned long long) * 2 * (size_t)W * (size_t)G;
+    if (scratch(h, me, h->d_widest, &h->widest_bytes, sizeof(unsigned long long) * 2 + plane_bytes, "the planes", true)) return -2;
+    unsigned long long* const d_bad = (unsigned long long*)h->d_widest;
+    const long long rows = (long long)m * (shared ? 1 : (long long)B), slots = (long long)B * p;
+    unsigned long long bad = ~0ull;
+    CK(hipMemcpyAsync(d_bad, &bad, sizeof(bad), hipMemcpyHostToDevice, h->stream));
+    CK(hipStreamSynchronize(h->stream));
+    CK(hipEventRecord(h->ev0, h->stream));
+    // the tail bits, then the rows, before any output is touched
+    auto first_bad = [&]() -> int {
+      CK(hipGetLastError());
+      CK(hipMemcpyAsync(&bad, d_bad, sizeof(bad), hipMemcpyDeviceToHost, h->stream));
+      CK(hipStreamSynchronize(h->stream));
+      h->d2h_small += 1;
+      return 0;
+    };
+    hipLaunchKernelGGL(k_cover_validate_tail, dim3((unsigned)std::min<long long>((rows + PF_COVER_THREADS - 1) / PF_COVER_THREADS, 2048)), dim3(PF_COVER_THREADS), 0,
+                       h->stream, (const unsigned long long*)d_mask, (int)n, W, rows, d_bad);
+    if (first_bad()) return -1;
+    if (bad != ~0ull) {
+      const long long e = (long long)bad;
+      return failmsg(h, me + ": bad arguments (the mask (b, i) = (" + std::to_string(e / m) + ", " + std::to_string(e % m) + ") holds a bit at an element >= n)");
+    }
+    hipLaunchKernelGGL(k_place_validate_rows, dim3((unsigned)std::min<long long>((slots + PF_PLACE_THREADS - 1) / PF_PLACE_THREADS, 2048)), dim3(PF_PLACE_THREADS), 0,
+                       h->stream, (const int*)d_sel, (int)m, (int)p, (int)fixed, slots, d_bad);
+    if (first_bad()) return -1;
+    if (bad != ~0ull) {
+      const long long e = (long long)bad;
+      return failmsg(h, me + ": bad arguments (the row (b, slot) = (" + std::to_string(e / p) + ", " + std::to_string(e % p) +
+                            ") lies outside [-1, m), repeats the site of a smaller slot or is empty below fixed)");
+    }
+    if (lds) {
+      const size_t bytes = sizeof(unsigned long long) * 2 * (size_t)W;   // any and once
+      CK(hipFuncSetAttribute((const void*)k_cover_group_per_start<true>, hipFuncAttributeMaxDynamicSharedMemorySize,
+                             (int)(sizeof(unsigned long long) * 2 * PF_COVER_LDS_WORDS)));   // (the most any call asks for: never shrunk between calls)
+      hipLaunchKernelGGL(k_cover_group_per_start<true>, dim3((unsigned)G), dim3(PF_COVER_GROUP), bytes, h->stream, (const unsigned long long*)d_mask, (int)m, (int)n, (int)p,
+                         (int)fixed, (int)B, (int)shared, (int)max_moves, (int*)d_sel, (unsigned long long*)d_covered, (long long*)d_value, (int*)d_status,
+                         (long long*)d_info, (unsigned long long*)nullptr);
+    } else {
+      hipLaunchKernelGGL(k_cover_group_per_start<false>, dim3((unsigned)G), dim3(PF_COVER_GROUP), 0, h->stream, (const unsigned long long*)d_mask, (int)m, (int)n, (int)p,
+                         (int)fixed, (int)B, (int)shared, (int)max_moves, (int*)d_sel, (unsigned long long*)d_covered, (long long*)d_value, (int*)d_status,
+                         (long long*)d_info, d_bad + 2);
+    }
     CK(hipGetLastError());
     CK(hipEventRecord(h->ev1, h->stream));
     CK(hipStreamSynchronize(h->stream));

@@ -30,3 +30,4 @@ from .assignment import Assignment  # noqa: F401
 from .tour_search import TourSearch  # noqa: F401
 from .fleet import FleetTours  # noqa: F401
 from .placement import Placement  # noqa: F401
+from .cover import Coverage  # noqa: F401

@@ -1,4 +1,4 @@
-"""What the field classes share (DistanceField, NearestSourceField, CostField, TurnField, PathSmoother, Components, Clearance, Visibility, SpaceTime, Tour, Assignment, TourSearch, FleetTours, Placement): the constructor's grid
+"""What the field classes share (DistanceField, NearestSourceField, CostField, TurnField, PathSmoother, Components, Clearance, Visibility, SpaceTime, Tour, Assignment, TourSearch, FleetTours, Placement, Coverage): the constructor's grid
 and engine checks, the (r, c) -> cell id parser with its two messages, the index check and the close / __del__ pair.  Every message
 starts with the class name; all checks run before the device is touched."""
 import numpy as np

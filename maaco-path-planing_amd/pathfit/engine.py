@@ -599,6 +599,25 @@ class Engine:
                                          d_status.ptr if d_status else None, d_info.ptr if d_info else None))
         self._logk("place_improve")
 
+    def cover_pack(self, kind, K, n, d_src, ld, d_targets, radius, row0, d_mask):
+        """K source rows in HBM (d_src uint8 for kind 0, the bit byte != 0: visibility_field's rows; float64 for kind 1, the bit
+        x <= radius: the fields' rows), leading dimension ld, read at the n cells d_targets (int32 on the device) -> the rows
+        row0 .. row0 + K - 1 of the bit masks d_mask uint64 [m, ceil(n / 64)], 64 targets a word, the tail bits 0 (pf_cover_pack)."""
+        self._ck(self.L.pf_cover_pack(self.h, int(kind), int(K), int(n), d_src.ptr if d_src else None, int(ld), d_targets.ptr if d_targets else None,
+                                      float(radius), int(row0), d_mask.ptr if d_mask else None))
+        self._logk("cover_pack")
+
+    def cover_improve(self, m, n, p, fixed, B, shared, d_mask, max_moves, d_sel, d_covered, d_value, d_status, d_info=None):
+        """B start rows d_sel int32 [B, p] (in and out: place_improve's rows) over one mask set d_mask uint64 [m, W] (`shared`) or over
+        [B, m, W], W = ceil(n / 64): best-improvement additions, swaps and drops under the key (n - covered, open), at most
+        max_moves moves a start -> d_covered uint64 [B, W] (or None), the union; d_value int64 [B, 4] = (covered after, open after,
+        covered before, open before); d_status int32 [B], 0 no better candidate is left, 2 stopped by the cap; d_info int64 [B, 4] =
+        (moves, sweeps, elements covered exactly once, drops) (pf_cover_improve)."""
+        self._ck(self.L.pf_cover_improve(self.h, int(m), int(n), int(p), int(fixed), int(B), int(bool(shared)), d_mask.ptr if d_mask else None, int(max_moves),
+                                         d_sel.ptr if d_sel else None, d_covered.ptr if d_covered else None, d_value.ptr if d_value else None,
+                                         d_status.ptr if d_status else None, d_info.ptr if d_info else None))
+        self._logk("cover_improve")
+
     # ------------------------------------------------------------------ assignments
     def assign_matrix(self, n_rows, cols, d_fields, d_mat, row0=0, ld=None, transpose=False):
         """A chunk of n_rows field rows in HBM (d_fields float64 [n_rows, R * C]) gathered at the host int32 cell ids `cols` ->
