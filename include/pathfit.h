@@ -938,6 +938,64 @@ int pf_fleet_improve(pf_handle* h, int32_t mode, int32_t k, int32_t n, int32_t B
                      const int32_t* d_cap, int32_t max_moves, int32_t* d_route, double* d_len, double* d_value, int32_t* d_status,
                      int64_t* d_info);
 
+/* ---- fleet routes under the min-max objective: the same candidates, priced by the largest length (pathfit.FleetTours,
+ * objective="makespan") -------------------------------------------------------------------------------------------------------------
+ * 
+ * What is pf_fleet_improve's.
+ * - The problem, the weights w, the route row, rob, cnt, nxt, END, the modes and the capacities.
+ * - The two candidate families (code 0: 2-opt inside a route; code L = 1, 2, 3: relocation of L tasks behind any position j,
+ *   markers included), their (i, j) and their admissibility.
+ * - Per candidate delta, and for a relocation rem and add: the formulas above, unchanged, each line fp64 in the order written.
+ * - How a candidate is applied.  The entries a problem may hold.  Status 1 for a problem with a +inf readable entry.
+ * The lengths the rule carries.
+ * - len[0 .. k-1] are doubles.  At the start len[r] is robot r's length in the start row: the left-to-right fp64 sum of
+ *   w(route[p], nxt(p)) over the positions of its stretch from its marker on (pf_fleet_improve's len).
+ * - span = the largest of len[0 .. k-1].  Lengths are compared by value.
+ * The price of a candidate.  s = rob(i), d = rob(j).
+ * - A 2-opt, or a relocation with s == d, touches route s alone:
+ *     len'[s] = fl( len[s] + delta ),
+ *     span'   = the largest of len'[s] and of len[r] over the robots r != s.
+ * - A relocation with s != d touches two routes.  rem and add are the changes of the legs AROUND the segment; the segment's own
+ *   L-1 legs leave route s and enter route d with it (in the total they cancel, in the two lengths they do not):
+ *     inner   = +0.0 for L = 1, w(s1,s2) for L = 2, fl( w(s1,s2) + w(s2,s3) ) for L = 3   (s1, s2, s3 = route[i], route[i+1], route[i+2]),
+ *     len'[s] = fl( fl(len[s] - rem) - inner ),
+ *     len'[d] = fl( fl(len[d] + add) + inner ),
+ *     span'   = the largest of len'[s], len'[d] and of len[r] over the robots r other than s and d.
+ * - Over no robots at all (k = 1, or k = 2 with s != d) the last term is absent.
+ * One sweep.
+ * - The move of the sweep is the admissible candidate with the smallest (span', delta, family code, i, j), compared
+ *   lexicographically.
+ * - It is applied iff span' < span, or span' == span and delta < 0; and only while fewer than max_moves moves were applied.
+ * - When it is applied, the row changes as in pf_fleet_improve, len[s] becomes len'[s] and, for s != d, len[d] becomes len'[d].
+ *   Every other len[r] stays.  Nothing is summed again from the row: the next sweep prices its candidates with these words, and
+ *   its span is their largest, which is the applied span'.  So span never rises from one sweep to the next.
+ * - Then sweep again.
+ * Stopping.
+ * - Status 0: a sweep has no admissible candidate, or its move fails the test above.
+ * - Status 2: a sweep's move passes the test after max_moves moves, 0 <= max_moves <= 2^20.
+ * - A call runs at most max_moves + 1 sweeps per start.
+ * - With weights that are integers below 2^53 / N every line is exact, the carried len are the true lengths and an applied move
+ *   lowers (makespan, total) lexicographically: no row can recur.  With other weights delta and the carried len are rounded,
+ *   a move whose true change is 0 may carry a delta of -1 ulp, and a search can walk among such rows until the cap.
+ * Results per start.
+ * - d_route: the final row.
+ * - d_len [k]: the left-to-right lengths of the FINAL ROW, summed again from it as pf_fleet_improve does (not the carried words).
+ * - value = {makespan after, total after, makespan before, total before}: total is the left-to-right sum of len[0 .. k-1],
+ *   makespan the largest; "after" of d_len, "before" of the start row's lengths.
+ * - info = {moves, sweeps, 2-opt moves, relocate moves, moves with span' < span}.
+ * - A problem with a +inf readable entry: status 1, a row of all -1, value = {+inf, +inf, +inf, +inf}, len all +inf, info all 0.
+ * pf_fleet_balance takes pf_fleet_improve's arguments: B starts d_route int32 [B][N], in and out, over d_mat [N][N] (shared = 1)
+ * or [B][N][N] (shared = 0), under d_cap int32 [k] (or NULL) -> d_len [B][k], d_value [B][4], d_status [B], d_info int64 [B][5]
+ * (or NULL).  One workgroup of 1024 threads per start runs the move loop inside the kernel, over pf_fleet_improve's LDS rows; LDS
+ * also holds len[k] and the three largest lengths with their robots, found at the head of a sweep, so that the largest length
+ * outside a candidate's one or two routes is a pick among three (by value: which robot a tie names changes nothing).  One launch
+ * per call, whatever B.  The device's routes, lengths, values, statuses and infos equal the rule's as 64-bit words, on every run
+ * and for every assignment of starts to workgroups.
+ * The argument errors, the validation kernels, their order and their messages are pf_fleet_improve's, under this call's name. */
+int pf_fleet_balance(pf_handle* h, int32_t mode, int32_t k, int32_t n, int32_t B, int32_t shared, const double* d_mat,
+                     const int32_t* d_cap, int32_t max_moves, int32_t* d_route, double* d_len, double* d_value, int32_t* d_status,
+                     int64_t* d_info);
+
 /* ---- placement: which p of m candidate sites to open for n demands, additions and swaps (pathfit.Placement) ---------------------
  * 
  * The problem.

@@ -1582,15 +1582,16 @@ int pf_tour_improve(pf_handle* h, int32_t mode, int32_t n, int32_t B, int32_t sh
 // pf_fleet_improve takes B start rows over one shared matrix or over B matrices, checks the entries, the rows and the capacities
 // with validation kernels, and runs the move loops in one launch, a workgroup per start.  Scratch: the first offending index and
 // the matrices' "holds +inf" words in the tile-queue block (h->d_widest, h->widest_bytes).  Nothing in it outlives a call.
+// pf_fleet_balance (pf_fleet_balance.h) is the same call with the move loop of the min-max rule: the argument
+// checks, the validation kernels and the launch geometry are one function, fleet_call, that takes the kernel.
 // ---------------------------------------------------------------------------
-#include "pf_fleet.h"
+#include "pf_fleet_balance.h"
 
-extern "C" {
+using fleet_kernel = void (*)(const double*, const int*, const int*, int, int, int, int, int, int, int*, double*, double*, int*, long long*);
 
-int pf_fleet_improve(pf_handle* h, int32_t mode, int32_t k, int32_t n, int32_t B, int32_t shared, const double* d_mat, const int32_t* d_cap, int32_t max_moves,
-                     int32_t* d_route, double* d_len, double* d_value, int32_t* d_status, int64_t* d_info) {
+static int fleet_call(pf_handle* h, const std::string& me, fleet_kernel kernel, int32_t mode, int32_t k, int32_t n, int32_t B, int32_t shared, const double* d_mat,
+                      const int32_t* d_cap, int32_t max_moves, int32_t* d_route, double* d_len, double* d_value, int32_t* d_status, int64_t* d_info) {
   if (!h) return -2;
-  const std::string me("pf_fleet_improve");
   auto run = [&]() -> int {
     if (mode < 0 || mode > 1) return failmsg(h, me + ": bad arguments (mode = " + std::to_string(mode) + ": 0 open, 1 return)");
     if (k < 1) return failmsg(h, me + ": bad arguments (k = " + std::to_string(k) + ": at least one robot is needed)");
@@ -1664,8 +1665,8 @@ int pf_fleet_improve(pf_handle* h, int32_t mode, int32_t k, int32_t n, int32_t B
     }
     long long* const info = (long long*)d_info;
     const long long groups = (long long)(32 * 64 / PF_FLEET_GROUP) * h->df_cus;                    // what is resident at once
-    hipLaunchKernelGGL(k_fleet_group_per_start, dim3((unsigned)std::min<long long>(B, groups)), dim3(PF_FLEET_GROUP), 0, h->stream, d_mat, (const int*)d_inf,
-                       (const int*)d_cap, (int)mode, (int)k, N, (int)B, (int)shared, (int)max_moves, (int*)d_route, d_len, d_value, (int*)d_status, info);
+    hipLaunchKernelGGL(kernel, dim3((unsigned)std::min<long long>(B, groups)), dim3(PF_FLEET_GROUP), 0, h->stream, d_mat, (const int*)d_inf, (const int*)d_cap, (int)mode,
+                       (int)k, N, (int)B, (int)shared, (int)max_moves, (int*)d_route, d_len, d_value, (int*)d_status, info);
     CK(hipGetLastError());
     CK(hipEventRecord(h->ev1, h->stream));
     CK(hipStreamSynchronize(h->stream));
@@ -1673,6 +1674,18 @@ int pf_fleet_improve(pf_handle* h, int32_t mode, int32_t k, int32_t n, int32_t B
     return 0;
   };
   return run() ? -1 : 0;
+}
+
+extern "C" {
+
+int pf_fleet_improve(pf_handle* h, int32_t mode, int32_t k, int32_t n, int32_t B, int32_t shared, const double* d_mat, const int32_t* d_cap, int32_t max_moves,
+                     int32_t* d_route, double* d_len, double* d_value, int32_t* d_status, int64_t* d_info) {
+  return fleet_call(h, "pf_fleet_improve", k_fleet_group_per_start, mode, k, n, B, shared, d_mat, d_cap, max_moves, d_route, d_len, d_value, d_status, d_info);
+}
+
+int pf_fleet_balance(pf_handle* h, int32_t mode, int32_t k, int32_t n, int32_t B, int32_t shared, const double* d_mat, const int32_t* d_cap, int32_t max_moves,
+                     int32_t* d_route, double* d_len, double* d_value, int32_t* d_status, int64_t* d_info) {
+  return fleet_call(h, "pf_fleet_balance", k_fleet_balance_group_per_start, mode, k, n, B, shared, d_mat, d_cap, max_moves, d_route, d_len, d_value, d_status, d_info);
 }
 
 }  // extern "C"

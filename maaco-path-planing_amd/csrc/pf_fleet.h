@@ -111,10 +111,81 @@ __global__ __launch_bounds__(PF_FLEET_THREADS) void k_fleet_validate_caps(const 
   }
 }
 
-__global__ __launch_bounds__(PF_FLEET_GROUP) void k_fleet_group_per_start(const double* __restrict__ mat, const int* __restrict__ has_inf, const int* __restrict__ cap, int mode,
-                                                                          int k, int N, int B, int shared, int max_moves, int* route, double* __restrict__ len,
-                                                                          double* __restrict__ value, int* __restrict__ status, long long* __restrict__ info) {
-  constexpr int T = PF_FLEET_GROUP, W = T / 64, U = PF_FLEET_UNROLL;
+// What the two rules (the sum of the lengths here, the largest length in pf_fleet_balance.h) do differently is a policy P: its
+// LDS words (P::Lds), a thread's best candidate, begin (the head of a sweep, by all threads), take (a thread looks at one admissible
+// candidate -- delta, and for a relocation rem, add and the length of the segment's own legs --; its candidates come in ascending key), reduce (the workgroup's best into every thread), improves, commit (the applied
+// candidate's bookkeeping) and the words of value and info.  fleet_group is everything else: the rows in LDS, the head of a sweep,
+// the candidates' gathers, the move.
+struct fleet_sum {
+  static constexpr int W = PF_FLEET_GROUP / 64;
+  struct Lds {
+    double rv[W];
+    int rk[W];
+  };
+  double bd;
+  int bk;
+  static __device__ __forceinline__ double* keep(Lds&) { return nullptr; }
+  __device__ __forceinline__ void begin(Lds&, int, int) {}
+  __device__ __forceinline__ void reset() {
+    bd = 0.0;                                   // only a delta < 0 is a move
+    bk = PF_FLEET_NONE;
+  }
+  __device__ __forceinline__ void take(const Lds&, double d, double, double, double, int, int, int key) {
+    if (d < bd) {
+      bd = d;
+      bk = key;
+    }
+  }
+  __device__ __forceinline__ void reduce(Lds& s, int tid) {
+#pragma unroll
+    for (int o = 32; o; o >>= 1) {
+      const double qv = __shfl_xor(bd, o);
+      const int qk = __shfl_xor(bk, o);
+      if (tsearch_before(qv, qk, bd, bk)) {
+        bd = qv;
+        bk = qk;
+      }
+    }
+    if ((tid & 63) == 0) {
+      s.rv[tid >> 6] = bd;
+      s.rk[tid >> 6] = bk;
+    }
+    __syncthreads();
+    bd = s.rv[0];
+    bk = s.rk[0];
+#pragma unroll
+    for (int q = 1; q < W; ++q) {
+      const double qv = s.rv[q];
+      const int qk = s.rk[q];
+      if (tsearch_before(qv, qk, bd, bk)) {
+        bd = qv;
+        bk = qk;
+      }
+    }
+  }
+  __device__ __forceinline__ bool improves() const { return bk != PF_FLEET_NONE; }   // no delta < 0 otherwise (the same in every thread)
+  __device__ __forceinline__ int key() const { return bk; }
+  __device__ __forceinline__ void commit(Lds&, int, int, int) {}
+  static __device__ __forceinline__ void not_searched(double* value, long long* info, size_t b) {
+    value[b * 3] = tsearch_inf();
+    value[b * 3 + 1] = tsearch_inf();
+    value[b * 3 + 2] = tsearch_inf();
+    if (info) { info[b * 4] = 0; info[b * 4 + 1] = 0; info[b * 4 + 2] = 0; info[b * 4 + 3] = 0; }
+  }
+  __device__ __forceinline__ void write(double* value, long long* info, size_t b, double before, double, double after, double span, int moves, int sweeps,
+                                        int two) const {
+    value[b * 3] = after;
+    value[b * 3 + 1] = before;
+    value[b * 3 + 2] = span;
+    if (info) { info[b * 4] = moves; info[b * 4 + 1] = sweeps; info[b * 4 + 2] = two; info[b * 4 + 3] = moves - two; }
+  }
+};
+
+template <class P>
+__device__ __forceinline__ void fleet_group(const double* __restrict__ mat, const int* __restrict__ has_inf, const int* __restrict__ cap, int mode, int k, int N, int B,
+                                            int shared, int max_moves, int* route, double* __restrict__ len, double* __restrict__ value, int* __restrict__ status,
+                                            long long* __restrict__ info) {
+  constexpr int T = PF_FLEET_GROUP, U = PF_FLEET_UNROLL;
   __shared__ int s_route[PF_FLEET_MAX];
   __shared__ int s_rob[PF_FLEET_MAX];
   __shared__ int s_nxt[PF_FLEET_MAX];           // nxt(p), -1 for "none"; the scratch row of a relocation
@@ -123,8 +194,7 @@ __global__ __launch_bounds__(PF_FLEET_GROUP) void k_fleet_group_per_start(const 
   __shared__ int s_cap[PF_FLEET_MAX];
   __shared__ double s_leg[PF_FLEET_MAX];
   __shared__ double s_rem[3 * PF_FLEET_MAX];    // rem[(L - 1) N + i], NaN where the segment is none; the lengths before and after
-  __shared__ double s_rv[W];
-  __shared__ int s_rk[W];
+  __shared__ typename P::Lds s_p;
   const int tid = (int)threadIdx.x;
   const int pairs = N >= 3 ? (N - 1) * (N - 2) / 2 : 0;               // the tour search's pairs with hi = N - 1
   const int cells = 3 * N * N;                                        // the relocations' grid
@@ -136,11 +206,8 @@ __global__ __launch_bounds__(PF_FLEET_GROUP) void k_fleet_group_per_start(const 
       for (int p = tid; p < N; p += T) row[p] = -1;
       for (int r = tid; r < k; r += T) len[(size_t)b * (size_t)k + r] = tsearch_inf();
       if (tid == 0) {
-        value[(size_t)b * 3] = tsearch_inf();
-        value[(size_t)b * 3 + 1] = tsearch_inf();
-        value[(size_t)b * 3 + 2] = tsearch_inf();
+        P::not_searched(value, info, (size_t)b);
         status[b] = 1;
-        if (info) { info[(size_t)b * 4] = 0; info[(size_t)b * 4 + 1] = 0; info[(size_t)b * 4 + 2] = 0; info[(size_t)b * 4 + 3] = 0; }
       }
       continue;
     }
@@ -153,12 +220,14 @@ __global__ __launch_bounds__(PF_FLEET_GROUP) void k_fleet_group_per_start(const 
       return x < y ? m[(size_t)x * (size_t)N + (size_t)y] : m[(size_t)y * (size_t)N + (size_t)x];
     };
     auto we = [&](int x, int e) -> double { return (e < 0 || e == x) ? 0.0 : w2(x, e); };
-    // len[r] into s_rem[r] (the legs are filled, rem is not in use): a thread per robot sums its legs in order, thread 0 the lengths
-    auto lengths = [&](double& total, double& span) {
+    // len[r] into s_rem[r] (the legs are filled, rem is not in use) and into keep[r] where the policy holds the lengths: a thread per
+    // robot sums its legs in order, thread 0 the lengths
+    auto lengths = [&](double& total, double& span, double* keep) {
       for (int r = tid; r < k; r += T) {
         double t = s_leg[s_at[r]];
         for (int p = s_at[r] + 1; p < s_at[r + 1]; ++p) t = t + s_leg[p];
         s_rem[r] = t;
+        if (keep) keep[r] = t;
       }
       __syncthreads();
       if (tid == 0) {
@@ -171,8 +240,9 @@ __global__ __launch_bounds__(PF_FLEET_GROUP) void k_fleet_group_per_start(const 
       }
       __syncthreads();                          // (s_rem is rem's again)
     };
-    double before = 0.0, after = 0.0, span = 0.0;
+    double before = 0.0, after = 0.0, span0 = 0.0, span = 0.0;
     int moves = 0, sweeps = 0, two = 0, st = 2;
+    P rule;
     for (int s = 0; s <= max_moves; ++s) {      // at most max_moves moves: at most max_moves + 1 sweeps; the loop ends by a break
       // the head of a sweep: the markers' positions; then rob, nxt and the leg of every position, cnt of every robot; then rem
       for (int p = tid; p < N; p += T)
@@ -192,7 +262,7 @@ __global__ __launch_bounds__(PF_FLEET_GROUP) void k_fleet_group_per_start(const 
       }
       for (int r = tid; r < k; r += T) s_cnt[r] = s_at[r + 1] - s_at[r] - 1;
       __syncthreads();
-      if (s == 0) lengths(before, span);
+      if (s == 0) lengths(before, span0, P::keep(s_p));
       for (int x = tid; x < 3 * N; x += T) {
         const int L = x / N + 1, i = x - (L - 1) * N, z = i + L - 1;
         double rem = __longlong_as_double(0x7FF8000000000000ll);
@@ -202,12 +272,12 @@ __global__ __launch_bounds__(PF_FLEET_GROUP) void k_fleet_group_per_start(const 
       }
       __syncthreads();
       ++sweeps;
-      double bd = 0.0;                          // only a delta < 0 is a move
-      int bk = PF_FLEET_NONE;
+      rule.begin(s_p, k, tid);
+      rule.reset();
       // code 0: the 2-opt pairs
       for (int c0 = tid; c0 < pairs; c0 += U * T) {
         double wac[U], wbe[U], old[U];
-        int key[U];
+        int key[U], ri[U];
         bool open_end[U];
 #pragma unroll
         for (int u = 0; u < U; ++u) {           // every load is issued before the first is used: a slot past the end reads pair 0
@@ -220,23 +290,21 @@ __global__ __launch_bounds__(PF_FLEET_GROUP) void k_fleet_group_per_start(const 
           wac[u] = w2(a, cn);
           wbe[u] = w2(bn, open_end[u] ? a : e);
           old[u] = s_leg[i - 1] + s_leg[j];
+          ri[u] = s_rob[i];
           key[u] = ok ? (i << 10) | j : PF_FLEET_NONE;
         }
 #pragma unroll
         for (int u = 0; u < U; ++u) {           // ascending keys: a strict < keeps the first smallest
           const double d = (wac[u] + (open_end[u] ? 0.0 : wbe[u])) - old[u];
-          if (key[u] != PF_FLEET_NONE && d < bd) {
-            bd = d;
-            bk = key[u];
-          }
+          if (key[u] != PF_FLEET_NONE) rule.take(s_p, d, 0.0, 0.0, 0.0, ri[u], ri[u], key[u]);
         }
       }
       // codes 1 .. 3: the relocations, cell c of the [3 N][N] grid = (L, i, j) with x = (L - 1) N + i = c / N, j = c % N
       {
         int x = tid / N, j = tid - x * N;
         for (int c0 = tid; c0 < cells; c0 += U * T) {
-          double wps[U], wsq[U], old[U], rem[U];
-          int key[U];
+          double wps[U], wsq[U], old[U], rem[U], inner[U];
+          int key[U], ri[U], rd[U];
           bool open_end[U];
 #pragma unroll
           for (int u = 0; u < U; ++u) {
@@ -254,6 +322,9 @@ __global__ __launch_bounds__(PF_FLEET_GROUP) void k_fleet_group_per_start(const 
             wsq[u] = w2(sL, open_end[u] ? (sL ? 0 : 1 % N) : q);
             old[u] = s_leg[jj];
             rem[u] = r;
+            inner[u] = L == 1 ? 0.0 : (L == 2 ? s_leg[iz] : s_leg[iz] + s_leg[zz - 1]);   // the segment's own legs (zz - 1 >= 0: iz >= 1)
+            ri[u] = s_rob[iz];
+            rd[u] = rj;
             key[u] = ok ? (L << 20) | (i << 10) | jj : PF_FLEET_NONE;
             j += T;                             // the thread's next cell
             while (j >= N) {
@@ -265,41 +336,16 @@ __global__ __launch_bounds__(PF_FLEET_GROUP) void k_fleet_group_per_start(const 
           for (int u = 0; u < U; ++u) {
             const double add = (wps[u] + (open_end[u] ? 0.0 : wsq[u])) - old[u];
             const double d = add - rem[u];
-            if (key[u] != PF_FLEET_NONE && d < bd) {
-              bd = d;
-              bk = key[u];
-            }
+            if (key[u] != PF_FLEET_NONE) rule.take(s_p, d, rem[u], add, inner[u], ri[u], rd[u], key[u]);
           }
         }
       }
-#pragma unroll
-      for (int o = 32; o; o >>= 1) {
-        const double qv = __shfl_xor(bd, o);
-        const int qk = __shfl_xor(bk, o);
-        if (tsearch_before(qv, qk, bd, bk)) {
-          bd = qv;
-          bk = qk;
-        }
-      }
-      if ((tid & 63) == 0) {
-        s_rv[tid >> 6] = bd;
-        s_rk[tid >> 6] = bk;
-      }
-      __syncthreads();
-      double dv = s_rv[0];
-      int dk = s_rk[0];
-#pragma unroll
-      for (int q = 1; q < W; ++q) {
-        const double qv = s_rv[q];
-        const int qk = s_rk[q];
-        if (tsearch_before(qv, qk, dv, dk)) {
-          dv = qv;
-          dk = qk;
-        }
-      }
-      if (dk == PF_FLEET_NONE) { st = 0; break; }                     // no delta < 0 (the same in every thread)
+      rule.reduce(s_p, tid);
+      if (!rule.improves()) { st = 0; break; }                        // (the same in every thread)
       if (moves == max_moves) { st = 2; break; }                      // a move is there and the cap forbids it
+      const int dk = rule.key();
       const int code = dk >> 20, i = (dk >> 10) & 1023, j = dk & 1023;   // an evaluated candidate: its positions lie in the row
+      rule.commit(s_p, s_rob[i], s_rob[j], tid);
       if (code == 0) {
         for (int t = tid; t < (j - i + 1) / 2; t += T) {
           const int v = s_route[i + t];
@@ -316,20 +362,23 @@ __global__ __launch_bounds__(PF_FLEET_GROUP) void k_fleet_group_per_start(const 
         for (int t = tid; t <= hi - lo; t += T) s_route[lo + t] = s_nxt[lo + t];
       }
       ++moves;
-      __syncthreads();                          // (also: every thread has read s_rv / s_rk before the next sweep writes them)
+      __syncthreads();                          // (also: every thread has read the policy's words before the next sweep writes them)
     }
-    lengths(after, span);                       // (no move since the legs were filled: they are the result's)
+    lengths(after, span, nullptr);              // (no move since the legs were filled: they are the result's)
     for (int p = tid; p < N; p += T) row[p] = s_route[p];
     for (int r = tid; r < k; r += T) len[(size_t)b * (size_t)k + r] = s_rem[r];
     if (tid == 0) {
-      value[(size_t)b * 3] = after;
-      value[(size_t)b * 3 + 1] = before;
-      value[(size_t)b * 3 + 2] = span;
+      rule.write(value, info, (size_t)b, before, span0, after, span, moves, sweeps, two);
       status[b] = st;
-      if (info) { info[(size_t)b * 4] = moves; info[(size_t)b * 4 + 1] = sweeps; info[(size_t)b * 4 + 2] = two; info[(size_t)b * 4 + 3] = moves - two; }
     }
     __syncthreads();
   }
+}
+
+__global__ __launch_bounds__(PF_FLEET_GROUP) void k_fleet_group_per_start(const double* __restrict__ mat, const int* __restrict__ has_inf, const int* __restrict__ cap, int mode,
+                                                                          int k, int N, int B, int shared, int max_moves, int* route, double* __restrict__ len,
+                                                                          double* __restrict__ value, int* __restrict__ status, long long* __restrict__ info) {
+  fleet_group<fleet_sum>(mat, has_inf, cap, mode, k, N, B, shared, max_moves, route, len, value, status, info);
 }
 
 }  // namespace pf

@@ -587,6 +587,17 @@ class Engine:
                                          d_value.ptr if d_value else None, d_status.ptr if d_status else None, d_info.ptr if d_info else None))
         self._logk("fleet_improve")
 
+    def fleet_balance(self, mode, k, n, B, shared, d_mat, d_cap, max_moves, d_route, d_len, d_value, d_status, d_info=None):
+        """fleet_improve's arguments under the min-max rule: a candidate is priced by the largest length it leaves, the move of a
+        sweep is the smallest (span', delta, code, i, j), applied iff it lowers the span or keeps it with a delta < 0 -> d_len
+        float64 [B, k]; d_value float64 [B, 4] = (makespan after, total after, makespan before, total before); d_status int32
+        [B] as fleet_improve's; d_info int64 [B, 5] = (moves, sweeps, 2-opt moves, relocate moves, moves that lowered the span)
+        (pf_fleet_balance)."""
+        self._ck(self.L.pf_fleet_balance(self.h, int(mode), int(k), int(n), int(B), int(bool(shared)), d_mat.ptr if d_mat else None,
+                                         d_cap.ptr if d_cap else None, int(max_moves), d_route.ptr if d_route else None, d_len.ptr if d_len else None,
+                                         d_value.ptr if d_value else None, d_status.ptr if d_status else None, d_info.ptr if d_info else None))
+        self._logk("fleet_balance")
+
     def place_improve(self, mode, m, n, p, fixed, B, shared, d_mat, max_moves, d_sel, d_owner, d_value, d_status, d_info=None):
         """B start rows d_sel int32 [B, p] (in and out: sites of [0, m), -1 an empty slot, no site twice, the slots below `fixed`
         not empty and kept) over one matrix d_mat float64 [m, n] (`shared`) or over [B, m, n] (entries +inf or in [+0.0, 2^1000]),

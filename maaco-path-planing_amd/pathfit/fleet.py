@@ -5,7 +5,10 @@ node-to-node matrix in HBM (pf_assign_matrix), and the routes are searched on th
 inside a route and relocation of segments of one to three tasks within a route or to another robot's, from a greedy start, then
 rounds of perturbed restarts of the incumbent, all starts of a round improved in one call over the one shared matrix.  Capacities
 bound the tasks a robot may hold.  The rule reads the matrix's upper triangle only and is identical run to run for a given seed;
-`route_cost` holds any other routes against it.  `legs` / `paths` trace the routes through the parent maps of the same fields."""
+`route_cost` holds any other routes against it.  `legs` / `paths` trace the routes through the parent maps of the same fields.
+objective="makespan" searches for the routes whose LONGEST is shortest instead (pf_fleet_balance: the same candidates, priced by the
+largest length they leave): the greedy start is improved under the sum rule, then balanced, and the rounds balance the perturbed
+restarts, keeping the strictly smallest (makespan, total)."""
 import collections
 
 import numpy as np
@@ -21,6 +24,7 @@ from .tour_search import BIG, MOVES_MAX, STARTS_MAX, _int_in, mirrored
 
 NODES_MAX = 1024                                                     # PF_FLEET_MAX
 ENDS = {"open": 0, "return": 1}
+OBJECTIVES = ("sum", "makespan")
 PERTURB_MOVES = 3                                                    # the relocations drawn per perturbed start
 
 Improved = collections.namedtuple("Improved", "route lengths value status info")
@@ -30,6 +34,12 @@ def _mode(who, end):
     if not isinstance(end, str) or end not in ENDS:
         raise ValueError(f"{who}: end must be 'open' or 'return', got {end!r}")
     return ENDS[end]
+
+
+def _objective(who, objective):
+    if not isinstance(objective, str) or objective not in OBJECTIVES:
+        raise ValueError(f"{who}: objective must be 'sum' or 'makespan', got {objective!r}")
+    return objective
 
 
 def _count_check(who, k, n):
@@ -155,18 +165,20 @@ def perturbations(rng, route, k, cap, starts):
     return [perturbed(route, k, cap, draws[s]) for s in range(starts)]
 
 
-def _improve(e, mode, k, n, dm, shared, dcap, routes, limit):
-    """One pf_fleet_improve call over the start rows `routes` [B, k + n] -> (Improved, kernel ms)."""
+def _improve(e, mode, k, n, dm, shared, dcap, routes, limit, balance=False):
+    """One pf_fleet_improve call (pf_fleet_balance with `balance`: four values and five infos a start) over the start rows `routes`
+    [B, k + n] -> (Improved, kernel ms)."""
     N = k + n
     routes = np.ascontiguousarray(routes, np.int32).reshape(-1, N)
     B = len(routes)
+    nv, ni = (4, 5) if balance else (3, 4)
     do = e.put(routes.reshape(-1), np.int32)
-    dl, dv, ds, di = e.buf((B, k), np.float64), e.buf((B, 3), np.float64), e.buf(B, np.int32), e.buf((B, 4), np.int64)
+    dl, dv, ds, di = e.buf((B, k), np.float64), e.buf((B, nv), np.float64), e.buf(B, np.int32), e.buf((B, ni), np.int64)
     try:
-        e.fleet_improve(mode, k, n, B, shared, dm, dcap, limit, do, dl, dv, ds, di)
+        (e.fleet_balance if balance else e.fleet_improve)(mode, k, n, B, shared, dm, dcap, limit, do, dl, dv, ds, di)
         ms = e.last_kernel_ms()
-        return Improved(do.download().reshape(B, N).astype(np.int32), dl.download().reshape(B, k), dv.download().reshape(B, 3), ds.download().reshape(B),
-                        di.download().reshape(B, 4)), ms
+        return Improved(do.download().reshape(B, N).astype(np.int32), dl.download().reshape(B, k), dv.download().reshape(B, nv), ds.download().reshape(B),
+                        di.download().reshape(B, ni)), ms
     finally:
         for b in (do, dl, dv, ds, di):
             b.free()
@@ -195,26 +207,59 @@ def search(e, mode, k, n, dm, w, cap, dcap, starts, rounds, seed, limit):
                 kernel_ms=ms)
 
 
+def search_makespan(e, mode, k, n, dm, w, cap, dcap, starts, rounds, seed, limit):
+    """The min-max search over the matrix dm holds -> search's dict, and total_history.  Round 0 improves the
+    start row under the sum rule (pf_fleet_improve), then balances the result (pf_fleet_balance); each later round balances
+    `starts` perturbations of the incumbent in one call and keeps the strictly smallest (makespan, total) at the smallest start
+    index.  history holds the incumbent's makespan per round, total_history its total."""
+    inf = float("inf")
+    got, ms = _improve(e, mode, k, n, dm, True, dcap, [start_row(w, k, cap)], limit)
+    if int(got.status[0]) == 1:
+        return dict(route=got.route[0], lengths=[inf] * k, total=inf, makespan=inf, feasible=False, start_total=inf, history=[inf], total_history=[inf], moves=0,
+                    kernel_ms=ms)
+    first, moves = float(got.value[0, 1]), int(got.info[0, 0])
+    got, t = _improve(e, mode, k, n, dm, True, dcap, got.route, limit, balance=True)
+    ms += t
+    moves += int(got.info[0, 0])
+    route, lens, best = got.route[0], got.lengths[0], (float(got.value[0, 0]), float(got.value[0, 1]))
+    history, totals = [best[0]], [best[1]]
+    rng = np.random.default_rng(seed)
+    for _ in range(rounds):
+        got, t = _improve(e, mode, k, n, dm, True, dcap, perturbations(rng, route, k, cap, starts), limit, balance=True)
+        ms += t
+        moves += int(got.info[:, 0].sum())
+        x = min(range(len(got.value)), key=lambda b: (float(got.value[b, 0]), float(got.value[b, 1]), b))      # (the first smallest pair)
+        if (float(got.value[x, 0]), float(got.value[x, 1])) < best:
+            best, route, lens = (float(got.value[x, 0]), float(got.value[x, 1])), got.route[x], got.lengths[x]
+        history.append(best[0])
+        totals.append(best[1])
+    return dict(route=route, lengths=[float(x) for x in lens], total=best[1], makespan=best[0], feasible=True, start_total=first, history=history,
+                total_history=totals, moves=moves, kernel_ms=ms)
+
+
 class FleetTours(Field):
     """robots, tasks: (r, c) pairs, at most 1024 together; robot r starts on robots[r].  end: "open" (a route ends at its last task)
     or "return" (every robot comes back to its own start).  capacity: None, the most tasks any robot may hold, or one number per
     robot.  cost: None (path lengths, pf_dist_field_batch) or an [R, C] cost map as CostField's (pf_cost_field).  starts, rounds,
     seed: `rounds` rounds of `starts` perturbed restarts drawn from np.random.default_rng(seed).  max_moves: the moves one start may
-    take (None: 16 per cell).
+    take (None: 16 per cell).  objective: "sum" (the smallest total) or "makespan" (the smallest largest length, then the smallest
+    total: pf_fleet_balance).
 
     routes: per robot the list of task indices in visiting order (a route may be empty); lengths: per robot its route's length;
-    total: their left-to-right sum under `matrix`; makespan: the largest (reported, not optimised); feasible: False where some
-    cell cannot be reached from another (routes are then empty, total inf: the rule needs finite weights).  start_total: the greedy
-    start's total; history: the incumbent's total after round 0, 1, ...; moves: the moves of all starts; matrix: float64 [N, N],
+    total: their left-to-right sum under `matrix`; makespan: the largest (reported, not optimised, under objective="sum"; what
+    is searched under "makespan"); feasible: False where some cell cannot be reached from another (routes are then empty, total inf:
+    the rule needs finite weights).  start_total, start_makespan: the greedy start's; history: the incumbent's objective (the total,
+    or the makespan) after round 0, 1, ...; total_history: its total; moves: the moves of all starts; matrix: float64 [N, N],
     N = k + n, robots first, the upper triangle of the gathered matrix on both sides."""
     _bufs = ("buf", "pbuf", "mbuf", "cost_device", "cap_device")
     CHUNK_BYTES = 256 << 20
 
     def __init__(self, grid, robots, tasks, end="open", capacity=None, cost=None, starts=8, rounds=3, seed=0, max_moves=None,
-                 allow_diagonal_moves=True, restrict_diagonal_near_obstacle=True, engine=None):
+                 allow_diagonal_moves=True, restrict_diagonal_near_obstacle=True, engine=None, objective="sum"):
         who = type(self).__name__
         self._set_grid(grid)
         self.mode = _mode(who, end)
+        self.objective = _objective(who, objective)
         self.end = end
         rid, tid = self._cell_ids("robots", robots), self._cell_ids("tasks", tasks)
         self.k, self.n = len(rid), len(tid)
@@ -266,12 +311,16 @@ class FleetTours(Field):
             e.assign_matrix(c, self.ids, self.buf, self.mbuf, r0, N, False)
             ms += e.last_kernel_ms()
         self.matrix = mirrored(self.mbuf.download().reshape(N, N))
-        got = search(e, self.mode, self.k, self.n, self.mbuf, self.matrix, self.capacity, self.cap_device, self.starts, self.rounds, self.seed, self.max_moves)
+        find = search_makespan if self.objective == "makespan" else search
+        got = find(e, self.mode, self.k, self.n, self.mbuf, self.matrix, self.capacity, self.cap_device, self.starts, self.rounds, self.seed, self.max_moves)
         self.feasible = got["feasible"]
         self.route = np.asarray(got["route"], np.int32)
         self.routes = [[v - self.k for v in tasks] for tasks in split(self.route, self.k)] if self.feasible else [[] for _ in range(self.k)]
         self.lengths, self.total, self.makespan, self.start_total = list(got["lengths"]), got["total"], got["makespan"], got["start_total"]
         self.history, self.moves = got["history"], got["moves"]
+        self.total_history = got.get("total_history", self.history)
+        start = split(start_row(self.matrix, self.k, self.capacity), self.k)
+        self.start_makespan = lengths(self.matrix, start, self.mode)[2] if self.feasible else float("inf")
         self.solve_kernel_ms = got["kernel_ms"]
         self.kernel_ms = ms + self.solve_kernel_ms
 
@@ -298,6 +347,10 @@ class FleetTours(Field):
         summed left to right, then the robots' lengths: what another heuristic's routes are compared with;
         route_cost(self.routes) == total.  Host side."""
         return lengths(self.matrix, self._nodes(routes), self.mode)[1]
+
+    def route_makespan(self, routes):
+        """The largest length of any routes (as route_cost's) under `matrix`; route_makespan(self.routes) == makespan.  Host side."""
+        return lengths(self.matrix, self._nodes(routes), self.mode)[2]
 
     def legs(self):
         """Per robot the list of CellPaths of its route's legs in visiting order (for end="return" the last one leads back to its
@@ -398,6 +451,18 @@ class FleetTours(Field):
         Improved(route int32 [B, N], lengths float64 [B, k], value float64 [B, 3] = (total after, total before, makespan after),
         status int32 [B]: 0 no improving move is left, 1 not searched (a +inf entry), 2 stopped by max_moves (None: 16 N), info
         int64 [B, 4] = (moves, sweeps, 2-opt moves, relocate moves))."""
+        return cls._matrices(engine, False, mats, k, routes, end, capacity, shared, max_moves)
+
+    @classmethod
+    def balance_matrices(cls, engine, mats, k, routes=None, end="open", capacity=None, shared=False, max_moves=None):
+        """solve_matrices under the min-max rule (pf_fleet_balance) -> Improved(route int32 [B, N], lengths float64 [B, k], value
+        float64 [B, 4] = (makespan after, total after, makespan before, total before), status int32 [B] as solve_matrices', info
+        int64 [B, 5] = (moves, sweeps, 2-opt moves, relocate moves, moves that lowered the span))."""
+        return cls._matrices(engine, True, mats, k, routes, end, capacity, shared, max_moves)
+
+    @classmethod
+    def _matrices(cls, engine, balance, mats, k, routes, end, capacity, shared, max_moves):
+        """solve_matrices and balance_matrices: the checks, the uploads and the one call."""
         who = cls.__name__
         mode = _mode(who, end)
         try:
@@ -450,7 +515,7 @@ class FleetTours(Field):
         dm = engine.put(m.reshape(-1), np.float64)
         dcap = None if cap is None else engine.put(cap, np.int32)
         try:
-            return _improve(engine, mode, k, n, dm, bool(shared), dcap, o, limit)[0]
+            return _improve(engine, mode, k, n, dm, bool(shared), dcap, o, limit, balance)[0]
         finally:
             dm.free()
             if dcap is not None:
