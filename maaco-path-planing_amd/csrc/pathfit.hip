@@ -857,6 +857,9 @@ __global__ __launch_bounds__(1024) void k_maaco_best_take_batch(int n, const dou
 __device__ unsigned long long g_trace[4 * 16384];   // diagnostic build only: per sweep item {t0, t1, pops, wave}
 __device__ unsigned long long g_trace3[4 * 16384];  // phase items {1 + idx, inter, cur, -}; fads items {1, node, -, -}
 __device__ unsigned long long g_trace2[4 * 16384];  // per sweep item {pops A*#1, result A*#1, pops A*#2, result A*#2}
+#ifdef PF_STAMPS
+__device__ unsigned long long g_trace_fw[8 * 16384]; // per sweep item: the FW_* sums of its searches (pf_astar.h), [7] = shader clocks of the item
+#endif
 #endif
 struct MpaDev {
   double P, levy_beta, sigma, fads;
@@ -1332,6 +1335,9 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(3, 8))) void
     if (first_i(j.kind) == 0) continue;
 #ifdef PF_TRACE
     const unsigned long long tr0 = wall_clock64(), pp0 = tot.pops;
+#ifdef PF_STAMPS
+    const AStat tot0 = tot; const unsigned long long fw0 = __builtin_amdgcn_s_memtime();
+#endif
 #endif
     const bool isph = first_i(j.kind) == 1;
     int* buf = isph ? p.ph_cells + (size_t)item * p.path_cap : p.fd_cells + (size_t)(item - p.n) * p.path_cap;
@@ -1374,6 +1380,10 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(3, 8))) void
 #ifdef PF_TRACE
     if (lane == 0 && item < 16384) {
       g_trace[4 * item] = tr0; g_trace[4 * item + 1] = wall_clock64(); g_trace[4 * item + 2] = tot.pops - pp0; g_trace[4 * item + 3] = blockIdx.x;
+#ifdef PF_STAMPS
+      for (int i = 0; i < 7; ++i) g_trace_fw[8 * item + i] = tot.fw[i] - tot0.fw[i];
+      g_trace_fw[8 * item + 7] = __builtin_amdgcn_s_memtime() - fw0;
+#endif
     }
 #endif
   }
@@ -2449,6 +2459,21 @@ extern "C" int pf_debug_stamps(pf_handle* h, uint64_t* out, int reset) {
   if (reset) { uint64_t z[24] = {0}; CK(hipMemcpyToSymbol(HIP_SYMBOL(pf::g_stamps), z, sizeof(z))); }
   return 0;
 }
+// ... and what astar() spends outside the pop loop (pf_astar.h: FW_*), summed over all searches since the last reset
+extern "C" int pf_debug_stamps_fw(pf_handle* h, uint64_t* out, int reset) {
+  CK(hipSetDevice(h->device));
+  CK(hipMemcpyFromSymbol(out, HIP_SYMBOL(pf::g_stamps_fw), sizeof(uint64_t) * pf::PF_FW_N));
+  if (reset) { uint64_t z[pf::PF_FW_N] = {0}; CK(hipMemcpyToSymbol(HIP_SYMBOL(pf::g_stamps_fw), z, sizeof(z))); }
+  return 0;
+}
+#ifdef PF_TRACE
+// ... and the same per item of the last fused MPA sweep
+extern "C" int pf_debug_trace_fw(pf_handle* h, uint64_t* out) {
+  CK(hipSetDevice(h->device));
+  CK(hipMemcpyFromSymbol(out, HIP_SYMBOL(g_trace_fw), sizeof(uint64_t) * 8 * 16384));
+  return 0;
+}
+#endif
 #endif
 int pf_set_option(pf_handle* h, const char* name, int64_t value) {
   if (!name) return failmsg(h, "pf_set_option: bad arguments");
