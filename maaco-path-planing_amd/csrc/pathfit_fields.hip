@@ -1,6 +1,8 @@
-// pathfit_fields.hip -- the field family of libpathfit.so: distance fields, routing trees, nearest-source fields, smoothing,
-// connected components, clearance, widest paths, cost fields, turn fields, visibility fields, space-time fields, tours and assignments.  A translation unit, and so a device code object, of its own (DESIGN.md
-// 4.18): it shares the handle and the error helpers with pathfit.hip (pf_host.h) and none of the solvers' device code.
+// pathfit_fields.hip -- the field family of libpathfit.so (distance fields, routing trees, nearest-source fields, smoothing,
+// connected components, clearance, widest paths, cost fields, turn fields, visibility fields, space-time fields) and the planners
+// over it (tours, assignments, the tour search, fleet routes, placement, coverage).  A translation unit, and so a device code
+// object, of its own: it shares the handle and the error helpers with pathfit.hip (pf_host.h) and none of the
+// solvers' device code.
 #include <algorithm>
 #include <limits>
 #include <string>
@@ -15,12 +17,9 @@ bool g_cc_phases = false;
 
 // ---- what the entry points below say once -----------------------------------------------------------------------------------
 // One timed stretch of work on the handle's stream: ev0, whatever `enqueue` puts on the stream (it may return a nonzero code
-// of its own), ev1, the error word at d_err where the kernels keep one, synchronise -> last_ms.
-template <typename F>
-static int timed(pf_handle* h, F&& enqueue, const int* d_err = nullptr, int* err = nullptr) {
-  CK(hipEventRecord(h->ev0, h->stream));
-  if constexpr (std::is_void<decltype(enqueue())>::value) enqueue();
-  else if (const int rc = enqueue()) return rc;
+// of its own), ev1, the error word at d_err where the kernels keep one, synchronise -> last_ms.  timed_end is the second half,
+// for a call that records ev0 itself and has reasons to leave between the two.
+static int timed_end(pf_handle* h, const int* d_err = nullptr, int* err = nullptr) {
   CK(hipGetLastError());
   CK(hipEventRecord(h->ev1, h->stream));
   if (d_err) CK(hipMemcpyAsync(err, d_err, sizeof(int), hipMemcpyDeviceToHost, h->stream));
@@ -28,6 +27,14 @@ static int timed(pf_handle* h, F&& enqueue, const int* d_err = nullptr, int* err
   CK(hipEventElapsedTime(&h->last_ms, h->ev0, h->ev1));
   if (d_err) h->d2h_small += 1;
   return 0;
+}
+
+template <typename F>
+static int timed(pf_handle* h, F&& enqueue, const int* d_err = nullptr, int* err = nullptr) {
+  CK(hipEventRecord(h->ev0, h->stream));
+  if constexpr (std::is_void<decltype(enqueue())>::value) enqueue();
+  else if (const int rc = enqueue()) return rc;
+  return timed_end(h, d_err, err);
 }
 
 // Scratch memory: allocated on first use; where `have` counts the bytes p holds, replaced when a call needs more.
@@ -45,6 +52,45 @@ static int scratch(pf_handle* h, const std::string& who, T*& p, size_t* have, si
   return 0;
 }
 
+// The device's compute units, asked for once per handle.
+static int cus(pf_handle* h) {
+  if (h->df_cus < 1) {
+    int n = 0;
+    if (hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, h->device) != hipSuccess || n < 1) n = 256;
+    h->df_cus = n;
+  }
+  return h->df_cus;
+}
+
+// The planners' validation kernels report the first offending index, an atomic minimum over the word at d_bad: arm_bad sets the
+// word to ~0 (nothing found; it holds over kernels that find nothing) and clears the `flags` ints behind it where a call keeps
+// some; first_bad, behind a validation kernel's launch, brings the word back.  Both synchronise the stream.
+static int arm_bad(pf_handle* h, unsigned long long* d_bad, int* d_flags = nullptr, size_t flags = 0) {
+  const unsigned long long none = ~0ull;
+  CK(hipMemcpyAsync(d_bad, &none, sizeof(none), hipMemcpyHostToDevice, h->stream));
+  if (d_flags) CK(hipMemsetAsync(d_flags, 0, sizeof(int) * flags, h->stream));
+  CK(hipStreamSynchronize(h->stream));
+  return 0;
+}
+
+static int first_bad(pf_handle* h, const unsigned long long* d_bad, unsigned long long& bad) {
+  CK(hipGetLastError());
+  CK(hipMemcpyAsync(&bad, d_bad, sizeof(bad), hipMemcpyDeviceToHost, h->stream));
+  CK(hipStreamSynchronize(h->stream));
+  h->d2h_small += 1;
+  return 0;
+}
+
+// The arguments every planner call shares: B problems or starts (`each`), and for the searches one matrix or mask set (`set`)
+// per start or one for all, and the moves a start may take.
+static int batch_args(pf_handle* h, const std::string& me, int B, const char* each, int shared = 0, int max_moves = 0, const char* set = "matrix") {
+  if (B < 1) return failmsg(h, me + ": bad arguments (B = " + std::to_string(B) + ": at least one " + each + " is needed)");
+  if (shared != 0 && shared != 1)
+    return failmsg(h, me + ": bad arguments (shared = " + std::to_string(shared) + ": 0 a " + set + " per start, 1 one " + set + " for all)");
+  if (max_moves < 0 || max_moves > (1 << 20)) return failmsg(h, me + ": bad arguments (max_moves = " + std::to_string(max_moves) + " must lie in [0, 2^20])");
+  return 0;
+}
+
 // ---------------------------------------------------------------------------
 // Distance fields: exact one-to-all path lengths from K sources or source sets (pf_dist_field.h).  One
 // workgroup per row, min(rows, CUs) of them looping over the rows; each owns one slot of three rolling cell lists in HBM.  The
@@ -56,13 +102,8 @@ static int scratch(pf_handle* h, const std::string& who, T*& p, size_t* have, si
 // the handle's list slots for G workgroups (fewer where memory is short: G falls) and a control block of `words` ints
 static int dist_field_reserve(pf_handle* h, const std::string& me, int& G, size_t words) {
   CK(hipSetDevice(h->device));
-  if (h->df_cus < 1) {
-    int cus = 0;
-    if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, h->device) != hipSuccess || cus < 1) cus = 256;
-    h->df_cus = cus;
-  }
   const size_t slot_bytes = sizeof(int) * 3 * (size_t)h->RC;
-  if (G > h->df_cus) G = h->df_cus;
+  if (G > cus(h)) G = cus(h);
   if (G > h->df_slots) {                                            // grow the slots (a workgroup's lists: 12 RC bytes)
     CK(hipStreamSynchronize(h->stream));
     if (h->d_df_lists) { (void)hipFree(h->d_df_lists); h->d_df_lists = nullptr; h->df_slots = 0; }
@@ -1194,15 +1235,10 @@ int pf_spacetime_field(pf_handle* h, int32_t allow_diag, int32_t restrict_corner
     for (int i = 0; i < ns; ++i)
       if (src[i] < 0 || src[i] >= h->RC) return failmsg(h, me + ": source " + std::to_string(i) + " = " + std::to_string(src[i]) + " lies outside the grid");
     CK(hipSetDevice(h->device));
-    if (h->df_cus < 1) {
-      int cus = 0;
-      if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, h->device) != hipSuccess || cus < 1) cus = 256;
-      h->df_cus = cus;
-    }
     const int R = h->R, C = h->C, Wc = (C + 63) / 64, W = R * Wc;
     const size_t plane = sizeof(st_u64) * (size_t)W;
     const bool lds = PF_STF_LDS_BYTES > 0 && 3 * plane <= (size_t)PF_STF_LDS_BYTES;
-    int G = B < h->df_cus ? B : h->df_cus;
+    int G = std::min<int>(B, cus(h));
     if (!lds) {                                                       // three planes per workgroup in HBM: at most 1 GiB of them
       const size_t fit = ((size_t)1 << 30) / (3 * plane);
       if ((size_t)G > fit) G = fit < 1 ? 1 : (int)fit;
@@ -1324,7 +1360,7 @@ int pf_tour_solve(pf_handle* h, int32_t mode, int32_t n, const uint32_t* need, i
     if (m > PF_TOUR_M_MAX)
       return failmsg(h, me + ": bad arguments (n = " + std::to_string(n) + " in mode " + std::to_string(mode) + " leaves " + std::to_string(m) +
                             " middle nodes: at most 16 are solved)");
-    if (B < 1) return failmsg(h, me + ": bad arguments (B = " + std::to_string(B) + ": at least one problem is needed)");
+    if (batch_args(h, me, B, "problem")) return -2;
     if (!d_mat || !d_total || !d_order || !d_status) return failmsg(h, me + ": bad arguments (the matrices, the totals, the orders and the statuses must not be null)");
     TourNeed nd;
     for (int k = 0; k < PF_TOUR_M_MAX; ++k) nd.nm[k] = 0u;
@@ -1339,11 +1375,7 @@ int pf_tour_solve(pf_handle* h, int32_t mode, int32_t n, const uint32_t* need, i
         nd.nm[k] = (mode == 2 && ((need[k + 1] >> (n - 1)) & 1u)) ? PF_TOUR_BLOCKED : ((need[k + 1] >> 1) & ((1u << m) - 1u));
     }
     CK(hipSetDevice(h->device));
-    if (h->df_cus < 1) {
-      int cus = 0;
-      if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, h->device) != hipSuccess || cus < 1) cus = 256;
-      h->df_cus = cus;
-    }
+    const int ncu = cus(h);                                           // (asked before the timed span)
     const bool lds = m >= 1 && m <= PF_TOUR_LDS_M;
     const size_t states = m >= 1 ? ((size_t)1 << m) * (size_t)m : 0;
     long long tables = 0;                                             // the problems in flight of the HBM form
@@ -1359,16 +1391,12 @@ int pf_tour_solve(pf_handle* h, int32_t mode, int32_t n, const uint32_t* need, i
     double* const d_tab = (double*)(d_finite + tables);
     // the entries, before any output is touched
     const long long nn = (long long)n * n, entries = nn * B;
-    unsigned long long bad = ~0ull;
-    CK(hipMemcpyAsync(d_bad, &bad, sizeof(bad), hipMemcpyHostToDevice, h->stream));
-    CK(hipStreamSynchronize(h->stream));
+    unsigned long long bad;
+    if (arm_bad(h, d_bad)) return -2;
     CK(hipEventRecord(h->ev0, h->stream));
     hipLaunchKernelGGL(k_tour_validate_entries, dim3((unsigned)std::min<long long>((entries + PF_TOUR_THREADS - 1) / PF_TOUR_THREADS, 2048)), dim3(PF_TOUR_THREADS), 0,
                        h->stream, d_mat, (int)n, entries, d_bad);
-    CK(hipGetLastError());
-    CK(hipMemcpyAsync(&bad, d_bad, sizeof(bad), hipMemcpyDeviceToHost, h->stream));
-    CK(hipStreamSynchronize(h->stream));
-    h->d2h_small += 1;
+    if (first_bad(h, d_bad, bad)) return -2;
     if (bad != ~0ull) {
       const long long e = (long long)bad;
       return failmsg(h, me + ": bad arguments (the entry (b, i, j) = (" + std::to_string(e / nn) + ", " + std::to_string(e % nn / n) + ", " + std::to_string(e % n) +
@@ -1379,7 +1407,7 @@ int pf_tour_solve(pf_handle* h, int32_t mode, int32_t n, const uint32_t* need, i
       hipLaunchKernelGGL(k_tour_no_middle_nodes, dim3(((unsigned)B + 63) / 64), dim3(64), 0, h->stream, d_mat, (int)mode, (int)n, (int)B, d_total, (int*)d_order,
                          (int*)d_status, info);
     } else if (lds) {
-      hipLaunchKernelGGL(k_tour_layers_in_lds_group_per_problem, dim3((unsigned)std::min<long long>(B, 8ll * h->df_cus)), dim3(PF_TOUR_THREADS), 0, h->stream, d_mat,
+      hipLaunchKernelGGL(k_tour_layers_in_lds_group_per_problem, dim3((unsigned)std::min<long long>(B, 8ll * ncu)), dim3(PF_TOUR_THREADS), 0, h->stream, d_mat,
                          (int)mode, (int)n, m, (int)B, nd, d_total, (int*)d_order, (int*)d_status, info);
     } else {
       const unsigned gx = (unsigned)((states + PF_TOUR_THREADS - 1) / PF_TOUR_THREADS);
@@ -1395,11 +1423,7 @@ int pf_tour_solve(pf_handle* h, int32_t mode, int32_t n, const uint32_t* need, i
                            info ? info + (size_t)b0 * 4 : nullptr);
       }
     }
-    CK(hipGetLastError());
-    CK(hipEventRecord(h->ev1, h->stream));
-    CK(hipStreamSynchronize(h->stream));
-    CK(hipEventElapsedTime(&h->last_ms, h->ev0, h->ev1));
-    return 0;
+    return timed_end(h);
   };
   return run() ? -1 : 0;
 }
@@ -1452,28 +1476,20 @@ int pf_assign_solve(pf_handle* h, int32_t mode, int32_t n, int32_t m, int32_t B,
     if (n < 1) return failmsg(h, me + ": bad arguments (n = " + std::to_string(n) + ": at least one row is needed)");
     if (m < n) return failmsg(h, me + ": bad arguments (m = " + std::to_string(m) + " < n = " + std::to_string(n) + ": rows must not outnumber columns)");
     if (m > PF_ASSIGN_MAX) return failmsg(h, me + ": bad arguments (m = " + std::to_string(m) + ": at most " + std::to_string(PF_ASSIGN_MAX) + " columns are solved)");
-    if (B < 1) return failmsg(h, me + ": bad arguments (B = " + std::to_string(B) + ": at least one problem is needed)");
+    if (batch_args(h, me, B, "problem")) return -2;
     if (!d_mat || !d_col || !d_value || !d_status) return failmsg(h, me + ": bad arguments (the matrices, the columns, the values and the statuses must not be null)");
     CK(hipSetDevice(h->device));
-    if (h->df_cus < 1) {
-      int cus = 0;
-      if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, h->device) != hipSuccess || cus < 1) cus = 256;
-      h->df_cus = cus;
-    }
+    const int ncu = cus(h);                                           // (asked before the timed span)
     if (scratch(h, me, h->d_widest, &h->widest_bytes, sizeof(unsigned long long) * 8, "the entry index", false)) return -2;
     unsigned long long* const d_bad = (unsigned long long*)h->d_widest;
     // the entries, before any output is touched
     const long long nm = (long long)n * m, entries = nm * B;
-    unsigned long long bad = ~0ull;
-    CK(hipMemcpyAsync(d_bad, &bad, sizeof(bad), hipMemcpyHostToDevice, h->stream));
-    CK(hipStreamSynchronize(h->stream));
+    unsigned long long bad;
+    if (arm_bad(h, d_bad)) return -2;
     CK(hipEventRecord(h->ev0, h->stream));
     hipLaunchKernelGGL(k_assign_validate_entries, dim3((unsigned)std::min<long long>((entries + PF_ASSIGN_GATHER_THREADS - 1) / PF_ASSIGN_GATHER_THREADS, 2048)),
                        dim3(PF_ASSIGN_GATHER_THREADS), 0, h->stream, d_mat, entries, d_bad);
-    CK(hipGetLastError());
-    CK(hipMemcpyAsync(&bad, d_bad, sizeof(bad), hipMemcpyDeviceToHost, h->stream));
-    CK(hipStreamSynchronize(h->stream));
-    h->d2h_small += 1;
+    if (first_bad(h, d_bad, bad)) return -2;
     if (bad != ~0ull) {
       const long long e = (long long)bad;
       return failmsg(h, me + ": bad arguments (the entry (b, i, j) = (" + std::to_string(e / nm) + ", " + std::to_string(e % nm / m) + ", " + std::to_string(e % m) +
@@ -1484,15 +1500,11 @@ int pf_assign_solve(pf_handle* h, int32_t mode, int32_t n, int32_t m, int32_t B,
       hipLaunchKernelGGL(k_assign_wave_per_problem, dim3((unsigned)(((long long)B + PF_ASSIGN_WAVES - 1) / PF_ASSIGN_WAVES)), dim3(64 * PF_ASSIGN_WAVES), 0, h->stream, d_mat,
                          (int)mode, (int)n, (int)m, (int)B, (int*)d_col, d_value, (int*)d_status, d_dual, info);
     } else {
-      const long long groups = (long long)(PF_ASSIGN_THREADS == 256 ? 8 : 2) * h->df_cus;
+      const long long groups = (long long)(PF_ASSIGN_THREADS == 256 ? 8 : 2) * ncu;
       hipLaunchKernelGGL(k_assign_group_per_problem<PF_ASSIGN_THREADS>, dim3((unsigned)std::min<long long>(B, groups)), dim3(PF_ASSIGN_THREADS), 0, h->stream, d_mat,
                          (int)mode, (int)n, (int)m, (int)B, (int*)d_col, d_value, (int*)d_status, d_dual, info);
     }
-    CK(hipGetLastError());
-    CK(hipEventRecord(h->ev1, h->stream));
-    CK(hipStreamSynchronize(h->stream));
-    CK(hipEventElapsedTime(&h->last_ms, h->ev0, h->ev1));
-    return 0;
+    return timed_end(h);
   };
   return run() ? -1 : 0;
 }
@@ -1517,60 +1529,41 @@ int pf_tour_improve(pf_handle* h, int32_t mode, int32_t n, int32_t B, int32_t sh
     if (mode < 0 || mode > 2) return failmsg(h, me + ": bad arguments (mode = " + std::to_string(mode) + ": 0 open, 1 return, 2 last)");
     if (n < 1 || n > PF_TOUR_SEARCH_MAX)
       return failmsg(h, me + ": bad arguments (n = " + std::to_string(n) + ": the number of nodes must lie in [1, " + std::to_string(PF_TOUR_SEARCH_MAX) + "])");
-    if (B < 1) return failmsg(h, me + ": bad arguments (B = " + std::to_string(B) + ": at least one start is needed)");
-    if (shared != 0 && shared != 1) return failmsg(h, me + ": bad arguments (shared = " + std::to_string(shared) + ": 0 a matrix per start, 1 one matrix for all)");
-    if (max_moves < 0 || max_moves > (1 << 20))
-      return failmsg(h, me + ": bad arguments (max_moves = " + std::to_string(max_moves) + " must lie in [0, 2^20])");
+    if (batch_args(h, me, B, "start", shared, max_moves)) return -2;
     if (!d_mat || !d_order || !d_value || !d_status) return failmsg(h, me + ": bad arguments (the matrices, the orders, the values and the statuses must not be null)");
     CK(hipSetDevice(h->device));
-    if (h->df_cus < 1) {
-      int cus = 0;
-      if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, h->device) != hipSuccess || cus < 1) cus = 256;
-      h->df_cus = cus;
-    }
+    const int ncu = cus(h);                                           // (asked before the timed span)
     const long long mats = shared ? 1 : (long long)B;
     // the block: {the first bad index, a spare word} in front, the matrices' "holds +inf" words behind
     if (scratch(h, me, h->d_widest, &h->widest_bytes, sizeof(unsigned long long) * 2 + sizeof(int) * (size_t)mats, "the entry index", false)) return -2;
     unsigned long long* const d_bad = (unsigned long long*)h->d_widest;
     int* const d_inf = (int*)(d_bad + 2);
     const long long nn = (long long)n * n, entries = nn * mats;
-    unsigned long long bad = ~0ull;
-    CK(hipMemcpyAsync(d_bad, &bad, sizeof(bad), hipMemcpyHostToDevice, h->stream));
-    CK(hipMemsetAsync(d_inf, 0, sizeof(int) * (size_t)mats, h->stream));
-    CK(hipStreamSynchronize(h->stream));
+    unsigned long long bad;
+    if (arm_bad(h, d_bad, d_inf, (size_t)mats)) return -2;
     CK(hipEventRecord(h->ev0, h->stream));
     // the entries, then the start rows, before any output is touched
     hipLaunchKernelGGL(k_tour_search_validate_entries, dim3((unsigned)std::min<long long>((entries + PF_TOUR_SEARCH_THREADS - 1) / PF_TOUR_SEARCH_THREADS, 2048)),
                        dim3(PF_TOUR_SEARCH_THREADS), 0, h->stream, d_mat, (int)n, entries, d_bad, d_inf);
-    CK(hipGetLastError());
-    CK(hipMemcpyAsync(&bad, d_bad, sizeof(bad), hipMemcpyDeviceToHost, h->stream));
-    CK(hipStreamSynchronize(h->stream));
-    h->d2h_small += 1;
+    if (first_bad(h, d_bad, bad)) return -2;
     if (bad != ~0ull) {
       const long long e = (long long)bad;
       return failmsg(h, me + ": bad arguments (the entry (b, i, j) = (" + std::to_string(e / nn) + ", " + std::to_string(e % nn / n) + ", " + std::to_string(e % n) +
                             ") is neither +inf nor a number in [0, 2^1000])");
     }
-    hipLaunchKernelGGL(k_tour_search_validate_orders, dim3((unsigned)std::min<long long>(B, 8ll * h->df_cus)), dim3(PF_TOUR_SEARCH_THREADS), 0, h->stream,
+    hipLaunchKernelGGL(k_tour_search_validate_orders, dim3((unsigned)std::min<long long>(B, 8ll * ncu)), dim3(PF_TOUR_SEARCH_THREADS), 0, h->stream,
                        (const int*)d_order, (int)mode, (int)n, (int)B, d_bad);
-    CK(hipGetLastError());
-    CK(hipMemcpyAsync(&bad, d_bad, sizeof(bad), hipMemcpyDeviceToHost, h->stream));
-    CK(hipStreamSynchronize(h->stream));
-    h->d2h_small += 1;
+    if (first_bad(h, d_bad, bad)) return -2;
     if (bad != ~0ull) {
       const long long e = (long long)bad;
       return failmsg(h, me + ": bad arguments (the start (b, position) = (" + std::to_string(e / n) + ", " + std::to_string(e % n) +
                             ") is no permutation of the nodes with node 0 first" + (mode == 2 ? " and node n - 1 last)" : ")"));
     }
     long long* const info = (long long*)d_info;
-    const long long groups = (long long)(32 * 64 / PF_TOUR_SEARCH_GROUP) * h->df_cus;               // what is resident at once
+    const long long groups = (long long)(32 * 64 / PF_TOUR_SEARCH_GROUP) * ncu;               // what is resident at once
     hipLaunchKernelGGL(k_tour_search_group_per_start, dim3((unsigned)std::min<long long>(B, groups)), dim3(PF_TOUR_SEARCH_GROUP), 0, h->stream, d_mat, (const int*)d_inf,
                        (int)mode, (int)n, (int)B, (int)shared, (int)max_moves, (int*)d_order, d_value, (int*)d_status, info);
-    CK(hipGetLastError());
-    CK(hipEventRecord(h->ev1, h->stream));
-    CK(hipStreamSynchronize(h->stream));
-    CK(hipEventElapsedTime(&h->last_ms, h->ev0, h->ev1));
-    return 0;
+    return timed_end(h);
   };
   return run() ? -1 : 0;
 }
@@ -1599,10 +1592,7 @@ static int fleet_call(pf_handle* h, const std::string& me, fleet_kernel kernel, 
     if ((long long)k + (long long)n > PF_FLEET_MAX)
       return failmsg(h, me + ": bad arguments (k + n = " + std::to_string((long long)k + (long long)n) + ": robots and tasks together must not exceed " +
                             std::to_string(PF_FLEET_MAX) + ")");
-    if (B < 1) return failmsg(h, me + ": bad arguments (B = " + std::to_string(B) + ": at least one start is needed)");
-    if (shared != 0 && shared != 1) return failmsg(h, me + ": bad arguments (shared = " + std::to_string(shared) + ": 0 a matrix per start, 1 one matrix for all)");
-    if (max_moves < 0 || max_moves > (1 << 20))
-      return failmsg(h, me + ": bad arguments (max_moves = " + std::to_string(max_moves) + " must lie in [0, 2^20])");
+    if (batch_args(h, me, B, "start", shared, max_moves)) return -2;
     if (!d_mat || !d_route || !d_len || !d_value || !d_status)
       return failmsg(h, me + ": bad arguments (the matrices, the routes, the lengths, the values and the statuses must not be null)");
     CK(hipSetDevice(h->device));
@@ -1615,41 +1605,28 @@ static int fleet_call(pf_handle* h, const std::string& me, fleet_kernel kernel, 
       for (int r = 0; r < k; ++r)
         if (cap[(size_t)r] < 0) return failmsg(h, me + ": bad arguments (cap[" + std::to_string(r) + "] = " + std::to_string(cap[(size_t)r]) + " is negative)");
     }
-    if (h->df_cus < 1) {
-      int cus = 0;
-      if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, h->device) != hipSuccess || cus < 1) cus = 256;
-      h->df_cus = cus;
-    }
+    const int ncu = cus(h);                                           // (asked before the timed span)
     const long long mats = shared ? 1 : (long long)B;
     // the block: {the first bad index, a spare word} in front, the matrices' "holds +inf" words behind
     if (scratch(h, me, h->d_widest, &h->widest_bytes, sizeof(unsigned long long) * 2 + sizeof(int) * (size_t)mats, "the entry index", false)) return -2;
     unsigned long long* const d_bad = (unsigned long long*)h->d_widest;
     int* const d_inf = (int*)(d_bad + 2);
     const long long nn = (long long)N * N, entries = nn * mats;
-    unsigned long long bad = ~0ull;
-    CK(hipMemcpyAsync(d_bad, &bad, sizeof(bad), hipMemcpyHostToDevice, h->stream));
-    CK(hipMemsetAsync(d_inf, 0, sizeof(int) * (size_t)mats, h->stream));
-    CK(hipStreamSynchronize(h->stream));
+    unsigned long long bad;
+    if (arm_bad(h, d_bad, d_inf, (size_t)mats)) return -2;
     CK(hipEventRecord(h->ev0, h->stream));
     // the entries, then the start rows, then the capacities, before any output is touched
-    auto first_bad = [&]() -> int {
-      CK(hipGetLastError());
-      CK(hipMemcpyAsync(&bad, d_bad, sizeof(bad), hipMemcpyDeviceToHost, h->stream));
-      CK(hipStreamSynchronize(h->stream));
-      h->d2h_small += 1;
-      return 0;
-    };
-    const dim3 rows_grid((unsigned)std::min<long long>(B, 8ll * h->df_cus));
+    const dim3 rows_grid((unsigned)std::min<long long>(B, 8ll * ncu));
     hipLaunchKernelGGL(k_fleet_validate_entries, dim3((unsigned)std::min<long long>((entries + PF_FLEET_THREADS - 1) / PF_FLEET_THREADS, 2048)), dim3(PF_FLEET_THREADS), 0,
                        h->stream, d_mat, (int)k, N, entries, d_bad, d_inf);
-    if (first_bad()) return -1;
+    if (first_bad(h, d_bad, bad)) return -2;
     if (bad != ~0ull) {
       const long long e = (long long)bad;
       return failmsg(h, me + ": bad arguments (the entry (b, i, j) = (" + std::to_string(e / nn) + ", " + std::to_string(e % nn / N) + ", " + std::to_string(e % N) +
                             ") is neither +inf nor a number in [0, 2^1000])");
     }
     hipLaunchKernelGGL(k_fleet_validate_rows, rows_grid, dim3(PF_FLEET_THREADS), 0, h->stream, (const int*)d_route, (int)k, N, (int)B, d_bad);
-    if (first_bad()) return -1;
+    if (first_bad(h, d_bad, bad)) return -2;
     if (bad != ~0ull) {
       const long long e = (long long)bad;
       return failmsg(h, me + ": bad arguments (the start (b, position) = (" + std::to_string(e / N) + ", " + std::to_string(e % N) +
@@ -1657,21 +1634,17 @@ static int fleet_call(pf_handle* h, const std::string& me, fleet_kernel kernel, 
     }
     if (d_cap) {
       hipLaunchKernelGGL(k_fleet_validate_caps, rows_grid, dim3(PF_FLEET_THREADS), 0, h->stream, (const int*)d_route, (const int*)d_cap, (int)k, N, (int)B, d_bad);
-      if (first_bad()) return -1;
+      if (first_bad(h, d_bad, bad)) return -2;
       if (bad != ~0ull) {
         const long long e = (long long)bad;
         return failmsg(h, me + ": bad arguments (the start (b, robot) = (" + std::to_string(e / k) + ", " + std::to_string(e % k) + ") holds more tasks than its capacity)");
       }
     }
     long long* const info = (long long*)d_info;
-    const long long groups = (long long)(32 * 64 / PF_FLEET_GROUP) * h->df_cus;                    // what is resident at once
+    const long long groups = (long long)(32 * 64 / PF_FLEET_GROUP) * ncu;                    // what is resident at once
     hipLaunchKernelGGL(kernel, dim3((unsigned)std::min<long long>(B, groups)), dim3(PF_FLEET_GROUP), 0, h->stream, d_mat, (const int*)d_inf, (const int*)d_cap, (int)mode,
                        (int)k, N, (int)B, (int)shared, (int)max_moves, (int*)d_route, d_len, d_value, (int*)d_status, info);
-    CK(hipGetLastError());
-    CK(hipEventRecord(h->ev1, h->stream));
-    CK(hipStreamSynchronize(h->stream));
-    CK(hipEventElapsedTime(&h->last_ms, h->ev0, h->ev1));
-    return 0;
+    return timed_end(h);
   };
   return run() ? -1 : 0;
 }
@@ -1713,35 +1686,20 @@ int pf_place_improve(pf_handle* h, int32_t mode, int32_t m, int32_t n, int32_t p
     if (p < 1 || p > std::min<int>(m, PF_PLACE_OPEN_MAX))
       return failmsg(h, me + ": bad arguments (p = " + std::to_string(p) + ": the number of slots must lie in [1, min(m, " + std::to_string(PF_PLACE_OPEN_MAX) + ")])");
     if (fixed < 0 || fixed > p) return failmsg(h, me + ": bad arguments (fixed = " + std::to_string(fixed) + " must lie in [0, p])");
-    if (B < 1) return failmsg(h, me + ": bad arguments (B = " + std::to_string(B) + ": at least one start is needed)");
-    if (shared != 0 && shared != 1) return failmsg(h, me + ": bad arguments (shared = " + std::to_string(shared) + ": 0 a matrix per start, 1 one matrix for all)");
-    if (max_moves < 0 || max_moves > (1 << 20))
-      return failmsg(h, me + ": bad arguments (max_moves = " + std::to_string(max_moves) + " must lie in [0, 2^20])");
+    if (batch_args(h, me, B, "start", shared, max_moves)) return -2;
     if (!d_mat || !d_sel || !d_value || !d_status) return failmsg(h, me + ": bad arguments (the matrices, the rows, the values and the statuses must not be null)");
     CK(hipSetDevice(h->device));
-    if (h->df_cus < 1) {
-      int cus = 0;
-      if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, h->device) != hipSuccess || cus < 1) cus = 256;
-      h->df_cus = cus;
-    }
+    const int ncu = cus(h);                                           // (asked before the timed span)
     if (scratch(h, me, h->d_widest, &h->widest_bytes, sizeof(unsigned long long) * 2, "the entry index", false)) return -2;
     unsigned long long* const d_bad = (unsigned long long*)h->d_widest;
     const long long mn = (long long)m * n, entries = mn * (shared ? 1 : (long long)B), slots = (long long)B * p;
-    unsigned long long bad = ~0ull;
-    CK(hipMemcpyAsync(d_bad, &bad, sizeof(bad), hipMemcpyHostToDevice, h->stream));
-    CK(hipStreamSynchronize(h->stream));
+    unsigned long long bad;
+    if (arm_bad(h, d_bad)) return -2;
     CK(hipEventRecord(h->ev0, h->stream));
     // the entries, then the rows, before any output is touched
-    auto first_bad = [&]() -> int {
-      CK(hipGetLastError());
-      CK(hipMemcpyAsync(&bad, d_bad, sizeof(bad), hipMemcpyDeviceToHost, h->stream));
-      CK(hipStreamSynchronize(h->stream));
-      h->d2h_small += 1;
-      return 0;
-    };
     hipLaunchKernelGGL(k_place_validate_entries, dim3((unsigned)std::min<long long>((entries + PF_PLACE_THREADS - 1) / PF_PLACE_THREADS, 2048)), dim3(PF_PLACE_THREADS), 0,
                        h->stream, d_mat, entries, d_bad);
-    if (first_bad()) return -1;
+    if (first_bad(h, d_bad, bad)) return -2;
     if (bad != ~0ull) {
       const long long e = (long long)bad;
       return failmsg(h, me + ": bad arguments (the entry (b, i, j) = (" + std::to_string(e / mn) + ", " + std::to_string(e % mn / n) + ", " + std::to_string(e % n) +
@@ -1749,7 +1707,7 @@ int pf_place_improve(pf_handle* h, int32_t mode, int32_t m, int32_t n, int32_t p
     }
     hipLaunchKernelGGL(k_place_validate_rows, dim3((unsigned)std::min<long long>((slots + PF_PLACE_THREADS - 1) / PF_PLACE_THREADS, 2048)), dim3(PF_PLACE_THREADS), 0,
                        h->stream, (const int*)d_sel, (int)m, (int)p, (int)fixed, slots, d_bad);
-    if (first_bad()) return -1;
+    if (first_bad(h, d_bad, bad)) return -2;
     if (bad != ~0ull) {
       const long long e = (long long)bad;
       return failmsg(h, me + ": bad arguments (the row (b, slot) = (" + std::to_string(e / p) + ", " + std::to_string(e % p) +
@@ -1757,13 +1715,9 @@ int pf_place_improve(pf_handle* h, int32_t mode, int32_t m, int32_t n, int32_t p
     }
     const size_t lds = (size_t)n * (2 * sizeof(double) + 1);          // d1, d2 and n1 per demand
     CK(hipFuncSetAttribute((const void*)k_place_group_per_start, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    hipLaunchKernelGGL(k_place_group_per_start, dim3((unsigned)std::min<long long>(B, 2ll * h->df_cus)), dim3(PF_PLACE_GROUP), lds, h->stream, d_mat, (int)mode, (int)m,
+    hipLaunchKernelGGL(k_place_group_per_start, dim3((unsigned)std::min<long long>(B, 2ll * ncu)), dim3(PF_PLACE_GROUP), lds, h->stream, d_mat, (int)mode, (int)m,
                        (int)n, (int)p, (int)fixed, (int)B, (int)shared, (int)max_moves, (int*)d_sel, (int*)d_owner, d_value, (int*)d_status, (long long*)d_info);
-    CK(hipGetLastError());
-    CK(hipEventRecord(h->ev1, h->stream));
-    CK(hipStreamSynchronize(h->stream));
-    CK(hipEventElapsedTime(&h->last_ms, h->ev0, h->ev1));
-    return 0;
+    return timed_end(h);
   };
   return run() ? -1 : 0;
 }
@@ -1802,17 +1756,13 @@ int pf_cover_pack(pf_handle* h, int32_t kind, int32_t K, int32_t n, const void* 
     CK(hipSetDevice(h->device));
     if (scratch(h, me, h->d_widest, &h->widest_bytes, sizeof(unsigned long long) * 2, "the target index", false)) return -2;
     unsigned long long* const d_bad = (unsigned long long*)h->d_widest;
-    unsigned long long bad = ~0ull;
-    CK(hipMemcpyAsync(d_bad, &bad, sizeof(bad), hipMemcpyHostToDevice, h->stream));
-    CK(hipStreamSynchronize(h->stream));
+    unsigned long long bad;
+    if (arm_bad(h, d_bad)) return -2;
     CK(hipEventRecord(h->ev0, h->stream));
     // the targets, before any source entry is read
     hipLaunchKernelGGL(k_cover_validate_targets, dim3((unsigned)std::min<long long>(((long long)n + PF_COVER_THREADS - 1) / PF_COVER_THREADS, 2048)), dim3(PF_COVER_THREADS), 0,
                        h->stream, (const int*)d_targets, (int)n, (int)ld, d_bad);
-    CK(hipGetLastError());
-    CK(hipMemcpyAsync(&bad, d_bad, sizeof(bad), hipMemcpyDeviceToHost, h->stream));
-    CK(hipStreamSynchronize(h->stream));
-    h->d2h_small += 1;
+    if (first_bad(h, d_bad, bad)) return -2;
     if (bad != ~0ull) return failmsg(h, me + ": bad arguments (target " + std::to_string((long long)bad) + " lies outside [0, ld))");
     const int W = (n + 63) / 64, per = PF_COVER_THREADS / 64;
     const dim3 grid((unsigned)((W + per - 1) / per), (unsigned)K);
@@ -1822,11 +1772,7 @@ int pf_cover_pack(pf_handle* h, int32_t kind, int32_t K, int32_t n, const void* 
     else
       hipLaunchKernelGGL(k_cover_pack<1>, grid, dim3(PF_COVER_THREADS), 0, h->stream, d_src, (const int*)d_targets, (int)n, (int)ld, radius, (int)row0,
                          (unsigned long long*)d_mask);
-    CK(hipGetLastError());
-    CK(hipEventRecord(h->ev1, h->stream));
-    CK(hipStreamSynchronize(h->stream));
-    CK(hipEventElapsedTime(&h->last_ms, h->ev0, h->ev1));
-    return 0;
+    return timed_end(h);
   };
   return run() ? -1 : 0;
 }
@@ -1843,47 +1789,31 @@ int pf_cover_improve(pf_handle* h, int32_t m, int32_t n, int32_t p, int32_t fixe
     if (p < 1 || p > std::min<int>(m, PF_COVER_OPEN_MAX))
       return failmsg(h, me + ": bad arguments (p = " + std::to_string(p) + ": the number of slots must lie in [1, min(m, " + std::to_string(PF_COVER_OPEN_MAX) + ")])");
     if (fixed < 0 || fixed > p) return failmsg(h, me + ": bad arguments (fixed = " + std::to_string(fixed) + " must lie in [0, p])");
-    if (B < 1) return failmsg(h, me + ": bad arguments (B = " + std::to_string(B) + ": at least one start is needed)");
-    if (shared != 0 && shared != 1) return failmsg(h, me + ": bad arguments (shared = " + std::to_string(shared) + ": 0 a mask set per start, 1 one mask set for all)");
-    if (max_moves < 0 || max_moves > (1 << 20))
-      return failmsg(h, me + ": bad arguments (max_moves = " + std::to_string(max_moves) + " must lie in [0, 2^20])");
+    if (batch_args(h, me, B, "start", shared, max_moves, "mask set")) return -2;
     if (!d_mask || !d_sel || !d_value || !d_status) return failmsg(h, me + ": bad arguments (the masks, the rows, the values and the statuses must not be null)");
     CK(hipSetDevice(h->device));
-    if (h->df_cus < 1) {
-      int cus = 0;
-      if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, h->device) != hipSuccess || cus < 1) cus = 256;
-      h->df_cus = cus;
-    }
     const int W = (n + 63) / 64;
     const bool lds = W <= PF_COVER_LDS_WORDS;
     // two workgroups a CU in the LDS form; the HBM form's registers leave room for one, so a second half of the grid would only queue
-    const long long G = std::min<long long>(B, (lds ? 2ll : 1ll) * h->df_cus);
+    const long long G = std::min<long long>(B, (lds ? 2ll : 1ll) * cus(h));
     const size_t plane_bytes = lds ? 0 : sizeof(unsigned long long) * 2 * (size_t)W * (size_t)G;
     if (scratch(h, me, h->d_widest, &h->widest_bytes, sizeof(unsigned long long) * 2 + plane_bytes, "the planes", true)) return -2;
     unsigned long long* const d_bad = (unsigned long long*)h->d_widest;
     const long long rows = (long long)m * (shared ? 1 : (long long)B), slots = (long long)B * p;
-    unsigned long long bad = ~0ull;
-    CK(hipMemcpyAsync(d_bad, &bad, sizeof(bad), hipMemcpyHostToDevice, h->stream));
-    CK(hipStreamSynchronize(h->stream));
+    unsigned long long bad;
+    if (arm_bad(h, d_bad)) return -2;
     CK(hipEventRecord(h->ev0, h->stream));
     // the tail bits, then the rows, before any output is touched
-    auto first_bad = [&]() -> int {
-      CK(hipGetLastError());
-      CK(hipMemcpyAsync(&bad, d_bad, sizeof(bad), hipMemcpyDeviceToHost, h->stream));
-      CK(hipStreamSynchronize(h->stream));
-      h->d2h_small += 1;
-      return 0;
-    };
     hipLaunchKernelGGL(k_cover_validate_tail, dim3((unsigned)std::min<long long>((rows + PF_COVER_THREADS - 1) / PF_COVER_THREADS, 2048)), dim3(PF_COVER_THREADS), 0,
                        h->stream, (const unsigned long long*)d_mask, (int)n, W, rows, d_bad);
-    if (first_bad()) return -1;
+    if (first_bad(h, d_bad, bad)) return -2;
     if (bad != ~0ull) {
       const long long e = (long long)bad;
       return failmsg(h, me + ": bad arguments (the mask (b, i) = (" + std::to_string(e / m) + ", " + std::to_string(e % m) + ") holds a bit at an element >= n)");
     }
     hipLaunchKernelGGL(k_place_validate_rows, dim3((unsigned)std::min<long long>((slots + PF_PLACE_THREADS - 1) / PF_PLACE_THREADS, 2048)), dim3(PF_PLACE_THREADS), 0,
                        h->stream, (const int*)d_sel, (int)m, (int)p, (int)fixed, slots, d_bad);
-    if (first_bad()) return -1;
+    if (first_bad(h, d_bad, bad)) return -2;
     if (bad != ~0ull) {
       const long long e = (long long)bad;
       return failmsg(h, me + ": bad arguments (the row (b, slot) = (" + std::to_string(e / p) + ", " + std::to_string(e % p) +
@@ -1901,11 +1831,7 @@ int pf_cover_improve(pf_handle* h, int32_t m, int32_t n, int32_t p, int32_t fixe
                          (int)fixed, (int)B, (int)shared, (int)max_moves, (int*)d_sel, (unsigned long long*)d_covered, (long long*)d_value, (int*)d_status,
                          (long long*)d_info, d_bad + 2);
     }
-    CK(hipGetLastError());
-    CK(hipEventRecord(h->ev1, h->stream));
-    CK(hipStreamSynchronize(h->stream));
-    CK(hipEventElapsedTime(&h->last_ms, h->ev0, h->ev1));
-    return 0;
+    return timed_end(h);
   };
   return run() ? -1 : 0;
 }

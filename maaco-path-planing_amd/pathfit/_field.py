@@ -1,6 +1,9 @@
-"""What the field classes share (DistanceField, NearestSourceField, CostField, TurnField, PathSmoother, Components, Clearance, Visibility, SpaceTime, Tour, Assignment, TourSearch, FleetTours, Placement, Coverage): the constructor's grid
-and engine checks, the (r, c) -> cell id parser with its two messages, the index check and the close / __del__ pair.  Every message
-starts with the class name; all checks run before the device is touched."""
+"""What the field classes share (DistanceField, NearestSourceField, CostField, TurnField, PathSmoother, Components, Clearance,
+Visibility, SpaceTime, and through Planner the six planners Tour, Assignment, TourSearch, FleetTours, Placement, Coverage): the
+constructor's grid and engine checks, the (r, c) -> cell id parser with its two messages, the index check and the close / __del__
+pair.  Every message starts with the class name; all checks run before the device is touched.  What only the planners share -- the
+device state around their fields, the chunk loop, the route tracer, refresh, the restart driver and the checks of their
+solve_matrices -- is _planner.py's."""
 import numpy as np
 
 

@@ -9,15 +9,11 @@ import collections
 
 import numpy as np
 
-from ._field import Field
-from ._lib import PathfitError
-from .cost_field import checked_cost
+from ._planner import BIG, Planner, as_matrices, chunk_rows, no_bad_entry  # noqa: F401  (chunk_rows and BIG are imported from here)
 from .engine import Engine
-from .paths import CellPath
 
 OBJECTIVES = {"sum": 0, "max": 1, "max_sum": 2}
 SIDE_MAX = 1024                                                      # PF_ASSIGN_MAX: the solver's columns
-BIG = 2.0 ** 1000
 
 Solved = collections.namedtuple("Solved", "task_of robot_of value status dual info")
 
@@ -26,11 +22,6 @@ def _mode(who, objective):
     if not isinstance(objective, str) or objective not in OBJECTIVES:
         raise ValueError(f"{who}: objective must be 'sum', 'max' or 'max_sum', got {objective!r}")
     return OBJECTIVES[objective]
-
-
-def chunk_rows(n_rows, cells, budget):
-    """How many field rows of `cells` doubles are computed at once: as many as fit `budget` bytes, at least one, at most n_rows."""
-    return int(max(1, min(int(n_rows), int(budget) // (8 * int(cells)))))
 
 
 def both_sides(col, n_cols):
@@ -58,7 +49,7 @@ def pairing_cost(matrix, task_of, by_task):
     return s, max(xs)
 
 
-class Assignment(Field):
+class Assignment(Planner):
     """robots, tasks: (r, c) pairs, at most 1024 of each.  objective: "sum", "max" or "max_sum".  cost: None (path lengths,
     pf_dist_field_batch) or an [R, C] cost map as CostField's (pf_cost_field).
 
@@ -67,8 +58,7 @@ class Assignment(Field):
     side cannot be matched completely (task_of and robot_of are then all -1).  duals: float64, the solver's u then v (its rows are
     the robots, or the tasks when robots outnumber tasks); info: int64 [4] = (tree steps of the sum phase, of the max phase, the
     first solver row that could not be placed or -1, 0).  matrix: float64 [robots, tasks], downloaded on first use."""
-    _bufs = ("buf", "pbuf", "mbuf", "cost_device")
-    CHUNK_BYTES = 256 << 20
+    _closed, _built = "the assignment is closed", "an assignment"
 
     def __init__(self, grid, robots, tasks, objective="sum", cost=None, allow_diagonal_moves=True, restrict_diagonal_near_obstacle=True, engine=None):
         who = type(self).__name__
@@ -85,43 +75,16 @@ class Assignment(Field):
                 raise ValueError(f"{who}: {k} {what}; at most {SIDE_MAX} are matched")
         self.robots = [(int(v) // self.cols, int(v) % self.cols) for v in self.robot_ids]
         self.tasks = [(int(v) // self.cols, int(v) % self.cols) for v in self.task_ids]
-        self.cost = None if cost is None else checked_cost(who, self.grid, cost)
-        self.allow_diagonal_moves = bool(allow_diagonal_moves)
-        self.restrict_diagonal_near_obstacle = bool(restrict_diagonal_near_obstacle)
+        self._set_cost_and_moves(cost, allow_diagonal_moves, restrict_diagonal_near_obstacle)
         self.transposed = self.nr > self.nt                           # the solver's rows are the tasks
         self.n, self.m = (self.nt, self.nr) if self.transposed else (self.nr, self.nt)
-        self.chunk = chunk_rows(self.nr, self.rows * self.cols, self.CHUNK_BYTES)
-        self._set_engine(engine, Engine)                             # every argument is checked: the device
-        e = self.engine
-        self.cost_device = None if self.cost is None else e.put(self.cost.reshape(-1), np.float64)
-        self.buf = e.buf((self.chunk, self.rows, self.cols), np.float64)
+        e = self._open(engine, Engine, self.robot_ids)                             # every argument is checked: the device
         self.mbuf = e.buf((self.n, self.m), np.float64)
-        self.pbuf = None
         self._compute()
-
-    def _check_open(self):
-        if self.buf is None or not getattr(self.engine, "h", None):
-            raise PathfitError(f"{type(self).__name__}: the assignment is closed")
-
-    def _fields(self, r0):
-        """The fields of robots r0 .. r0 + k - 1 into buf (k = the chunk's rows) -> k."""
-        e, k = self.engine, min(self.chunk, self.nr - r0)
-        ids = self.robot_ids[r0:r0 + k]
-        if self.cost_device is None:
-            e.dist_field_batch(ids, self.buf, self.allow_diagonal_moves, self.restrict_diagonal_near_obstacle)
-        else:
-            e.cost_field(self.cost_device, np.arange(k + 1, dtype=np.int32), ids, self.buf, self.allow_diagonal_moves, self.restrict_diagonal_near_obstacle)
-        self._held = r0
-        return k
 
     def _compute(self):
         e = self.engine
-        ms = 0.0
-        for r0 in range(0, self.nr, self.chunk):
-            k = self._fields(r0)
-            ms += e.last_kernel_ms()
-            e.assign_matrix(k, self.task_ids, self.buf, self.mbuf, r0, self.m, self.transposed)
-            ms += e.last_kernel_ms()
+        ms = self._gather(lambda k, r0: e.assign_matrix(k, self.task_ids, self.buf, self.mbuf, r0, self.m, self.transposed))
         n, m = self.n, self.m
         dc, dv, ds, dd, di = e.buf(n, np.int32), e.buf(2, np.float64), e.buf(1, np.int32), e.buf(n + m, np.float64), e.buf(4, np.int64)
         try:
@@ -172,82 +135,9 @@ class Assignment(Field):
         return [self.robots[i] for i in on], [self.tasks[int(self.task_of[i])] for i in on]
 
     def paths(self):
-        """One CellPath per matched robot in robot order, from the robot to its task; [] where nothing is matched.  Each is
-        DistanceField.paths' route cell for cell: a parent-map call over a chunk of the fields and one trace call with a field
-        index per query.  A chunk of fields that was released for a later one is computed again."""
+        """One CellPath per matched robot in robot order, from the robot to its task; [] where nothing is matched (Planner._trace)."""
         self._check_open()
-        on = [i for i in range(self.nr) if self.task_of[i] >= 0]
-        if not on:
-            return []
-        e, full = self.engine, self.rows * self.cols
-        ad, rs = self.allow_diagonal_moves, self.restrict_diagonal_near_obstacle
-        out = {}
-        for r0 in range(0, self.nr, self.chunk):
-            mine = [i for i in on if r0 <= i < r0 + self.chunk]
-            if not mine:
-                continue
-            k = min(self.chunk, self.nr - r0)
-            if self._held != r0:
-                self._fields(r0)
-                if self.pbuf is not None:
-                    self.pbuf.free()
-                    self.pbuf = None
-            if self.pbuf is None:
-                pbuf = e.buf((self.chunk, self.rows, self.cols), np.uint8)
-                try:
-                    if self.cost_device is None:
-                        e.dist_field_parents(k, self.buf, pbuf, ad, rs)
-                    else:
-                        e.cost_field_parents(self.cost_device, k, self.buf, pbuf, ad, rs)
-                except Exception:
-                    pbuf.free()
-                    raise
-                self.pbuf = pbuf
-            q = len(mine)
-            dk = e.put(np.array([i - r0 for i in mine], np.int32))
-            dt = e.put(self.task_ids[self.task_of[np.array(mine)]].astype(np.int32))
-            dl, dst = e.buf(q, np.int32), e.buf(q, np.int32)
-            dcl, cap = None, e.default_path_cap()
-            try:
-                while True:
-                    dcl = e.buf((q, cap), np.int32)
-                    e.dist_field_paths(k, self.pbuf, dt, q, cap, dcl, dl, dst, dk, self.buf, False, None)
-                    st = dst.download()
-                    if cap >= full or not (st == 3).any():
-                        break
-                    dcl.free()
-                    dcl, cap = None, full
-                if (st == 3).any():
-                    raise PathfitError(f"{type(self).__name__}: {int((st == 3).sum())} routes hold more than {cap} cells")
-                lens, cells = dl.download(), dcl.download().reshape(q, cap)
-                for x, i in enumerate(mine):
-                    out[i] = CellPath(cells[x, :lens[x]].copy(), self.cols)
-            finally:
-                for b in (dk, dt, dl, dst, dcl):
-                    if b is not None:
-                        b.free()
-        return [out[i] for i in on]
-
-    def refresh(self, cost=None):
-        """Compute the assignment again on the map the engine holds now (after engine.update_grid) and, when given, under a new
-        cost map (for an assignment built with one)."""
-        who = type(self).__name__
-        self._check_open()
-        if cost is not None and self.cost is None:
-            raise ValueError(f"{who}: refresh(cost) needs an assignment built with a cost map")
-        held = getattr(self.engine, "grid_u8", None)
-        grid = np.array(held, dtype=int) if held is not None else self.grid
-        if self.cost is not None:
-            new = checked_cost(who, grid, self.cost if cost is None else cost)
-            if cost is not None:
-                self.cost = new
-                self.cost_device.upload(new.reshape(-1))
-        self.grid = grid
-        if self.pbuf is not None:
-            self.pbuf.free()
-            self.pbuf = None
-        self._compute()
-        return self
+        return self._trace([(i, int(self.task_ids[self.task_of[i]])) for i in range(self.nr) if self.task_of[i] >= 0], "routes")
 
     @classmethod
     def solve_matrices(cls, matrices, objective="sum", engine=None):
@@ -257,22 +147,12 @@ class Assignment(Field):
         transposed on the host: the solver's rows are then the columns given.  engine: any Engine (None: one of the call's own)."""
         who = cls.__name__
         mode = _mode(who, objective)
-        try:
-            a = np.ascontiguousarray(matrices, np.float64)
-        except (TypeError, ValueError):
-            raise ValueError(f"{who}: matrices must be a [B, n, m] array of numbers") from None
-        if a.ndim == 2:
-            a = a[None]
-        if a.ndim != 3 or min(a.shape) < 1:
-            raise ValueError(f"{who}: matrices has shape {a.shape}, not [B, n, m] with B, n, m >= 1")
+        a = as_matrices(who, "matrices", matrices, "n", "m")
         B, rows, cols = (int(v) for v in a.shape)
         if max(rows, cols) > SIDE_MAX:
             raise ValueError(f"{who}: matrices of {rows} x {cols}; at most {SIDE_MAX} rows and columns are matched")
         with np.errstate(invalid="ignore"):
-            bad = np.argwhere(~((a == np.inf) | (np.abs(a) <= BIG)))  # (NaN fails both)
-        if len(bad):
-            b, i, j = (int(v) for v in bad[0])
-            raise ValueError(f"{who}: matrices[{b}, {i}, {j}] = {float(a[b, i, j])!r} is neither +inf nor finite within 2^1000")
+            no_bad_entry(who, "matrices", a, ~((a == np.inf) | (np.abs(a) <= BIG)), "neither +inf nor finite within 2^1000")   # (NaN fails both)
         flip = rows > cols
         if flip:
             a = np.ascontiguousarray(a.transpose(0, 2, 1))

@@ -13,16 +13,14 @@ import math
 
 import numpy as np
 
-from ._field import Field
 from ._lib import PathfitError
-from .assignment import Assignment, chunk_rows
-from .cost_field import checked_cost
+from ._planner import OPEN_MAX, SITES_MAX, Planner, _int_in, chunk_rows, improve_call, move_limit, one_if_shared, restarts  # noqa: F401
+from ._planner import slot_count, slot_rows, start_rows
+from ._planner import slot_perturbations as perturbations
 from .engine import Engine
-from .placement import perturbations
-from .tour_search import MOVES_MAX, STARTS_MAX, _int_in
 from .visibility import range_to_sq
 
-SITES_MAX, ELEMS_MAX, OPEN_MAX = 1024, 1 << 20, 64                   # PF_COVER_SITES_MAX, PF_COVER_ELEMS_MAX, PF_COVER_OPEN_MAX
+ELEMS_MAX = 1 << 20                                                  # PF_COVER_ELEMS_MAX
 KINDS = {"sight": 0, "reach": 1}
 
 Improved = collections.namedtuple("Improved", "row covered value status info")
@@ -53,62 +51,34 @@ def key_of(n, covered, open_sites):
 
 
 def _shape_check(who, m, n, p):
-    if m < 1:
-        raise ValueError(f"{who}: sites is empty")
-    if n < 1:
-        raise ValueError(f"{who}: targets is empty")
-    if m > SITES_MAX:
-        raise ValueError(f"{who}: {m} sites; at most {SITES_MAX} are searched")
-    if n > ELEMS_MAX:
-        raise ValueError(f"{who}: {n} targets; at most {ELEMS_MAX} are covered")
-    if not isinstance(p, (int, np.integer)) or isinstance(p, bool) or not 1 <= int(p) <= min(m, OPEN_MAX):
-        raise ValueError(f"{who}: count must be an integer in [1, {min(m, OPEN_MAX)}] (at most the sites, at most {OPEN_MAX}), got {p!r}")
-    return int(p)
+    return slot_count(who, m, n, p, "targets", ELEMS_MAX, "covered")
 
 
 def _improve(e, m, n, fixed, dm, shared, rows, limit):
     """One pf_cover_improve call over the start rows [B, p] -> (Improved, kernel ms)."""
-    rows = np.ascontiguousarray(rows, np.int32)
-    B, p = rows.shape
-    W = words_of(n)
-    ds = e.put(rows.reshape(-1), np.int32)
-    dc, dv, dst, di = e.buf((B, W), np.uint64), e.buf((B, 4), np.int64), e.buf(B, np.int32), e.buf((B, 4), np.int64)
-    try:
-        e.cover_improve(m, n, p, fixed, B, shared, dm, limit, ds, dc, dv, dst, di)
-        ms = e.last_kernel_ms()
-        return Improved(ds.download().reshape(B, p).astype(np.int32), dc.download().reshape(B, W), dv.download().reshape(B, 4), dst.download().reshape(B),
-                        di.download().reshape(B, 4)), ms
-    finally:
-        for b in (ds, dc, dv, dst, di):
-            b.free()
+    B, p = np.shape(rows)
+    return improve_call(e, Improved, rows, (((B, words_of(n)), np.uint64), ((B, 4), np.int64), (B, np.int32), ((B, 4), np.int64)),
+                        lambda ds, dc, dv, dst, di: e.cover_improve(m, n, p, fixed, B, shared, dm, limit, ds, dc, dv, dst, di))
 
 
 def search(e, m, n, p, keep, dm, starts, rounds, seed, limit):
     """The search over the masks dm holds -> dict(row, covered, count, open, unique, history, moves, drops, kernel_ms).  Round 0
     improves [keep..., -1, ...]; each later round improves `starts` perturbations of the incumbent (Placement's stream) in one call
-    and keeps the strictly smallest key at the smallest start index.  With every slot kept there are no later rounds."""
+    and keeps the strictly smallest key at the smallest start index (restarts).  With every slot kept there are no later rounds."""
     f = len(keep)
-    got, ms = _improve(e, m, n, f, dm, True, [[int(v) for v in keep] + [-1] * (p - f)], limit)
+    tried = []                                                        # every call's Improved: the drops are summed over all starts
 
-    def key(g, x):
-        return key_of(n, g.value[x, 0], g.value[x, 1])
-    best, row, covered, value, unique = key(got, 0), got.row[0], got.covered[0], got.value[0], int(got.info[0, 2])
-    history, moves, drops = [best], int(got.info[0, 0]), int(got.info[0, 3])
-    rng = np.random.default_rng(seed)
-    for _ in range(rounds if p > f else 0):
-        got, t = _improve(e, m, n, f, dm, True, perturbations(rng, row, f, m, starts), limit)
-        ms += t
-        moves += int(got.info[:, 0].sum())
-        drops += int(got.info[:, 3].sum())
-        keys = [key(got, x) for x in range(len(got.row))]
-        x = keys.index(min(keys))                                     # (the first smallest)
-        if keys[x] < best:
-            best, row, covered, value, unique = keys[x], got.row[x], got.covered[x], got.value[x], int(got.info[x, 2])
-        history.append(best)
-    return dict(row=row, covered=covered, count=int(value[0]), open=int(value[1]), unique=unique, history=history, moves=moves, drops=drops, kernel_ms=ms)
+    def improve(rows):
+        tried.append(_improve(e, m, n, f, dm, True, rows, limit))
+        return tried[-1]
+    got, ms = improve([[int(v) for v in keep] + [-1] * (p - f)])
+    got, x, history, moves, t = restarts(got, rounds if p > f else 0, seed, lambda rng, row: perturbations(rng, row, f, m, starts), improve,
+                                         lambda g, b: key_of(n, g.value[b, 0], g.value[b, 1]))
+    return dict(row=got.row[x], covered=got.covered[x], count=int(got.value[x, 0]), open=int(got.value[x, 1]), unique=int(got.info[x, 2]), history=history,
+                moves=moves, drops=sum(int(g.info[:, 3].sum()) for g, _ in tried), kernel_ms=ms + t)
 
 
-class Coverage(Field):
+class Coverage(Planner):
     """sites: (r, c) pairs, at most 1024 candidate cells.  count: the slots p, at most min(len(sites), 64) (None: that); it includes
     `keep`, indices into `sites` that are open whatever happens.  targets: (r, c) pairs, at most 2^20 (None: every free cell in
     cell-id order; a target listed twice counts twice).  by: "sight" -- Visibility's rule from the site cells, max_range as
@@ -123,7 +93,7 @@ class Coverage(Field):
     unique: per open site, the targets only it covers.  history: the key (not covered, open) after round 0, 1, ...; moves, drops:
     over all starts.  The packed masks stay in HBM (mask_device uint64 [m, ceil(n / 64)]); `masks` downloads them when asked."""
     _bufs = ("buf", "mask_device", "target_device", "cost_device")
-    CHUNK_BYTES = Assignment.CHUNK_BYTES
+    _closed, _built = "the coverage is closed", "a coverage"
 
     def __init__(self, grid, sites, count=None, targets=None, by="sight", max_range=None, radius=None, restrict_diagonal_near_obstacle=True, cost=None, keep=(),
                  starts=8, rounds=3, seed=0, max_moves=None, engine=None):
@@ -141,15 +111,7 @@ class Coverage(Field):
         self.count = _shape_check(who, self.m, self.n, min(self.m, OPEN_MAX) if count is None and self.m >= 1 else count)
         self.candidates = [(int(v) // self.cols, int(v) % self.cols) for v in self.site_ids]
         self.targets = [(int(v) // self.cols, int(v) % self.cols) for v in self.target_ids]
-        try:
-            keep = list(keep)
-        except TypeError:
-            raise ValueError(f"{who}: keep must be a list of indices into sites, got {keep!r}") from None
-        self.keep = [self._index(f"keep[{x}]", v, self.m) for x, v in enumerate(keep)]
-        if len(set(self.keep)) != len(self.keep):
-            raise ValueError(f"{who}: keep names a site twice")
-        if len(self.keep) > self.count:
-            raise ValueError(f"{who}: keep holds {len(self.keep)} sites, more than count = {self.count}")
+        self._set_keep(keep)
         self.max_range, self.radius, self.cost = max_range, None, None
         if self.kind == 0:
             if radius is not None or cost is not None:
@@ -170,20 +132,12 @@ class Coverage(Field):
             if not 0.0 <= r < math.inf:
                 raise ValueError(f"{who}: radius must be a finite number >= 0, got {radius!r}")
             self.radius = r
-            self.cost = None if cost is None else checked_cost(who, self.grid, cost)
-        self.starts = _int_in(who, "starts", starts, 1, STARTS_MAX)
-        self.rounds = _int_in(who, "rounds", rounds, 0, 1 << 20)
-        self.seed = _int_in(who, "seed", seed, 0, (1 << 63) - 1)
-        limit = _int_in(who, "max_moves", max_moves, 0, MOVES_MAX, none_ok=True)
-        self.max_moves = 16 * self.count if limit is None else limit
-        self.restrict_diagonal_near_obstacle = bool(restrict_diagonal_near_obstacle)
-        # a chunk holds at most CHUNK_BYTES of source rows: bytes for sight (an eighth of a double), doubles for reach
-        self.chunk = chunk_rows(self.m, self.rows * self.cols, self.CHUNK_BYTES * (8 if self.kind == 0 else 1))
+        self._set_cost_and_moves(cost, True, restrict_diagonal_near_obstacle)
+        self._set_search(starts, rounds, seed, max_moves, self.count)
         self.words = words_of(self.n)
-        self._set_engine(engine, Engine)                             # every argument is checked: the device
-        e = self.engine
-        self.cost_device = None if self.cost is None else e.put(self.cost.reshape(-1), np.float64)
-        self.buf = e.buf((self.chunk, self.rows, self.cols), np.uint8 if self.kind == 0 else np.float64)
+        # a chunk holds at most CHUNK_BYTES of source rows: bytes for sight (an eighth of a double), doubles for reach
+        chunk = chunk_rows(self.m, self.rows * self.cols, self.CHUNK_BYTES * (8 if self.kind == 0 else 1))
+        e = self._open(engine, Engine, self.site_ids, chunk, np.uint8 if self.kind == 0 else np.float64)   # every argument is checked: the device
         self.target_device = e.put(self.target_ids, np.int32)
         self.mask_device = e.buf((self.m, self.words), np.uint64)
         try:
@@ -192,30 +146,19 @@ class Coverage(Field):
             self.close()                                             # a failed constructor holds no HBM
             raise
 
-    def _check_open(self):
-        if self.buf is None or not getattr(self.engine, "h", None):
-            raise PathfitError(f"{type(self).__name__}: the coverage is closed")
-
-    def _sources(self, r0):
-        """The visibility rows or fields of the sites r0 .. r0 + c - 1 into buf (c = the chunk's rows) -> c."""
-        e, c = self.engine, min(self.chunk, self.m - r0)
-        ids = self.site_ids[r0:r0 + c]
-        if self.kind == 0:
-            e.visibility_field(ids, self.buf, self.restrict_diagonal_near_obstacle, self.range_sq)
-        elif self.cost_device is None:
-            e.dist_field_batch(ids, self.buf, True, self.restrict_diagonal_near_obstacle)
-        else:
-            e.cost_field(self.cost_device, np.arange(c + 1, dtype=np.int32), ids, self.buf, True, self.restrict_diagonal_near_obstacle)
+    def _fields(self, r0):
+        """The visibility rows (by="sight") or the fields of the sites r0 .. r0 + c - 1 into buf (c = the chunk's rows) -> c."""
+        if self.kind != 0:
+            return super()._fields(r0)
+        c = min(self.chunk, self.m - r0)
+        self.engine.visibility_field(self.site_ids[r0:r0 + c], self.buf, self.restrict_diagonal_near_obstacle, self.range_sq)
+        self._held = r0
         return c
 
     def _compute(self):
         e = self.engine
-        ms = 0.0
-        for r0 in range(0, self.m, self.chunk):
-            c = self._sources(r0)
-            ms += e.last_kernel_ms()
-            e.cover_pack(self.kind, c, self.n, self.buf, self.rows * self.cols, self.target_device, 0.0 if self.radius is None else self.radius, r0, self.mask_device)
-            ms += e.last_kernel_ms()
+        ms = self._gather(lambda c, r0: e.cover_pack(self.kind, c, self.n, self.buf, self.rows * self.cols, self.target_device,
+                                                     0.0 if self.radius is None else self.radius, r0, self.mask_device))
         self._masks = None
         got = search(e, self.m, self.n, self.count, self.keep, self.mask_device, self.starts, self.rounds, self.seed, self.max_moves)
         self.row = np.asarray(got["row"], np.int32)
@@ -289,24 +232,6 @@ class Coverage(Field):
             raise PathfitError(f"{who}: no site is open")
         return NearestSourceField(self.grid, [list(self.cells)], True, self.restrict_diagonal_near_obstacle, engine=self.engine)
 
-    def refresh(self, cost=None):
-        """Search the sites again on the map the engine holds now (after engine.update_grid) and, when given, under a new cost map
-        (for a coverage built with one).  The targets stay the constructor's."""
-        who = type(self).__name__
-        self._check_open()
-        if cost is not None and self.cost is None:
-            raise ValueError(f"{who}: refresh(cost) needs a coverage built with a cost map")
-        held = getattr(self.engine, "grid_u8", None)
-        grid = np.array(held, dtype=int) if held is not None else self.grid
-        if self.cost is not None:
-            new = checked_cost(who, grid, self.cost if cost is None else cost)
-            if cost is not None:
-                self.cost = new
-                self.cost_device.upload(new.reshape(-1))
-        self.grid = grid
-        self._compute()
-        return self
-
     @classmethod
     def solve_masks(cls, engine, masks, rows, n, fixed=0, shared=False, max_moves=None):
         """For callers with their own masks and starts: masks uint64 [B, m, W] -- or, with `shared`, one [m, W] for all starts -- with
@@ -324,32 +249,16 @@ class Coverage(Field):
         m = int(a.shape[1])
         if a.shape[2] != words_of(n):
             raise ValueError(f"{who}: masks holds {a.shape[2]} words a row, n = {n} needs {words_of(n)}")
-        if shared and a.shape[0] != 1:
-            raise ValueError(f"{who}: shared=True takes one [m, W] mask set, got {a.shape[0]}")
-        try:
-            o = np.array(rows)
-            o = o[None] if o.ndim == 1 else o
-            ok = o.ndim == 2 and o.shape[0] >= 1 and o.shape[1] >= 1 and o.dtype.kind in "iu"
-        except (TypeError, ValueError):
-            ok = False
-        if not ok or (not shared and o.shape[0] != a.shape[0]):
-            raise ValueError(f"{who}: rows must be an integer array [B, p] with a row per mask set (any B >= 1 with shared=True)")
+        one_if_shared(who, shared, a, "[m, W] mask set")
+        o = start_rows(who, "rows", rows, a, shared, "p", per="mask set")
         p = _shape_check(who, m, n, int(o.shape[1]))
         fixed = _int_in(who, "fixed", fixed, 0, p)
-        limit = _int_in(who, "max_moves", max_moves, 0, MOVES_MAX, none_ok=True)
-        limit = 16 * p if limit is None else limit
+        limit = move_limit(who, max_moves, p)
         if n % 64:
             bad = np.argwhere(a[:, :, -1] >> np.uint64(n % 64) != 0)
             if len(bad):
                 raise ValueError(f"{who}: masks[{int(bad[0][0])}, {int(bad[0][1])}] holds a bit at an element >= n = {n}")
-        for b, row in enumerate(o):
-            seen = set()
-            for s, v in enumerate(row):
-                v = int(v)
-                if not -1 <= v < m or v in seen or (v < 0 and s < fixed):
-                    raise ValueError(f"{who}: rows[{b}, {s}] = {v}: a start holds sites of [0, {m}) or -1, no site twice, and no empty slot below fixed")
-                if v >= 0:
-                    seen.add(v)
+        slot_rows(who, o, m, fixed)
         dm = engine.put(a.reshape(-1), np.uint64)
         try:
             return _improve(engine, m, n, fixed, dm, bool(shared), o, limit)[0]

@@ -13,14 +13,11 @@ import collections
 
 import numpy as np
 
-from ._field import Field
-from ._lib import PathfitError
-from .assignment import chunk_rows
-from .cost_field import checked_cost
+from ._planner import BIG, Planner, _int_in, as_matrices, improve_call, move_limit, no_bad_entry, one_if_shared, restarts, start_rows
 from .engine import Engine
 from .paths import CellPath
 from .tour import join_legs
-from .tour_search import BIG, MOVES_MAX, STARTS_MAX, _int_in, mirrored
+from .tour_search import mirrored
 
 NODES_MAX = 1024                                                     # PF_FLEET_MAX
 ENDS = {"open": 0, "return": 1}
@@ -168,76 +165,51 @@ def perturbations(rng, route, k, cap, starts):
 def _improve(e, mode, k, n, dm, shared, dcap, routes, limit, balance=False):
     """One pf_fleet_improve call (pf_fleet_balance with `balance`: four values and five infos a start) over the start rows `routes`
     [B, k + n] -> (Improved, kernel ms)."""
-    N = k + n
-    routes = np.ascontiguousarray(routes, np.int32).reshape(-1, N)
+    routes = np.ascontiguousarray(routes, np.int32).reshape(-1, k + n)
     B = len(routes)
     nv, ni = (4, 5) if balance else (3, 4)
-    do = e.put(routes.reshape(-1), np.int32)
-    dl, dv, ds, di = e.buf((B, k), np.float64), e.buf((B, nv), np.float64), e.buf(B, np.int32), e.buf((B, ni), np.int64)
-    try:
-        (e.fleet_balance if balance else e.fleet_improve)(mode, k, n, B, shared, dm, dcap, limit, do, dl, dv, ds, di)
-        ms = e.last_kernel_ms()
-        return Improved(do.download().reshape(B, N).astype(np.int32), dl.download().reshape(B, k), dv.download().reshape(B, nv), ds.download().reshape(B),
-                        di.download().reshape(B, ni)), ms
-    finally:
-        for b in (do, dl, dv, ds, di):
-            b.free()
+    call = e.fleet_balance if balance else e.fleet_improve
+    return improve_call(e, Improved, routes, (((B, k), np.float64), ((B, nv), np.float64), (B, np.int32), ((B, ni), np.int64)),
+                        lambda do, dl, dv, ds, di: call(mode, k, n, B, shared, dm, dcap, limit, do, dl, dv, ds, di))
+
+
+def _infeasible(got, k, ms, **more):
+    inf = float("inf")
+    return dict(route=got.route[0], lengths=[inf] * k, total=inf, makespan=inf, feasible=False, start_total=inf, history=[inf], moves=0, kernel_ms=ms, **more)
 
 
 def search(e, mode, k, n, dm, w, cap, dcap, starts, rounds, seed, limit):
     """The search over the matrix dm holds (w: its mirrored copy on the host) -> dict(route, lengths, total, makespan, feasible,
     start_total, history, moves, kernel_ms).  Round 0 improves the start row; each later round improves `starts` perturbations of the
-    incumbent in one call and keeps the strictly smallest total at the smallest start index."""
-    inf = float("inf")
+    incumbent in one call and keeps the strictly smallest total at the smallest start index (restarts)."""
     got, ms = _improve(e, mode, k, n, dm, True, dcap, [start_row(w, k, cap)], limit)
     if int(got.status[0]) == 1:
-        return dict(route=got.route[0], lengths=[inf] * k, total=inf, makespan=inf, feasible=False, start_total=inf, history=[inf], moves=0, kernel_ms=ms)
-    route, lens, best, span, first = got.route[0], got.lengths[0], float(got.value[0, 0]), float(got.value[0, 2]), float(got.value[0, 1])
-    history, moves = [best], int(got.info[0, 0])
-    rng = np.random.default_rng(seed)
-    for _ in range(rounds):
-        got, t = _improve(e, mode, k, n, dm, True, dcap, perturbations(rng, route, k, cap, starts), limit)
-        ms += t
-        moves += int(got.info[:, 0].sum())
-        x = int(np.argmin(got.value[:, 0]))                           # (the first smallest)
-        if got.value[x, 0] < best:
-            best, span, route, lens = float(got.value[x, 0]), float(got.value[x, 2]), got.route[x], got.lengths[x]
-        history.append(best)
-    return dict(route=route, lengths=[float(x) for x in lens], total=best, makespan=span, feasible=True, start_total=first, history=history, moves=moves,
-                kernel_ms=ms)
+        return _infeasible(got, k, ms)
+    first = float(got.value[0, 1])
+    got, x, history, moves, t = restarts(got, rounds, seed, lambda rng, route: perturbations(rng, route, k, cap, starts),
+                                         lambda rows: _improve(e, mode, k, n, dm, True, dcap, rows, limit), lambda g, b: float(g.value[b, 0]))
+    return dict(route=got.route[x], lengths=[float(v) for v in got.lengths[x]], total=history[-1], makespan=float(got.value[x, 2]), feasible=True,
+                start_total=first, history=history, moves=moves, kernel_ms=ms + t)
 
 
 def search_makespan(e, mode, k, n, dm, w, cap, dcap, starts, rounds, seed, limit):
     """The min-max search over the matrix dm holds -> search's dict, and total_history.  Round 0 improves the
     start row under the sum rule (pf_fleet_improve), then balances the result (pf_fleet_balance); each later round balances
     `starts` perturbations of the incumbent in one call and keeps the strictly smallest (makespan, total) at the smallest start
-    index.  history holds the incumbent's makespan per round, total_history its total."""
-    inf = float("inf")
+    index (restarts).  history holds the incumbent's makespan per round, total_history its total."""
     got, ms = _improve(e, mode, k, n, dm, True, dcap, [start_row(w, k, cap)], limit)
     if int(got.status[0]) == 1:
-        return dict(route=got.route[0], lengths=[inf] * k, total=inf, makespan=inf, feasible=False, start_total=inf, history=[inf], total_history=[inf], moves=0,
-                    kernel_ms=ms)
-    first, moves = float(got.value[0, 1]), int(got.info[0, 0])
-    got, t = _improve(e, mode, k, n, dm, True, dcap, got.route, limit, balance=True)
-    ms += t
-    moves += int(got.info[0, 0])
-    route, lens, best = got.route[0], got.lengths[0], (float(got.value[0, 0]), float(got.value[0, 1]))
-    history, totals = [best[0]], [best[1]]
-    rng = np.random.default_rng(seed)
-    for _ in range(rounds):
-        got, t = _improve(e, mode, k, n, dm, True, dcap, perturbations(rng, route, k, cap, starts), limit, balance=True)
-        ms += t
-        moves += int(got.info[:, 0].sum())
-        x = min(range(len(got.value)), key=lambda b: (float(got.value[b, 0]), float(got.value[b, 1]), b))      # (the first smallest pair)
-        if (float(got.value[x, 0]), float(got.value[x, 1])) < best:
-            best, route, lens = (float(got.value[x, 0]), float(got.value[x, 1])), got.route[x], got.lengths[x]
-        history.append(best[0])
-        totals.append(best[1])
-    return dict(route=route, lengths=[float(x) for x in lens], total=best[1], makespan=best[0], feasible=True, start_total=first, history=history,
-                total_history=totals, moves=moves, kernel_ms=ms)
+        return _infeasible(got, k, ms, total_history=[float("inf")])
+    first, summed = float(got.value[0, 1]), int(got.info[0, 0])
+    got, t0 = _improve(e, mode, k, n, dm, True, dcap, got.route, limit, balance=True)
+    got, x, keys, moves, t = restarts(got, rounds, seed, lambda rng, route: perturbations(rng, route, k, cap, starts),
+                                      lambda rows: _improve(e, mode, k, n, dm, True, dcap, rows, limit, balance=True),
+                                      lambda g, b: (float(g.value[b, 0]), float(g.value[b, 1])))
+    return dict(route=got.route[x], lengths=[float(v) for v in got.lengths[x]], total=keys[-1][1], makespan=keys[-1][0], feasible=True, start_total=first,
+                history=[key[0] for key in keys], total_history=[key[1] for key in keys], moves=summed + moves, kernel_ms=ms + t0 + t)
 
 
-class FleetTours(Field):
+class FleetTours(Planner):
     """robots, tasks: (r, c) pairs, at most 1024 together; robot r starts on robots[r].  end: "open" (a route ends at its last task)
     or "return" (every robot comes back to its own start).  capacity: None, the most tasks any robot may hold, or one number per
     robot.  cost: None (path lengths, pf_dist_field_batch) or an [R, C] cost map as CostField's (pf_cost_field).  starts, rounds,
@@ -251,8 +223,8 @@ class FleetTours(Field):
     the rule needs finite weights).  start_total, start_makespan: the greedy start's; history: the incumbent's objective (the total,
     or the makespan) after round 0, 1, ...; total_history: its total; moves: the moves of all starts; matrix: float64 [N, N],
     N = k + n, robots first, the upper triangle of the gathered matrix on both sides."""
-    _bufs = ("buf", "pbuf", "mbuf", "cost_device", "cap_device")
-    CHUNK_BYTES = 256 << 20
+    _bufs = Planner._bufs + ("cap_device",)
+    _closed, _built = "the fleet tours are closed", "fleet tours"
 
     def __init__(self, grid, robots, tasks, end="open", capacity=None, cost=None, starts=8, rounds=3, seed=0, max_moves=None,
                  allow_diagonal_moves=True, restrict_diagonal_near_obstacle=True, engine=None, objective="sum"):
@@ -269,47 +241,16 @@ class FleetTours(Field):
         self.robots = [(int(v) // self.cols, int(v) % self.cols) for v in rid]
         self.tasks = [(int(v) // self.cols, int(v) % self.cols) for v in tid]
         self.capacity = _capacity(who, capacity, self.k, self.n)
-        self.cost = None if cost is None else checked_cost(who, self.grid, cost)
-        self.starts = _int_in(who, "starts", starts, 1, STARTS_MAX)
-        self.rounds = _int_in(who, "rounds", rounds, 0, 1 << 20)
-        self.seed = _int_in(who, "seed", seed, 0, (1 << 63) - 1)
-        limit = _int_in(who, "max_moves", max_moves, 0, MOVES_MAX, none_ok=True)
-        self.max_moves = 16 * self.N if limit is None else limit
-        self.allow_diagonal_moves = bool(allow_diagonal_moves)
-        self.restrict_diagonal_near_obstacle = bool(restrict_diagonal_near_obstacle)
-        self.chunk = chunk_rows(self.N, self.rows * self.cols, self.CHUNK_BYTES)
-        self._set_engine(engine, Engine)                             # every argument is checked: the device
-        e = self.engine
-        self.cost_device = None if self.cost is None else e.put(self.cost.reshape(-1), np.float64)
+        self._set_cost_and_moves(cost, allow_diagonal_moves, restrict_diagonal_near_obstacle)
+        self._set_search(starts, rounds, seed, max_moves, self.N)
+        e = self._open(engine, Engine, self.ids)                             # every argument is checked: the device
         self.cap_device = None if self.capacity is None else e.put(self.capacity, np.int32)
-        self.buf = e.buf((self.chunk, self.rows, self.cols), np.float64)
         self.mbuf = e.buf((self.N, self.N), np.float64)
-        self.pbuf = None
         self._compute()
-
-    def _check_open(self):
-        if self.buf is None or not getattr(self.engine, "h", None):
-            raise PathfitError(f"{type(self).__name__}: the fleet tours are closed")
-
-    def _fields(self, r0):
-        """The fields of the cells r0 .. r0 + c - 1 into buf (c = the chunk's rows) -> c."""
-        e, c = self.engine, min(self.chunk, self.N - r0)
-        ids = self.ids[r0:r0 + c]
-        if self.cost_device is None:
-            e.dist_field_batch(ids, self.buf, self.allow_diagonal_moves, self.restrict_diagonal_near_obstacle)
-        else:
-            e.cost_field(self.cost_device, np.arange(c + 1, dtype=np.int32), ids, self.buf, self.allow_diagonal_moves, self.restrict_diagonal_near_obstacle)
-        self._held = r0
-        return c
 
     def _compute(self):
         e, N = self.engine, self.N
-        ms = 0.0
-        for r0 in range(0, N, self.chunk):
-            c = self._fields(r0)
-            ms += e.last_kernel_ms()
-            e.assign_matrix(c, self.ids, self.buf, self.mbuf, r0, N, False)
-            ms += e.last_kernel_ms()
+        ms = self._gather(lambda c, r0: e.assign_matrix(c, self.ids, self.buf, self.mbuf, r0, N, False))
         self.matrix = mirrored(self.mbuf.download().reshape(N, N))
         find = search_makespan if self.objective == "makespan" else search
         got = find(e, self.mode, self.k, self.n, self.mbuf, self.matrix, self.capacity, self.cap_device, self.starts, self.rounds, self.seed, self.max_moves)
@@ -354,94 +295,25 @@ class FleetTours(Field):
 
     def legs(self):
         """Per robot the list of CellPaths of its route's legs in visiting order (for end="return" the last one leads back to its
-        start; [] for an empty route); [] where the problem is infeasible.  Each leg is DistanceField.paths' route from its first
-        cell to its second, cell for cell.  The legs are grouped by the chunk of fields their first cell lies in: a parent-map call per
-        chunk and one trace call with a field index per query.  A chunk of fields that was released for a later one is computed again."""
+        start; [] for an empty route); [] where the problem is infeasible (Planner._trace: the legs are grouped by the chunk of fields
+        their first cell lies in)."""
         self._check_open()
         if not self.feasible:
             return []
-        pairs, owner = [], []
+        queries, owner = [], []
         for r, tasks in enumerate(split(self.route, self.k)):
             seq = [r] + tasks + ([r] if self.mode == 1 and tasks else [])
-            pairs += list(zip(seq[:-1], seq[1:]))
+            queries += [(a, int(self.ids[b])) for a, b in zip(seq[:-1], seq[1:])]
             owner += [r] * (len(seq) - 1)
-        out = {}
-        e, full = self.engine, self.rows * self.cols
-        ad, rs = self.allow_diagonal_moves, self.restrict_diagonal_near_obstacle
-        for r0 in sorted(range(0, self.N, self.chunk), key=lambda r: r != self._held):      # the chunk held first: it is not computed again
-            mine = [x for x in range(len(pairs)) if r0 <= pairs[x][0] < r0 + self.chunk]
-            if not mine:
-                continue
-            c = min(self.chunk, self.N - r0)
-            if self._held != r0:
-                self._fields(r0)
-                if self.pbuf is not None:
-                    self.pbuf.free()
-                    self.pbuf = None
-            if self.pbuf is None:
-                pbuf = e.buf((self.chunk, self.rows, self.cols), np.uint8)
-                try:
-                    if self.cost_device is None:
-                        e.dist_field_parents(c, self.buf, pbuf, ad, rs)
-                    else:
-                        e.cost_field_parents(self.cost_device, c, self.buf, pbuf, ad, rs)
-                except Exception:
-                    pbuf.free()
-                    raise
-                self.pbuf = pbuf
-            q = len(mine)
-            dk = e.put(np.array([pairs[x][0] - r0 for x in mine], np.int32))
-            dt = e.put(self.ids[np.array([pairs[x][1] for x in mine])].astype(np.int32))
-            dl, dst = e.buf(q, np.int32), e.buf(q, np.int32)
-            dcl, cap = None, e.default_path_cap()
-            try:
-                while True:
-                    dcl = e.buf((q, cap), np.int32)
-                    e.dist_field_paths(c, self.pbuf, dt, q, cap, dcl, dl, dst, dk, self.buf, False, None)
-                    st = dst.download()
-                    if cap >= full or not (st == 3).any():
-                        break
-                    dcl.free()
-                    dcl, cap = None, full
-                if (st == 3).any():
-                    raise PathfitError(f"{type(self).__name__}: {int((st == 3).sum())} legs hold more than {cap} cells")
-                lens, cells = dl.download(), dcl.download().reshape(q, cap)
-                for y, x in enumerate(mine):
-                    out[x] = CellPath(cells[y, :lens[y]].copy(), self.cols)
-            finally:
-                for b in (dk, dt, dl, dst, dcl):
-                    if b is not None:
-                        b.free()
         legs = [[] for _ in range(self.k)]
-        for x, r in enumerate(owner):
-            legs[r].append(out[x])
+        for r, leg in zip(owner, self._trace(queries, "legs")):
+            legs[r].append(leg)
         return legs
 
     def paths(self):
         """Per robot its legs joined into one CellPath (a shared cell is not repeated; a robot without tasks stays on its start
         cell); [] where the problem is infeasible."""
         return [join_legs(legs, self.cols) if legs else CellPath(np.array([self.ids[r]], np.int32), self.cols) for r, legs in enumerate(self.legs())]
-
-    def refresh(self, cost=None):
-        """Search the routes again on the map the engine holds now (after engine.update_grid) and, when given, under a new cost map
-        (for a search built with one)."""
-        who = type(self).__name__
-        self._check_open()
-        if cost is not None and self.cost is None:
-            raise ValueError(f"{who}: refresh(cost) needs fleet tours built with a cost map")
-        held = getattr(self.engine, "grid_u8", None)
-        grid = np.array(held, dtype=int) if held is not None else self.grid
-        if self.cost is not None:
-            new = checked_cost(who, grid, self.cost if cost is None else cost)
-            if cost is not None:
-                self.cost = new
-                self.cost_device.upload(new.reshape(-1))
-        self.grid = grid
-        if self.pbuf is not None:
-            self.pbuf.free()
-            self.pbuf = None
-        self._compute()
-        return self
 
     @classmethod
     def solve_matrices(cls, engine, mats, k, routes=None, end="open", capacity=None, shared=False, max_moves=None):
@@ -465,41 +337,22 @@ class FleetTours(Field):
         """solve_matrices and balance_matrices: the checks, the uploads and the one call."""
         who = cls.__name__
         mode = _mode(who, end)
-        try:
-            m = np.ascontiguousarray(mats, np.float64)
-        except (TypeError, ValueError):
-            raise ValueError(f"{who}: mats must be a [B, N, N] array of numbers") from None
-        if m.ndim == 2:
-            m = m[None]
-        if m.ndim != 3 or m.shape[1] != m.shape[2] or m.shape[0] < 1:
-            raise ValueError(f"{who}: mats has shape {m.shape}, not [B, N, N] with B >= 1")
+        m = as_matrices(who, "mats", mats, "N", "N")
         N = int(m.shape[1])
         k = _int_in(who, "k", k, 1, NODES_MAX)
         _count_check(who, k, N - k)
         n = N - k
-        if shared and m.shape[0] != 1:
-            raise ValueError(f"{who}: shared=True takes one [N, N] matrix, got {m.shape[0]}")
+        one_if_shared(who, shared, m, "[N, N] matrix")
         cap = _capacity(who, capacity, k, n)
-        limit = _int_in(who, "max_moves", max_moves, 0, MOVES_MAX, none_ok=True)
-        limit = 16 * N if limit is None else limit
+        limit = move_limit(who, max_moves, N)
         read = np.triu(np.ones((N, N), bool), 1)
         read[:, :k] = False
-        with np.errstate(invalid="ignore"):
-            bad = np.argwhere(~(((m >= 0.0) & ((m <= BIG) | (m == np.inf))) | ~read[None]))      # (NaN fails the comparisons)
-        if len(bad):
-            b, i, j = (int(v) for v in bad[0])
-            raise ValueError(f"{who}: mats[{b}, {i}, {j}] = {float(m[b, i, j])!r} is neither +inf nor a number in [0, 2^1000]")
+        with np.errstate(invalid="ignore"):                           # (NaN fails the comparisons)
+            no_bad_entry(who, "mats", m, ~(((m >= 0.0) & ((m <= BIG) | (m == np.inf))) | ~read[None]), "neither +inf nor a number in [0, 2^1000]")
         if routes is None:
             o = np.array([start_row(mirrored(a), k, cap) for a in m], np.int64).reshape(len(m), N)
         else:
-            try:
-                o = np.array(routes)
-                o = o[None] if o.ndim == 1 else o
-                ok = o.ndim == 2 and o.shape[1] == N and o.shape[0] >= 1 and o.dtype.kind in "iu"
-            except (TypeError, ValueError):
-                ok = False
-            if not ok or (not shared and o.shape[0] != m.shape[0]):
-                raise ValueError(f"{who}: routes must be an integer array [B, N] with a row per matrix (any B >= 1 with shared=True)")
+            o = start_rows(who, "routes", routes, m, shared, "N", N)
             for b, row in enumerate(o):
                 seen = set()
                 for p, v in enumerate(row):

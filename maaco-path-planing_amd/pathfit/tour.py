@@ -5,9 +5,7 @@ map), the stop-to-stop matrix is gathered out of the fields in HBM (pf_tour_matr
 heuristic's order can be held against (`route_cost`).  `legs` / `path` trace the route through the parent maps of the same fields."""
 import numpy as np
 
-from ._field import Field
-from ._lib import PathfitError
-from .cost_field import checked_cost
+from ._planner import Planner, as_matrices, no_bad_entry
 from .engine import Engine
 from .paths import CellPath
 
@@ -79,7 +77,7 @@ def join_legs(legs, cols):
     return CellPath(np.array(out, np.int32), cols)
 
 
-class Tour(Field):
+class Tour(Planner):
     """stops: (r, c) pairs, stops[0] the start.  end: "open" (the tour ends anywhere), "return" (back to the start) or "last" (it
     ends at stops[-1]).  before: (a, b) index pairs, stop a is visited before stop b.  cost: None (path lengths, pf_dist_field_batch)
     or an [R, C] cost map as CostField's (pf_cost_field).
@@ -87,7 +85,7 @@ class Tour(Field):
     order: int32 stop indices in visiting order (it begins with 0, does not repeat 0 for "return"); total: the exact optimum;
     feasible: False where a stop is out of reach or `before` is cyclic (order is then all -1, total inf).  matrix: float64 [n, n],
     downloaded on first use; info: int64 [4] = (finite states of the table, the last middle stop or -1, 0, 0)."""
-    _bufs = ("buf", "pbuf", "mbuf", "cost_device")
+    _closed, _built = "the tour is closed", "a tour"
 
     def __init__(self, grid, stops, end="open", before=(), cost=None, allow_diagonal_moves=True, restrict_diagonal_near_obstacle=True, engine=None):
         who = type(self).__name__
@@ -99,31 +97,14 @@ class Tour(Field):
         _count_check(who, self.n, self.mode)
         self.stops = [(int(v) // self.cols, int(v) % self.cols) for v in self.ids]
         self.need = _need(who, self.n, self.mode, before)
-        self.cost = None if cost is None else checked_cost(who, self.grid, cost)
-        self.allow_diagonal_moves = bool(allow_diagonal_moves)
-        self.restrict_diagonal_near_obstacle = bool(restrict_diagonal_near_obstacle)
-        self._set_engine(engine, Engine)                             # every argument is checked: the device
-        e = self.engine
-        self.cost_device = None if self.cost is None else e.put(self.cost.reshape(-1), np.float64)
-        self.buf = e.buf((self.n, self.rows, self.cols), np.float64)
+        self._set_cost_and_moves(cost, allow_diagonal_moves, restrict_diagonal_near_obstacle)
+        e = self._open(engine, Engine, self.ids, self.n)             # every argument is checked: the device; the fields are one chunk
         self.mbuf = e.buf((self.n, self.n), np.float64)
-        self.pbuf = None
         self._compute()
-
-    def _check_open(self):
-        if self.buf is None or not getattr(self.engine, "h", None):
-            raise PathfitError(f"{type(self).__name__}: the tour is closed")
 
     def _compute(self):
         e, n = self.engine, self.n
-        ad, rs = self.allow_diagonal_moves, self.restrict_diagonal_near_obstacle
-        if self.cost_device is None:
-            e.dist_field_batch(self.ids, self.buf, ad, rs)
-        else:
-            e.cost_field(self.cost_device, np.arange(n + 1, dtype=np.int32), self.ids, self.buf, ad, rs)
-        ms = e.last_kernel_ms()
-        e.tour_matrix(self.ids, self.buf, self.mbuf)
-        ms += e.last_kernel_ms()
+        ms = self._gather(lambda k, r0: e.tour_matrix(self.ids, self.buf, self.mbuf))
         dt, do, ds, di = e.buf(1, np.float64), e.buf(n, np.int32), e.buf(1, np.int32), e.buf(4, np.int64)
         try:
             e.tour_solve(self.mode, n, 1, self.mbuf, dt, do, ds, self.need, di)
@@ -158,72 +139,16 @@ class Tour(Field):
 
     def legs(self):
         """One CellPath per leg of the tour in visiting order (for end="return" the last one leads back to the start); [] where the
-        tour is infeasible.  Each leg is DistanceField.paths' route from its first stop to its second, cell for cell: all legs come
-        from one parent-map call over the fields and one trace call with a field index per query."""
+        tour is infeasible (Planner._trace: all legs come from one parent-map call over the fields and one trace call)."""
         self._check_open()
         if not self.feasible:
             return []
         seq = [int(v) for v in self.order] + ([0] if self.mode == 1 and self.n > 1 else [])
-        q = len(seq) - 1
-        if q < 1:
-            return []
-        e, full = self.engine, self.rows * self.cols
-        if self.pbuf is None:
-            pbuf = e.buf((self.n, self.rows, self.cols), np.uint8)
-            try:
-                if self.cost_device is None:
-                    e.dist_field_parents(self.n, self.buf, pbuf, self.allow_diagonal_moves, self.restrict_diagonal_near_obstacle)
-                else:
-                    e.cost_field_parents(self.cost_device, self.n, self.buf, pbuf, self.allow_diagonal_moves, self.restrict_diagonal_near_obstacle)
-            except Exception:
-                pbuf.free()
-                raise
-            self.pbuf = pbuf
-        dk, dt = e.put(np.array(seq[:-1], np.int32)), e.put(self.ids[np.array(seq[1:])].astype(np.int32))
-        dl, dst = e.buf(q, np.int32), e.buf(q, np.int32)
-        dc, cap = None, e.default_path_cap()
-        try:
-            while True:
-                dc = e.buf((q, cap), np.int32)
-                e.dist_field_paths(self.n, self.pbuf, dt, q, cap, dc, dl, dst, dk, self.buf, False, None)
-                st = dst.download()
-                if cap >= full or not (st == 3).any():
-                    break
-                dc.free()
-                dc, cap = None, full
-            if (st == 3).any():
-                raise PathfitError(f"{type(self).__name__}: {int((st == 3).sum())} legs hold more than {cap} cells")
-            lens, cells = dl.download(), dc.download().reshape(q, cap)
-            return [CellPath(cells[i, :lens[i]].copy(), self.cols) for i in range(q)]
-        finally:
-            for b in (dk, dt, dl, dst, dc):
-                if b is not None:
-                    b.free()
+        return self._trace([(a, int(self.ids[b])) for a, b in zip(seq[:-1], seq[1:])], "legs")
 
     def path(self):
         """The legs joined into one CellPath (a shared stop cell is not repeated); empty where the tour is infeasible."""
         return join_legs(self.legs(), self.cols)
-
-    def refresh(self, cost=None):
-        """Compute the tour again on the map the engine holds now (after engine.update_grid) and, when given, under a new cost map
-        (for a tour built with one)."""
-        who = type(self).__name__
-        self._check_open()
-        if cost is not None and self.cost is None:
-            raise ValueError(f"{who}: refresh(cost) needs a tour built with a cost map")
-        held = getattr(self.engine, "grid_u8", None)
-        grid = np.array(held, dtype=int) if held is not None else self.grid
-        if self.cost is not None:
-            new = checked_cost(who, grid, self.cost if cost is None else cost)
-            if cost is not None:
-                self.cost = new
-                self.cost_device.upload(new.reshape(-1))
-        self.grid = grid
-        if self.pbuf is not None:
-            self.pbuf.free()
-            self.pbuf = None
-        self._compute()
-        return self
 
     @classmethod
     def solve_matrices(cls, engine, mats, end="open", before=()):
@@ -231,22 +156,12 @@ class Tour(Field):
         `before` for all -> (totals float64 [B], orders int32 [B, n], status int32 [B] with 1 = infeasible, info int64 [B, 4])."""
         who = cls.__name__
         mode = _mode(who, end)
-        try:
-            m = np.ascontiguousarray(mats, np.float64)
-        except (TypeError, ValueError):
-            raise ValueError(f"{who}: mats must be a [B, n, n] array of numbers") from None
-        if m.ndim == 2:
-            m = m[None]
-        if m.ndim != 3 or m.shape[1] != m.shape[2] or m.shape[0] < 1:
-            raise ValueError(f"{who}: mats has shape {m.shape}, not [B, n, n] with B >= 1")
+        m = as_matrices(who, "mats", mats, "n", "n")
         B, n = int(m.shape[0]), int(m.shape[1])
         _count_check(who, n, mode)
         need = _need(who, n, mode, before)
         off = ~np.eye(n, dtype=bool)
-        bad = np.argwhere(~((m >= 0.0) | ~off[None]))                # (NaN fails the comparison)
-        if len(bad):
-            b, i, j = (int(v) for v in bad[0])
-            raise ValueError(f"{who}: mats[{b}, {i}, {j}] = {float(m[b, i, j])!r} is neither >= 0 nor +inf")
+        no_bad_entry(who, "mats", m, ~((m >= 0.0) | ~off[None]), "neither >= 0 nor +inf")      # (NaN fails the comparison)
         dm = engine.put(m.reshape(-1), np.float64)
         dt, do, ds, di = engine.buf(B, np.float64), engine.buf((B, n), np.int32), engine.buf(B, np.int32), engine.buf((B, 4), np.int64)
         try:
