@@ -1135,6 +1135,61 @@ int pf_cover_improve(pf_handle* h, int32_t m, int32_t n, int32_t p, int32_t fixe
                      const uint64_t* d_mask, int32_t max_moves, int32_t* d_sel, uint64_t* d_covered, int64_t* d_value,
                      int32_t* d_status, int64_t* d_info);
 
+/* ---- the sight graph: exact any-angle shortest paths between cell centres (pathfit.AnyAngle) --------------------------------
+ * The yardstick for Euclidean any-angle length: the shortest polyline whose vertices are cell centres and whose
+ * segments all pass the smoothing section's visible(a, b, restrict_corner).
+ * The nodes.
+ * - `nodes` is a host array of M cell ids, strictly increasing, each in [0, R C), 1 <= M <= PF_SIGHT_NODES_MAX.
+ * - Everything below speaks of node INDICES 0 .. M - 1, not of cell ids; "smallest" means the smallest node index.
+ * The graph.
+ * - d_adj is uint64 [M][ld], ld >= W = ceil(M / 64).  Bit j & 63 of word j >> 6 of row i is the pair (i, j).
+ * - The bit is set iff visible(nodes[i], nodes[j], restrict_corner) holds and, when max_range_sq >= 0, dr^2 + dc^2 <= max_range_sq.
+ * - The diagonal bit (i, i) is the rule's a == b case: set iff the node's cell is free.  It is the node's "usable" flag below.
+ * - A node on an obstacle has an all-zero row and column.  The rule is symmetric, and so is the matrix.
+ * - The tail bits of word W - 1 are zero.  The words [W, ld) of a row are not written.
+ * - The occupancy is the handle's at call time: after pf_update_grid the next pack sees the new map.
+ * pf_sight_pack: fills d_adj, one lane per ordered pair, all M^2 pairs.  d_info (or NULL), int64 [4] = {set off-diagonal bits, the
+ * largest off-diagonal degree over all M nodes, the smallest node index that attains it, nodes on obstacles}.
+ * The labels.
+ * - w(i, j) = sqrt((double)(dr^2 + dc^2)), correctly rounded, between the cells of nodes i and j.
+ * - set_off and src are host arrays laid out as pf_dist_field_merged's, src holding node indices; here a set may be empty.
+ * - A source is usable iff its diagonal bit is set.  d_dist[b][v] = 0 at a usable source of set b.
+ * - Elsewhere d_dist[b][v] is the least value, over all walks u0 .. uk = v along set bits from a usable source u0 of set b, of the
+ *   left-to-right sum fl(.. fl(fl(0 + w(u0, u1)) + w(u1, u2)) ..), and +inf where there is no such walk (a node on an obstacle, a
+ *   set with no usable source).
+ * - An edge into v is read from ROW v: bit (v, u).  The matrix must be symmetric, as pf_sight_pack leaves it.
+ * - fp64 addition is monotone and every w >= 1, so these are a heap Dijkstra's labels bit for bit, and the unique fixed point of
+ *   d[v] = min_u fl(d[u] + w(u, v)): the device relaxes in rounds, in whatever order, and lands on the same words on every run.
+ * pf_sight_field: B source sets -> d_dist double [B][M]; d_parent (or NULL) int32 [B][M]; d_info (or NULL) int64 [B][4].
+ * - d_parent[b][v] = -1 at a usable source and at a +inf label; else the smallest u with bit (v, u) set, d[u] < d[v] and
+ *   fl(d[u] + w(u, v)) == d[v].  A field-only rule, as pf_dist_field_parents has one.
+ * - d_info[b] = {finite labels, nodes with label 0 (the distinct usable sources), the smallest node index that holds the largest
+ *   finite label or -1, 0}.
+ * - One workgroup of 1 024 threads per set, the round loop inside the kernel; the labels of a set live in LDS.
+ * pf_sight_field_work: out4 = {the most rounds a set took, the rounds of all sets, candidate sums formed, labels lowered} of the
+ * last pf_sight_field call on the handle.  For the probe; the last two depend on the order the device happened to take.
+ * pf_sight_paths: n queries.  Query i chases d_parent from node d_target[i] in set d_set[i] (d_set NULL: set 0).
+ * - d_way int32 [n][way_cap]: the waypoints' CELL ids source -> target, or target -> source when reverse != 0; d_way_len their number.
+ * - d_stats (or NULL) double [n][2] = {the left-to-right sum of the segments' lengths taken source -> target, the turns as
+ *   pf_smooth_batch counts them}; both 0 unless the status is 0.  With pf_sight_field's parents the sum is d_dist's word.
+ * - d_status: 0 ok; 1 = a set outside [0, B) or a target outside [0, M); 2 = the label is +inf; 3 = more waypoints than way_cap;
+ *   4 = parents that are not pf_sight_field's: an index outside [-1, M), a chain of more than M nodes or one that ends at a node
+ *   whose label is not 0.  Every walk ends within M steps.  The length is 0 and the row untouched unless the status is 0.
+ * All three: a null handle (-2).  M out of range, a node outside the grid or not above its predecessor (the message names the first
+ * such index), ld < W, max_range_sq < -1, B < 1, offsets that do not start at 0 or that decrease, a source outside [0, M) (the
+ * message names the first index), n < 0, way_cap < 1 or a missing required pointer (-1, with a message) is found on the host before
+ * any launch.  pf_sight_paths with n == 0 returns 0 and launches nothing.  Synchronous, ordered on the handle's stream;
+ * pf_last_kernel_ms reports the kernels. */
+#define PF_SIGHT_NODES_MAX 16384
+int pf_sight_pack(pf_handle* h, int32_t restrict_corner, int32_t max_range_sq, int32_t M, const int32_t* nodes, uint64_t* d_adj,
+                  int32_t ld, int64_t* d_info);
+int pf_sight_field(pf_handle* h, int32_t M, const int32_t* nodes, const uint64_t* d_adj, int32_t ld, int32_t B,
+                   const int32_t* set_off, const int32_t* src, double* d_dist, int32_t* d_parent, int64_t* d_info);
+int pf_sight_field_work(pf_handle* h, int64_t* out4);
+int pf_sight_paths(pf_handle* h, int32_t M, const int32_t* nodes, int32_t B, const double* d_dist, const int32_t* d_parent,
+                   int32_t n, const int32_t* d_set, const int32_t* d_target, int32_t reverse, int32_t way_cap, int32_t* d_way,
+                   int32_t* d_way_len, double* d_stats, int32_t* d_status);
+
 /* Tuning knobs (results never change): "tour_tables" the most Held-Karp tables pf_tour_solve keeps in flight in HBM (default 0:
  * as many as fit 256 MiB); "components_phases" 0/1 pf_components records a HIP event after each phase
  * (pf_components_phase_ms; default 0); "maaco_pack8_min" ants per batch from which eight ants share a wavefront

@@ -14,7 +14,8 @@ a bucket geometry that makes its rare branches common, with the branch counters 
 (tests/test_gpu_open_list_stress.py runs tests/open_list_cases.py against each), and the stress variants of the parallel closed-set
 engine (SETTLE_VARIANTS: tests/test_gpu_settle_stress.py runs tests/settle_cases.py against each), the assignment solver's
 workgroup form at every m (ASSIGN_VARIANTS: tests/test_gpu_assign.py holds it against the shipped library), and the coverage
-search's other deal with the planes in HBM from three words on (COVER_VARIANTS: tests/test_gpu_cover.py does the same).
+search's other deal with the planes in HBM from three words on (COVER_VARIANTS: tests/test_gpu_cover.py does the same), and the
+sight graph's field with its labels in HBM from 65 nodes on (SIGHT_VARIANTS: tests/test_gpu_sight.py does the same).
 """
 import os
 import subprocess
@@ -56,6 +57,11 @@ ASSIGN_VARIANTS = {
 COVER_VARIANTS = {
     "cv_lanes": ["-DPF_COVER_DEAL=0", "-DPF_COVER_LDS_WORDS=2"],
 }
+# The stress variant of the sight graph's field (pf_sight.h): the labels of a set in the output row (HBM) instead of LDS from 65
+# nodes on -- the form that is not shipped, reachable at small sizes, and both sides of its switch at 64 / 65 nodes.
+SIGHT_VARIANTS = {
+    "sg_hbm": ["-DPF_SIGHT_LDS_NODES=64"],
+}
 VARIANT_COMMON = ["-DPF_OPEN_PATHS"]
 MAX_JOBS = 16
 
@@ -84,7 +90,7 @@ def variant_path(name):
 
 
 def variant_flags(name):
-    for group in (VARIANTS, SETTLE_VARIANTS, ASSIGN_VARIANTS, COVER_VARIANTS):
+    for group in (VARIANTS, SETTLE_VARIANTS, ASSIGN_VARIANTS, COVER_VARIANTS, SIGHT_VARIANTS):
         if name in group:
             return VARIANT_COMMON + group[name]
     raise KeyError(name)
@@ -97,7 +103,7 @@ def build_variant(name, force=False, verbose=False):
 
 def build_variants(names=None, force=False, verbose=False):
     """Several variants at once: one hipcc child each, at most MAX_JOBS at a time."""
-    names = list(VARIANTS) + list(SETTLE_VARIANTS) + list(ASSIGN_VARIANTS) + list(COVER_VARIANTS) if names is None else list(names)
+    names = list(VARIANTS) + list(SETTLE_VARIANTS) + list(ASSIGN_VARIANTS) + list(COVER_VARIANTS) + list(SIGHT_VARIANTS) if names is None else list(names)
     outs = [variant_path(n) for n in names]
     os.makedirs(os.path.dirname(variant_path("x")), exist_ok=True)
     todo = [(n, o) for n, o in zip(names, outs) if force or _stale(o)]

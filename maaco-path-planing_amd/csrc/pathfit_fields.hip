@@ -1,6 +1,6 @@
 // pathfit_fields.hip -- the field family of libpathfit.so (distance fields, routing trees, nearest-source fields, smoothing,
-// connected components, clearance, widest paths, cost fields, turn fields, visibility fields, space-time fields) and the planners
-// over it (tours, assignments, the tour search, fleet routes, placement, coverage).  A translation unit, and so a device code
+// connected components, clearance, widest paths, cost fields, turn fields, visibility fields, space-time fields, the sight graph)
+// and the planners over it (tours, assignments, the tour search, fleet routes, placement, coverage).  A translation unit, and so a device code
 // object, of its own: it shares the handle and the error helpers with pathfit.hip (pf_host.h) and none of the
 // solvers' device code.
 #include <algorithm>
@@ -1832,6 +1832,163 @@ int pf_cover_improve(pf_handle* h, int32_t m, int32_t n, int32_t p, int32_t fixe
                          (long long*)d_info, d_bad + 2);
     }
     return timed_end(h);
+  };
+  return run() ? -1 : 0;
+}
+
+}  // extern "C"
+
+// ---------------------------------------------------------------------------
+// The sight graph and exact any-angle shortest paths in it (pf_sight.h).  pf_sight_pack reads the handle's
+// occupancy at call time (pf_update_grid keeps working); the matrix, the labels and the parents are the caller's buffers.  Scratch:
+// four 64-bit words (info keys or work counters), the node list, the nodes' coordinates and the sets of a call, all in the
+// distance fields' control block; nothing in it outlives a call.  The handle keeps the last field call's work counters.
+// ---------------------------------------------------------------------------
+#include "pf_sight.h"
+
+// The node list of a call, checked on the host, then the call's view of the control block: four 64-bit words in front (the caller zeroes them), the
+// node cells, their coordinates and `extra` ints behind them.
+static int sight_nodes_check(pf_handle* h, const std::string& me, int M, const int32_t* nodes) {
+  if (M < 1 || M > PF_SIGHT_NODES_MAX)
+    return failmsg(h, me + ": bad arguments (M = " + std::to_string(M) + ": the number of nodes must lie in [1, " + std::to_string(PF_SIGHT_NODES_MAX) + "])");
+  if (!nodes) return failmsg(h, me + ": bad arguments (the nodes must not be null)");
+  if ((long long)h->R * h->R + (long long)h->C * h->C >= 0x7FFFFFFFll) return failmsg(h, me + ": bad arguments (R^2 + C^2 must stay below 2^31 - 1)");
+  for (int i = 0; i < M; ++i) {
+    if (nodes[i] < 0 || nodes[i] >= h->RC) return failmsg(h, me + ": node " + std::to_string(i) + " = " + std::to_string(nodes[i]) + " lies outside the grid");
+    if (i > 0 && nodes[i] <= nodes[i - 1])
+      return failmsg(h, me + ": node " + std::to_string(i) + " = " + std::to_string(nodes[i]) + " does not lie above node " + std::to_string(i - 1) + " = " +
+                            std::to_string(nodes[i - 1]) + ": the cells must increase strictly");
+  }
+  return 0;
+}
+
+static int sight_nodes(pf_handle* h, const std::string& me, int M, const int32_t* nodes, size_t extra, unsigned long long*& ctl, int*& d_nodes, int*& d_rc, int*& d_extra) {
+  if (sight_nodes_check(h, me, M, nodes)) return -2;
+  CK(hipSetDevice(h->device));
+  const size_t bytes = sizeof(unsigned long long) * 4 + sizeof(int) * (2 * (size_t)M + extra);
+  if (scratch(h, me, h->d_df_ctl, &h->df_ctl_bytes, std::max<size_t>(bytes, 256), "the nodes", false)) return -2;
+  ctl = (unsigned long long*)h->d_df_ctl;                             // (in front: 8-byte aligned)
+  d_nodes = (int*)(ctl + 4);
+  d_rc = d_nodes + M;
+  d_extra = d_rc + M;
+  CK(hipMemcpyAsync(d_nodes, nodes, sizeof(int) * (size_t)M, hipMemcpyHostToDevice, h->stream));
+  CK(hipStreamSynchronize(h->stream));                                // (nodes is pageable and the caller's)
+  return 0;
+}
+
+static int sight_matrix_args(pf_handle* h, const std::string& me, int M, const void* d_adj, int ld) {
+  if (!d_adj) return failmsg(h, me + ": bad arguments (the adjacency matrix must not be null)");
+  if (M >= 1 && ld < (M + 63) / 64)
+    return failmsg(h, me + ": bad arguments (ld = " + std::to_string(ld) + ": a row holds at least ceil(M / 64) = " + std::to_string((M + 63) / 64) + " words)");
+  return 0;
+}
+
+extern "C" {
+
+int pf_sight_pack(pf_handle* h, int32_t restrict_corner, int32_t max_range_sq, int32_t M, const int32_t* nodes, uint64_t* d_adj, int32_t ld, int64_t* d_info) {
+  if (!h) return -2;
+  const std::string me("pf_sight_pack");
+  auto run = [&]() -> int {
+    if (max_range_sq < -1) return failmsg(h, me + ": bad arguments (max_range_sq = " + std::to_string(max_range_sq) + ": -1 means no limit, else >= 0)");
+    if (sight_matrix_args(h, me, M, d_adj, ld)) return -2;
+    unsigned long long* ctl = nullptr;
+    int *d_nodes = nullptr, *d_rc = nullptr, *d_extra = nullptr;
+    if (const int rc = sight_nodes(h, me, M, nodes, 0, ctl, d_nodes, d_rc, d_extra)) return rc;
+    const int W = (M + 63) / 64, per = PF_SIGHT_THREADS / 64;
+    return timed(h, [&]() -> int {
+      hipLaunchKernelGGL(k_sight_pack_lane_per_pair, dim3((unsigned)((W + per - 1) / per), (unsigned)M), dim3(PF_SIGHT_THREADS), 0, h->stream, (const uint8_t*)h->d_occ,
+                         h->C, restrict_corner ? 1 : 0, (int)max_range_sq, (int)M, (const int*)d_nodes, (unsigned long long*)d_adj, (int)ld);
+      if (d_info) {
+        CK(hipMemsetAsync(ctl, 0, sizeof(unsigned long long) * 4, h->stream));
+        const unsigned nb = (unsigned)((M + per - 1) / per);
+        hipLaunchKernelGGL(k_sight_pack_info_reduce, dim3(nb < 1024u ? nb : 1024u), dim3(PF_SIGHT_THREADS), 0, h->stream, (const unsigned long long*)d_adj, (int)ld, (int)M,
+                           ctl);
+        hipLaunchKernelGGL(k_sight_pack_write_info, dim3(1), dim3(64), 0, h->stream, (const unsigned long long*)ctl, (long long*)d_info);
+      }
+      return 0;
+    });
+  };
+  return run() ? -1 : 0;
+}
+
+int pf_sight_field(pf_handle* h, int32_t M, const int32_t* nodes, const uint64_t* d_adj, int32_t ld, int32_t B, const int32_t* set_off, const int32_t* src,
+                   double* d_dist, int32_t* d_parent, int64_t* d_info) {
+  if (!h) return -2;
+  const std::string me("pf_sight_field");
+  auto run = [&]() -> int {
+    if (sight_matrix_args(h, me, M, d_adj, ld)) return -2;
+    if (B < 1) return failmsg(h, me + ": bad arguments (B = " + std::to_string(B) + ": at least one source set is needed)");
+    if (!set_off) return failmsg(h, me + ": bad arguments (the set offsets must not be null)");
+    if (set_off[0] != 0) return failmsg(h, me + ": set_off[0] = " + std::to_string(set_off[0]) + ": the offsets must start at 0");
+    for (int b = 0; b < B; ++b)
+      if (set_off[b + 1] < set_off[b])
+        return failmsg(h, me + ": set " + std::to_string(b) + ": set_off[" + std::to_string(b + 1) + "] = " + std::to_string(set_off[b + 1]) + " lies below set_off[" +
+                              std::to_string(b) + "] = " + std::to_string(set_off[b]));
+    const int total = set_off[B];
+    if (total > 0 && !src) return failmsg(h, me + ": bad arguments (the sources must not be null)");
+    if (!d_dist) return failmsg(h, me + ": bad arguments (the labels must not be null)");
+    if (M >= 1 && M <= PF_SIGHT_NODES_MAX)
+      for (int j = 0; j < total; ++j)
+        if (src[j] < 0 || src[j] >= M) return failmsg(h, me + ": source " + std::to_string(j) + " = " + std::to_string(src[j]) + " lies outside [0, M)");
+    unsigned long long* work = nullptr;
+    int *d_nodes = nullptr, *d_rc = nullptr, *d_sets = nullptr;
+    if (const int rc = sight_nodes(h, me, M, nodes, (size_t)B + 1 + (size_t)total, work, d_nodes, d_rc, d_sets)) return rc;
+    CK(hipMemcpyAsync(d_sets, set_off, sizeof(int) * ((size_t)B + 1), hipMemcpyHostToDevice, h->stream));
+    if (total) CK(hipMemcpyAsync(d_sets + B + 1, src, sizeof(int) * (size_t)total, hipMemcpyHostToDevice, h->stream));
+    CK(hipMemsetAsync(work, 0, sizeof(unsigned long long) * 4, h->stream));
+    CK(hipStreamSynchronize(h->stream));                              // (the sets are pageable and the caller's)
+    const bool lds = M <= PF_SIGHT_LDS_NODES;
+    const unsigned G = (unsigned)std::min<long long>(B, 8ll * cus(h));
+    const unsigned nb = (unsigned)((M + PF_SIGHT_THREADS - 1) / PF_SIGHT_THREADS);
+    const int rc = timed(h, [&]() -> int {
+      hipLaunchKernelGGL(k_sight_node_coords, dim3(nb), dim3(PF_SIGHT_THREADS), 0, h->stream, (const int*)d_nodes, (int)M, h->C, d_rc);
+      if (lds) {
+        CK(hipFuncSetAttribute((const void*)k_sight_field_group_per_set<true>, hipFuncAttributeMaxDynamicSharedMemorySize,
+                               (int)(sizeof(double) * (PF_SIGHT_LDS_NODES < PF_SIGHT_NODES_MAX ? PF_SIGHT_LDS_NODES : PF_SIGHT_NODES_MAX))));   // (the most any call asks for)
+        hipLaunchKernelGGL(k_sight_field_group_per_set<true>, dim3(G), dim3(PF_SIGHT_GROUP), sizeof(double) * (size_t)M, h->stream, (const unsigned long long*)d_adj, (int)ld,
+                           (int)M, (const int*)d_rc, (int)B, (const int*)d_sets, (const int*)(d_sets + B + 1), d_dist, (long long*)d_info, work);
+      } else {
+        hipLaunchKernelGGL(k_sight_field_group_per_set<false>, dim3(G), dim3(PF_SIGHT_GROUP), 0, h->stream, (const unsigned long long*)d_adj, (int)ld, (int)M,
+                           (const int*)d_rc, (int)B, (const int*)d_sets, (const int*)(d_sets + B + 1), d_dist, (long long*)d_info, work);
+      }
+      if (d_parent)
+        hipLaunchKernelGGL(k_sight_parents, dim3(nb, (unsigned)(B < 65535 ? B : 65535)), dim3(PF_SIGHT_THREADS), 0, h->stream, (const unsigned long long*)d_adj, (int)ld,
+                           (int)M, (const int*)d_rc, (int)B, (const double*)d_dist, (int*)d_parent);
+      return 0;
+    });
+    if (rc) return rc;
+    unsigned long long w4[4];
+    CK(hipMemcpyAsync(w4, work, sizeof(w4), hipMemcpyDeviceToHost, h->stream));
+    CK(hipStreamSynchronize(h->stream));
+    h->d2h_small += 1;
+    for (int i = 0; i < 4; ++i) h->sight_work[i] = (long long)w4[i];
+    return 0;
+  };
+  return run() ? -1 : 0;
+}
+
+int pf_sight_field_work(pf_handle* h, int64_t* out4) { return tile_work(h, "pf_sight_field_work", h ? h->sight_work : nullptr, out4); }
+
+int pf_sight_paths(pf_handle* h, int32_t M, const int32_t* nodes, int32_t B, const double* d_dist, const int32_t* d_parent, int32_t n, const int32_t* d_set,
+                   const int32_t* d_target, int32_t reverse, int32_t way_cap, int32_t* d_way, int32_t* d_way_len, double* d_stats, int32_t* d_status) {
+  if (!h) return -2;
+  const std::string me("pf_sight_paths");
+  auto run = [&]() -> int {
+    if (n < 0 || B < 1 || way_cap < 1)
+      return failmsg(h, me + ": bad arguments (n = " + std::to_string(n) + ", B = " + std::to_string(B) + ", way_cap = " + std::to_string(way_cap) +
+                            ": n >= 0, B >= 1 and way_cap >= 1 are needed)");
+    if (!d_dist || !d_parent || !d_target || !d_way || !d_way_len || !d_status)
+      return failmsg(h, me + ": bad arguments (the labels, the parents, the targets, the waypoint rows, their lengths and the statuses must not be null)");
+    if (sight_nodes_check(h, me, M, nodes)) return -2;
+    if (n == 0) return 0;
+    unsigned long long* ctl = nullptr;
+    int *d_nodes = nullptr, *d_rc = nullptr, *d_extra = nullptr;
+    if (const int rc = sight_nodes(h, me, M, nodes, 0, ctl, d_nodes, d_rc, d_extra)) return rc;
+    return timed(h, [&] {
+      hipLaunchKernelGGL(k_sight_paths, dim3((unsigned)((n + PF_SIGHT_THREADS - 1) / PF_SIGHT_THREADS)), dim3(PF_SIGHT_THREADS), 0, h->stream, (int)M, (const int*)d_nodes,
+                         h->C, (int)B, (const double*)d_dist, (const int*)d_parent, (int)n, (const int*)d_set, (const int*)d_target, reverse ? 1 : 0, (int)way_cap,
+                         (int*)d_way, (int*)d_way_len, (double*)d_stats, (int*)d_status);
+    });
   };
   return run() ? -1 : 0;
 }

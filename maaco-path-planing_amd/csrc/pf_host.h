@@ -89,6 +89,7 @@ struct pf_handle {
   char* d_widest = nullptr; size_t widest_bytes = 0; long long widest_work[4] = {0, 0, 0, 0};   // pf_clearance_widest: counters, info words, the sets, tile queues and flags (first use, grown on demand); the last call's work
   long long cost_work[4] = {0, 0, 0, 0};                              // pf_cost_field / pf_cost_field_repair: the last call's work (their scratch is d_widest's block: nothing in it outlives a call)
   long long turn_work[4] = {0, 0, 0, 0};                              // pf_turn_field / pf_turn_field_repair: likewise (pf_spacetime_field keeps its static bit plane and, in the HBM form, its live planes in the same block)
+  long long sight_work[4] = {0, 0, 0, 0};                             // pf_sight_field: the last call's work (its scratch is the distance fields' control block: nothing in it outlives a call)
 };
 
 PF_INTERNAL int fail(pf_handle* h, const char* what, hipError_t e);   // -> -1, the message on the handle

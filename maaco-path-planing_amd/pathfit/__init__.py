@@ -24,6 +24,7 @@ from .clearance import Clearance, PF_CLEAR_NONE  # noqa: F401
 from .cost_field import CostField  # noqa: F401
 from .turn_field import TurnField  # noqa: F401
 from .visibility import Visibility  # noqa: F401
+from .any_angle import AnyAngle  # noqa: F401
 from .spacetime import SpaceTime  # noqa: F401
 from .tour import Tour  # noqa: F401
 from .assignment import Assignment  # noqa: F401

@@ -186,6 +186,10 @@ SYMBOLS = {
     "pf_visibility_field": (C.c_int, [_vp, _i32, _i32, _i32, _vp, _vp, _vp]),
     "pf_visibility_count": (C.c_int, [_vp, _i32, _i32, _i32, _vp, _vp, _vp]),
     "pf_visibility_paths": (C.c_int, [_vp, _vp, _i32, _i32, _vp, _vp, _vp, _vp, _vp]),
+    "pf_sight_pack": (C.c_int, [_vp, _i32, _i32, _i32, _vp, _vp, _i32, _vp]),
+    "pf_sight_field": (C.c_int, [_vp, _i32, _vp, _vp, _i32, _i32, _vp, _vp, _vp, _vp, _vp]),
+    "pf_sight_field_work": (C.c_int, [_vp, _vp]),
+    "pf_sight_paths": (C.c_int, [_vp, _i32, _vp, _i32, _vp, _vp, _i32, _vp, _vp, _i32, _i32, _vp, _vp, _vp, _vp]),
     "pf_spacetime_stamp": (C.c_int, [_vp, _i32, _vp, _i32, _i32, _vp, _vp, _vp, _i32, _i32, _i32, _vp]),
     "pf_spacetime_field": (C.c_int, [_vp, _i32, _i32, _i32, _vp, _i32, _vp, _vp, _vp, _vp, _vp]),
     "pf_spacetime_paths": (C.c_int, [_vp, _i32, _i32, _i32, _vp, _i32, _vp, _i32, _vp, _vp, _vp, _i32, _vp, _vp, _vp, _vp]),

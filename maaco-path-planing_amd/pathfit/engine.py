@@ -498,6 +498,48 @@ class Engine:
                                             d_status.ptr if d_status else None))
         self._logk("visibility_paths")
 
+    # ------------------------------------------------------------------ the sight graph
+    def sight_pack(self, nodes, d_adj, ld, restrict_corner=True, max_range_sq=-1, d_info=None):
+        """The sight graph over the M cells `nodes` (host int32 ids, strictly increasing), on the map the handle holds now -> d_adj
+        uint64 [M, ld] in HBM: bit j & 63 of word j >> 6 of row i is set iff nodes[i] sees nodes[j] (within max_range_sq unless that is
+        -1); the diagonal bit says the node's cell is free.  d_info int64 [4] = (set off-diagonal bits, the largest off-diagonal
+        degree, the smallest node index that attains it, nodes on obstacles) (pf_sight_pack)."""
+        nd = np.ascontiguousarray(nodes, np.int32).reshape(-1)
+        self._ck(self.L.pf_sight_pack(self.h, int(bool(restrict_corner)), int(max_range_sq), int(nd.size), nd.ctypes.data if nd.size else None,
+                                      d_adj.ptr if d_adj else None, int(ld), d_info.ptr if d_info else None))
+        self._logk("sight_pack")
+
+    def sight_field(self, nodes, d_adj, ld, set_off, sources, d_dist, d_parent=None, d_info=None):
+        """Exact any-angle labels over a sight graph: one row per source SET of node indices (host int32 CSR as dist_field_merged's;
+        a set may be empty) -> d_dist [B, M] doubles, the least left-to-right sum of sqrt(dr^2 + dc^2) over the walks from a usable
+        source, +inf where none arrives; d_parent int32 [B, M] (the smallest node index that explains the label, -1 at sources and
+        at +inf); d_info int64 [B, 4] = (finite labels, usable sources, the smallest node index with the largest finite label or -1,
+        0) (pf_sight_field)."""
+        nd = np.ascontiguousarray(nodes, np.int32).reshape(-1)
+        off = np.ascontiguousarray(set_off, np.int32).reshape(-1)
+        src = np.ascontiguousarray(sources, np.int32).reshape(-1)
+        self._ck(self.L.pf_sight_field(self.h, int(nd.size), nd.ctypes.data if nd.size else None, d_adj.ptr if d_adj else None, int(ld), int(off.size) - 1,
+                                       off.ctypes.data if off.size else None, src.ctypes.data if src.size else None, d_dist.ptr if d_dist else None,
+                                       d_parent.ptr if d_parent else None, d_info.ptr if d_info else None))
+        self._logk("sight_field")
+
+    def sight_field_work(self):
+        """(the most rounds a set took, the rounds of all sets, candidate sums formed, labels lowered) of the last sight_field call."""
+        out = (C.c_int64 * 4)()
+        self._ck(self.L.pf_sight_field_work(self.h, out))
+        return tuple(int(v) for v in out)
+
+    def sight_paths(self, nodes, B, d_dist, d_parent, n, d_target, way_cap, d_way, d_way_len, d_status, d_set=None, d_stats=None, reverse=False):
+        """n queries in HBM: the parents chased from node d_target[i] of set d_set[i] (None: set 0) -> d_way int32 [n, way_cap] the
+        waypoints' cell ids source -> target (target -> source when reverse), d_way_len, d_stats [n, 2] = (length, turns), d_status
+        (0 ok, 1 out of range, 2 infeasible, 3 more waypoints than way_cap, 4 parents that end nowhere) (pf_sight_paths)."""
+        nd = np.ascontiguousarray(nodes, np.int32).reshape(-1)
+        self._ck(self.L.pf_sight_paths(self.h, int(nd.size), nd.ctypes.data if nd.size else None, int(B), d_dist.ptr if d_dist else None,
+                                       d_parent.ptr if d_parent else None, int(n), d_set.ptr if d_set else None, d_target.ptr if d_target else None,
+                                       int(bool(reverse)), int(way_cap), d_way.ptr if d_way else None, d_way_len.ptr if d_way_len else None,
+                                       d_stats.ptr if d_stats else None, d_status.ptr if d_status else None))
+        self._logk("sight_paths")
+
     # ------------------------------------------------------------------ space-time fields
     def spacetime_stamp(self, horizon, d_occ, n, path_cap, d_cells, d_len, d_status, d_t0=None, after_end=True, corners=False, clear=False):
         """ORs n path rows of astar_batch's layout into the dynamic planes d_occ uint64 [T + 1, R, ceil(C / 64)]: the cell at position
